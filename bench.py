@@ -2,6 +2,7 @@
 """bench.py -- one "step" = one frame of the hot path (G-buffer + indirect-lighting pass) on synthetic/fixture input.
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --dump-outputs DIR                 (+ the last timed frame's output images as DIR/<name>.npy)
 
 Metric (BASELINE.json): Mrays/s (+ ms/frame) at 1920x1080, 3 non-transmissive bounces, Cornell-Box-class scene.
 A ray = one BVH query (closest-hit or any-hit), counted on the device.  Scene, BVH, G-buffer
@@ -245,6 +246,52 @@ def read_prof(api):
     return res
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(args, ctx, r, p_denoise, ext, tile, frame_num):
+    """--dump-outputs: the images the timed path handed its caller in its last frame -- the indirect integrator's FINAL radiance, the DI passes'
+    outputs, the denoised image -- as DIR/<name>.npy (float32, H x W x 4 over the full frame; N > 1: every rank's owned tile, stitched on rank 0).
+    When they would exceed DUMP_LIMIT_BYTES together, every array keeps the same fixed, seeded sample of pixels (rows of a (pixels, 4) array, pixel
+    indices ascending, np.random.default_rng(DUMP_SAMPLE_SEED)).  Returns the description that goes on the JSON line (rank 0), None elsewhere."""
+    planes = {}
+    if not r.skip_indirect:
+        planes["final"] = r.final()
+    if r.p_direct is not None:
+        planes["direct"] = r.p_direct.download()
+    if r.p_sky_direct is not None:
+        planes["sky_direct"] = r.p_sky_direct.download()
+    if p_denoise is not None:
+        planes["denoised"] = p_denoise.download_plane("denoised")
+    x0, y0, tw, th = tile
+    ox, oy = x0 - ext[0], y0 - ext[1]
+    mine = (tile, {k: np.ascontiguousarray(v[oy:oy + th, ox:ox + tw], np.float32) for k, v in planes.items()})
+    parts = [mine]
+    if ctx["dist"] is not None:
+        parts = [None] * ctx["world"] if ctx["rank"] == 0 else None
+        ctx["dist"].gather_object(mine, parts, dst=0)
+    if ctx["rank"] != 0:
+        return None
+    W, H = args.width, args.height
+    full = {}
+    for (x0, y0, tw, th), arrays in parts:
+        for k, v in arrays.items():
+            full.setdefault(k, np.zeros((H, W) + v.shape[2:], np.float32))[y0:y0 + th, x0:x0 + tw] = v
+    n = W * H
+    per_pixel = sum(v.nbytes // n for v in full.values())
+    sample = None
+    if n * per_pixel > DUMP_LIMIT_BYTES - 4096:      # (room for the .npy headers)
+        k = (DUMP_LIMIT_BYTES - 4096) // per_pixel
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False))
+        full = {name: v.reshape(n, -1)[idx] for name, v in full.items()}
+        sample = {"pixels": int(k), "of": n, "seed": DUMP_SAMPLE_SEED}
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, v in full.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), v)
+    return {"dir": args.dump_outputs, "frame_num": frame_num, "arrays": {name: list(v.shape) for name, v in full.items()}, "pixel_sample": sample}
+
+
 def measure(args, ctx):
     """One workload end to end on the devices of this job: scene + passes resident in HBM, settle + warm-up frames, the timed region of
     args.steps frames (barrier + torch.cuda.synchronize() on both sides, max over ranks), then -- rank 0, N = 1 -- the roofline block of the
@@ -296,12 +343,14 @@ def measure(args, ctx):
             dist.all_reduce(cost, op=dist.ReduceOp.SUM)
             layout = tiling.choose_layout(W, H, world, cost.cpu().numpy())
             r.p_indirect.enable_cost_map(False)
-            if layout is not None:
+            # (--dump-outputs: fresh passes whichever layout the timing-dependent probe chose, so that its frames never make the history of the dumped frame)
+            if layout is not None or args.dump_outputs:
                 if tiled.native is not None:
                     tiled.native.close()
                 del tiled, r
                 tiled = tiling.TiledRestirPT(sc, W, H, world, rank, device=local_rank, params=prm, dist=dist, kind=args.integrator, transport=transport, layout=layout)
                 r = tiled.r
+            if layout is not None:
                 layout_kind = "cost-balanced kd-split on the per-cell GPU time of 12 probe frames: " + str([list(t) for t in layout])
             else:
                 layout_kind = "equal-area grid (the probe frames' cost map predicts < 15 % gain from re-balancing)"
@@ -348,10 +397,14 @@ def measure(args, ctx):
         # frame N.  Bit-identical frames (test_frame_overlap_changes_nothing); ms_per_step is then a THROUGHPUT, the latency of one frame is frame_ms_median
         (tiled if tiled is not None else r).enable_frame_overlap(True)
 
-    def frame(i):
+    def frame_constants(i):
         cb = scene_io.make_frame_constants(W, H, frame_num=i, num_emissives=len(sc.emissives), **cam)
         if tex_offsets is not None:
             scene_io.set_texture_heap_offsets(cb, tex_offsets)
+        return cb
+
+    def frame(i):
+        cb = frame_constants(i)
         if tiled is not None:
             tiled.render_frame(cb, exchange_final=not args.no_final_halo)      # (runs the denoise schedule too when the pass is enabled)
         else:
@@ -365,6 +418,7 @@ def measure(args, ctx):
     # steady state first: the ray count per frame grows until the temporal reservoirs sit at their M caps (7.98 M rays / frame after 5
     # frames against 8.74 M after 64 on the Cornell box), so a short --warmup must not change the reported rate
     settle = args.settle if args.settle is not None else (32 if (rpt or args.integrator == "restir_gi" or di_passes) else 0)
+    settle_frames = settle
     # the device as it is right now, measured before anything is timed (every rank probes its own device; rank 0's block goes on the line as `device_state`,
     # N > 1 adds one summary row per rank)
     dev_state = device_state(api, local_rank) if not args.no_device_state else None
@@ -386,9 +440,33 @@ def measure(args, ctx):
             tr = torch.tensor([ramp], dtype=torch.int64, device=cdev)
             dist.all_reduce(tr, op=dist.ReduceOp.MAX)
             ramp = int(tr.item())
-        for i in range(ramp):
-            frame(1 + settle + i)
-    settle += ramp
+        if args.dump_outputs:
+            # the ramp's length follows the clock: its frames go to a renderer of their own (same scene, tile and passes), so that the renderer
+            # that is timed -- and dumped -- sees the same frames in every run with these arguments (N > 1: the rank's tile + apron, no halo exchanges)
+            ex0, ey0, ew, eh = tiled.ext if tiled is not None else (x0, y0, tw, th)
+            rr = api.Renderer(sc, ew, eh, device=local_rank, params=prm, tile_origin=(ex0, ey0),
+                              integrator={"restir_pt": api.INTEGRATOR_RESTIR_PT, "restir_gi": api.INTEGRATOR_RESTIR_GI}.get(args.integrator, api.INTEGRATOR_PATH_TRACING))
+            if r.p_direct is not None:
+                dip = wire.default_params_di()
+                dip.presampling, dip.num_sample_sets, dip.sample_set_size = prm.presampling, prm.num_sample_sets, prm.sample_set_size
+                rr.enable_direct(dip, device=local_rank)
+            if r.p_sky_direct is not None:
+                rr.enable_sky_direct(wire.default_params_sky_di(), device=local_rank)
+            rr.skip_indirect = r.skip_indirect
+            if tiled is not None and world > 1:      # (the tile object's halo pass owns the tile inside its G-buffer apron)
+                (rr.p_direct if tiled.kind == "di" else rr.p_sky_direct if tiled.kind == "sky_di" else rr.p_indirect).set_owned_rect(*tiled.tile)
+            if p_denoise is not None:
+                rr.enable_denoise(device=local_rank)
+            if overlap:
+                rr.enable_frame_overlap(True)
+            for i in range(ramp):
+                rr.render_frame(frame_constants(1 + settle + i))
+            torch.cuda.synchronize()
+            del rr
+        else:
+            for i in range(ramp):
+                frame(1 + settle + i)
+            settle += ramp
     for i in range(args.warmup):
         frame(1 + settle + i)
     barrier()
@@ -404,6 +482,10 @@ def measure(args, ctx):
     barrier()
     dt = time.perf_counter() - t0
     exch_per_frame = ((tiled.exchanges_done - exch0) / args.steps) if tiled is not None else 0.0
+    dumped = None
+    if args.dump_outputs:      # (before anything else renders on these passes)
+        dumped = dump_outputs(args, ctx, r, p_denoise, tiled.ext if tiled is not None else (x0, y0, tw, th), (x0, y0, tw, th),
+                              settle + args.warmup + args.steps)
 
     c1 = r.p_gbuffer.read_counters(reset=True)
     c2 = r.p_indirect.read_counters(reset=True)
@@ -454,7 +536,7 @@ def measure(args, ctx):
                        f"rank per exchange, {exch_per_frame:g} exchanges per frame (the previous frame's final reservoirs are fetched only by frames whose reprojection can cross a tile border: not while camera and scene stand still)"
                        if (tiled is not None and world > 1) else "") + ("; every rank's FINAL tile stays on its device (no gather inside the timed region)" if world > 1 else ""),
                    "halo_transport": (tiled.transport if (tiled is not None and world > 1) else None),
-                   "preset": args.config, "settle_frames": settle - ramp, "ramp_frames": ramp, "arith": args.arith, "library": os.path.basename(api.LIB_PATH),
+                   "preset": args.config, "settle_frames": settle_frames, "ramp_frames": ramp, "arith": args.arith, "library": os.path.basename(api.LIB_PATH),
                    # which permutation of the ReSTIR kernels this scene ran (zr_kernels.h PLAIN: scenes whose material table has no metal, transmission, thin
                    # wall, coat or texture run kernels without code for those lobes; one such material anywhere and the frame runs the general kernels)
                    "frame_overlap": overlap,
@@ -464,6 +546,8 @@ def measure(args, ctx):
                    "fps": round(1e3 / ms_per_step, 2)},
     }
 
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if dev_state is not None:
         out["device_state"] = dev_state
         if dist is not None:
@@ -721,8 +805,8 @@ def measure(args, ctx):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=256)
-    ap.add_argument("--warmup", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=None, help="timed frames (default 256, or the --config preset's when it names one)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed frames right before the timed ones (default 64, or the --config preset's)")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -764,12 +848,20 @@ def main():
     ap.add_argument("--settle", type=int, default=None,
                     help="untimed frames rendered BEFORE the warm-up so that the temporal reservoirs have reached their M caps whatever --warmup is "
                          "(default: 32 for the ReSTIR integrators, 0 otherwise)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames, write the images the timed path returned in its last frame as DIR/<name>.npy (float32, full frame; a fixed "
+                         "seeded sample of pixels when they would exceed 64 MB).  The clock-ramp frames then run on a renderer of their own, so that the "
+                         "timed renderer sees the same frames in every run with the same arguments")
     args = ap.parse_args()
     if args.config:
         for k, v in CONFIGS[args.config][1].items():
-            if k in ("steps", "warmup") and getattr(args, k) != ap.get_default(k):
+            if k in ("steps", "warmup") and getattr(args, k) is not None:
                 continue        # an explicit --steps / --warmup wins over the preset's
             setattr(args, k, v)
+    args.steps = 256 if args.steps is None else args.steps
+    args.warmup = 64 if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher (the shape of the driver's N = 1 command): start the N ranks here -- one process per GPU
@@ -829,6 +921,7 @@ def main():
         for preset in ("4", "5"):
             a2 = argparse.Namespace(**vars(args))
             a2.config = preset
+            a2.dump_outputs = None      # (the dump is the metric's own workload)
             for k, v in CONFIGS[preset][1].items():
                 setattr(a2, k, v)
             if preset == "5":

@@ -1954,19 +1954,21 @@ def test_material_edit_between_frames(api):
 
 
 def test_bench_multi_rank_protocol_on_one_gpu():
-    """`bench.py --gpus 2`, `--gpus 4` and `--gpus 8` end to end on a box with ONE GPU: the ranks are real processes launched by torch.distributed.run exactly as the
+    """`bench.py --gpus 2` and `--gpus 4` end to end on a box with ONE GPU: the ranks are real processes launched by torch.distributed.run exactly as the
     driver launches them, but share device 0 and talk over gloo (ZR_BENCH_SHARED_GPU=1, halo strips staged through the host).  What runs is the
     multi-GPU orchestration -- tile split, halo plan, probe frames with the cost map, choose_layout + re-tiling, barrier / max-over-ranks timing,
-    whole-job ray count -- everything except RCCL itself (exercised by test_fused_halo_transfer_and_rccl_exchange_on_one_gpu)."""
+    whole-job ray count -- everything except RCCL itself (exercised by test_fused_halo_transfer_and_rccl_exchange_on_one_gpu).  At most four rank
+    processes share the one device (with the test's own, five processes have it open at once); the 8-way split of the same frame size runs as eight
+    tile objects in one process in tests/test_denoise.py::test_denoise_on_tiles_equals_one_device."""
     import json
     import subprocess
     import sys
     env = dict(os.environ, ZR_BENCH_SHARED_GPU="1", MASTER_ADDR="127.0.0.1")
     singles = []
-    # (the last run adds the denoise pass: BASELINE config 5's shape on two ranks -- the three denoise halo exchanges of tiling.denoise_schedule per frame)
+    # (the denoise runs add the denoise pass: BASELINE config 5's shape on two and four ranks -- the three denoise halo exchanges of tiling.denoise_schedule per frame)
     # ... and BASELINE config 2 (the DI passes alone, sharded as the pass whose reservoirs cross tile borders: `--config 2a / 2b --gpus 2`)
-    for n, port, settle, more in ((1, 0, 4, []), (1, 0, 16, []), (2, 29631, 4, []), (4, 29632, 4, []), (8, 29634, 4, []), (2, 29633, 4, ["--denoise"]),
-                                  (2, 29635, 4, ["--config", "2a"]), (2, 29636, 4, ["--config", "2b"]), (8, 29637, 4, ["--denoise"])):
+    for n, port, settle, more in ((1, 0, 4, []), (1, 0, 16, []), (2, 29631, 4, []), (4, 29632, 4, []), (2, 29633, 4, ["--denoise"]),
+                                  (2, 29635, 4, ["--config", "2a"]), (2, 29636, 4, ["--config", "2b"]), (4, 29637, 4, ["--denoise"])):
         # n == 2 without --denoise is started as plain `python bench.py --gpus 2` (no launcher: bench.py starts its ranks itself, the shape of
         # the driver's N = 1 command); the other N > 1 runs go through torch.distributed.run the way the driver launches them
         self_launch = n == 2 and not more
@@ -2050,22 +2052,36 @@ def test_k11_kernel_variants_produce_identical_frames(scene):
     assert len(set(digests.values())) == 1, digests
 
 
-def test_bench_two_ranks_over_rccl_when_two_gpus_are_visible():
-    """The real multi-GPU path -- one process per GPU, halo strips through the C++ HaloExchange node over RCCL (grouped ncclSend / ncclRecv on the
-    pass's stream, unique id bootstrapped over the launcher's process group): `bench.py --gpus 2` launched the way the driver launches it.  Needs two
-    devices; on a one-GPU box the protocol is covered by test_bench_multi_rank_protocol_on_one_gpu and RCCL itself by the one-rank exchange test."""
+def test_bench_two_ranks_over_rccl_when_two_gpus_are_visible(tmp_path):
+    """`bench.py --gpus 2` launched the way the driver launches it (torch.distributed.run, one process per rank), and the image its ranks computed in
+    the last timed frame, stitched (--dump-outputs), bit-identical to `bench.py --gpus 1`'s.  With two devices visible this is the real multi-GPU
+    path -- one process per GPU, halo strips through the C++ HaloExchange node over RCCL (grouped ncclSend / ncclRecv on the pass's stream, unique id
+    bootstrapped over the launcher's process group).  RCCL refuses two ranks on one device, so with one device visible the two ranks share it and
+    talk over gloo (ZR_BENCH_SHARED_GPU=1, halo strips through torch P2P): everything but RCCL, which
+    test_fused_halo_transfer_and_rccl_exchange_on_one_gpu exercises on one device."""
     import json
     import subprocess
     import sys
     import torch
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs")
+    two = torch.cuda.device_count() >= 2
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1")
+    if not two:
+        env["ZR_BENCH_SHARED_GPU"] = "1"
+    args = ["--steps", "4", "--warmup", "2", "--settle", "4", "--width", "512", "--height", "288", "--no-cpu-baseline", "--no-general-kernels"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29641",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--settle", "4", "--width", "512", "--height", "288", "--no-cpu-baseline"]
-    res = subprocess.run(cmd, env=dict(os.environ, MASTER_ADDR="127.0.0.1"), cwd=ROOT, capture_output=True, text=True, timeout=900)
+           os.path.join(ROOT, "bench.py"), "--gpus", "2"] + args + ["--dump-outputs", str(tmp_path / "two")]
+    res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     d = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
-    assert d["n_gpus"] == 2 and d["value"] > 0 and d["config"]["halo_transport"] == "rccl_cpp", d["config"]
+    assert d["n_gpus"] == 2 and d["value"] > 0 and d["config"]["halo_transport"] == ("rccl_cpp" if two else "torch_p2p"), d["config"]
+    assert d["dump_outputs"]["arrays"] == {"final": [288, 512, 4]} and d["dump_outputs"]["pixel_sample"] is None, d["dump_outputs"]
+    res1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args + ["--dump-outputs", str(tmp_path / "one")],
+                          cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert res1.returncode == 0, res1.stdout[-2000:] + res1.stderr[-4000:]
+    d1 = json.loads([l for l in res1.stdout.splitlines() if l.startswith("{")][0])
+    assert d1["dump_outputs"]["frame_num"] == d["dump_outputs"]["frame_num"], (d1["dump_outputs"], d["dump_outputs"])
+    a, b = np.load(tmp_path / "two" / "final.npy"), np.load(tmp_path / "one" / "final.npy")
+    assert a[..., :3].max() > 0 and np.array_equal(a.view(np.uint32), b.view(np.uint32)), "two ranks' stitched FINAL differs from one device's"
 
 
 def test_final_halo_is_exchanged_only_by_frames_that_read_it(api, cornell_emissive, oracle_emissive):

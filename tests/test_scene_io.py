@@ -2,11 +2,15 @@
 
 Pinned three ways: (1) against the reference's own transform math and EmissiveTriangle packing compiled in place (oracle/_ref/libzref.so:
 affineTransformation x parent, decomposeSRT, quaternionFromRotationMat1, unorm4::FromNormalized, half3, RT::EmissiveTriangle), bit for bit on
-random inputs; (2) against the Python loader (zetaray_amd/scene_io.py) on the reference's Cornell scenes; (3) on a synthetic glTF with a node
+seeded random inputs -- where oracle/_ref is not built, against the outputs that code produced for the same inputs (tests/golden/ref_scene_io.npz);
+(2) against the Python loader (zetaray_amd/scene_io.py) on the reference's Cornell scenes (tests/golden/cornell_gltf); (3) on a synthetic glTF with a node
 hierarchy, a matrix node, KHR material extensions and an emissive mesh.  Block decompression is checked against Pillow's decoders."""
 import ctypes as C
+import gzip
+import hashlib
 import json
 import os
+import shutil
 import struct
 
 import numpy as np
@@ -15,8 +19,53 @@ import pytest
 from zetaray_amd import scene_io, wire
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_GLTF = "/root/reference/Assets/CornellBox"
+# the reference's Cornell glTF scenes (Assets/CornellBox, CC-BY-4.0, see license.txt there; the floor texture is stored gzipped)
+REF_GLTF = os.path.join(ROOT, "tests", "golden", "cornell_gltf")
 ZREF = os.path.join(ROOT, "oracle", "_ref", "libzref.so")
+REF_GOLD = os.path.join(ROOT, "tests", "golden", "ref_scene_io.npz")
+# the reference functions the tests below call: per argument the byte size of a pointer argument or the ctypes type of a scalar one, inputs first,
+# then the outputs (pointers)
+_REF_CALLS = {
+    "zref_compose_world": ((12, 16, 12, 48), (48,)),
+    "zref_fill_mesh_instance": ((48,), (12, 16, 12, 8, 6)),
+    "zref_emissive_triangle": ((12, 12, 12, 24, C.c_uint32, C.c_uint32, C.c_uint16, C.c_uint32, C.c_int), (48,)),
+    "zref_emissive_to_world": ((48, 48), (48,)),
+}
+RECORDING = None      # tools/make_ref_scene_io_goldens.py: {name: {input digest: output bytes}} filled by the live calls
+
+
+class _Ref:
+    """the reference's code for the tests below: live from oracle/_ref/libzref.so where it was built, else the outputs it produced for the very same
+    inputs (tests/golden/ref_scene_io.npz, keyed by a SHA-1 of the call's input bytes: an input the stored set does not hold fails the test)"""
+
+    def __init__(self):
+        self.live = C.CDLL(ZREF) if os.path.exists(ZREF) else None
+        if self.live is None:
+            g = np.load(REF_GOLD)
+            self.gold = {n: dict(zip(map(bytes, g[n + "/keys"]), map(bytes, g[n + "/outs"]))) for n in _REF_CALLS}
+        else:
+            for n, (ins, outs) in _REF_CALLS.items():
+                getattr(self.live, n).argtypes = [C.c_void_p if isinstance(a, int) else a for a in ins] + [C.c_void_p] * len(outs)
+
+    def __getattr__(self, name):
+        ins, outs = _REF_CALLS[name]
+
+        def call(*args):
+            key = hashlib.sha1(name.encode() + b"".join(C.string_at(a, k) if isinstance(k, int) else int(a).to_bytes(8, "little", signed=True)
+                                                         for a, k in zip(args, ins))).digest()
+            ptrs = args[len(ins):]
+            if self.live is not None:
+                getattr(self.live, name)(*args)
+                if RECORDING is not None:
+                    RECORDING.setdefault(name, {})[key] = b"".join(C.string_at(p, k) for p, k in zip(ptrs, outs))
+                return
+            got = self.gold[name].get(key)
+            assert got is not None, f"{name}: inputs not in {os.path.basename(REF_GOLD)} (regenerate it: tools/make_ref_scene_io_goldens.py)"
+            o = 0
+            for p, k in zip(ptrs, outs):
+                C.memmove(p, got[o:o + k], k)
+                o += k
+        return call
 
 
 def sio():
@@ -49,13 +98,10 @@ def random_trs(rng):
     return s, q, t
 
 
-@pytest.mark.skipif(not os.path.exists(ZREF), reason="needs oracle/_ref/libzref.so (built from /root/reference)")
 def test_transform_math_matches_reference_code():
     """world = affineTransformation(s, q, t) x parent over 3-level hierarchies, then FillMeshInstanceData's decomposeSRT + quantisation:
     2000 random chains, every float and every quantised field identical to the reference's SSE code"""
-    R = C.CDLL(ZREF)
-    R.zref_compose_world.argtypes = [C.c_void_p] * 5
-    R.zref_fill_mesh_instance.argtypes = [C.c_void_p] * 6
+    R = _Ref()
     L = sio()
     rng = np.random.default_rng(3)
     ident = np.hstack([np.eye(3, dtype=np.float32), np.zeros((3, 1), np.float32)])
@@ -89,10 +135,8 @@ def test_transform_math_matches_reference_code():
                 break       # non-uniform scale under a rotated parent shears: the reference does not support decomposing that either
 
 
-@pytest.mark.skipif(not os.path.exists(ZREF), reason="needs oracle/_ref/libzref.so (built from /root/reference)")
 def test_emissive_triangle_packing_matches_reference_code():
-    R = C.CDLL(ZREF)
-    R.zref_emissive_triangle.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.c_uint32, C.c_uint16, C.c_uint32, C.c_int, C.c_void_p]
+    R = _Ref()
     L = sio()
     rng = np.random.default_rng(9)
     for it in range(3000):
@@ -116,14 +160,12 @@ def test_emissive_triangle_packing_matches_reference_code():
         assert p.tobytes() == a.tobytes(), it
 
 
-@pytest.mark.skipif(not os.path.exists(ZREF), reason="needs oracle/_ref/libzref.so (built from /root/reference)")
 def test_emissive_world_transform_matches_reference_code():
     """zrh_emissive_to_world (decode the 16-bit octahedral edges + half lengths, transform, re-encode: what SceneCore does to every emissive
     triangle of a transformed instance on the first frame and to moving ones every frame) against the reference's own
     EmissiveTriangle::LoadVertices -> mul(toWorld, v) -> StoreVertices, 8000 random triangles x random rotations / scales / translations."""
-    R, L = C.CDLL(ZREF), sio()
-    for f in (R.zref_emissive_to_world, L.zrh_emissive_to_world):
-        f.argtypes = [C.c_void_p] * 3
+    R, L = _Ref(), sio()
+    L.zrh_emissive_to_world.argtypes = [C.c_void_p] * 3
     L.zrh_pack_emissive_triangle.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.c_uint32, C.c_uint16, C.c_uint32, C.c_int, C.c_void_p]
     rng = np.random.default_rng(21)
     for it in range(8000):
@@ -146,10 +188,19 @@ def test_emissive_world_transform_matches_reference_code():
         assert scene_io.emissive_to_world(e, M).tobytes() == a.tobytes()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_GLTF), reason="the reference's assets are not on this machine")
+def _cornell_gltf(tmp_path, name):
+    """the fixture laid out as the scene references its files: <name>.gltf, cornell.bin, compressed/checkerboard.dds"""
+    for f in (name + ".gltf", "cornell.bin"):
+        shutil.copy(os.path.join(REF_GLTF, f), tmp_path / f)
+    (tmp_path / "compressed").mkdir()
+    with gzip.open(os.path.join(REF_GLTF, "compressed", "checkerboard.dds.gz"), "rb") as src:
+        (tmp_path / "compressed" / "checkerboard.dds").write_bytes(src.read())
+    return str(tmp_path / (name + ".gltf"))
+
+
 @pytest.mark.parametrize("name", ["cornell", "cornell_emissive"])
-def test_native_loader_matches_python_loader_on_the_cornell_scenes(name):
-    path = os.path.join(REF_GLTF, name + ".gltf")
+def test_native_loader_matches_python_loader_on_the_cornell_scenes(name, tmp_path):
+    path = _cornell_gltf(tmp_path, name)
     a = scene_io.load_gltf(path)
     b, offs = scene_io.load_gltf_native(path)
     for f in ("vertices", "indices", "instance_mask", "instance_num_tris", "emissives"):
@@ -413,21 +464,18 @@ def test_cornell_with_the_reference_floor_texture_on_gpu():
     assert got[..., :3].max() > 0
 
 
-@pytest.mark.skipif(not os.path.exists(ZREF), reason="needs oracle/_ref/libzref.so (built from /root/reference)")
 def test_per_frame_scene_maintenance_matches_reference_code(tmp_path):
     """zrh_scene_data_begin_frame / _set_instance_world (the C++ host's per-frame scene update) against the reference's own code: MeshInstance
     records = TLAS::FillMeshInstanceData's !staticMesh branch (decomposeSRT of the current and the previous world matrix, dTranslation =
     half3(t - t_prev)), the moved light's EmissiveTriangle records = LoadVertices -> mul -> StoreVertices of the object-space ones; instances
     that do not move turn static (Prev* = current, dTranslation = 0)."""
     path, g, pos = _write_gltf(tmp_path)
-    L, R = sio(), C.CDLL(ZREF)
+    L, R = sio(), _Ref()
     L.zrh_scene_data_begin_frame.argtypes = [C.c_void_p]
     L.zrh_scene_data_set_instance_world.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     L.zrh_scene_data_dirty_emissives.argtypes = [C.c_void_p] * 3
     L.zrh_scene_data_initial_emissives.restype = C.c_void_p
     L.zrh_scene_data_initial_emissives.argtypes = [C.c_void_p]
-    R.zref_fill_mesh_instance.argtypes = [C.c_void_p] * 6
-    R.zref_emissive_to_world.argtypes = [C.c_void_p] * 3
     rho, dim = scene_io.load_rho_default()
     rho = np.ascontiguousarray(rho, np.uint16)
     h = C.c_void_p()
