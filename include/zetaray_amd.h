@@ -64,7 +64,21 @@ typedef enum zr_pass_kind {
        uses 256 x 128, DefaultRendererImpl.h:165-166); zr_pass_render writes the sky-view LUT from cbFrameConstants' sun and
        atmosphere fields and binds it to the scene, where Le_Sky of every later pass samples it (the reference does the same
        through EnvMapDescHeapOffset).  Pinned: R11G11B10_FLOAT store rounds to nearest even; the LUT is sampled with fp32 bilinear
-       interpolation, texel centres at (i + 0.5) / N, wrap addressing.  Inscattering voxel grid: out of scope (post stack). */
+       interpolation, texel centres at (i + 0.5) / N, wrap addressing.
+       Inscattering voxel grid (RP/Sky/Inscattering.hlsl; zr_pass_set_inscattering): aerial perspective over a camera-frustum grid of
+       voxels_x x voxels_y x 128 slices, one thread per voxel, one 128-thread group per (x, y) column; each voxel traces an any-hit shadow ray
+       toward -SunDir (tmin 0, tmax FLT_MAX, ZR_SUBGROUP_ALL, RAY_FLAG_CULL_NON_OPAQUE: ZR_INSTANCE_NON_OPAQUE instances are not candidates)
+       and an 8-step transmittance march.  zr_pass_render runs K17, then the grid (Sky.cpp:120-164); zr_pass_render_stage runs K17 on
+       ZR_STAGE_TEMPORAL and the grid on ZR_STAGE_SPATIAL.  Output ZR_OUT_INSCATTERING.  Pinned where D3D leaves it open:
+         WavePrefixSum over a 32-lane segment (Gidx & ~31, so [WaveSize(32)] holds on wave64), fp32: the values shifted up one lane (lane 0 = 0),
+           then a Hillis-Steele inclusive scan with offsets 1, 2, 4, 8, 16 (a lane adds the value of lane - s when lane >= s), then the lane's
+           own value added, as the shader's WavePrefixSum(x) + x;
+         the segments are combined as Inscattering.hlsl:179-198 is written: segment totals from lane 31 of each segment, serially over the
+           earlier segments prevLs += waveLs * totalTr, totalTr *= waveTr, then Ls = Ls * totalTr + prevLs;
+         store: max(Ls, 0) * SunIlluminance -> f16 (zr_f32_to_f16, the shader writes half3) -> R11G11B10_FLOAT, round to nearest even;
+         compositing's Texture3D.SampleLevel(g_samLinearClamp, (posTS, p), 0): fp32 trilinear, texel centres at (i + 0.5) / N, clamp
+           addressing, R11G11B10 decoded exactly, the result rounded to half (`half3 inscattering`) before `color += ...`.
+       The grid is computed for the whole screen: compositing with it on a G-buffer with a non-zero tile origin is refused. */
     ZR_PASS_SKY         = 6,
     /* TAA (RP/TAA/TAA.cpp, TAA.hlsl): temporal anti-aliasing of the composited image.  Input: an
        RGBA32F image bound with zr_pass_set_input(ZR_IN_TAA_SIGNAL) -- e.g. the COMPOSITING pass's FINAL -- plus the depth and
@@ -473,6 +487,19 @@ int zr_pass_download_output(const zr_pass* pass, int which, void* hip_stream, vo
 #define ZR_IN_DISPLAY_EXPOSURE 6   /* ZR_PASS_DISPLAY: RG32F 1 x 1 (ZR_OUT_EXPOSURE) */
 #define ZR_IN_DENOISE_SIGNAL   7   /* ZR_PASS_DENOISE: the RGBA32F image to filter */
 int zr_pass_set_input(zr_pass* pass, int which, const void* dev_plane);
+/* ZR_PASS_SKY: Sky::SetInscatteringEnablement + the "Inscattering" UI parameters (Sky.cpp:69-117, 210-223). voxels 0 = reference
+   default (192 x 108); depth_map_exp 1..5 (default 2), 0 <= near_z < far_z (defaults 0.5, 30).  Allocates / frees the grid. */
+int zr_pass_set_inscattering(zr_pass* sky, int enable, uint32_t voxels_x, uint32_t voxels_y, float depth_map_exp, float near_z, float far_z);
+/* ZR_PASS_COMPOSITING: CB_COMPOSIT_FLAGS::INSCATTERING + SetVoxelGridDepth / SetVoxelGridMappingExp + the INSCATTERING descriptor, all taken
+   from `sky` at render time (PostProcessor.cpp:123-136); NULL unbinds.  The pass keeps `sky` itself, not its grid (re-enabling the sky pass
+   with other voxel counts reallocates the grid): unbind before destroying the sky pass.  Rendering fails with ZR_ERR_INVALID_ARG when the
+   sky pass's inscattering is disabled or the G-buffer has a non-zero tile origin. */
+int zr_pass_bind_inscattering(zr_pass* compositing, const zr_pass* sky);
+/* ZR_PASS_SKY with inscattering enabled: the voxel grid, R11G11B10_FLOAT 4 B (Sky::SHADER_OUT_RES::INSCATTERING); voxels_x x voxels_y x 128,
+   x fastest, then y, then the slice; zr_pass_get_output reports width = voxels_x, height = voxels_y * 128 */
+#define ZR_OUT_INSCATTERING 49
+#define ZR_INSCATTERING_VOXELS_X 192      /* Sky.h DefaultParamVals */
+#define ZR_INSCATTERING_VOXELS_Y 108
 /* ZR_PASS_DISPLAY: the Tony McMapface LUT of the NEUTRAL tone mapper, dim^3 R9G9B9E5_SHAREDEXP texels on the host (the payload of
    Assets/LUT/tony_mc_mapface.dds, 48^3; shipped as zetaray_amd/assets/tony_mc_mapface_rgb9e5.bin).  Display.cpp:196-205. */
 int zr_pass_set_tonemap_lut(zr_pass* pass, const uint32_t* rgb9e5, uint32_t dim);

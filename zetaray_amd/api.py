@@ -58,6 +58,7 @@ EXPORTS = [
     "zr_pass_set_owned_rect", "zr_pass_render_stage", "zr_pass_halo_pack", "zr_pass_halo_unpack", "zr_pass_halo_bytes_per_pixel", "zr_pass_set_input",
     "zr_pass_set_tonemap_lut", "zr_pass_halo_pack_all", "zr_pass_halo_unpack_all",
     "zr_pass_set_frame_overlap", "zr_pass_frame_overlap_stream", "zr_device_synchronize",
+    "zr_pass_set_inscattering", "zr_pass_bind_inscattering",
 ]
 STAGE_TEMPORAL, STAGE_SPATIAL, STAGE_ALL = 1, 2, 3
 STAGE_SPATIAL2 = 4          # ReSTIR PT, num_spatial_passes = 2 on tiles: the second round, behind one more HALO_POST_TEMPORAL exchange
@@ -125,6 +126,8 @@ def lib():
         L.zr_pass_read_counters.argtypes = [vp, vp, vp, i32]
         L.zr_pass_read_kernel_counters.argtypes = [vp, vp, u32, vp, vp, vp, vp]
         L.zr_pass_set_input.argtypes = [vp, i32, vp]
+        L.zr_pass_set_inscattering.argtypes = [vp, i32, u32, u32, C.c_float, C.c_float, C.c_float]
+        L.zr_pass_bind_inscattering.argtypes = [vp, vp]
         L.zr_pass_set_tonemap_lut.argtypes = [vp, vp, u32]
         L.zr_pass_halo_pack_all.argtypes = [vp, vp, vp, i32, vp, u32, vp, C.c_size_t]
         L.zr_pass_halo_unpack_all.argtypes = [vp, vp, vp, i32, vp, u32, vp, C.c_size_t]
@@ -420,8 +423,23 @@ class Pass:
         _check(lib().zr_pass_download_output(self.h, which, stream, out.ctypes.data, out.nbytes))
         return out
 
+    # SKY pass: Sky::SetInscatteringEnablement + its "Inscattering" parameters (zetaray_amd.h zr_pass_set_inscattering)
+    def set_inscattering(self, enable=True, voxels=wire.INSCATTERING_VOXELS, depth_map_exp=wire.INSCATTERING_DEPTH_MAP_EXP,
+                         near_z=wire.INSCATTERING_NEAR_Z, far_z=wire.INSCATTERING_FAR_Z):
+        _check(lib().zr_pass_set_inscattering(self.h, int(enable), int(voxels[0]), int(voxels[1]), float(depth_map_exp), float(near_z), float(far_z)))
+
+    # COMPOSITING pass: composite the inscattering grid of `sky_pass` (a SKY Pass, read at render time), None unbinds
+    def bind_inscattering(self, sky_pass):
+        _check(lib().zr_pass_bind_inscattering(self.h, sky_pass.h if sky_pass is not None else None))
+
     def download_plane(self, name, stream=None):
-        """ReSTIR PT reservoir / target / neighbour planes (see RPT_OUTPUTS)."""
+        """ReSTIR PT reservoir / target / neighbour planes (see RPT_OUTPUTS); "inscattering" on a SKY pass: the voxel grid as
+        (128, voxels_y, voxels_x) uint32 R11G11B10_FLOAT texels."""
+        if name == "inscattering":
+            _, w, h, _ = self.output_ptr(wire.OUT_INSCATTERING)
+            out = np.zeros((wire.INSCATTERING_SLICES, h // wire.INSCATTERING_SLICES, w), np.uint32)
+            _check(lib().zr_pass_download_output(self.h, wire.OUT_INSCATTERING, stream, out.ctypes.data, out.nbytes))
+            return out
         which, dt, ch = RPT_OUTPUTS[name] if name in RPT_OUTPUTS else RPT_OUTPUTS_EXTRA[name]
         out = np.zeros((self.h_, self.w, ch), dt)
         _check(lib().zr_pass_download_output(self.h, which, stream, out.ctypes.data, out.nbytes))
@@ -509,6 +527,7 @@ class Renderer:
         self.p_composit = None        # Compositing: enable_compositing()
         self._alias_ready = False
         self._overlap_stream = None   # frame overlap: enable_frame_overlap()
+        self._inscattering = False    # the sky pass's inscattering voxel grid: enable_inscattering()
         self._device = device
 
     def enable_frame_overlap(self, on=True, carry=False):
@@ -533,6 +552,21 @@ class Renderer:
         self.p_composit = Pass(PASS_COMPOSITING, self.p_indirect.w, self.p_indirect.h_, device=device, params=prm)
         self._bind_post_inputs()
         return self.p_composit
+
+    def enable_inscattering(self, voxels=wire.INSCATTERING_VOXELS, depth_map_exp=wire.INSCATTERING_DEPTH_MAP_EXP, near_z=wire.INSCATTERING_NEAR_Z,
+                            far_z=wire.INSCATTERING_FAR_Z, device=0):
+        """Renderer > Inscattering (PathTracer.cpp:26-36, 165-181; PostProcessor.cpp:123-136): the sky pass computes the inscattering voxel grid
+        every frame (after its LUT) and Compositing adds it to every surface pixel.  Adds the Sky pass (scenes with emissives have none here; the
+        reference always has one) and the Compositing pass if they are absent."""
+        assert self._overlap_stream is None, "frame overlap covers GBuffer + PreLighting + Indirect (ReSTIR PT) [+ denoise]"
+        if self.p_sky is None:
+            self.p_sky = Pass(PASS_SKY, 256, 128, device=device)
+        self.p_sky.set_inscattering(True, voxels, depth_map_exp, near_z, far_z)
+        if self.p_composit is None:
+            self.enable_compositing(device=device)
+        self.p_composit.bind_inscattering(self.p_sky)
+        self._inscattering = True
+        return self.p_sky
 
     def _bind_post_inputs(self):
         """(re)bind the Compositing / TAA inputs to the current output planes of the lighting passes: called whenever a pass is
@@ -597,9 +631,16 @@ class Renderer:
         if self.p_sky is None:
             return
         key = b"".join(np.asarray(cb[f]).tobytes() for f in self._SKY_FIELDS)
+        if not self._inscattering:
+            if key != getattr(self, "_sky_key", None):
+                self.p_sky.render(cb, self.scene, None, stream)
+                self._sky_key = key
+            return
+        # with inscattering: the LUT (STAGE_TEMPORAL) when its inputs changed, the voxel grid (STAGE_SPATIAL; it follows the camera and the scene) every frame
         if key != getattr(self, "_sky_key", None):
-            self.p_sky.render(cb, self.scene, None, stream)
+            self.p_sky.render_stage(cb, self.scene, None, STAGE_TEMPORAL, stream)
             self._sky_key = key
+        self.p_sky.render_stage(cb, self.scene, None, STAGE_SPATIAL, stream)
 
     def render_frame(self, cb, stream=None):
         if self._overlap_stream is not None:

@@ -62,6 +62,7 @@ static int RequireDevice(int device)
 #endif
 #include "zr_bvh_device.h"
 namespace zr { int DeviceProbeRun(int device, float min_ms, zr_device_probe* out, std::string& err); }      // zr_tu_probe.hip
+namespace zr { hipError_t LaunchInscattering(hipStream_t s, const SceneView& sc, const zr_frame_constants& g, const InscatterParams& c, uint32_t* grid); }   // zr_tu_sky.hip
 // the ReSTIR PT kernels are compiled in zr_tu_rpt_[a-i].hip (see zr_kernels.h)
 ZR_RPT_GROUPS_PRODUCT(extern template)
 #ifdef ZR_EXPERIMENTS
@@ -380,6 +381,15 @@ __global__ void __launch_bounds__(256) k_composite(zr_frame_constants g, const u
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = CompositePixel(g, mr[i], skyDI, emissiveDI, indirect, i, out[i], sky, i % w, i / w);
+}
+// Compositing with the inscattering voxel grid bound (zr_pass_bind_inscattering): + 4 B depth read and the grid's 8 texels per pixel
+__global__ void __launch_bounds__(256) k_composite_inscattering(zr_frame_constants g, const uint16_t* mr, const float* depth, const F4* skyDI, const F4* emissiveDI,
+    const F4* indirect, F4* out, uint32_t n, SkyLutView sky, uint32_t w, InscatterGridView grid)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const F4 c = CompositePixel(g, mr[i], skyDI, emissiveDI, indirect, i, out[i], sky, i % w, i / w);
+    out[i] = CompositeInscattering(g, mr[i], c, depth[i], grid, i % w, i / w);
 }
 
 // Firefly filter (FireflyFilter.hlsl): a 3 x 3 stencil over RGBA32F + depth.  A block filters a 64 x 16 pixel tile, 4 pixels per thread;
@@ -812,6 +822,9 @@ struct zr_pass
     // INDIRECT
     QueueStorage q[2];
     DevBuf<uint32_t> skyLut;                       // ZR_PASS_SKY: R11G11B10F texels
+    // ZR_PASS_SKY: the inscattering voxel grid (Sky::SetInscatteringEnablement, zr_pass_set_inscattering), numVoxelsX x numVoxelsY x 128 R11G11B10F texels
+    bool inscatterOn = false; InscatterParams inscatter{}; DevBuf<uint32_t> inscatterGrid;
+    const zr_pass* inscatterSky = nullptr;         // ZR_PASS_COMPOSITING: the SKY pass whose grid is composited (zr_pass_bind_inscattering), read at render time
     DevBuf<float> finalRGBA; DevBuf<F4> firstBOP; DevBuf<uint32_t> counts; DevBuf<unsigned long long> counters;
     DevBuf<uint32_t> groupMax;      // kMaxRounds x (8x8 groups of the tile): RR reduction keys
     zr_counters hostCounters{0, 0};
@@ -2111,14 +2124,26 @@ int zr_pass_read_pick(zr_pass* p, void* stream, uint32_t* mesh_idx)
     return ZR_OK;
 }
 
-// Sky::Render (Sky.cpp:120-164): K17, then bind the LUT to the scene
-static int RenderSky(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, zr_scene* sc)
+// Sky::Render (Sky.cpp:120-164): K17 (ZR_STAGE_TEMPORAL), then bind the LUT to the scene; then, with inscattering enabled, the voxel grid
+// (ZR_STAGE_SPATIAL: a caller that keeps the LUT -- it does not depend on the camera -- renders the grid alone every frame)
+static int RenderSky(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, zr_scene* sc, int stages)
 {
-    TimerBegin(p, s, "sky_view_lut");
-    hipLaunchKernelGGL(k_sky_lut, dim3((p->w + 7) / 8, (p->h + 7) / 8), dim3(64), 0, s, *cb, p->w, p->h, p->skyLut.p);
-    TimerEnd(p, s);
-    HIP_TRY(hipGetLastError());
-    { std::lock_guard<std::mutex> lock(sc->mtx); sc->view.sky.data = p->skyLut.p; sc->view.sky.w = p->w; sc->view.sky.h = p->h; }
+    if (stages & ZR_STAGE_TEMPORAL)
+    {
+        TimerBegin(p, s, "sky_view_lut");
+        hipLaunchKernelGGL(k_sky_lut, dim3((p->w + 7) / 8, (p->h + 7) / 8), dim3(64), 0, s, *cb, p->w, p->h, p->skyLut.p);
+        TimerEnd(p, s);
+        HIP_TRY(hipGetLastError());
+        { std::lock_guard<std::mutex> lock(sc->mtx); sc->view.sky.data = p->skyLut.p; sc->view.sky.w = p->w; sc->view.sky.h = p->h; }
+    }
+    if (p->inscatterOn && (stages & ZR_STAGE_SPATIAL))
+    {
+        if (!(stages & ZR_STAGE_TEMPORAL)) p->numTimers = 0;      // the grid alone is this pass's whole frame
+        TimerBegin(p, s, "inscattering");
+        const hipError_t e = LaunchInscattering(s, FrameView(sc, cb), *cb, p->inscatter, p->inscatterGrid.p);
+        TimerEnd(p, s);
+        if (e != hipSuccess) return Fail(ZR_ERR_HIP, "inscattering launch failed: %s", hipGetErrorString(e));
+    }
     return ZR_OK;
 }
 
@@ -2714,6 +2739,43 @@ int zr_pass_set_input(zr_pass* p, int which, const void* dev)
     p->compIn[which] = (const F4*)dev;
     return ZR_OK;
 }
+// Sky::SetInscatteringEnablement + the "Inscattering" UI parameters (Sky.cpp:69-117, 210-223)
+extern "C" int zr_pass_set_inscattering(zr_pass* p, int enable, uint32_t voxels_x, uint32_t voxels_y, float depth_map_exp, float near_z, float far_z)
+{
+    if (!p || p->kind != ZR_PASS_SKY) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_inscattering: needs a SKY pass");
+    if (!p->initialized) return Fail(ZR_ERR_NOT_INITIALIZED, "zr_pass_set_inscattering: pass not initialised (zr_pass_init)");
+    HIP_TRY(hipSetDevice(p->device));
+    if (!enable)
+    {
+        p->inscatterOn = false; p->inscatterGrid.Free();      // m_voxelGrid.Reset()
+        return ZR_OK;
+    }
+    if (voxels_x == 0 && voxels_y == 0) { voxels_x = ZR_INSCATTERING_VOXELS_X; voxels_y = ZR_INSCATTERING_VOXELS_Y; }     // Sky.h DefaultParamVals
+    if (voxels_x == 0 || voxels_y == 0 || voxels_x > 4096 || voxels_y > 4096)
+        return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_inscattering: voxel counts %u x %u outside 1..4096 (0 x 0 = the default)", voxels_x, voxels_y);
+    if (!(depth_map_exp >= 1.0f && depth_map_exp <= 5.0f))
+        return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_inscattering: depth_map_exp %g outside 1..5", (double)depth_map_exp);
+    if (!(near_z >= 0.0f && near_z < far_z && far_z <= ZR_FLT_MAX))
+        return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_inscattering: needs 0 <= near_z < far_z (got %g, %g)", (double)near_z, (double)far_z);
+    const size_t n = (size_t)voxels_x * voxels_y * kInscatterSlices;
+    if (!p->inscatterOn || p->inscatterGrid.n != n)
+    {
+        int r; if ((r = p->inscatterGrid.Alloc(n))) { p->inscatterOn = false; return r; }
+        HIP_TRY(hipMemset(p->inscatterGrid.p, 0, n * sizeof(uint32_t)));
+    }
+    p->inscatter.numVoxelsX = voxels_x; p->inscatter.numVoxelsY = voxels_y;
+    p->inscatter.depthMappingExp = depth_map_exp; p->inscatter.nearZ = near_z; p->inscatter.farZ = far_z;
+    p->inscatterOn = true;
+    return ZR_OK;
+}
+// Compositing::SetInscatteringEnablement + SetVoxelGridDepth / SetVoxelGridMappingExp + SHADER_IN_GPU_DESC::INSCATTERING, all read from `sky` at render time
+extern "C" int zr_pass_bind_inscattering(zr_pass* p, const zr_pass* sky)
+{
+    if (!p || p->kind != ZR_PASS_COMPOSITING) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_bind_inscattering: needs a COMPOSITING pass");
+    if (sky && sky->kind != ZR_PASS_SKY) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_bind_inscattering: the grid comes from a SKY pass");
+    p->inscatterSky = sky;
+    return ZR_OK;
+}
 extern "C" int zr_pass_set_tonemap_lut(zr_pass* p, const uint32_t* rgb9e5, uint32_t dim)
 {
     if (!p || p->kind != ZR_PASS_DISPLAY || !rgb9e5 || dim == 0 || dim > 256) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_tonemap_lut: needs a DISPLAY pass and a dim^3 LUT");
@@ -2861,13 +2923,30 @@ static int RenderDenoise(zr_pass* p, hipStream_t s, const zr_frame_constants* cb
 static int RenderCompositing(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, const zr_scene* sc, zr_gbuffer* gb)
 {
     if (!gb || gb->w != p->w || gb->h != p->h) return Fail(ZR_ERR_INVALID_ARG, "COMPOSITING needs a gbuffer of the pass size");
+    if (const zr_pass* sky = p->inscatterSky)
+    {
+        if (!sky->inscatterOn) return Fail(ZR_ERR_INVALID_ARG, "COMPOSITING is bound to a SKY pass whose inscattering is disabled (zr_pass_set_inscattering)");
+        if (sky->device != p->device) return Fail(ZR_ERR_INVALID_ARG, "COMPOSITING and the bound SKY pass live on different devices");
+        // (the grid covers the whole screen; the N-way tile split of compositing with it is out of scope)
+        if (gb->x0 || gb->y0) return Fail(ZR_ERR_INVALID_ARG, "compositing with inscattering on a tile of the split screen is not supported (gbuffer tile origin %u, %u)", gb->x0, gb->y0);
+    }
     const uint32_t n = p->w * p->h;
     TimerBegin(p, s, "compositing");
     // with the firefly filter on (Compositing.cpp: m_filterFirefly) the composited image goes to a scratch plane and the filter writes FINAL
     const bool firefly = (p->params.flags & ZR_COMPOSIT_FIREFLY_FILTER) != 0;
     F4* composited = firefly ? p->firstBOP.p : (F4*)p->finalRGBA.p;
-    hipLaunchKernelGGL(k_composite, dim3((n + 255) / 256), dim3(256), 0, s, *cb, (const uint16_t*)gb->Planes()[ZR_GB_METALLIC_ROUGHNESS].p, p->compIn[ZR_IN_SKY_DI],
-        p->compIn[ZR_IN_EMISSIVE_DI], p->compIn[ZR_IN_INDIRECT], composited, n, FrameView(sc, cb).sky, p->w);
+    if (const zr_pass* sky = p->inscatterSky)
+    {
+        // PostProcessor.cpp:123-136: the grid, its depth range and mapping exponent come from the sky pass as it is now
+        const InscatterGridView grid = {sky->inscatterGrid.p, sky->inscatter.numVoxelsX, sky->inscatter.numVoxelsY, sky->inscatter.depthMappingExp,
+                                        sky->inscatter.nearZ, sky->inscatter.farZ};
+        hipLaunchKernelGGL(k_composite_inscattering, dim3((n + 255) / 256), dim3(256), 0, s, *cb, (const uint16_t*)gb->Planes()[ZR_GB_METALLIC_ROUGHNESS].p,
+            (const float*)gb->Planes()[ZR_GB_DEPTH].p, p->compIn[ZR_IN_SKY_DI], p->compIn[ZR_IN_EMISSIVE_DI], p->compIn[ZR_IN_INDIRECT], composited, n,
+            FrameView(sc, cb).sky, p->w, grid);
+    }
+    else
+        hipLaunchKernelGGL(k_composite, dim3((n + 255) / 256), dim3(256), 0, s, *cb, (const uint16_t*)gb->Planes()[ZR_GB_METALLIC_ROUGHNESS].p, p->compIn[ZR_IN_SKY_DI],
+            p->compIn[ZR_IN_EMISSIVE_DI], p->compIn[ZR_IN_INDIRECT], composited, n, FrameView(sc, cb).sky, p->w);
     TimerEnd(p, s);
     if (firefly)
     {
@@ -3090,7 +3169,7 @@ static int RenderStageInner(zr_pass* p, void* stream, const zr_frame_constants* 
     case ZR_PASS_DI_EMISSIVE: return RenderDirectEmissive(p, s, cb, sc, gb, stages);
     case ZR_PASS_DI_SKY: return RenderDirectSky(p, s, cb, sc, gb, stages);
     case ZR_PASS_COMPOSITING: return (stages & ZR_STAGE_SPATIAL) ? RenderCompositing(p, s, cb, sc, gb) : ZR_OK;
-    case ZR_PASS_SKY: return (stages & ZR_STAGE_TEMPORAL) ? RenderSky(p, s, cb, const_cast<zr_scene*>(sc)) : ZR_OK;
+    case ZR_PASS_SKY: return RenderSky(p, s, cb, const_cast<zr_scene*>(sc), stages);
     case ZR_PASS_TAA: return (stages & ZR_STAGE_SPATIAL) ? RenderTAA(p, s, cb, gb) : ZR_OK;
     case ZR_PASS_AUTO_EXPOSURE: return (stages & ZR_STAGE_SPATIAL) ? RenderAutoExposure(p, s, cb) : ZR_OK;
     case ZR_PASS_DISPLAY: return (stages & ZR_STAGE_SPATIAL) ? RenderDisplay(p, s, cb) : ZR_OK;
@@ -3107,6 +3186,15 @@ int zr_pass_get_output(const zr_pass* p, int which, void** dev, uint32_t* w, uin
 {
     if (!p || !dev) return Fail(ZR_ERR_INVALID_ARG, "null argument");
     if (!p->initialized) return Fail(ZR_ERR_NOT_INITIALIZED, "pass not initialised");
+    if (p->kind == ZR_PASS_SKY && which == ZR_OUT_INSCATTERING)
+    {
+        if (!p->inscatterOn) return Fail(ZR_ERR_INVALID_ARG, "SKY pass: inscattering is disabled (zr_pass_set_inscattering)");
+        *dev = p->inscatterGrid.p;
+        if (w) *w = p->inscatter.numVoxelsX;
+        if (h) *h = p->inscatter.numVoxelsY * kInscatterSlices;
+        if (bpp) *bpp = 4;
+        return ZR_OK;
+    }
     if (p->kind == ZR_PASS_SKY)
     {
         if (which != ZR_OUT_SKY_LUT) return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");

@@ -144,11 +144,14 @@ ZR_HD bool TestOpacity(const SceneView& sc, uint32_t meshIdx, uint32_t primIdx, 
 
 struct TravStack;
 ZR_HD BvhTri FetchTri(const SceneView& sc, uint32_t i, const TravStack* st);
+// CullNonOpaque (RAY_FLAG_CULL_NON_OPAQUE, a compile-time choice): triangles of ZR_INSTANCE_NON_OPAQUE instances are not candidates
+template<bool CullNonOpaque = false>
 ZR_HD void IntersectTri(const SceneView& sc, uint32_t i, V3 o, V3 d, float tmin, float tmax,
     uint32_t mask, RawHit& best, bool filterID = false, uint32_t ignoreID = 0, bool alphaTest = false, const TravStack* st = nullptr)
 {
     const BvhTri T = FetchTri(sc, i, st);
     if (!(T.mask & mask)) return;
+    if (CullNonOpaque && (T.mask & ZR_INSTANCE_NON_OPAQUE)) return;
     // (before the intersection test on purpose: behind it -- hits only -- every traversal kernel got 8-12 % slower on the atrium, measured A/B in one run)
     if (filterID && T.id == ignoreID) return;
     float t, u, v;
@@ -162,10 +165,11 @@ ZR_HD void IntersectTri(const SceneView& sc, uint32_t i, V3 o, V3 d, float tmin,
         { best.t = t; best.u = u; best.v = v; best.tri = T.gidx; }
     }
 }
+template<bool CullNonOpaque = false>
 ZR_HD void IntersectLeaf(const SceneView& sc, uint32_t first, uint32_t count, V3 o, V3 d, float tmin, float tmax,
     uint32_t mask, RawHit& best, bool filterID = false, uint32_t ignoreID = 0, bool alphaTest = false)
 {
-    for (uint32_t i = first; i < first + count; i++) IntersectTri(sc, i, o, d, tmin, tmax, mask, best, filterID, ignoreID, alphaTest);
+    for (uint32_t i = first; i < first + count; i++) IntersectTri<CullNonOpaque>(sc, i, o, d, tmin, tmax, mask, best, filterID, ignoreID, alphaTest);
 }
 
 // Stack-based BVH4 traversal, written as an explicit state machine so that a kernel can either run it to completion
@@ -372,13 +376,14 @@ ZR_HD uint32_t TravNode(const SceneView& sc, TravState& s, const TravStack& stac
 #undef ZR_TRAV_CSWAP
 
 // one step: a leaf (all its triangles) or an inner node (4 box tests).  Returns true when the ray is finished.
+template<bool CullNonOpaque = false>
 ZR_HD bool TravStep(const SceneView& sc, TravState& s, const TravStack& stack, bool anyHit, bool alphaTest = false)
 {
     if (s.cur & kLeafBit)
     {
         uint32_t first = (s.cur & 0x7fffffffu) >> 3, count = (s.cur & 7u) + 1u;
         if (s.cur == kWholeSceneLeaf) { first = 0; count = sc.numTris; }
-        IntersectLeaf(sc, first, count, s.o, s.d, s.tmin, s.tmax, s.mask, s.best, s.filterID, s.ignoreID, alphaTest);
+        IntersectLeaf<CullNonOpaque>(sc, first, count, s.o, s.d, s.tmin, s.tmax, s.mask, s.best, s.filterID, s.ignoreID, alphaTest);
         if (anyHit && s.best.tri != kInvalidTri) return true;
         return !TravPop(s, stack);
     }
@@ -415,21 +420,22 @@ ZR_HD void TravNodePhase(const SceneView& sc, TravState& s, TravLane& L, const T
     if (next == kEmptyChild) TravPopEnter(sc, s, L, stack);
     else TravEnter(sc, s, L, next);
 }
+template<bool CullNonOpaque = false>
 ZR_HD void TravTriPhase(const SceneView& sc, TravState& s, TravLane& L, const TravStack& stack, bool anyHit, bool alphaTest = false)
 {
 #if ZR_TRI_PHASE_WHOLE_LEAF
     // leaves hold at most two triangles (zr_bvh.h): both in one phase
     if (L.triEnd - L.triCur <= 2u)
     {
-        IntersectTri(sc, L.triCur, s.o, s.d, s.tmin, s.tmax, s.mask, s.best, s.filterID, s.ignoreID, alphaTest, &stack);
-        if (L.triCur + 1u < L.triEnd) IntersectTri(sc, L.triCur + 1u, s.o, s.d, s.tmin, s.tmax, s.mask, s.best, s.filterID, s.ignoreID, alphaTest, &stack);
+        IntersectTri<CullNonOpaque>(sc, L.triCur, s.o, s.d, s.tmin, s.tmax, s.mask, s.best, s.filterID, s.ignoreID, alphaTest, &stack);
+        if (L.triCur + 1u < L.triEnd) IntersectTri<CullNonOpaque>(sc, L.triCur + 1u, s.o, s.d, s.tmin, s.tmax, s.mask, s.best, s.filterID, s.ignoreID, alphaTest, &stack);
         L.triCur = L.triEnd;
         if (anyHit && s.best.tri != kInvalidTri) L.done = true;
         else TravPopEnter(sc, s, L, stack);
         return;
     }
 #endif
-    IntersectTri(sc, L.triCur, s.o, s.d, s.tmin, s.tmax, s.mask, s.best, s.filterID, s.ignoreID, alphaTest, &stack);
+    IntersectTri<CullNonOpaque>(sc, L.triCur, s.o, s.d, s.tmin, s.tmax, s.mask, s.best, s.filterID, s.ignoreID, alphaTest, &stack);
     L.triCur++;
     if (anyHit && s.best.tri != kInvalidTri) { L.done = true; L.triCur = L.triEnd; }
     else if (L.triCur == L.triEnd) TravPopEnter(sc, s, L, stack);
@@ -461,7 +467,9 @@ __device__ __forceinline__ void StealPublish(const TravStack& st, uint32_t owner
 }
 #endif
 
-// alphaTest (primary rays): candidates on ZR_INSTANCE_NON_OPAQUE geometry must pass TestOpacity
+// alphaTest (primary rays): candidates on ZR_INSTANCE_NON_OPAQUE geometry must pass TestOpacity.  CullNonOpaque (RAY_FLAG_CULL_NON_OPAQUE):
+// they are not candidates at all -- a separate instantiation, so the kernels that do not cull compile to what they did without it
+template<bool CullNonOpaque = false>
 ZR_HD RawHit TraverseDyn(const SceneView& sc, V3 o, V3 d, float tmin, float tmax, uint32_t mask, const TravStack& stack, bool anyHit,
     bool filterID = false, uint32_t ignoreID = 0, bool alphaTest = false)
 {
@@ -544,7 +552,7 @@ ZR_HD RawHit TraverseDyn(const SceneView& sc, V3 o, V3 d, float tmin, float tmax
         if (ZR_VOTE_WN * __popcll(mNode) >= (int)stack.voteTri * __popcll(mTri)) { pNI++; pNL += __popcll(mNode); } else { pTI++; pTL += __popcll(mTri); }
 #endif
         if (ZR_VOTE_WN * __popcll(mNode) >= (int)stack.voteTri * __popcll(mTri)) { if (atNode) TravNodePhase(sc, s, L, stack, ZR_STEAL_ANYHIT); }
-        else { if (atTri) TravTriPhase(sc, s, L, stack, ZR_STEAL_ANYHIT, alphaTest); }
+        else { if (atTri) TravTriPhase<CullNonOpaque>(sc, s, L, stack, ZR_STEAL_ANYHIT, alphaTest); }
     }
 #if ZR_STEAL
     if (stolen)
@@ -564,7 +572,7 @@ ZR_HD RawHit TraverseDyn(const SceneView& sc, V3 o, V3 d, float tmin, float tmax
     ProfAdd(ZRP_STEALS, pST); ProfAdd(ZRP_STEAL_PAIRS, pSP);
 #endif
 #else
-    while (!TravStep(sc, s, stack, anyHit, alphaTest)) {}
+    while (!TravStep<CullNonOpaque>(sc, s, stack, anyHit, alphaTest)) {}
 #endif
     return s.best;
 }

@@ -958,6 +958,16 @@ ZR_HD F4 CompositePixel(const zr_frame_constants& g, uint16_t mrp, const F4* sky
     color = color / (float)numFramesAccumulated;
     return f4(color, prevOut.w);
 }
+// Compositing.hlsl:74-97, CB_COMPOSIT_FLAGS::INSCATTERING: CompositePixel's result plus the voxel grid's term (half-rounded) for the pixels that get past
+// the early-out of :41-46; z_view = the G-buffer's DEPTH plane at the pixel
+ZR_HD F4 CompositeInscattering(const zr_frame_constants& g, uint16_t mrp, F4 composited, float z_view, const InscatterGridView& grid, uint32_t x, uint32_t y)
+{
+    const uint32_t fl = (uint32_t)zr_fma(zr_div255((float)(mrp & 0xff)), 255.0f, 0.5f);
+    const bool accumulate = g.accumulate && g.camera_static;
+    if ((fl & ZR_GBUF_INVALID) && !accumulate) return composited;
+    const V3 inscattering = InscatteringTerm(g, grid, z_view, x, y);
+    return f4(xyz(composited) + inscattering, composited.w);
+}
 
 // FireflyFilter.hlsl:33-85 (the ReLAX firefly clamp): the centre colour is clamped to the [min, max]-luminance colours of its 3 x 3
 // neighbours that have geometry (depth != FLT_MAX).  `lum` / `col` / `dep` address a tile with a 1-texel border: (tx, ty) = centre.

@@ -275,19 +275,35 @@ void* DirectLighting::GetOutput(SHADER_OUT_RES i) const
 }
 void DirectLighting::Render(Core::CommandList& cl) { ZR_CHECK(zr_pass_render(m_pass, cl.Stream(), &m_ctx->frameConstants, m_ctx->scene, m_ctx->gbuffer)); }
 
-void Sky::Init(FrameContext* ctx, int lutWidth, int lutHeight)
+void Sky::Init(FrameContext* ctx, int lutWidth, int lutHeight, bool doInscattering)
 {
     // the LUT has its own size: InitRenderPass would use the render size
     m_ctx = ctx;
     ZR_CHECK(zr_pass_create(ZR_PASS_SKY, ctx->device, &m_pass));
     ZR_CHECK(zr_pass_init(m_pass, (uint32_t)lutWidth, (uint32_t)lutHeight, 0));
     m_initialized = true;
+    SetInscatteringEnablement(doInscattering);
 }
+void Sky::Apply()
+{
+    if (m_doInscattering) ZR_CHECK(zr_pass_set_inscattering(m_pass, 1, m_numVoxelsX, m_numVoxelsY, m_depthMapExp, m_nearZ, m_farZ));
+}
+void Sky::SetInscatteringEnablement(bool b)
+{
+    if (b == m_doInscattering) return;
+    m_doInscattering = b;
+    if (b) Apply();
+    else ZR_CHECK(zr_pass_set_inscattering(m_pass, 0, 0, 0, 0.0f, 0.0f, 0.0f));
+}
+void Sky::SetVoxelGridSize(uint32_t numVoxelsX, uint32_t numVoxelsY) { m_numVoxelsX = numVoxelsX; m_numVoxelsY = numVoxelsY; Apply(); }
+void Sky::SetDepthMapExp(float exp) { m_depthMapExp = exp; Apply(); }
+void Sky::SetVoxelGridNearZ(float zNear) { m_nearZ = zNear; Apply(); }
+void Sky::SetVoxelGridFarZ(float zFar) { m_farZ = zFar; Apply(); }
 void* Sky::GetOutput(SHADER_OUT_RES i) const
 {
-    if (i != SHADER_OUT_RES::SKY_VIEW_LUT) { std::fprintf(stderr, "Invalid shader output.\n"); std::abort(); }
+    if (i >= SHADER_OUT_RES::COUNT || (i == SHADER_OUT_RES::INSCATTERING && !m_doInscattering)) { std::fprintf(stderr, "Invalid shader output.\n"); std::abort(); }
     void* dev = nullptr; uint32_t w, h, bpp;
-    ZR_CHECK(zr_pass_get_output(m_pass, ZR_OUT_SKY_LUT, &dev, &w, &h, &bpp));
+    ZR_CHECK(zr_pass_get_output(m_pass, i == SHADER_OUT_RES::SKY_VIEW_LUT ? ZR_OUT_SKY_LUT : ZR_OUT_INSCATTERING, &dev, &w, &h, &bpp));
     return dev;
 }
 void Sky::Render(Core::CommandList& cl) { ZR_CHECK(zr_pass_render(m_pass, cl.Stream(), &m_ctx->frameConstants, m_ctx->scene, nullptr)); }
@@ -322,9 +338,15 @@ void SkyDI::Render(Core::CommandList& cl) { ZR_CHECK(zr_pass_render(m_pass, cl.S
 
 void Compositing::Init(FrameContext* ctx) { InitRenderPass(ZR_PASS_COMPOSITING, ctx, 0); ZR_CHECK(zr_params_default(&m_params)); }
 void Compositing::OnWindowResized() { ZR_CHECK(zr_pass_resize(m_pass, m_ctx->renderWidth, m_ctx->renderHeight)); }
+void Compositing::SetGpuDescriptor(SHADER_IN_GPU_DESC i, const Sky& sky)
+{
+    if (i != SHADER_IN_GPU_DESC::INSCATTERING) { std::fprintf(stderr, "Invalid shader input.\n"); std::abort(); }
+    m_inscatteringSky = &sky;
+}
+void Compositing::SetInscatteringEnablement(bool b) { m_inscattering = b; }
 void Compositing::SetGpuDescriptor(SHADER_IN_GPU_DESC i, const void* dev)
 {
-    if (i >= SHADER_IN_GPU_DESC::COUNT) { std::fprintf(stderr, "Invalid shader input.\n"); std::abort(); }
+    if (i >= SHADER_IN_GPU_DESC::INSCATTERING) { std::fprintf(stderr, "Invalid shader input.\n"); std::abort(); }
     m_desc[(int)i] = dev;
     Rebind();
 }
@@ -349,7 +371,19 @@ void* Compositing::GetOutput(SHADER_OUT_RES i) const
     ZR_CHECK(zr_pass_get_output(m_pass, ZR_OUT_FINAL, &dev, &w, &h, &bpp));
     return dev;
 }
-void Compositing::Render(Core::CommandList& cl) { ZR_CHECK(zr_pass_render(m_pass, cl.Stream(), &m_ctx->frameConstants, m_ctx->scene, m_ctx->gbuffer)); }
+void Compositing::Render(Core::CommandList& cl)
+{
+    const Sky* sky = m_inscattering ? m_inscatteringSky : nullptr;
+    if (m_inscattering)
+    {
+        if (!sky) { std::fprintf(stderr, "Gpu descriptor for inscattering texture hasn't been set.\n"); std::abort(); }      // Compositing.cpp:103-108
+        const Sky::VoxelGridDepth d = sky->GetVoxelGridDepth();
+        if (d.nearZ != m_voxelGridNearZ || d.farZ != m_voxelGridFarZ || sky->GetVoxelGridMappingExp() != m_depthMappingExp)
+        { std::fprintf(stderr, "Compositing: voxel grid depth / mapping exponent differ from the sky pass's.\n"); std::abort(); }
+    }
+    ZR_CHECK(zr_pass_bind_inscattering(m_pass, sky ? sky->Pass() : nullptr));
+    ZR_CHECK(zr_pass_render(m_pass, cl.Stream(), &m_ctx->frameConstants, m_ctx->scene, m_ctx->gbuffer));
+}
 
 void TAA::Init(FrameContext* ctx) { InitRenderPass(ZR_PASS_TAA, ctx, 0); ZR_CHECK(zr_params_default(&m_params)); }
 void TAA::OnWindowResized() { ZR_CHECK(zr_pass_resize(m_pass, m_ctx->renderWidth, m_ctx->renderHeight)); }
@@ -848,6 +882,68 @@ int zrh_render_sequence_sky_display(const zr_scene_desc* desc, const zr_frame_co
         if (taaOut && hipMemcpy(taaOut, taa.GetOutput(RenderPass::TAA::SHADER_OUT_RES::OUTPUT_A), (size_t)w * h * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
         if (hipMemcpy(finalOut, ind.GetOutput(RenderPass::IndirectLighting::SHADER_OUT_RES::FINAL), (size_t)w * h * 16, hipMemcpyDeviceToHost) != hipSuccess) return -1;
         if (skyDiOut && hipMemcpy(skyDiOut, sdi.GetOutput(RenderPass::SkyDI::SHADER_OUT_RES::DENOISED), (size_t)w * h * 16, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    }
+    zr_gbuffer_destroy(ctx.gbuffer);
+    zr_scene_destroy(ctx.scene);
+    return 0;
+}
+
+// Renderer > Inscattering on (PathTracer.cpp:26-36, 165-181; PostProcessor.cpp:123-136): Sky (LUT + voxel grid) -> GBuffer -> {SkyDI, Indirect} ->
+// Compositing with the grid's term, through the RenderGraph, n frames.  compositedOut = RGBA32F, gridOut = the numVoxelsX x numVoxelsY x 128
+// R11G11B10 texels of the last frame (voxels 0 x 0 = the reference's 192 x 108)
+int zrh_render_sequence_sky_inscattering(const zr_scene_desc* desc, const zr_frame_constants* cbs, uint32_t n, uint32_t w, uint32_t h, int integrator,
+    uint32_t numVoxelsX, uint32_t numVoxelsY, float* compositedOut, uint32_t* gridOut)
+{
+    RenderPass::FrameContext ctx;
+    ctx.device = 0; ctx.renderWidth = w; ctx.renderHeight = h;
+    ZR_CHECK(zr_scene_create(0, desc, &ctx.scene));
+    ZR_CHECK(zr_gbuffer_create(0, w, h, &ctx.gbuffer));
+    {
+        RenderPass::Sky sky; RenderPass::GBufferRT gb; RenderPass::IndirectLighting ind; RenderPass::SkyDI sdi; RenderPass::Compositing comp;
+        sky.Init(&ctx, 256, 128, false);
+        if (numVoxelsX || numVoxelsY) sky.SetVoxelGridSize(numVoxelsX, numVoxelsY);
+        sky.SetInscatteringEnablement(true);
+        gb.Init(&ctx); ind.Init(&ctx, (RenderPass::IndirectLighting::INTEGRATOR)integrator); sdi.Init(&ctx); comp.Init(&ctx);
+        comp.SetGpuDescriptor(RenderPass::Compositing::SHADER_IN_GPU_DESC::SKY_DI, sdi.GetOutput(RenderPass::SkyDI::SHADER_OUT_RES::DENOISED));
+        comp.SetGpuDescriptor(RenderPass::Compositing::SHADER_IN_GPU_DESC::INDIRECT, ind.GetOutput(RenderPass::IndirectLighting::SHADER_OUT_RES::FINAL));
+        // PostProcessor.cpp:123-136
+        comp.SetInscatteringEnablement(sky.IsInscatteringEnabled());
+        comp.SetGpuDescriptor(RenderPass::Compositing::SHADER_IN_GPU_DESC::INSCATTERING, sky);
+        comp.SetVoxelGridDepth(sky.GetVoxelGridDepth().nearZ, sky.GetVoxelGridDepth().farZ);
+        comp.SetVoxelGridMappingExp(sky.GetVoxelGridMappingExp());
+        Core::RenderGraph g;
+        enum : uint64_t { R_LUT = 1, R_GRID, R_GBUF, R_IND, R_SDI, R_COMP };
+        for (uint32_t f = 0; f < n; f++)
+        {
+            ctx.frameConstants = cbs[f];
+            g.BeginFrame();
+            auto hSky = g.RegisterRenderPass("Sky", Core::RENDER_NODE_TYPE::COMPUTE, Core::MakeDelegate(&sky, &RenderPass::Sky::Render));
+            auto hGB = g.RegisterRenderPass("GBuffer", Core::RENDER_NODE_TYPE::COMPUTE, Core::MakeDelegate(&gb, &RenderPass::GBufferRT::Render));
+            auto hSdi = g.RegisterRenderPass("SkyDI", Core::RENDER_NODE_TYPE::COMPUTE, Core::MakeDelegate(&sdi, &RenderPass::SkyDI::Render));
+            auto hInd = g.RegisterRenderPass("Indirect", Core::RENDER_NODE_TYPE::COMPUTE, Core::MakeDelegate(&ind, &RenderPass::IndirectLighting::Render));
+            auto hComp = g.RegisterRenderPass("Compositing", Core::RENDER_NODE_TYPE::COMPUTE, Core::MakeDelegate(&comp, &RenderPass::Compositing::Render));
+            g.RegisterResource(sky.GetOutput(RenderPass::Sky::SHADER_OUT_RES::SKY_VIEW_LUT), R_LUT);
+            g.RegisterResource(sky.GetOutput(RenderPass::Sky::SHADER_OUT_RES::INSCATTERING), R_GRID);
+            g.RegisterResource(nullptr, R_GBUF);
+            g.RegisterResource(ind.GetOutput(RenderPass::IndirectLighting::SHADER_OUT_RES::FINAL), R_IND);
+            g.RegisterResource(sdi.GetOutput(RenderPass::SkyDI::SHADER_OUT_RES::DENOISED), R_SDI);
+            g.RegisterResource(comp.GetOutput(RenderPass::Compositing::SHADER_OUT_RES::COMPOSITED), R_COMP);
+            g.MoveToPostRegister();
+            g.AddOutput(hSky, R_LUT, Core::STATE_UNORDERED_ACCESS); g.AddOutput(hSky, R_GRID, Core::STATE_UNORDERED_ACCESS);
+            g.AddOutput(hGB, R_GBUF, Core::STATE_UNORDERED_ACCESS);
+            g.AddInput(hSdi, R_LUT, Core::STATE_SHADER_READ); g.AddInput(hSdi, R_GBUF, Core::STATE_SHADER_READ); g.AddOutput(hSdi, R_SDI, Core::STATE_UNORDERED_ACCESS);
+            g.AddInput(hInd, R_LUT, Core::STATE_SHADER_READ); g.AddInput(hInd, R_GBUF, Core::STATE_SHADER_READ); g.AddOutput(hInd, R_IND, Core::STATE_UNORDERED_ACCESS);
+            g.AddInput(hComp, R_SDI, Core::STATE_SHADER_READ); g.AddInput(hComp, R_IND, Core::STATE_SHADER_READ); g.AddInput(hComp, R_GBUF, Core::STATE_SHADER_READ);
+            g.AddInput(hComp, R_GRID, Core::STATE_SHADER_READ); g.AddInput(hComp, R_LUT, Core::STATE_SHADER_READ);
+            g.AddOutput(hComp, R_COMP, Core::STATE_UNORDERED_ACCESS);
+            Support::TaskSet ts;
+            g.Build(ts);
+            ts.Run(true);
+            g.WaitForFrame();
+        }
+        const RenderPass::Sky::VoxelGridDim dim = sky.GetVoxelGridDim();
+        if (compositedOut && hipMemcpy(compositedOut, comp.GetOutput(RenderPass::Compositing::SHADER_OUT_RES::COMPOSITED), (size_t)w * h * 16, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        if (gridOut && hipMemcpy(gridOut, sky.GetOutput(RenderPass::Sky::SHADER_OUT_RES::INSCATTERING), (size_t)dim.x * dim.y * dim.z * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     }
     zr_gbuffer_destroy(ctx.gbuffer);
     zr_scene_destroy(ctx.scene);

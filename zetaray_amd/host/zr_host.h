@@ -240,13 +240,32 @@ namespace RenderPass {
         zr_params m_params{};
     };
 
-    // RP/Sky/Sky.h:12-112: sky-view LUT (the in-scattering voxel grid is out of scope)
+    // RP/Sky/Sky.h:12-112: sky-view LUT + the inscattering voxel grid (zr_pass_set_inscattering)
     struct Sky final : public RenderPassBase
     {
-        enum class SHADER_OUT_RES { SKY_VIEW_LUT, COUNT };
-        void Init(FrameContext* ctx, int lutWidth, int lutHeight);
+        enum class SHADER_OUT_RES { SKY_VIEW_LUT, INSCATTERING, COUNT };
+        struct VoxelGridDim { uint32_t x, y, z; };
+        struct VoxelGridDepth { float nearZ, farZ; };
+        void Init(FrameContext* ctx, int lutWidth, int lutHeight, bool doInscattering = false);
+        bool IsInscatteringEnabled() const { return m_doInscattering; }
+        void SetInscatteringEnablement(bool b);                  // allocates / frees the grid (Sky.cpp:69-117)
+        // voxel counts of the grid the next enablement allocates (cbSky::NumVoxelsX / Y; the reference keeps its defaults, 192 x 108)
+        void SetVoxelGridSize(uint32_t numVoxelsX, uint32_t numVoxelsY);
+        VoxelGridDim GetVoxelGridDim() const { return {m_numVoxelsX, m_numVoxelsY, 128u}; }     // z = INSCATTERING_THREAD_GROUP_SIZE_X
+        VoxelGridDepth GetVoxelGridDepth() const { return {m_nearZ, m_farZ}; }
+        float GetVoxelGridMappingExp() const { return m_depthMapExp; }
+        // the "Inscattering" UI parameters (Sky.cpp:210-223: DepthMapExpCallback, VoxelGridNearZCallback, VoxelGridFarZCallback)
+        void SetDepthMapExp(float exp);                          // 1..5
+        void SetVoxelGridNearZ(float zNear);                     // 0 <= near < far
+        void SetVoxelGridFarZ(float zFar);
         void* GetOutput(SHADER_OUT_RES i) const;
-        void Render(Core::CommandList& cmdList);
+        void Render(Core::CommandList& cmdList);                  // the LUT, then the grid when enabled (Sky.cpp:120-164)
+        zr_pass* Pass() const { return m_pass; }                 // (what Compositing binds: the grid moves when it is reallocated)
+    private:
+        void Apply();
+        bool m_doInscattering = false;
+        uint32_t m_numVoxelsX = ZR_INSCATTERING_VOXELS_X, m_numVoxelsY = ZR_INSCATTERING_VOXELS_Y;
+        float m_depthMapExp = 2.0f, m_nearZ = 0.5f, m_farZ = 30.0f;       // Sky.h DefaultParamVals
     };
 
     // RP/DirectLighting/Sky/SkyDI.h:19-137: ReSTIR DI for sun + sky
@@ -272,11 +291,18 @@ namespace RenderPass {
     // RP/Compositing/Compositing.h:19-115: (sky DI | emissive DI) + indirect, optional firefly filter
     struct Compositing final : public RenderPassBase
     {
-        enum class SHADER_IN_GPU_DESC { SKY_DI, EMISSIVE_DI, INDIRECT, COUNT };
+        enum class SHADER_IN_GPU_DESC { SKY_DI, EMISSIVE_DI, INDIRECT, INSCATTERING, COUNT };
         enum class SHADER_OUT_RES { COMPOSITED, COUNT };
         void Init(FrameContext* ctx);
         void OnWindowResized();
-        void SetGpuDescriptor(SHADER_IN_GPU_DESC i, const void* devicePlane);       // RGBA32F FINAL plane of the producing pass
+        void SetGpuDescriptor(SHADER_IN_GPU_DESC i, const void* devicePlane);       // RGBA32F FINAL plane of the producing pass (not INSCATTERING)
+        // SHADER_IN_GPU_DESC::INSCATTERING: the library binds the sky pass, not its grid (re-enabling the sky pass reallocates the grid)
+        void SetGpuDescriptor(SHADER_IN_GPU_DESC i, const Sky& sky);
+        // CB_COMPOSIT_FLAGS::INSCATTERING + SetVoxelGridDepth / SetVoxelGridMappingExp (Compositing.h:48-50).  The library reads the depth range and the
+        // mapping exponent from the bound sky pass; PostProcessor.cpp:123-136 copies them from there, and Render checks that they agree.
+        void SetInscatteringEnablement(bool b);
+        void SetVoxelGridDepth(float zNear, float zFar) { m_voxelGridNearZ = zNear; m_voxelGridFarZ = zFar; }
+        void SetVoxelGridMappingExp(float exp) { m_depthMappingExp = exp; }
         void SetFireflyFilterEnablement(bool b);
         // "Direct" / "Indirect" toggles of the settings UI (Compositing.cpp:166-179: they clear the CB_COMPOSIT_FLAGS bit of the input; the descriptor stays bound)
         void SetDirectEnablement(bool b);
@@ -286,8 +312,10 @@ namespace RenderPass {
     private:
         void Rebind();
         zr_params m_params{};
-        const void* m_desc[3] = {nullptr, nullptr, nullptr};      // by SHADER_IN_GPU_DESC
+        const void* m_desc[3] = {nullptr, nullptr, nullptr};      // by SHADER_IN_GPU_DESC (SKY_DI, EMISSIVE_DI, INDIRECT)
         bool m_direct = true, m_indirect = true;
+        const Sky* m_inscatteringSky = nullptr; bool m_inscattering = false;
+        float m_voxelGridNearZ = 0.5f, m_voxelGridFarZ = 30.0f, m_depthMappingExp = 2.0f;
     };
 
     // RP/TAA/TAA.h:20-80: temporal anti-aliasing of the composited image

@@ -160,6 +160,13 @@ def set_post_defaults(p):
 
 
 COMPOSIT_FIREFLY_FILTER = 1 << 10
+# inscattering voxel grid of the sky pass (zr_pass_set_inscattering; Sky.h DefaultParamVals): voxels x / y, slices, depth mapping exponent, near / far z
+OUT_INSCATTERING = 49
+INSCATTERING_VOXELS = (192, 108)
+INSCATTERING_SLICES = 128
+INSCATTERING_DEPTH_MAP_EXP = 2.0
+INSCATTERING_NEAR_Z = 0.5
+INSCATTERING_FAR_Z = 30.0
 DI_STOCHASTIC_SPATIAL = 1 << 8
 DI_EXTRA_DISOCCLUSION_SAMPLING = 1 << 9
 DI_HALF_VECTOR_COPY_SHIFT = 1 << 11      # the reference's compile-time USE_HALF_VECTOR_COPY_SHIFT (Emissive/Params.hlsli:12) as a run-time flag of the emissive DI pass
