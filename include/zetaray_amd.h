@@ -554,6 +554,16 @@ int zr_pass_destroy(zr_pass* pass);
 
 /* ---- ray-query microbenchmark surface (bench.py roofline leg / parity tests of traversal) ---- */
 /* rays: n x 8 floats (ox,oy,oz,tmin,dx,dy,dz,tmax) device pointer; hits: n x 4 uint32 (t bits, u bits, v bits, tri) */
+/* Rules of both queries (zr_intersect.h; tests/test_ray_queries_cpu.py and tests/test_ray_queries_gpu.py test both sides of each).  They are
+ * exact for rays within the condition stated in zr_intersect.h; outside it a query may miss a triangle that zr_ray_tri accepts (closest hit may
+ * return a farther triangle or a miss, any hit may report unoccluded), but never reports a hit or an occlusion that zr_ray_tri does not accept.
+ *   - a triangle is hit iff zr_ray_tri accepts it: tmin < t < tmax, open at both ends (tmax = t misses, tmax = the next float above t hits);
+ *   - tmin may be negative or -inf: hits behind the origin count, and the closest hit is then the most negative t;
+ *   - tmax <= tmin, a zero direction, or a NaN in any of the 8 components: nothing is hit;
+ *   - directions need not be normalised; t is in units of |d|;
+ *   - the closest hit is the smallest t, equal t going to the smaller global triangle index; a miss is (0, 0, 0, 0xffffffff);
+ *   - mask selects triangles whose instance_mask shares a bit with it (mask 0 hits nothing).
+ * Within that condition the answers do not depend on the acceptance structure (tree, build path, refit); outside it they may. */
 int zr_trace_closest(const zr_scene* scene, void* hip_stream, const float* d_rays, uint32_t n, uint32_t mask,
                      uint32_t* d_hits);
 int zr_trace_any(const zr_scene* scene, void* hip_stream, const float* d_rays, uint32_t n, uint32_t mask,

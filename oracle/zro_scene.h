@@ -181,13 +181,8 @@ struct Scene
     // ---- oracle BVH: median split on the largest centroid axis, leaves of <= 4 triangles ----
     void TriBounds(const WorldTri& t, float bmin[3], float bmax[3]) const
     {
-        for (int r = 0; r < 3; r++)
-        {
-            float a = t.v0[r], b = t.v0[r] + t.e1[r], c = t.v0[r] + t.e2[r];
-            // e1 = v1 - v0 was rounded, so v0 + e1 may differ from v1 by an ulp: pad the box by one ulp each side
-            float lo = zr_min(a, zr_min(b, c)), hi = zr_max(a, zr_max(b, c));
-            bmin[r] = Math::PrevFloat32(lo); bmax[r] = Math::NextFloat32(hi);
-        }
+        // padded so that the box test never rejects a triangle zr_ray_tri accepts (include/zr_intersect.h)
+        zr_tri_bounds(t.v0, t.e1, t.e2, bmin, bmax);
     }
     uint32_t BuildNode(uint32_t first, uint32_t count, std::vector<float>& cent)
     {

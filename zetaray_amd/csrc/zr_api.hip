@@ -1037,7 +1037,7 @@ __global__ void __launch_bounds__(256) k_install_topology(Bvh4Node* nodes, const
         tris[i] = t;
     }
 }
-// bounds of leaf `c` (1-ulp padded like the builder's, since v0 + e1 is a rounded v1)
+// bounds of leaf `c`: the union of its triangles' padded boxes (zr_intersect.h zr_tri_bounds, like the builder's)
 __device__ __forceinline__ void LeafBounds(const BvhTri* tris, uint32_t c, float lo[3], float hi[3])
 {
     const uint32_t first = (c & 0x7fffffffu) >> 3, count = (c & 7u) + 1u;
@@ -1045,11 +1045,9 @@ __device__ __forceinline__ void LeafBounds(const BvhTri* tris, uint32_t c, float
     for (uint32_t i = first; i < first + count; i++)
     {
         const BvhTri t = tris[i];
-        for (int r = 0; r < 3; r++)
-        {
-            const float a = t.v0[r], b = t.v0[r] + t.e1[r], cc = t.v0[r] + t.e2[r];
-            lo[r] = fminf(lo[r], zr::PrevFloat32(fminf(a, fminf(b, cc)))); hi[r] = fmaxf(hi[r], zr::NextFloat32(fmaxf(a, fmaxf(b, cc))));
-        }
+        float tlo[3], thi[3];
+        zr_tri_bounds(t.v0, t.e1, t.e2, tlo, thi);
+        for (int r = 0; r < 3; r++) { lo[r] = fminf(lo[r], tlo[r]); hi[r] = fmaxf(hi[r], thi[r]); }
     }
 }
 // one level: node = levelNodes[i]; its inner children were finished by the previous (deeper) launch.  Quantisation = BvhBuilder::Collapse:

@@ -70,7 +70,7 @@ public:
     // false (ZR_BVH_COLLAPSE=greedy): rounds 1 - 5's rule -- open the inner child of largest area until there are four.  The greedy rule leaves the bottom of the
     // tree half empty (a 4-triangle range is a node with two 2-triangle leaves and two empty slots: 99.7 k nodes, 2.9 children per node on the 380 k-triangle
     // atrium); measured per ray by tools/bvh_quality.py and in the kernels by the section profiler.  collapseNodeCost_: one node visit (4 box
-    // tests, sort, pushes: ~190 VALU instructions) in units of one triangle test (~65).  Results never depend on the tree (zr_intersect.h).
+    // tests, sort, pushes: ~190 VALU instructions) in units of one triangle test (~65).  Results do not depend on the tree (within the condition of zr_intersect.h).
     bool optimalCollapse_ = true; float collapseNodeCost_ = 3.0f;
     uint32_t medianBelow_ = 0;      // (experiment, ZR_BVH_SPLIT=median | N: ranges of fewer than N triangles are split at the object median of the widest centroid axis)
 
@@ -112,11 +112,11 @@ public:
         for (uint32_t i = 0; i < N; i++)
         {
             const BvhTri& t = soup[i];
+            zr_tri_bounds(t.v0, t.e1, t.e2, bt_[i].bmin, bt_[i].bmax);      // padded (zr_intersect.h: what keeps the box tests conservative)
             for (int r = 0; r < 3; r++)
             {
                 float a = t.v0[r], b = t.v0[r] + t.e1[r], c = t.v0[r] + t.e2[r];
                 float lo = std::min(a, std::min(b, c)), hi = std::max(a, std::max(b, c));
-                bt_[i].bmin[r] = PrevF(lo); bt_[i].bmax[r] = NextF(hi);   // one-ulp pad: v0 + e1 is a rounded v1
                 bt_[i].cent[r] = 0.5f * (lo + hi);
             }
             bt_[i].gidx = i;

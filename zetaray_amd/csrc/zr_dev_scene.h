@@ -175,8 +175,9 @@ ZR_HD void IntersectLeaf(const SceneView& sc, uint32_t first, uint32_t count, V3
 // Stack-based BVH4 traversal, written as an explicit state machine so that a kernel can either run it to completion
 // (Traverse, used inline by the ReSTIR kernels) or advance many rays one step at a time and refill finished lanes
 // (k_trace).  `stack` is this lane's private stack of (child, entry distance) pairs.  Children
-// are visited near-to-far and a popped child whose entry distance lies beyond the current closest hit is skipped; none
-// of that changes the result (closest hit + index tie-break / any hit are order independent, zr_intersect.h).
+// are visited near-to-far and a popped child whose entry distance lies beyond the current closest hit (widened like the box
+// test's exit, zr_widen_far) is skipped; none of that changes the result (closest hit + index tie-break / any hit are order
+// independent; tree independent within the condition of zr_intersect.h, whose padded triangle boxes every builder uses).
 static constexpr int kTravStack = 64;                     // entries; the host checks the built tree against it
 static constexpr int kTravStackWords = 2 * kTravStack;
 #ifndef ZR_TRI_PHASE_WHOLE_LEAF
@@ -301,7 +302,7 @@ ZR_HD bool TravPop(TravState& s, const TravStack& stack)
         uint32_t c; float t;
         StackRead(stack, s.sp, c, t);
         // same condition as re-running zr_ray_box with the current best t
-        if (t <= s.best.t * 1.0000003576278687f) { s.cur = c; return true; }
+        if (t <= zr_widen_far(s.best.t)) { s.cur = c; return true; }
     }
     return false;
 }
@@ -337,7 +338,7 @@ ZR_HD uint32_t TravNode(const SceneView& sc, TravState& s, const TravStack& stac
     const float sx = zr_asfloat((n.exps & 0xffu) << 23), sy = zr_asfloat(((n.exps >> 8) & 0xffu) << 23), sz = zr_asfloat(((n.exps >> 16) & 0xffu) << 23);
     uint32_t c0 = n.child[0], c1 = n.child[1], c2 = n.child[2], c3 = n.child[3];
     float t0, t1, t2, t3;
-    // cull against the current best t (inclusive + widened, so equal-t candidates for the tie-break are visited)
+    // cull against the current best t (inclusive + widened in either sign, so equal-t candidates for the tie-break are visited)
 #define ZR_Q(w, k) ((float)(((w) >> (8 * (k))) & 0xffu))
     // (all four slots are tested unconditionally -- an empty slot decodes to a harmless box -- to keep the phase branch-free.)
     // Per axis the ray's direction sign says which quantised plane is the entry and which the exit, so the words are swapped once per node
@@ -351,7 +352,7 @@ ZR_HD uint32_t TravNode(const SceneView& sc, TravState& s, const TravStack& stac
         const float nx = (zr_fma(ZR_Q(qnx, k), sx, n.ox) - s.o.x) * s.idx, ny = (zr_fma(ZR_Q(qny, k), sy, n.oy) - s.o.y) * s.idy, nz = (zr_fma(ZR_Q(qnz, k), sz, n.oz) - s.o.z) * s.idz; \
         const float fx = (zr_fma(ZR_Q(qfx, k), sx, n.ox) - s.o.x) * s.idx, fy = (zr_fma(ZR_Q(qfy, k), sy, n.oy) - s.o.y) * s.idy, fz = (zr_fma(ZR_Q(qfz, k), sz, n.oz) - s.o.z) * s.idz; \
         const float tn = __builtin_fmaxf(__builtin_fmaxf(nx, ny), __builtin_fmaxf(nz, s.tmin)); \
-        const float tf = __builtin_fminf(__builtin_fminf(fx, fy), __builtin_fminf(fz, tfmax)) * 1.0000003576278687f; \
+        const float tf = zr_widen_far(__builtin_fminf(__builtin_fminf(fx, fy), __builtin_fminf(fz, tfmax))); \
         const bool ok = (tn <= tf) & (c##k != kEmptyChild); t##k = ok ? tn : inf; c##k = ok ? c##k : kEmptyChild; }
     ZR_TRAV_BOX(0) ZR_TRAV_BOX(1) ZR_TRAV_BOX(2) ZR_TRAV_BOX(3)
 #undef ZR_TRAV_BOX
@@ -534,7 +535,7 @@ ZR_HD RawHit TraverseDyn(const SceneView& sc, V3 o, V3 d, float tmin, float tmax
                         const ZR_LDS_AS StackEntry* e = stack.lds + (uint32_t)(dsp - 1) * stack.stride + (src - (int)lane);
                         const uint32_t c = e->child; const float et = e->t;
                         L.triCur = 0; L.triEnd = 0;
-                        if (et <= bt * 1.0000003576278687f) { L.done = false; TravEnter(sc, s, L, c); }
+                        if (et <= zr_widen_far(bt)) { L.done = false; TravEnter(sc, s, L, c); }
                     }
                     if (give) s.sp--;
                     // any-hit rays: a piece that hit ends the whole ray
