@@ -91,7 +91,7 @@ typedef enum zr_pass_kind {
        the ISO-100 exposure.  zr_params.ae_*.  Outputs ZR_OUT_EXPOSURE (persistent across frames), ZR_OUT_AE_HISTOGRAM.
        The pass size is the render size; zr_pass_render needs no gbuffer (pass NULL). */
     ZR_PASS_AUTO_EXPOSURE = 8,
-    /* DisplayPass (RP/Display/Display.hlsl:41-77, DisplayOption::DEFAULT; Tonemap.hlsli): exposure x tone mapper over the image bound
+    /* DisplayPass (RP/Display/Display.hlsl:41-77, DisplayOption::DEFAULT; Tonemap.hlsli; the G-buffer debug views: zr_pass_set_display_option): exposure x tone mapper over the image bound
        with ZR_IN_POST_SIGNAL_*, point-sampled from render to display resolution.  The pass size is the DISPLAY size; the input has
        cb.render_width x render_height texels.  zr_params.display_*; ZR_IN_DISPLAY_EXPOSURE = ZR_OUT_EXPOSURE of the auto-exposure pass;
        the NEUTRAL tone mapper needs zr_pass_set_tonemap_lut.  Outputs ZR_OUT_DISPLAY (the pixel shader's float4) and
@@ -503,6 +503,58 @@ int zr_pass_bind_inscattering(zr_pass* compositing, const zr_pass* sky);
 /* ZR_PASS_DISPLAY: the Tony McMapface LUT of the NEUTRAL tone mapper, dim^3 R9G9B9E5_SHAREDEXP texels on the host (the payload of
    Assets/LUT/tony_mc_mapface.dds, 48^3; shipped as zetaray_amd/assets/tony_mc_mapface_rgb9e5.bin).  Display.cpp:196-205. */
 int zr_pass_set_tonemap_lut(zr_pass* pass, const uint32_t* rgb9e5, uint32_t dim);
+/* ZR_PASS_DISPLAY: DisplayOption (Display_Common.h:6-19), the reference's order.  DEFAULT is the tone-mapped image; the others are the
+   G-buffer debug views of Display.hlsl:77-168, drawn from the gbuffer passed to zr_pass_render (its current plane set; the render size, tile
+   origin (0, 0), else ZR_ERR_INVALID_ARG).  The planes are point-sampled at the display UV like the input image; the COAT views load the
+   coat plane at the display pixel itself (g_coat[psin.PosSS.xy]), 0 outside the plane.  A miss (depth FLT_MAX) is float4(0) in every view,
+   sRGB8 word 0.  BASE_COLOR: .rgb; NORMAL: DecodeUnitVector * 0.5 + 0.5; METALNESS_ROUGHNESS: (metallic flag, roughness, 0);
+   COAT_WEIGHT / COAT_COLOR: the coat's weight / colour where the coated flag is set, else 0; ROUGHNESS_TH: (roughness >= roughness_th) x
+   (0.26, 0.014, 0.021); EMISSIVE: the emissive colour where the emissive flag is set, else base colour x 0.005; TRANSMISSION:
+   (transmissive, !transmissive, 0); DEPTH: cb.camera_near / depth.  Every view overwrites the tone-mapped colour, so the tone mapper and
+   exposure do not change it (their inputs are still required as for DEFAULT).  ZR_OUT_DISPLAY_SRGB8 is the same encode as DEFAULT's. */
+enum zr_display_option
+{
+    ZR_DISPLAY_DEFAULT = 0,
+    ZR_DISPLAY_BASE_COLOR,
+    ZR_DISPLAY_NORMAL,
+    ZR_DISPLAY_METALNESS_ROUGHNESS,
+    ZR_DISPLAY_COAT_WEIGHT,
+    ZR_DISPLAY_COAT_COLOR,
+    ZR_DISPLAY_ROUGHNESS_TH,
+    ZR_DISPLAY_EMISSIVE,
+    ZR_DISPLAY_TRANSMISSION,
+    ZR_DISPLAY_DEPTH,
+    ZR_DISPLAY_COUNT
+};
+/* ZR_PASS_DISPLAY: the view and cbDisplayPass::RoughnessTh of ROUGHNESS_TH (DisplayPass defaults DEFAULT and 1.0, Display.cpp:69-73).
+   ZR_ERR_INVALID_ARG for another pass kind, an unknown option or a NaN threshold. */
+int zr_pass_set_display_option(zr_pass* pass, int option, float roughness_th);
+/* ZR_PASS_DISPLAY: outline the picked instances (DisplayPass::DrawPicked, Display.cpp:293-400; DrawPicked.hlsl, Sobel.hlsl).  mesh_idx: n instance indices
+   as zr_pass_read_pick returns them, kept until the next call; n = 0 clears.  They are checked against the scene passed to zr_pass_render
+   (ZR_ERR_INVALID_ARG for an index that is not one of its instances).  After the display kernel, on the same stream, for each pick in order:
+   1. WVP = mul(W, VP): W = the instance's instance_to_world of the latest zr_scene_create / zr_scene_update_instances* as the reference's float4x3
+      (row-vector convention: W[i][j] = instance_to_world[4 j + i] for j < 3, W[i][3] = (i == 3)); VP = cb.curr_view_proj read row-major in the
+      same convention (the frame constants' CurrViewProj = mul(view, proj), DefaultRenderer.cpp:72-79); WVP[i][j] = ((W[i][0] VP[0][j] +
+      W[i][1] VP[1][j]) + W[i][2] VP[2][j]) + W[i][3] VP[3][j] in fp32, no fma.
+   2. The mask, R8 at render size (ZR_OUT_PICK_MASK, 255 covered / 0), redrawn for the pick: the instance's triangles (object-space vertices
+      through base_vtx_offset / base_idx_offset, the instance's triangle count) with no culling and no depth test.  The raster contract:
+      - transform: clip_j = ((x WVP[0][j] + y WVP[1][j]) + z WVP[2][j]) + WVP[3][j], fp32, no fma;
+      - clipping: Sutherland-Hodgman of the triangle against z >= 0, w - z >= 0, x + 16 w >= 0, 16 w - x >= 0, y + 16 w >= 0, 16 w - y >= 0 in
+        this order (a vertex is kept when its distance is >= 0; a crossing edge a -> b adds a + t (b - a), t = d_a / (d_a - d_b)); the 16 w guard
+        band only moves edges outside the viewport; a polygon with a vertex of w <= 0 is dropped; the polygon is fanned from its first vertex;
+      - viewport (the display size dw x dh, Display.cpp:233-235): sx = (x / w * 0.5 + 0.5) * dw, sy = (0.5 - y / w * 0.5) * dh;
+      - snapping: rint(s * 256), 16.8 fixed point; pixel centres at (px + 0.5, py + 0.5);
+      - coverage: exact int64 edge functions E_ab(p) = (b.x - a.x)(p.y - a.y) - (b.y - a.y)(p.x - a.x) on the triangle ordered so that
+        E_ab(c) > 0 (zero-area triangles cover nothing); p is covered when every edge has E > 0, or E = 0 on a top-left edge (d = b - a:
+        d.y < 0, or d.y = 0 and d.x > 0 -- D3D's top-left rule in y-down screen space);
+      - only pixels inside the render size are written.  The mask is an OR of coverage: it does not depend on the order of triangles, threads or waves.
+   3. The outline (Sobel.hlsl): at every display pixel whose 3 x 3 neighbourhood, within the render size, holds a mask pixel and whose Sobel gradient of the
+      mask (out-of-range loads 0) is not zero, ZR_OUT_DISPLAY = (0.913098693, 0.332451582, 0.048171822, 1) and ZR_OUT_DISPLAY_SRGB8 its sRGB8 encode;
+      other pixels are left as they are.  Several picks give the union of the per-instance outlines.
+   The display and render sizes must be <= 16384.  Not implemented: the wireframe fill mode (DRAW_PICKED_WIREFRAME). */
+int zr_pass_set_picked_instances(zr_pass* pass, const uint32_t* mesh_idx, uint32_t n);
+/* ZR_PASS_DISPLAY: the mask of the last pick of the last render, R8 1 B, render size (Display.cpp m_pickMask) */
+#define ZR_OUT_PICK_MASK 50
 /* ray counters accumulated since the last call (device -> host copy; synchronises the stream) */
 int zr_pass_read_counters(zr_pass* pass, void* hip_stream, zr_counters* out, int reset);
 /* ReSTIR PT: GPU time per 32 x 32-pixel cell of the pass's planes ((w + 31) / 32 + 1 by (h + 31) / 32 + 1 cells, cell (0, 0) at the plane origin): the summed

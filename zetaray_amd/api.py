@@ -59,6 +59,7 @@ EXPORTS = [
     "zr_pass_set_tonemap_lut", "zr_pass_halo_pack_all", "zr_pass_halo_unpack_all",
     "zr_pass_set_frame_overlap", "zr_pass_frame_overlap_stream", "zr_device_synchronize",
     "zr_pass_set_inscattering", "zr_pass_bind_inscattering",
+    "zr_pass_set_display_option", "zr_pass_set_picked_instances",
 ]
 STAGE_TEMPORAL, STAGE_SPATIAL, STAGE_ALL = 1, 2, 3
 STAGE_SPATIAL2 = 4          # ReSTIR PT, num_spatial_passes = 2 on tiles: the second round, behind one more HALO_POST_TEMPORAL exchange
@@ -129,6 +130,8 @@ def lib():
         L.zr_pass_set_inscattering.argtypes = [vp, i32, u32, u32, C.c_float, C.c_float, C.c_float]
         L.zr_pass_bind_inscattering.argtypes = [vp, vp]
         L.zr_pass_set_tonemap_lut.argtypes = [vp, vp, u32]
+        L.zr_pass_set_display_option.argtypes = [vp, i32, C.c_float]
+        L.zr_pass_set_picked_instances.argtypes = [vp, vp, u32]
         L.zr_pass_halo_pack_all.argtypes = [vp, vp, vp, i32, vp, u32, vp, C.c_size_t]
         L.zr_pass_halo_unpack_all.argtypes = [vp, vp, vp, i32, vp, u32, vp, C.c_size_t]
         L.zr_pass_set_owned_rect.argtypes = [vp, u32, u32, u32, u32]
@@ -385,6 +388,16 @@ class Pass:
         dim = int(round(lut.size ** (1.0 / 3.0)))
         _check(lib().zr_pass_set_tonemap_lut(self.h, lut.ctypes.data, dim))
 
+    # DISPLAY pass: DisplayPass's "Display" option and "Roughness Th." (zetaray_amd.h zr_pass_set_display_option); a view other than
+    # wire.DISPLAY_DEFAULT makes render() read the gbuffer passed to it
+    def set_display_option(self, option, roughness_th=wire.DISPLAY_ROUGHNESS_TH_DEFAULT):
+        _check(lib().zr_pass_set_display_option(self.h, int(option), float(roughness_th)))
+
+    # DISPLAY pass: outline these instances (zr_pass_read_pick values) after the display kernel; [] clears (zetaray_amd.h zr_pass_set_picked_instances)
+    def set_picked_instances(self, mesh_idx):
+        a = np.ascontiguousarray(mesh_idx, np.uint32).reshape(-1)
+        _check(lib().zr_pass_set_picked_instances(self.h, a.ctypes.data if a.size else None, a.size))
+
     def download_raw(self, which, dtype, shape, stream=None):
         out = np.zeros(shape, dtype)
         _check(lib().zr_pass_download_output(self.h, which, stream, out.ctypes.data, out.nbytes))
@@ -435,6 +448,11 @@ class Pass:
     def download_plane(self, name, stream=None):
         """ReSTIR PT reservoir / target / neighbour planes (see RPT_OUTPUTS); "inscattering" on a SKY pass: the voxel grid as
         (128, voxels_y, voxels_x) uint32 R11G11B10_FLOAT texels."""
+        if name == "pick_mask":
+            _, w, h, _ = self.output_ptr(wire.OUT_PICK_MASK)
+            out = np.zeros((h, w), np.uint8)
+            _check(lib().zr_pass_download_output(self.h, wire.OUT_PICK_MASK, stream, out.ctypes.data, out.nbytes))
+            return out
         if name == "inscattering":
             _, w, h, _ = self.output_ptr(wire.OUT_INSCATTERING)
             out = np.zeros((wire.INSCATTERING_SLICES, h // wire.INSCATTERING_SLICES, w), np.uint32)

@@ -63,6 +63,9 @@ static int RequireDevice(int device)
 #include "zr_bvh_device.h"
 namespace zr { int DeviceProbeRun(int device, float min_ms, zr_device_probe* out, std::string& err); }      // zr_tu_probe.hip
 namespace zr { hipError_t LaunchInscattering(hipStream_t s, const SceneView& sc, const zr_frame_constants& g, const InscatterParams& c, uint32_t* grid); }   // zr_tu_sky.hip
+namespace zr { hipError_t LaunchDisplayView(hipStream_t s, int option, const GBuf& gb, uint32_t dw, uint32_t dh, float cameraNear, float roughnessTh, F4* out, uint32_t* outSrgb); }   // zr_tu_display.hip
+namespace zr { hipError_t LaunchPickOutline(hipStream_t s, const zr_vertex* vertices, const uint32_t* indices, const zr_mesh_instance* instances, uint32_t inst, uint32_t numTris,
+    const post::PickWvp& m, uint32_t dw, uint32_t dh, uint32_t rw, uint32_t rh, int4* tris, uint32_t* count, uint8_t* mask, F4* out, uint32_t* outSrgb); }   // zr_tu_display.hip
 // the ReSTIR PT kernels are compiled in zr_tu_rpt_[a-i].hip (see zr_kernels.h)
 ZR_RPT_GROUPS_PRODUCT(extern template)
 #ifdef ZR_EXPERIMENTS
@@ -883,6 +886,9 @@ struct zr_pass
     const uint16_t* postIn16 = nullptr; const F4* postIn32 = nullptr; const float* exposureIn = nullptr;
     DevBuf<uint32_t> aeHist; DevBuf<float> aeExposure;
     DevBuf<uint32_t> tonemapLut; uint32_t tonemapLutDim = 0; DevBuf<F4> displayOut; DevBuf<uint32_t> displaySrgb;
+    int displayOption = ZR_DISPLAY_DEFAULT; float roughnessTh = 1.0f;      // DISPLAY: zr_pass_set_display_option (Display.cpp:69-73)
+    std::vector<uint32_t> picks; DevBuf<uint8_t> pickMask; DevBuf<int4> pickTris; DevBuf<uint32_t> pickCount;     // DISPLAY: zr_pass_set_picked_instances
+    uint32_t pickMaskW = 0, pickMaskH = 0;
     uint32_t own[4] = {0, 0, 0, 0};                // owned rect (global pixels); w == 0 -> the whole G-buffer rect
     // PRELIGHTING
     DevBuf<float> power;
@@ -2785,6 +2791,23 @@ extern "C" int zr_pass_set_tonemap_lut(zr_pass* p, const uint32_t* rgb9e5, uint3
     return ZR_OK;
 }
 
+extern "C" int zr_pass_set_display_option(zr_pass* p, int option, float roughness_th)
+{
+    if (!p || p->kind != ZR_PASS_DISPLAY) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_display_option: needs a DISPLAY pass");
+    if (option < ZR_DISPLAY_DEFAULT || option >= ZR_DISPLAY_COUNT) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_display_option: unknown option %d", option);
+    if (zr_isnan(roughness_th)) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_display_option: roughness_th is NaN");
+    p->displayOption = option; p->roughnessTh = roughness_th;
+    return ZR_OK;
+}
+
+extern "C" int zr_pass_set_picked_instances(zr_pass* p, const uint32_t* mesh_idx, uint32_t n)
+{
+    if (!p || p->kind != ZR_PASS_DISPLAY) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_picked_instances: needs a DISPLAY pass");
+    if (n && !mesh_idx) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_picked_instances: null indices");
+    p->picks.assign(mesh_idx, mesh_idx + n);
+    return ZR_OK;
+}
+
 static post::AeParams AeParamsOf(const zr_params& ip)
 { post::AeParams a; a.minLum = ip.ae_min_lum; a.lumRange = ip.ae_max_lum - ip.ae_min_lum; a.lumMapExp = ip.ae_lum_map_exp; a.adaptationRate = ip.ae_adaptation_rate; return a; }
 
@@ -2807,7 +2830,8 @@ static int RenderAutoExposure(zr_pass* p, hipStream_t s, const zr_frame_constant
     return ZR_OK;
 }
 // DisplayPass::Render (Display.cpp:188-260), the full-screen triangle of mainPS as one thread per display pixel
-static int RenderDisplay(zr_pass* p, hipStream_t s, const zr_frame_constants* cb)
+static int RenderPickOutlines(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, const zr_scene* sc);
+static int RenderDisplay(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, const zr_scene* sc, const zr_gbuffer* gb)
 {
     if (cb->display_width != p->w || cb->display_height != p->h) return Fail(ZR_ERR_INVALID_ARG, "DISPLAY: the pass size must be the display size of the frame constants");
     if (!p->postIn16 && !p->postIn32) return Fail(ZR_ERR_NOT_INITIALIZED, "DISPLAY: no input bound (zr_pass_set_input(ZR_IN_POST_SIGNAL_*))");
@@ -2817,12 +2841,68 @@ static int RenderDisplay(zr_pass* p, hipStream_t s, const zr_frame_constants* cb
     if (ip.display_auto_exposure && !p->exposureIn) return Fail(ZR_ERR_NOT_INITIALIZED, "DISPLAY: auto exposure is on but no exposure bound (ZR_IN_DISPLAY_EXPOSURE)");
     post::DisplayParams prm; prm.tonemapper = ip.display_tonemapper; prm.autoExposure = ip.display_auto_exposure; prm.saturation = ip.display_saturation; prm.agxExp = ip.display_agx_exp;
     post::Lut3D lut; lut.data = p->tonemapLut.p; lut.dim = p->tonemapLutDim;
+    if (p->displayOption != ZR_DISPLAY_DEFAULT)
+    {
+        // the G-buffer debug views (Display.hlsl:77-168) read the current planes at render resolution
+        if (!gb) return Fail(ZR_ERR_INVALID_ARG, "DISPLAY: display option %d needs the gbuffer", p->displayOption);
+        if (gb->w != cb->render_width || gb->h != cb->render_height) return Fail(ZR_ERR_INVALID_ARG, "DISPLAY: gbuffer %ux%u is not the render size %ux%u", gb->w, gb->h, cb->render_width, cb->render_height);
+        if (gb->x0 || gb->y0) return Fail(ZR_ERR_INVALID_ARG, "DISPLAY: display option %d needs a gbuffer with tile origin (0, 0)", p->displayOption);
+        TimerBegin(p, s, "display_view");
+        const hipError_t e = LaunchDisplayView(s, p->displayOption, gb->View(), p->w, p->h, cb->camera_near, p->roughnessTh, p->displayOut.p, p->displaySrgb.p);
+        TimerEnd(p, s);
+        HIP_TRY(e);
+        return RenderPickOutlines(p, s, cb, sc);
+    }
     const uint32_t n = p->w * p->h;
     TimerBegin(p, s, "display");
     hipLaunchKernelGGL(k_display, dim3((n + 255) / 256), dim3(256), 0, s, p->postIn16, p->postIn32, cb->render_width, cb->render_height, p->w, p->h,
         p->exposureIn, prm, lut, p->displayOut.p, p->displaySrgb.p);
     TimerEnd(p, s);
     HIP_TRY(hipGetLastError());
+    return RenderPickOutlines(p, s, cb, sc);
+}
+
+// DisplayPass::DrawPicked (Display.cpp:293-400) for every pick, in order: WVP = mul(W, VP) on the host, the instance's triangles rasterised into the
+// render-size R8 mask, then Sobel.hlsl over the display planes.  The host frustum cull of the reference is left out (an instance outside the frustum
+// covers no pixel and outlines nothing either way).
+static int RenderPickOutlines(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, const zr_scene* sc)
+{
+    if (p->picks.empty()) return ZR_OK;
+    const uint32_t rw = cb->render_width, rh = cb->render_height;
+    if (p->w > 16384 || p->h > 16384 || rw > 16384 || rh > 16384) return Fail(ZR_ERR_INVALID_ARG, "DISPLAY: the picked-instance outline needs display and render sizes <= 16384");
+    uint32_t maxTris = 0;
+    for (uint32_t idx : p->picks)
+    {
+        if (idx >= sc->hNumTris.size()) return Fail(ZR_ERR_INVALID_ARG, "DISPLAY: picked instance %u is not an instance of the scene (%zu instances)", idx, sc->hNumTris.size());
+        maxTris = std::max(maxTris, sc->hNumTris[idx]);
+    }
+    int r;
+    if (p->pickMaskW != rw || p->pickMaskH != rh)
+    {
+        if ((r = p->pickMask.Alloc((size_t)rw * rh))) return r;
+        p->pickMaskW = rw; p->pickMaskH = rh;
+    }
+    if (!p->pickCount.p && (r = p->pickCount.Alloc(1))) return r;
+    if (p->pickTris.n < 14 * (size_t)maxTris + 2 && (r = p->pickTris.Alloc(14 * (size_t)maxTris + 2))) return r;
+    for (uint32_t idx : p->picks)
+    {
+        // W: the 3x4 object-to-world matrix as the reference's float4x3 (row-vector convention); WVP[i][j] = ((W[i][0] VP[0][j] + W[i][1] VP[1][j]) + W[i][2] VP[2][j]) + W[i][3] VP[3][j]
+        const float* M = sc->hToWorld.data() + 12 * (size_t)idx;
+        float W[4][4];
+        for (int i = 0; i < 4; i++) { for (int j = 0; j < 3; j++) W[i][j] = M[4 * j + i]; W[i][3] = i == 3 ? 1.0f : 0.0f; }
+        post::PickWvp m;
+        for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++)
+        {
+            const float* VP = cb->curr_view_proj;
+            const float a = W[i][0] * VP[j], b = W[i][1] * VP[4 + j], c = W[i][2] * VP[8 + j], d = W[i][3] * VP[12 + j];
+            m.m[4 * i + j] = ((a + b) + c) + d;
+        }
+        TimerBegin(p, s, "pick_outline");
+        const hipError_t e = LaunchPickOutline(s, sc->vertices.p, sc->indices.p, sc->instances.p, idx, sc->hNumTris[idx], m, p->w, p->h, rw, rh, p->pickTris.p,
+            p->pickCount.p, p->pickMask.p, p->displayOut.p, p->displaySrgb.p);
+        TimerEnd(p, s);
+        HIP_TRY(e);
+    }
     return ZR_OK;
 }
 
@@ -3170,7 +3250,7 @@ static int RenderStageInner(zr_pass* p, void* stream, const zr_frame_constants* 
     case ZR_PASS_SKY: return RenderSky(p, s, cb, const_cast<zr_scene*>(sc), stages);
     case ZR_PASS_TAA: return (stages & ZR_STAGE_SPATIAL) ? RenderTAA(p, s, cb, gb) : ZR_OK;
     case ZR_PASS_AUTO_EXPOSURE: return (stages & ZR_STAGE_SPATIAL) ? RenderAutoExposure(p, s, cb) : ZR_OK;
-    case ZR_PASS_DISPLAY: return (stages & ZR_STAGE_SPATIAL) ? RenderDisplay(p, s, cb) : ZR_OK;
+    case ZR_PASS_DISPLAY: return (stages & ZR_STAGE_SPATIAL) ? RenderDisplay(p, s, cb, sc, gb) : ZR_OK;
     case ZR_PASS_DENOISE:
     {   // ZR_STAGE_SPATIAL (what zr_pass_render passes): the whole pass; ZR_STAGE_DENOISE_* bits: the steps of a tile's schedule
         const uint32_t steps = ((uint32_t)stages & ZR_STAGE_DENOISE_MASK) | ((stages & ZR_STAGE_SPATIAL) ? (uint32_t)ZR_STAGE_DENOISE_MASK : 0u);
@@ -3212,6 +3292,11 @@ int zr_pass_get_output(const zr_pass* p, int which, void** dev, uint32_t* w, uin
     {
         if (which == ZR_OUT_DISPLAY) { *dev = p->displayOut.p; if (w) *w = p->w; if (h) *h = p->h; if (bpp) *bpp = 16; return ZR_OK; }
         if (which == ZR_OUT_DISPLAY_SRGB8) { *dev = p->displaySrgb.p; if (w) *w = p->w; if (h) *h = p->h; if (bpp) *bpp = 4; return ZR_OK; }
+        if (which == ZR_OUT_PICK_MASK)
+        {
+            if (!p->pickMaskW) return Fail(ZR_ERR_INVALID_ARG, "DISPLAY: no picked instance has been rendered (zr_pass_set_picked_instances)");
+            *dev = p->pickMask.p; if (w) *w = p->pickMaskW; if (h) *h = p->pickMaskH; if (bpp) *bpp = 1; return ZR_OK;
+        }
         return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
     }
     if (p->kind == ZR_PASS_DENOISE)

@@ -155,6 +155,8 @@ ZR_HD V3 AgxLook(V3 val, float offset, V3 slope, float exp, float saturation)
 }
 
 struct DisplayParams { uint32_t tonemapper, autoExposure; float saturation, agxExp; };
+// the picked-instance outline's object-to-clip matrix, row-vector convention: clip = (x, y, z, 1) * m, m row-major (zr_pass_set_picked_instances)
+struct PickWvp { float m[16]; };
 
 // mainPS of Display.hlsl:41-77 with DisplayOption::DEFAULT: `composited` = the sampled input, returns .rgb (alpha is 1)
 ZR_HD V3 DisplayPixel(V3 composited, float exposure, const DisplayParams& p, const Lut3D& lut)

@@ -454,10 +454,14 @@ void* DisplayPass::GetOutput(SHADER_OUT_RES i) const
 {
     if (i >= SHADER_OUT_RES::COUNT) { std::fprintf(stderr, "Invalid shader output.\n"); std::abort(); }
     void* dev = nullptr; uint32_t w, h, bpp;
-    ZR_CHECK(zr_pass_get_output(m_pass, i == SHADER_OUT_RES::BACK_BUFFER_LINEAR ? ZR_OUT_DISPLAY : ZR_OUT_DISPLAY_SRGB8, &dev, &w, &h, &bpp));
+    ZR_CHECK(zr_pass_get_output(m_pass, i == SHADER_OUT_RES::BACK_BUFFER_LINEAR ? ZR_OUT_DISPLAY : (i == SHADER_OUT_RES::BACK_BUFFER_SRGB8 ? ZR_OUT_DISPLAY_SRGB8 : ZR_OUT_PICK_MASK), &dev, &w, &h, &bpp));
     return dev;
 }
-void DisplayPass::Render(Core::CommandList& cl) { ZR_CHECK(zr_pass_render(m_pass, cl.Stream(), &m_ctx->frameConstants, m_ctx->scene, nullptr)); }
+void DisplayPass::SetDisplayOption(DisplayOption o) { m_option = o; ZR_CHECK(zr_pass_set_display_option(m_pass, (int)o, m_roughnessTh)); }
+void DisplayPass::SetRoughnessTh(float v) { m_roughnessTh = v; ZR_CHECK(zr_pass_set_display_option(m_pass, (int)m_option, v)); }
+void DisplayPass::SetPickedInstances(const uint32_t* meshIdx, uint32_t n) { ZR_CHECK(zr_pass_set_picked_instances(m_pass, meshIdx, n)); }
+void DisplayPass::Render(Core::CommandList& cl)
+{ ZR_CHECK(zr_pass_render(m_pass, cl.Stream(), &m_ctx->frameConstants, m_ctx->scene, m_option == DisplayOption::DEFAULT ? nullptr : m_ctx->gbuffer)); }
 
 void IndirectLighting::Init(FrameContext* ctx, INTEGRATOR method)
 {
@@ -948,6 +952,58 @@ int zrh_render_sequence_sky_inscattering(const zr_scene_desc* desc, const zr_fra
     zr_gbuffer_destroy(ctx.gbuffer);
     zr_scene_destroy(ctx.scene);
     return 0;
+}
+
+int zrh_render_display_pick(const zr_scene_desc* desc, const zr_frame_constants* cb, uint32_t w, uint32_t h, const uint16_t* imageRGBA16F, uint32_t pickX,
+    uint32_t pickY, int option, float roughnessTh, float* displayOut, uint8_t* srgbOut, uint8_t* maskOut, uint32_t* pickOut)
+{
+    RenderPass::FrameContext ctx;
+    ctx.device = 0; ctx.renderWidth = w; ctx.renderHeight = h;
+    ZR_CHECK(zr_scene_create(0, desc, &ctx.scene));
+    ZR_CHECK(zr_gbuffer_create(0, w, h, &ctx.gbuffer));
+    void* image = nullptr;
+    if (hipMalloc(&image, (size_t)w * h * 8) != hipSuccess || hipMemcpy(image, imageRGBA16F, (size_t)w * h * 8, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    int ret = 0;
+    {
+        RenderPass::GBufferRT gb; RenderPass::DisplayPass disp;
+        gb.Init(&ctx);
+        disp.Init(&ctx, w, h, nullptr, 0);
+        disp.SetAutoExposure(false);
+        disp.SetGpuDescriptor(RenderPass::DisplayPass::SHADER_IN_GPU_DESC::COMPOSITED, image, true);
+        disp.SetDisplayOption((RenderPass::DisplayPass::DisplayOption)option);
+        disp.SetRoughnessTh(roughnessTh);
+        ctx.frameConstants = *cb;
+        Core::RenderGraph g;
+        enum : uint64_t { R_GBUF = 1, R_BACKBUFFER };
+        for (int f = 0; f < 2; f++)
+        {
+            if (f == 0) gb.PickPixel((uint16_t)pickX, (uint16_t)pickY);
+            else { const uint32_t pick = gb.ReadPick(); *pickOut = pick; disp.SetPickedInstances(&pick, 1); }
+            g.BeginFrame();
+            auto hGB = g.RegisterRenderPass("GBuffer", Core::RENDER_NODE_TYPE::COMPUTE, Core::MakeDelegate(&gb, &RenderPass::GBufferRT::Render));
+            Core::RenderNodeHandle hDisp{};
+            g.RegisterResource(nullptr, R_GBUF);
+            if (f == 1)
+            {
+                hDisp = g.RegisterRenderPass("Display", Core::RENDER_NODE_TYPE::COMPUTE, Core::MakeDelegate(&disp, &RenderPass::DisplayPass::Render));
+                g.RegisterResource(disp.GetOutput(RenderPass::DisplayPass::SHADER_OUT_RES::BACK_BUFFER_LINEAR), R_BACKBUFFER);
+            }
+            g.MoveToPostRegister();
+            g.AddOutput(hGB, R_GBUF, Core::STATE_UNORDERED_ACCESS);
+            if (f == 1) { g.AddInput(hDisp, R_GBUF, Core::STATE_SHADER_READ); g.AddOutput(hDisp, R_BACKBUFFER, Core::STATE_UNORDERED_ACCESS); }
+            Support::TaskSet ts;
+            g.Build(ts);
+            ts.Run(true);
+            g.WaitForFrame();
+        }
+        if (displayOut && hipMemcpy(displayOut, disp.GetOutput(RenderPass::DisplayPass::SHADER_OUT_RES::BACK_BUFFER_LINEAR), (size_t)w * h * 16, hipMemcpyDeviceToHost) != hipSuccess) ret = -1;
+        if (srgbOut && hipMemcpy(srgbOut, disp.GetOutput(RenderPass::DisplayPass::SHADER_OUT_RES::BACK_BUFFER_SRGB8), (size_t)w * h * 4, hipMemcpyDeviceToHost) != hipSuccess) ret = -1;
+        if (maskOut && hipMemcpy(maskOut, disp.GetOutput(RenderPass::DisplayPass::SHADER_OUT_RES::PICK_MASK), (size_t)w * h, hipMemcpyDeviceToHost) != hipSuccess) ret = -1;
+    }
+    (void)hipFree(image);
+    zr_gbuffer_destroy(ctx.gbuffer);
+    zr_scene_destroy(ctx.scene);
+    return ret;
 }
 
 // GBuffer -> PreLighting -> IndirectLighting (ReSTIR PT) -> Denoise through the RenderGraph, n frames; finalOut = the indirect pass's FINAL and

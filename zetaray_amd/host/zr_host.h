@@ -35,6 +35,10 @@ typedef struct zrh_comm zrh_comm;                     // one RCCL communicator (
 typedef struct zrh_halo_exchange zrh_halo_exchange;   // send / receive buffers + the rect lists of one pass's exchange
 typedef struct zrh_halo_peer { int peer; uint32_t send_x0, send_y0, send_w, send_h, recv_x0, recv_y0, recv_w, recv_h; } zrh_halo_peer;
 const char* zrh_halo_last_error(void);
+/* GBuffer (PickPixel) -> ReadPick -> GBuffer + Display (SetDisplayOption, SetPickedInstances) through the RenderGraph, display = render = w x h: the
+   composited input is `imageRGBA16F` (w x h RGBA16F texels), AgX default, no auto exposure.  Outputs the display planes, the pick mask and the pick. */
+int zrh_render_display_pick(const zr_scene_desc* desc, const zr_frame_constants* cb, uint32_t w, uint32_t h, const uint16_t* imageRGBA16F, uint32_t pickX,
+    uint32_t pickY, int option, float roughnessTh, float* displayOut, uint8_t* srgbOut, uint8_t* maskOut, uint32_t* pickOut);
 int zrh_rccl_unique_id(uint8_t* out128);
 int zrh_comm_create(int device, int world, int rank, const uint8_t* id128, zrh_comm** out);
 void zrh_comm_destroy(zrh_comm* c);
@@ -369,19 +373,26 @@ namespace RenderPass {
         zr_params m_params{};
     };
 
-    // RP/Display/Display.h:35-153: exposure + tone mapping of the final image (DisplayOption::DEFAULT; picking / wireframe overlays are UI)
+    // RP/Display/Display.h:35-153: exposure + tone mapping of the final image and the G-buffer debug views (DisplayOption; picking / wireframe
+    // overlays are UI)
     struct DisplayPass final : public RenderPassBase
     {
+        enum class DisplayOption { DEFAULT, BASE_COLOR, NORMAL, METALNESS_ROUGHNESS, COAT_WEIGHT, COAT_COLOR, ROUGHNESS_TH, EMISSIVE, TRANSMISSION, DEPTH, COUNT };
         enum class SHADER_IN_GPU_DESC { COMPOSITED, EXPOSURE, COUNT };
-        enum class SHADER_OUT_RES { BACK_BUFFER_LINEAR, BACK_BUFFER_SRGB8, COUNT };       // the reference renders into the swap chain's RTV
+        enum class SHADER_OUT_RES { BACK_BUFFER_LINEAR, BACK_BUFFER_SRGB8, PICK_MASK, COUNT };       // the reference renders into the swap chain's RTV
         // display size = ctx.frameConstants.display_*; lutRGB9E5 = dim^3 texels of Assets/LUT/tony_mc_mapface.dds (Display.cpp:196-205), may be null
         void Init(FrameContext* ctx, uint32_t displayWidth, uint32_t displayHeight, const uint32_t* lutRGB9E5, uint32_t lutDim);
         void SetGpuDescriptor(SHADER_IN_GPU_DESC i, const void* devicePlane, bool rgba16f = false);
         void SetTonemapper(zr_tonemapper t); void SetAutoExposure(bool b); void SetSaturation(float v); void SetAgXExp(float v);   // Display.cpp:565-619
+        // a view other than DEFAULT reads ctx->gbuffer (render size, tile origin (0, 0)); Display.cpp:69-73 defaults DEFAULT and 1.0
+        void SetDisplayOption(DisplayOption o); void SetRoughnessTh(float v);
+        // outline these instances (GBufferRT::ReadPick values) after the display pass, DisplayPass::DrawPicked (Display.cpp:293-400); n = 0 clears
+        void SetPickedInstances(const uint32_t* meshIdx, uint32_t n);
         void* GetOutput(SHADER_OUT_RES i) const;
         void Render(Core::CommandList& cmdList);
     private:
         zr_params m_params{};
+        DisplayOption m_option = DisplayOption::DEFAULT; float m_roughnessTh = 1.0f;
     };
 
     // Multi-device only (not in the reference): the reservoir halo exchange of the screen-tile split as a graph node between the temporal and

@@ -147,6 +147,11 @@ def default_params() -> Params:
 
 TEX_FILTER_MIP0, TEX_FILTER_TRI_LINEAR, TEX_FILTER_ANISOTROPIC_2X, TEX_FILTER_ANISOTROPIC_4X, TEX_FILTER_ANISOTROPIC_16X = range(5)
 TONEMAP_NONE, TONEMAP_NEUTRAL, TONEMAP_AGX_DEFAULT, TONEMAP_AGX_GOLDEN, TONEMAP_AGX_PUNCHY, TONEMAP_AGX_CUSTOM = range(6)
+# enum zr_display_option (DisplayOption, Display_Common.h:6-19): zr_pass_set_display_option
+(DISPLAY_DEFAULT, DISPLAY_BASE_COLOR, DISPLAY_NORMAL, DISPLAY_METALNESS_ROUGHNESS, DISPLAY_COAT_WEIGHT, DISPLAY_COAT_COLOR, DISPLAY_ROUGHNESS_TH,
+ DISPLAY_EMISSIVE, DISPLAY_TRANSMISSION, DISPLAY_DEPTH, DISPLAY_COUNT) = range(11)
+DISPLAY_ROUGHNESS_TH_DEFAULT = 1.0
+OUT_PICK_MASK = 50          # ZR_PASS_DISPLAY: R8, render size (zr_pass_set_picked_instances)
 
 
 def set_post_defaults(p):
