@@ -3,6 +3,7 @@
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
   python bench.py ... --dump-outputs DIR                 (+ the last timed frame's output images as DIR/<name>.npy)
+  python bench.py ... --full                             (+ everything the headline figure does not need: see below)
 
 Metric (BASELINE.json): Mrays/s (+ ms/frame) at 1920x1080, 3 non-transmissive bounces, Cornell-Box-class scene.
 A ray = one BVH query (closest-hit or any-hit), counted on the device.  Scene, BVH, G-buffer
@@ -11,9 +12,14 @@ torch.cuda.synchronize(), max over ranks.  N > 1 shards the frame by 32-px-align
 the path-tracing integrator has no cross-pixel reads, so there is no data-path collective ("scaling": weak would be
 wrong here -- the total work is fixed, so this reports "strong").
 
-Extra objects on the JSON line (rank 0, N = 1): "roofline" for the dominant kernel (hipEvent timing inside the library,
-algorithmic bytes from the per-ray model of DESIGN.md section 6) and "cpu_baseline" (the CPU oracle's single-thread
-traversal of its own BVH2 over a bounded sample of the same frame's rays).
+A plain run sets up, settles and warms up, times the K frames, writes --dump-outputs and prints the line; nothing else.
+--full adds what takes runs or processes of its own, each after the timed region except "device_state" (the device
+probes, before it): "general_kernels" and "frame_overlap_off" (the same frames on the general kernels / in the plain
+order), "roofline" for the dominant kernel (hipEvent timing inside the library, algorithmic bytes from the per-ray model
+of DESIGN.md section 6) with config.frame_ms_median / p95, "cpu_baseline" (the CPU oracle's single-thread traversal of
+its own BVH2 over a bounded sample of the same frame's rays), "extra_workloads" (BASELINE configs 4 and 5) and
+"tolerance_mode" (the fast-arithmetic build) on the default line, and for N > 1 "multi_gpu" and the whole-job roofline.
+The --no-* switches below drop single items of --full.
 """
 import argparse
 import json
@@ -294,8 +300,9 @@ def dump_outputs(args, ctx, r, p_denoise, ext, tile, frame_num):
 
 def measure(args, ctx):
     """One workload end to end on the devices of this job: scene + passes resident in HBM, settle + warm-up frames, the timed region of
-    args.steps frames (barrier + torch.cuda.synchronize() on both sides, max over ranks), then -- rank 0, N = 1 -- the roofline block of the
-    dominant kernel (hipEvent timing inside the library) and the CPU baseline.  Returns the JSON line as a dict."""
+    args.steps frames (barrier + torch.cuda.synchronize() on both sides, max over ranks), then -- with --full only -- the device probes (before the
+    settle frames), the general-kernel and plain-order timings, the roofline block of the dominant kernel (hipEvent timing inside the library), the
+    CPU baseline and the N > 1 blocks.  Returns the JSON line as a dict."""
     import torch
     from zetaray_amd import api, scene_io, wire
     world, rank, local_rank, dist, cdev = ctx["world"], ctx["rank"], ctx["local_rank"], ctx["dist"], ctx["cdev"]
@@ -420,8 +427,8 @@ def measure(args, ctx):
     settle = args.settle if args.settle is not None else (32 if (rpt or args.integrator == "restir_gi" or di_passes) else 0)
     settle_frames = settle
     # the device as it is right now, measured before anything is timed (every rank probes its own device; rank 0's block goes on the line as `device_state`,
-    # N > 1 adds one summary row per rank)
-    dev_state = device_state(api, local_rank) if not args.no_device_state else None
+    # N > 1 adds one summary row per rank; --full only)
+    dev_state = device_state(api, local_rank) if (args.full and not args.no_device_state) else None
     barrier()
     t_s = time.perf_counter()
     for i in range(settle):
@@ -557,7 +564,7 @@ def measure(args, ctx):
             rows = [None] * world
             dist.all_gather_object(rows, row)
             out["device_state"]["ranks"] = rows
-    if world == 1 and (rpt or args.integrator == "restir_gi") and out["config"]["kernel_class"] == "plain" and not args.no_general_kernels:
+    if args.full and world == 1 and (rpt or args.integrator == "restir_gi") and out["config"]["kernel_class"] == "plain" and not args.no_general_kernels:
         # the same frames on the GENERAL kernel permutations (zr_debug_set_material_class_kernels(0): what this scene would run with one glass sphere in it),
         # same protocol: a few frames to settle, then args.steps frames between two barriers.  Results are identical (test_material_class_kernels_change_nothing)
         L = api.lib()
@@ -583,7 +590,7 @@ def measure(args, ctx):
         # diagnostic build of K11: lanes alive at its bounce boundaries; the timings of this run mean nothing
         a, b, wds = r.p_indirect.debug_trip_stats()
         out["config"]["k11_bounce_boundaries"] = {"alive_lanes": a, "lane_slots": b, "alive_frac": round(a / max(b, 1), 4), "carried_state_bytes_per_path": 4 * wds}
-    if overlap and world == 1:
+    if args.full and overlap and world == 1:
         # what follows times kernels and single frames one at a time: the plain order on one stream (kernel times under overlap are the times of two kernels sharing the device).
         # Before that, the same protocol once more with the switch off: the pair (overlapped, plain) goes on the line
         barrier()
@@ -599,7 +606,7 @@ def measure(args, ctx):
                                     "note": "the same frames in the plain order on one stream (zr_pass_set_frame_overlap(0)); bit-identical output"}
         r.p_gbuffer.read_counters(reset=True)
         r.p_indirect.read_counters(reset=True)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # ---- roofline of the dominant kernel: hipEvent timing inside the library over a few timed frames
         r.p_gbuffer.enable_timing(True)
         r.p_indirect.enable_timing(True)
@@ -734,7 +741,7 @@ def measure(args, ctx):
                 scene_io.set_texture_heap_offsets(cbf, tex_offsets)
             out["cpu_baseline"] = cpu_baseline(sc, cbf, rpt_params=prm if rpt else None, max_rays=1_000_000 if args.scene != "synthetic" else 200_000,
                                                sample=(2, 8) if args.scene != "synthetic" else (4, 4))
-    if world > 1 and tiled is not None:
+    if args.full and world > 1 and tiled is not None:
         # ---- first contact with a multi-GPU node (a run nobody can debug afterwards): every rank reports where it ran, what it sends and how long ONE halo
         # exchange takes on its own (8 back-to-back exchanges of the planes as they stand -- idempotent -- between two barriers)
         post, _final = tiled.EXCHANGES[tiled.kind]
@@ -760,7 +767,7 @@ def measure(args, ctx):
         dist.all_gather_object(rows, row)
         out["multi_gpu"] = {"backend": dist.get_backend(), "rccl_version": rccl, "communicator_size": dist.get_world_size(), "exchanges_per_frame": exch_per_frame,
                             "halo_pass": tiled.kind, "ranks": rows}
-    if world > 1 and tiled is not None and rpt:
+    if args.full and world > 1 and tiled is not None and rpt:
         # ---- N > 1: the fraction of the HBM roofline of the whole job (north_star: "at 1 / 2 / 4 / 8 GPUs ... as fraction of the HBM roofline").  Every rank
         # times the metric's kernel (K11) on its tile with the library's hipEvents over a few frames; achieved = the ranks' algorithmic bytes per launch
         # (per-ray model on the rays the kernel issued + the planes of the OWNED pixels) summed, over the slowest rank's launch time; peak = N x 8 TB/s.
@@ -809,13 +816,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=None, help="untimed frames right before the timed ones (default 64, or the --config preset's)")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: device probes, general-kernel and plain-order timings, roofline, CPU baseline, "
+                         "and on the default line BASELINE configs 4 and 5 and the tolerance-mode build; N > 1: the multi_gpu block and the whole-job roofline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline block")
     ap.add_argument("--arith", choices=["contract", "fast"], default="contract",
                     help="contract = libzetaray_amd.so, the bit-exact arithmetic contract of include/zr_detmath.h (the product default, what every parity test "
                          "loads); fast = libzetaray_amd_fast.so, the tolerance-mode build of the same sources (hardware rcp / rsq / exp / log / sin / cos, "
                          "contracted FMAs; parity = tests/test_fast_arith.py).  A fast line says so in config.arith and is never the default.")
     ap.add_argument("--no-extra-workloads", action="store_true",
-                    help="the default line also measures BASELINE config 4 (atrium 1080p ReSTIR PT) in the same process as extra_workloads[0]; this skips it")
+                    help="--full on the default line also measures BASELINE configs 4 and 5 in the same process (extra_workloads) and the tolerance-mode build "
+                         "in a child process (tolerance_mode); this skips them")
     ap.add_argument("--denoise", action="store_true", help="add the denoise pass (ZR_PASS_DENOISE) on the indirect image (tile-split like the integrator for N > 1)")
     ap.add_argument("--scene", default=os.path.join(ROOT, "tests", "golden", "cornell_emissive.npz"),
                     help="wire-format .npz, or 'synthetic' = the procedural Sponza-class scene of BASELINE config 4 "
@@ -837,14 +848,14 @@ def main():
                          "Cornell (emissive) 1920x1080 ReSTIR PT): " + "; ".join(f"{k} = {v[0]}" for k, v in sorted(CONFIGS.items())))
     ap.add_argument("--ramp-s", type=float, default=0.6,
                     help="seconds of back-to-back frames of the workload rendered before --warmup so that the device's clocks have ramped (0 = none)")
-    ap.add_argument("--no-device-state", action="store_true", help="skip the device_state block (zr_device_probe_run + amdsmi)")
-    ap.add_argument("--no-general-kernels", action="store_true", help="skip the general-kernel timing of a plain-class scene (general_kernels)")
+    ap.add_argument("--no-device-state", action="store_true", help="--full without the device_state block (zr_device_probe_run + amdsmi)")
+    ap.add_argument("--no-general-kernels", action="store_true", help="--full without the general-kernel timing of a plain-class scene (general_kernels)")
     ap.add_argument("--kernel-class", choices=["auto", "general"], default="auto",
                     help="general = run a plain-class scene on the general kernel permutations (zr_debug_set_material_class_kernels(0)) for the whole run")
     ap.add_argument("--frame-overlap", type=int, choices=[0, 1], default=1,
                     help="1 (default) = consecutive ReSTIR PT frames software-pipelined on two streams: the G-buffer and K11 of frames N + 1 / N + 2 beside the reuse passes of frame N "
-                         "(zetaray_amd.h zr_pass_set_frame_overlap; bit-identical frames) -- ms_per_step is then the frame THROUGHPUT, config.frame_ms_median the latency of one "
-                         "frame rendered alone, and frame_overlap_off carries the plain order's ms_per_step; 0 = the plain order on one stream")
+                         "(zetaray_amd.h zr_pass_set_frame_overlap; bit-identical frames) -- ms_per_step is then the frame THROUGHPUT; with --full, config.frame_ms_median is the latency "
+                         "of one frame rendered alone and frame_overlap_off carries the plain order's ms_per_step; 0 = the plain order on one stream")
     ap.add_argument("--settle", type=int, default=None,
                     help="untimed frames rendered BEFORE the warm-up so that the temporal reservoirs have reached their M caps whatever --warmup is "
                          "(default: 32 for the ReSTIR integrators, 0 otherwise)")
@@ -912,8 +923,8 @@ def main():
     out = measure(args, ctx)
     default_line = (args.config is None and world == 1 and args.scene.endswith("cornell_emissive.npz") and args.integrator == "restir_pt"
                     and (args.width, args.height) == (1920, 1080) and not (args.direct or args.sky_direct or args.denoise or args.di_only or args.textured))
-    if default_line and not args.no_extra_workloads:
-        # the driver runs `bench.py --gpus 1`: `value` stays the metric's own configuration (Cornell), and BASELINE config 4's scene -- the
+    if default_line and args.full and not args.no_extra_workloads:
+        # `bench.py --gpus 1 --full`: `value` stays the metric's own configuration (Cornell), and BASELINE config 4's scene -- the
         # 380k-triangle / 100k-light atrium at 1080p -- is measured in the same process with its own roofline and CPU baseline
         # ... and config 5's (the same scene at 3840 x 2160 with the denoise pass; its CPU sample would be the very one of config 4 -- the oracle at
         # 480 x 270 on that scene -- so it is referenced, not re-run)
@@ -941,7 +952,7 @@ def main():
         if os.path.exists(fast_lib):
             import subprocess
             try:
-                cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--arith", "fast", "--no-extra-workloads", "--no-cpu-baseline", "--no-device-state", "--no-general-kernels",
+                cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--arith", "fast", "--full", "--no-extra-workloads", "--no-cpu-baseline", "--no-device-state", "--no-general-kernels",
                                      "--steps", str(args.steps), "--warmup", str(args.warmup)], capture_output=True, text=True, timeout=600)
                 o3 = json.loads([l for l in cp.stdout.splitlines() if l.startswith("{")][-1])
                 out["tolerance_mode"] = {"arith": "fast", "library": o3["config"]["library"], "ms_per_step": o3["ms_per_step"], "value": o3["value"], "unit": o3["unit"],

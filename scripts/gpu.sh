@@ -5,7 +5,7 @@
 #   ab LIB...          A/B of library builds: for each name ("" or "default" = libzetaray_amd.so, X = libzetaray_amd_X.so) the bench lines of the
 #                      workloads in WORKLOADS (default "cornell atrium"), then one table of frame + kernel times
 #   suite [PYTEST_ARGS] the -m gpu parity suite (+ smoke)
-#   bench [ARGS]       the default driver line (python bench.py ARGS)
+#   bench [ARGS]       the benchmark line (python bench.py ARGS; add --full for the roofline, CPU baseline, configs 4 / 5 and tolerance mode)
 #   profiles           per workload in WORKLOADS (rpt_cornell rpt_atrium gi_cornell ...): --kernel-trace --stats + separate --pmc passes
 #                      (FETCH_SIZE, WRITE_SIZE, SQ sets A / B / C / E) of one bench command -> ${TAG}_pmc_<wl>.json, ${TAG}_kernel_stats_<wl>.csv
 #   stats [ARGS]       one rocprofv3 --kernel-trace --stats run of bench.py ARGS -> ${TAG}_kernel_stats.csv
@@ -25,7 +25,7 @@ ab)
     tag=${lib:-default}; p=$(libpath "$lib")
     if [ -n "$p" ]; then export ZETARAY_AMD_LIB=$p; else unset ZETARAY_AMD_LIB; fi
     for wl in ${WORKLOADS:-cornell atrium}; do
-      extra="--no-extra-workloads --no-cpu-baseline"; [ $wl = cornell ] && extra="$extra --steps ${STEPS:-256} --warmup ${WARMUP:-64}"
+      extra="--full --no-extra-workloads --no-cpu-baseline"; [ $wl = cornell ] && extra="$extra --steps ${STEPS:-256} --warmup ${WARMUP:-64}"
       timeout 600 python bench.py $(wl_args $wl) $extra > $OUT/${TAG}_ab_${wl}_$tag.json 2> $OUT/${TAG}_ab_err.log || { echo "FAILED $tag $wl"; tail -5 $OUT/${TAG}_ab_err.log; }
     done
   done
@@ -53,7 +53,7 @@ bench)
   ;;
 stats)
   cd /tmp && export TMPDIR=/tmp; rm -rf /tmp/st_d
-  timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/st_d -- python $R/bench.py --gpus 1 --steps 16 --warmup 4 --settle 8 --ramp-s 0 --no-device-state --no-general-kernels --no-cpu-baseline --no-extra-workloads "$@" > $OUT/${TAG}_stats.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/st_d -- python $R/bench.py --gpus 1 --steps 16 --warmup 4 --settle 8 --ramp-s 0 --full --no-device-state --no-general-kernels --no-cpu-baseline --no-extra-workloads "$@" > $OUT/${TAG}_stats.log 2>&1
   python $R/tools/rocpd_summary.py stats $(find /tmp/st_d -name "*results.db" | head -1) $OUT/${TAG}_kernel_stats.csv | head -25
   ;;
 profiles)
@@ -71,7 +71,7 @@ profiles)
   for wl in ${WORKLOADS:-rpt_cornell rpt_atrium gi_cornell}; do
     # (--no-extra-workloads: the default line would otherwise render configs 4 and 5 in the same process, and their launches share kernel names with Cornell's)
     # (--frame-overlap 0: a kernel's counters and duration alone on the device; --ramp-s 0: the counter passes serialise the kernels, nothing to ramp)
-    CMD="python $R/bench.py --gpus 1 --steps 6 --warmup 2 --settle 8 --ramp-s 0 --frame-overlap 0 --no-device-state --no-general-kernels --no-cpu-baseline --no-extra-workloads $(wl_args $wl)"
+    CMD="python $R/bench.py --gpus 1 --steps 6 --warmup 2 --settle 8 --ramp-s 0 --frame-overlap 0 --full --no-device-state --no-general-kernels --no-cpu-baseline --no-extra-workloads $(wl_args $wl)"
     O=$OUT/${TAG}_$wl
     pmc ${O}_fetch FETCH_SIZE $CMD; pmc ${O}_write WRITE_SIZE $CMD
     for p in ${SQ_SETS:-A B C E}; do eval CTR=\$SQ_$p; pmc ${O}_sq$p "$CTR" $CMD; done
@@ -95,7 +95,7 @@ prof)
   cd $R; export ZETARAY_AMD_LIB=$(libpath "$1")
   P='import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps({"ms": d["ms_per_step"], "kernels": d["roofline"]["kernel_ms_per_frame"], "prof": d.get("prof")}, indent=1))'
   for wl in ${WORKLOADS:-cornell atrium}; do
-    timeout 600 python bench.py --gpus 1 --steps 16 --warmup 4 --frame-overlap 0 --no-device-state --no-general-kernels --no-cpu-baseline --no-extra-workloads $(wl_args $wl) 2> $OUT/${TAG}_prof_err.log | tail -1 | python -c "$P" > $OUT/${TAG}_section_profile_$wl.json || tail -5 $OUT/${TAG}_prof_err.log
+    timeout 600 python bench.py --gpus 1 --steps 16 --warmup 4 --frame-overlap 0 --full --no-device-state --no-general-kernels --no-cpu-baseline --no-extra-workloads $(wl_args $wl) 2> $OUT/${TAG}_prof_err.log | tail -1 | python -c "$P" > $OUT/${TAG}_section_profile_$wl.json || tail -5 $OUT/${TAG}_prof_err.log
   done
   ;;
 *) echo "unknown task $task"; exit 2;;

@@ -1975,7 +1975,9 @@ def test_bench_multi_rank_protocol_on_one_gpu():
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] if (n == 1 or self_launch) else \
             [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1", "--master-port", str(port),
              os.path.join(ROOT, "bench.py")]
-        cmd += ["--gpus", str(n), "--steps", "4", "--warmup", "2", "--settle", str(settle), "--ramp-s", "0", "--no-general-kernels", "--width", "512", "--height", "288", "--no-cpu-baseline"] + more
+        # (--full: the device probes, the multi_gpu block and the whole-job roofline asserted below are not part of a plain line)
+        cmd += ["--gpus", str(n), "--steps", "4", "--warmup", "2", "--settle", str(settle), "--ramp-s", "0", "--no-general-kernels", "--width", "512", "--height", "288", "--no-cpu-baseline",
+                "--full"] + more
         res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
         assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
         lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -2012,6 +2014,33 @@ def test_bench_multi_rank_protocol_on_one_gpu():
         # the grid.  (Equal frame numbers give bit-identical frames, hence equal counts; the probe frames shift the numbering in the second case.)
         rel = min(abs(d["config"]["rays_per_frame"] / s1 - 1) for s1 in singles)
         assert rel < 0.03, (d["config"]["rays_per_frame"], singles, d["config"]["parallelism"])
+
+
+def test_bench_plain_line_is_lean_and_full_renders_the_same_frames(tmp_path):
+    """A plain `bench.py --gpus 1` run times its frames and prints the headline keys, none of the blocks that --full measures in runs of their own; --full
+    on the same arguments adds them after the timed region, and the timed renderer's last frame (--dump-outputs) is bit-identical between the two."""
+    import json
+    import subprocess
+    import sys
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--settle", "4", "--ramp-s", "0.05", "--width", "256", "--height", "144"]
+    lines = {}
+    for mode, more in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + more + ["--dump-outputs", str(tmp_path / mode)],
+                             cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        out = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, res.stdout[-2000:]
+        lines[mode] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["metric"] == "Mrays/s" and d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32", d
+        assert d["steps"] == 3 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0, d
+    extras = ("device_state", "general_kernels", "frame_overlap_off", "roofline", "cpu_baseline", "extra_workloads", "tolerance_mode", "multi_gpu")
+    assert not any(k in plain for k in extras) and "frame_ms_median" not in plain["config"], sorted(plain)
+    assert all(k in full for k in ("device_state", "general_kernels", "frame_overlap_off", "roofline")) and "frame_ms_median" in full["config"], sorted(full)
+    assert plain["dump_outputs"]["frame_num"] == full["dump_outputs"]["frame_num"] and plain["dump_outputs"]["arrays"] == {"final": [144, 256, 4]}
+    a, b = np.load(tmp_path / "plain" / "final.npy"), np.load(tmp_path / "full" / "final.npy")
+    assert a[..., :3].max() > 0 and np.array_equal(a.view(np.uint32), b.view(np.uint32)), "--full changed the timed frames"
 
 
 _VARIANT_SNIPPET = r"""
