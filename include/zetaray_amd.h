@@ -529,6 +529,35 @@ enum zr_display_option
 /* ZR_PASS_DISPLAY: the view and cbDisplayPass::RoughnessTh of ROUGHNESS_TH (DisplayPass defaults DEFAULT and 1.0, Display.cpp:69-73).
    ZR_ERR_INVALID_ARG for another pass kind, an unknown option or a NaN threshold. */
 int zr_pass_set_display_option(zr_pass* pass, int option, float roughness_th);
+/* The ReSTIR PT reconnection debug views (RPT_DEBUG_VIEW, IndirectLighting_Common.h:58-67; RPT_Util::DebugColor, ReSTIR_PT/Util.hlsli:69-139).
+   With a view selected, the kernel that writes a pixel's radiance at the END of the frame's last reuse pass (K11 without temporal reuse,
+   the temporal reconnect kernel without spatial reuse, else the spatial one) writes a constant colour chosen from the pixel's selected
+   reconnection rc instead; every EARLY write of a pixel (no temporal history, no reusable neighbour, a neighbour without a reconnection) writes
+   0.  The colour goes through the kernel's ordinary store-or-accumulate rule.  (r, g, b), "black" = (0, 0, 0); a class no row names leaves
+   the radiance as it is:
+     K                 rc empty: black; k = 2: (0.1, 0.25, 0.88); k = 3: (0.13, 0.55, 0.14); k = 4: (0.69, 0.45, 0.1); k >= 5: (0.88, 0.08, 0.1)
+     CASE              rc empty: black; case 1: (0.85, 0.096, 0.1); case 2: (0.13, 0.6, 0.14); case 3: (0.1, 0.27, 0.888)
+     FOUND_CONNECTION  rc empty: black; else (0.234, 0.12, 0.2134)
+     LOBE_K_MIN_1      rc empty: black; lobe at x_{k-1} DIFFUSE_R: (0.384, 0.12, 0.2134); GLOSSY_R: (0.12, 0.4284, 0.2134); GLOSSY_T: (0.1134, 0.12, 0.634);
+                       DIFFUSE_T: (0.25, 0.25, 0.25); any other: (0.55, 0.55, 0)
+     LOBE_K            rc empty or case 3: black; lobe at x_k DIFFUSE_R: (0.384, 0.12, 0.2134); GLOSSY_R: (0.12, 0.284, 0.2134); GLOSSY_T: (0.1134, 0.12, 0.634);
+                       DIFFUSE_T: (0.25, 0.25, 0); any other: (0.25, 0.25, 0.25) */
+typedef enum zr_rpt_debug_view
+{
+    ZR_RPT_VIEW_NONE = 0,
+    ZR_RPT_VIEW_K,
+    ZR_RPT_VIEW_CASE,
+    ZR_RPT_VIEW_FOUND_CONNECTION,
+    ZR_RPT_VIEW_LOBE_K_MIN_1,
+    ZR_RPT_VIEW_LOBE_K,
+    ZR_RPT_VIEW_COUNT
+} zr_rpt_debug_view;
+/* ZR_PASS_INDIRECT: select a view (IndirectLighting::DebugViewCallback, IndirectLighting.cpp:1543-1550).  It takes effect with the next frame's first
+   stage and holds until changed; NONE restores the ordinary frame exactly.  Only ZR_OUT_FINAL (rgb) changes: reservoirs, target, r-buffers, thread maps,
+   the neighbour plane and the ray counters are those of the same frame without a view.  Read by the ReSTIR PT integrator only: with another integrator the
+   value is stored and has no effect.  Works unchanged with zr_pass_set_owned_rect (a view is per pixel) and with zr_pass_set_frame_overlap.
+   ZR_ERR_INVALID_ARG for a null pass, another pass kind or a value outside the enum. */
+int zr_pass_set_rpt_debug_view(zr_pass* pass, int view);
 /* ZR_PASS_DISPLAY: outline the picked instances (DisplayPass::DrawPicked, Display.cpp:293-400; DrawPicked.hlsl, Sobel.hlsl).  mesh_idx: n instance indices
    as zr_pass_read_pick returns them, kept until the next call; n = 0 clears.  They are checked against the scene passed to zr_pass_render
    (ZR_ERR_INVALID_ARG for an index that is not one of its instances).  After the display kernel, on the same stream, for each pick in order:

@@ -60,6 +60,7 @@ EXPORTS = [
     "zr_pass_set_frame_overlap", "zr_pass_frame_overlap_stream", "zr_device_synchronize",
     "zr_pass_set_inscattering", "zr_pass_bind_inscattering",
     "zr_pass_set_display_option", "zr_pass_set_picked_instances",
+    "zr_pass_set_rpt_debug_view",
 ]
 STAGE_TEMPORAL, STAGE_SPATIAL, STAGE_ALL = 1, 2, 3
 STAGE_SPATIAL2 = 4          # ReSTIR PT, num_spatial_passes = 2 on tiles: the second round, behind one more HALO_POST_TEMPORAL exchange
@@ -132,6 +133,7 @@ def lib():
         L.zr_pass_set_tonemap_lut.argtypes = [vp, vp, u32]
         L.zr_pass_set_display_option.argtypes = [vp, i32, C.c_float]
         L.zr_pass_set_picked_instances.argtypes = [vp, vp, u32]
+        L.zr_pass_set_rpt_debug_view.argtypes = [vp, i32]
         L.zr_pass_halo_pack_all.argtypes = [vp, vp, vp, i32, vp, u32, vp, C.c_size_t]
         L.zr_pass_halo_unpack_all.argtypes = [vp, vp, vp, i32, vp, u32, vp, C.c_size_t]
         L.zr_pass_set_owned_rect.argtypes = [vp, u32, u32, u32, u32]
@@ -392,6 +394,10 @@ class Pass:
     # wire.DISPLAY_DEFAULT makes render() read the gbuffer passed to it
     def set_display_option(self, option, roughness_th=wire.DISPLAY_ROUGHNESS_TH_DEFAULT):
         _check(lib().zr_pass_set_display_option(self.h, int(option), float(roughness_th)))
+
+    # INDIRECT pass: ReSTIR PT's reconnection debug view (wire.RPT_VIEW_*; zetaray_amd.h zr_pass_set_rpt_debug_view), from the next frame on; only FINAL changes
+    def set_rpt_debug_view(self, view):
+        _check(lib().zr_pass_set_rpt_debug_view(self.h, int(view)))
 
     # DISPLAY pass: outline these instances (zr_pass_read_pick values) after the display kernel; [] clears (zetaray_amd.h zr_pass_set_picked_instances)
     def set_picked_instances(self, mesh_idx):

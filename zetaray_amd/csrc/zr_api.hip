@@ -887,6 +887,8 @@ struct zr_pass
     DevBuf<uint32_t> aeHist; DevBuf<float> aeExposure;
     DevBuf<uint32_t> tonemapLut; uint32_t tonemapLutDim = 0; DevBuf<F4> displayOut; DevBuf<uint32_t> displaySrgb;
     int displayOption = ZR_DISPLAY_DEFAULT; float roughnessTh = 1.0f;      // DISPLAY: zr_pass_set_display_option (Display.cpp:69-73)
+    // INDIRECT: zr_pass_set_rpt_debug_view (IndirectLighting.cpp:1543-1550); rptViewFrame = the view of the frame being rendered (latched by its first stage)
+    int rptView = ZR_RPT_VIEW_NONE, rptViewFrame = ZR_RPT_VIEW_NONE;
     std::vector<uint32_t> picks; DevBuf<uint8_t> pickMask; DevBuf<int4> pickTris; DevBuf<uint32_t> pickCount;     // DISPLAY: zr_pass_set_picked_instances
     uint32_t pickMaskW = 0, pickMaskH = 0;
     uint32_t own[4] = {0, 0, 0, 0};                // owned rect (global pixels); w == 0 -> the whole G-buffer rect
@@ -2480,6 +2482,7 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
     prm.temporalMap = prm.sortTemporal ? temporalMapEnv : 0u;
     if (stageCand)
     {
+        p->rptViewFrame = p->rptView;
         p->doTemporal = (ip.flags & ZR_IND_TEMPORAL_RESAMPLE) && p->temporalValid && havePrevGBuffer;
         p->doSpatial = (ip.flags & ZR_IND_SPATIAL_RESAMPLE) && p->doTemporal && ip.num_spatial_passes > 0;      // IndirectLighting.cpp:906
     }
@@ -2523,6 +2526,11 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
 #define RPT_LAUNCH_PE(kern, PASS, ...) do { \
         if (emissiveVariant) { if (texVariant) hipLaunchKernelGGL((kern<PASS, true, true>), __VA_ARGS__); else hipLaunchKernelGGL((kern<PASS, true, false>), __VA_ARGS__); } \
         else { if (texVariant) hipLaunchKernelGGL((kern<PASS, false, true>), __VA_ARGS__); else hipLaunchKernelGGL((kern<PASS, false, false>), __VA_ARGS__); } } while (0)
+    // a reconnection debug view: the VIEW instantiations of the three kernels that write FINAL (zr_kernels.h), general material class
+    const uint32_t view = (uint32_t)p->rptViewFrame;
+#define RPT_LAUNCH_VIEW(kern, ...) do { \
+        if (emissiveVariant) { if (texVariant) hipLaunchKernelGGL((kern<true, true>), __VA_ARGS__, view); else hipLaunchKernelGGL((kern<true, false>), __VA_ARGS__, view); } \
+        else { if (texVariant) hipLaunchKernelGGL((kern<false, true>), __VA_ARGS__, view); else hipLaunchKernelGGL((kern<false, false>), __VA_ARGS__, view); } } while (0)
     if (stageCand)
     {
         if (int ar = GBufferAcquireRead(gb, s)) return ar;
@@ -2536,6 +2544,9 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
                 (const F4*)(p->tgtIdx ? p->rptTarget.p : p->rptTargetAlt.p), n));
         }
         TimerBegin(p, s, "rpt_pathtrace");
+        if (view != ZR_RPT_VIEW_NONE) RPT_LAUNCH_VIEW(k_rpt_pathtrace_view, gridRpt, blockRpt, 0, s, F, *cb, tilesX, ctr + 2 * 1);
+        else
+        {
 #ifdef ZR_EXPERIMENTS
         // (experiments build, zr_kernels_exp.h) ZR_K11=pool: K11 with block-pooled traces (k_rpt_pathtrace_coop; emissive untextured permutation);
         // compact: a kernel per bounce; trip: the alive-lane diagnostic; ZR_K11=inline: the megakernel
@@ -2588,6 +2599,7 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
             if (plainVariant) { if (emissiveVariant) hipLaunchKernelGGL((k_rpt_pathtrace<true, true>), gridRpt, blockRpt, 0, s, F, *cb, tilesX, ctr + 2 * 1); else hipLaunchKernelGGL((k_rpt_pathtrace<false, true>), gridRpt, blockRpt, 0, s, F, *cb, tilesX, ctr + 2 * 1); }
             else if (emissiveVariant) hipLaunchKernelGGL((k_rpt_pathtrace<true, false>), gridRpt, blockRpt, 0, s, F, *cb, tilesX, ctr + 2 * 1); else hipLaunchKernelGGL((k_rpt_pathtrace<false, false>), gridRpt, blockRpt, 0, s, F, *cb, tilesX, ctr + 2 * 1);
         }
+        }
         TimerEnd(p, s);
         if (p->overlap) { HIP_TRY(hipEventRecord(p->evCand, s)); p->candStream = s; p->haveCand = true; }
     }
@@ -2603,7 +2615,8 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
             RPT_TIMED("rpt_sort_temporal", hipLaunchKernelGGL((k_rpt_sort<rpt::RPT_SORT_TTC, rpt::RPT_SORT_CTT>), dim3(gridSort.x * 2), dim3(256), 0, s, F, *cb, sortTilesX, F.ox0 / 32u, F.oy0 / 32u, F.mapNtC, F.mapCtN));
             RPT_TIMED("rpt_classify_temporal", hipLaunchKernelGGL(k_rpt_light<0>, gridLight, block, 0, s, F, *cb, tilesX, lists[0], lists[1], listCnt + 0));
             RPT_TIMED("rpt_replay_temporal", RPT_LAUNCH_PE(k_rpt_replay, RPT_REPLAY_CTT, gridReplay, block, 0, s, F, *cb, lists[0], lists[1], listCnt + 0, ctr + 2 * 2));
-            RPT_TIMED("rpt_reconnect_temporal", RPT_LAUNCH_E(k_rpt_temporal, gridRecon, blockRecon, 0, s, F, *cb, tilesX, ctr + 2 * 4));
+            if (view != ZR_RPT_VIEW_NONE) RPT_TIMED("rpt_reconnect_temporal", RPT_LAUNCH_VIEW(k_rpt_temporal_view, gridRecon, blockRecon, 0, s, F, *cb, tilesX, ctr + 2 * 4));
+            else RPT_TIMED("rpt_reconnect_temporal", RPT_LAUNCH_E(k_rpt_temporal, gridRecon, blockRecon, 0, s, F, *cb, tilesX, ctr + 2 * 4));
         }
         // nothing after this point reads the PREVIOUS frame's G-buffer, its final reservoirs or scene (the spatial passes read this frame's only)
         if (p->overlap) { HIP_TRY(hipEventRecord(p->evTemporal, s)); p->reuseStream = s; p->haveTemporal = true; }
@@ -2630,13 +2643,15 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
             RPT_TIMED("rpt_sort_spatial", hipLaunchKernelGGL((k_rpt_sort<rpt::RPT_SORT_CTS, rpt::RPT_SORT_STC>), dim3(gridSort.x * 2), dim3(256), 0, s, F, *cb, sortTilesX, F.ox0 / 32u, F.oy0 / 32u, F.mapCtN, F.mapNtC));
         }
         RPT_TIMED("rpt_replay_spatial", RPT_LAUNCH_PE(k_rpt_replay, RPT_REPLAY_CTS, dim3(gridList.x * 2), block, 0, s, F, *cb, lists[2], lists[3], sCnt, ctr + 2 * 5));
-        RPT_TIMED("rpt_reconnect_spatial", RPT_LAUNCH_E(k_rpt_stc, gridStc, blockStc, 0, s, F, *cb, tilesX, ctr + 2 * 7));
+        if (view != ZR_RPT_VIEW_NONE) RPT_TIMED("rpt_reconnect_spatial", RPT_LAUNCH_VIEW(k_rpt_stc_view, gridStc, blockStc, 0, s, F, *cb, tilesX, ctr + 2 * 7));
+        else RPT_TIMED("rpt_reconnect_spatial", RPT_LAUNCH_E(k_rpt_stc, gridStc, blockStc, 0, s, F, *cb, tilesX, ctr + 2 * 7));
         // "Prepare for next iteration" (IndirectLighting.cpp:860-870: std::swap(inputs, outputs)) is the flip itself here: the next round starts from res[currIdx]
         p->currIdx = 1 - p->currIdx;
     }
 #undef RPT_TIMED
 #undef RPT_LAUNCH_E
 #undef RPT_LAUNCH_PE
+#undef RPT_LAUNCH_VIEW
     HIP_TRY(hipGetLastError());
     if (stageCand) p->frameOpen = true;
     // the frame ends with its last stage: the second round when there is one this frame, else ZR_STAGE_SPATIAL; Render() flips once more (:1018-1024)
@@ -2797,6 +2812,14 @@ extern "C" int zr_pass_set_display_option(zr_pass* p, int option, float roughnes
     if (option < ZR_DISPLAY_DEFAULT || option >= ZR_DISPLAY_COUNT) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_display_option: unknown option %d", option);
     if (zr_isnan(roughness_th)) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_display_option: roughness_th is NaN");
     p->displayOption = option; p->roughnessTh = roughness_th;
+    return ZR_OK;
+}
+
+extern "C" int zr_pass_set_rpt_debug_view(zr_pass* p, int view)
+{
+    if (!p || p->kind != ZR_PASS_INDIRECT) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_rpt_debug_view: needs an INDIRECT pass");
+    if (view < ZR_RPT_VIEW_NONE || view >= ZR_RPT_VIEW_COUNT) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_rpt_debug_view: unknown view %d", view);
+    p->rptView = view;      // read by ReSTIR PT only (the other integrators never look at it), from the next frame's first stage on
     return ZR_OK;
 }
 

@@ -7,6 +7,7 @@
 //   zr_tu_rpt_a.hip  explicit instantiations of K11 (k_rpt_pathtrace, k_rpt_pathtrace_tex) and K14 (k_rpt_temporal)
 //   zr_tu_rpt_b.hip  explicit instantiations of K13 (k_rpt_replay)
 //   zr_tu_rpt_d.hip  explicit instantiations of K16 (k_rpt_stc)
+//   zr_tu_rpt_view_{p,t,s}.hip  the reconnection-debug-view instantiations of K11 / K14 / K16 (k_rpt_*_view)
 //   zr_tu_di.hip     K5 - K8 and K10 (zr_kernels_di.h)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -275,8 +276,9 @@ __device__ __forceinline__ void FlushRayCountersCost(const rpt::RptFrame& F, uns
 // PARK: the reservoir's selected reconnection in LDS instead of registers / scratch (zr_rpt.h RcPark: 17 words x 64 lanes = 4.25 KB per one-wave block)
 // PLAIN: the scene's material class (SceneView::plain: opaque uncoated non-metallic dielectrics only); likewise a template constant -- the kernel then has
 // no code for the other lobes (24 283 -> 9 529 VALU instructions; Cornell 1080p 0.853 -> 0.77 ms).  The host launches it only for such scenes.
-template<bool EMISSIVE, bool TEX, bool NODE_CACHE = false, bool PARK = false, bool PLAIN = false>
-__device__ __forceinline__ void RptPathtraceBody(rpt::RptFrame& F, const zr_frame_constants& g, uint32_t tilesX, unsigned long long* counters)
+// VIEW: the instantiation draws the reconnection debug view `view` (zr_rpt.h DebugColor) instead of the radiance; the ordinary kernels are VIEW = false
+template<bool EMISSIVE, bool TEX, bool NODE_CACHE = false, bool PARK = false, bool PLAIN = false, bool VIEW = false>
+__device__ __forceinline__ void RptPathtraceBody(rpt::RptFrame& F, const zr_frame_constants& g, uint32_t tilesX, unsigned long long* counters, uint32_t view = 0)
 {
     const unsigned long long t0 = __builtin_readcyclecounter();
     F.prm.emissive = EMISSIVE ? 1u : 0u; F.prm.textured = TEX ? 1u : 0u;
@@ -307,7 +309,7 @@ __device__ __forceinline__ void RptPathtraceBody(rpt::RptFrame& F, const zr_fram
         }
         { ZR_PROF_SCOPE(ZRP_MISC1); rpt::PtPhaseB(F.sc, F.prm, P, key); }
     }
-    { ZR_PROF_SCOPE(ZRP_MISC2); rpt::PtFinishLane(F.gb, F.prm, F.cur, F.tex, F.finalRGBA, P); }
+    { ZR_PROF_SCOPE(ZRP_MISC2); rpt::PtFinishLane<VIEW>(F.gb, F.prm, F.cur, F.tex, F.finalRGBA, P, view); }
     FlushRayCountersCost(F, counters, cnt, x, y, F.Owns(x, y), t0);
 }
 template<bool EMISSIVE, bool PLAIN = false>
@@ -664,6 +666,74 @@ __global__ void __launch_bounds__(kStcBlock) ZR_WAVES_STC k_rpt_stc(rpt::RptFram
     FlushRayCountersCost(F, counters, cnt, x, y, x != 0xffffffffu && F.Owns(x, y), t0);
 }
 
+// The reconnection debug views (zetaray_amd.h zr_pass_set_rpt_debug_view): the three kernels that can write the frame's radiance, instantiated once more
+// with VIEW = true and the selected view as a run-time argument.  Launched only while a view is selected.  They need not be fast: general material class
+// only (a PLAIN scene runs them too -- the class only removes code), at the occupancy of the general kernels -- K11 in its 4-wave form (textured: 6).
+template<bool EMISSIVE, bool TEX>
+__global__ void __launch_bounds__(kRptBlock) __attribute__((amdgpu_waves_per_eu(TEX ? 6 : ZR_WAVES_PATHTRACE_LARGE_N, TEX ? 6 : ZR_WAVES_PATHTRACE_LARGE_N)))
+k_rpt_pathtrace_view(rpt::RptFrame F, zr_frame_constants g, uint32_t tilesX, unsigned long long* counters, uint32_t view)
+{ RptPathtraceBody<EMISSIVE, TEX, !TEX, false, false, true>(F, g, tilesX, counters, view); }
+template<bool EMISSIVE, bool TEX>
+__global__ void __launch_bounds__(kReconBlock) ZR_WAVES(ZR_WAVES_TEMPORAL_N) k_rpt_temporal_view(rpt::RptFrame F, zr_frame_constants g, uint32_t tilesX, unsigned long long* counters, uint32_t view)
+{      // (k_rpt_temporal with ReconnectTemporalPixel<VIEW = true>: a body of its own, so that the ordinary kernel stays the code it was)
+    const unsigned long long t0 = __builtin_readcyclecounter();
+    F.prm.emissive = EMISSIVE ? 1u : 0u; F.prm.textured = TEX ? 1u : 0u;
+    rpt::SetMaterialClass(F, false);
+    uint32_t x, y; PixelOfThreadB<kReconBlock>(tilesX, F.ox0, F.oy0, &x, &y);
+    // SORT_TEMPORAL: threads take their pixel from a K12 map, which puts reservoirs of equal reconnection depth into the same wave.  Scheduling
+    // only (no wave operation in CtT / TtC); the error bit is ignored because the fused kernel runs both shifts of a pixel
+    if (F.prm.temporalMap && F.Owns(x, y)) { const uint16_t e = (F.prm.temporalMap == 1u ? F.mapCtN : F.mapNtC)[rpt::Pix(F.gb, x, y)]; rpt::DecodeSorted(e & 0x7fffu, x, y); }
+    ZR_TRAV_STACK_B(stack, kReconBlock);
+#if ZR_SCENE_LDS
+    ZR_SCENE_CACHE_FILL(stack, F.sc, kReconBlock);
+#endif
+    ZR_PROF_KERNEL(F.sc, 2);
+    uint32_t cnt[2] = {0u, 0u};
+    if (F.Owns(x, y)) rpt::ReconnectTemporalPixel<true>(F, g, x, y, stack, cnt, view);
+    FlushRayCountersCost(F, counters, cnt, x, y, F.Owns(x, y), t0);
+}
+template<bool EMISSIVE, bool TEX>
+__global__ void __launch_bounds__(kStcBlock) ZR_WAVES(ZR_WAVES_STC_N) k_rpt_stc_view(rpt::RptFrame F, zr_frame_constants g, uint32_t tilesX, unsigned long long* counters, uint32_t view)
+{      // (k_rpt_stc with StcPhase1 - 3<VIEW = true>)
+    const unsigned long long t0 = __builtin_readcyclecounter();
+    F.prm.emissive = EMISSIVE ? 1u : 0u; F.prm.textured = TEX ? 1u : 0u;
+    rpt::SetMaterialClass(F, false);
+    uint32_t x, y; PixelOfThreadB<kStcBlock>(tilesX, F.ox0, F.oy0, &x, &y);
+    // SORT_SPATIAL (ReSTIR_PT_Reconnect_StC.hlsl:133-140): the thread at (x, y) shifts the pixel the NtC map assigns to its position, so the
+    // four wave sums below run over the 64 pixels K12 put together (error bit: nothing to do -- the lane stays in the wave, contributing 0)
+    if (F.prm.sortSpatial && F.Owns(x, y) && !rpt::DecodeSorted(F.mapNtC[rpt::Pix(F.gb, x, y)], x, y)) x = 0xffffffffu;
+    ZR_TRAV_STACK_B(stack, kStcBlock);
+    stack.voteTri = ZR_VOTE_WT_STC;      // (zr_dev_scene.h TravStack::voteTri)
+#if ZR_SCENE_LDS
+    ZR_SCENE_CACHE_FILL(stack, F.sc, kStcBlock);
+#endif
+    uint32_t cnt[2] = {0u, 0u};
+    ZR_PROF_KERNEL(F.sc, 3);
+#if ZR_STC_LDS
+    // (raw words: a __shared__ object may not have initialisers, and StcLane's reservoirs carry default member initialisers)
+    __shared__ __attribute__((aligned(16))) uint32_t stcLaneLds[kStcBlock * ((sizeof(rpt::StcLane) + 15) / 16 * 4)];
+    rpt::StcLane& a = *reinterpret_cast<rpt::StcLane*>(stcLaneLds + threadIdx.x * ((sizeof(rpt::StcLane) + 15) / 16 * 4));
+    a.r_curr.park.p = nullptr; a.r_curr.park.stride = 0; a.r_curr.parked = false; a.r_spatial.park.p = nullptr; a.r_spatial.park.stride = 0; a.r_spatial.parked = false;
+#else
+    rpt::StcLane a;
+    // The general permutation keeps the lane's two reservoirs (304 B) as an object in scratch memory: split into registers they cost it 160 - 220 spilled
+    // VGPRs at its 128 (atrium: 2.72 -> 2.85 ms), whereas the PLAIN permutation, a third of the code, gains from the split (Cornell: 0.578 -> 0.539 ms).
+    ZR_KEEP_IN_MEMORY(a);
+#endif
+    float v1, v2, v3, v4;
+    { ZR_PROF_SCOPE(ZRP_MISC0); rpt::StcPhase0(F, g, x, y, a, v1, v2); }
+    { ZR_PROF_SCOPE(ZRP_MISC1);
+    if (a.valid && a.hasN) rpt::ReconnectCtSPixel(F, g, x, y, stack, cnt); }      // K16 CtS of this pixel (see zr_rpt.h)
+    const float sum1 = WaveSumButterfly(v1), sum2 = WaveSumButterfly(v2);
+    rpt::StcPhase1<true>(F, g, a, sum1, v3, view);
+    const float sum3 = WaveSumButterfly(v3);
+    ZR_PROF_SCOPE(ZRP_MISC2);
+    rpt::StcPhase2<true>(F, g, a, sum1, stack, cnt, v4, view);
+    const float sum4 = WaveSumButterfly(v4);
+    rpt::StcPhase3<true>(F, g, a, sum2 + sum3 + sum4, view);
+    FlushRayCountersCost(F, counters, cnt, x, y, x != 0xffffffffu && F.Owns(x, y), t0);
+}
+
 
 // ------------------------------------------------------------------------------------------------ translation-unit split
 // ZR_RPT_GROUP_*(X): X = `template` in the TU that owns the group (zr_tu_rpt_<letter>.hip), `extern template` everywhere else.  The groups are cut for
@@ -706,4 +776,12 @@ __global__ void __launch_bounds__(kStcBlock) ZR_WAVES_STC k_rpt_stc(rpt::RptFram
 #define ZR_RPT_GROUP_F(X) \
     X __global__ void k_rpt_replay<RPT_REPLAY_CTS, true, true> ZR_RPT_ARGS_LIST; X __global__ void k_rpt_replay<RPT_REPLAY_CTS, true, false> ZR_RPT_ARGS_LIST; \
     X __global__ void k_rpt_replay<RPT_REPLAY_CTS, false, true> ZR_RPT_ARGS_LIST; X __global__ void k_rpt_replay<RPT_REPLAY_CTS, false, false> ZR_RPT_ARGS_LIST;
-#define ZR_RPT_GROUPS_PRODUCT(X) ZR_RPT_GROUP_A(X) ZR_RPT_GROUP_B(X) ZR_RPT_GROUP_D(X) ZR_RPT_GROUP_E(X) ZR_RPT_GROUP_F(X) ZR_RPT_GROUP_G(X) ZR_RPT_GROUP_H(X) ZR_RPT_GROUP_I(X)
+// the reconnection debug views: K11 (VP), K14 (VT), K16 (VS)
+#define ZR_RPT_ARGS_VIEW (rpt::RptFrame, zr_frame_constants, uint32_t, unsigned long long*, uint32_t)
+#define ZR_RPT_VIEW_PERMS(X, kern) \
+    X __global__ void kern<true, true> ZR_RPT_ARGS_VIEW; X __global__ void kern<true, false> ZR_RPT_ARGS_VIEW; \
+    X __global__ void kern<false, true> ZR_RPT_ARGS_VIEW; X __global__ void kern<false, false> ZR_RPT_ARGS_VIEW;
+#define ZR_RPT_GROUP_VP(X) ZR_RPT_VIEW_PERMS(X, k_rpt_pathtrace_view)
+#define ZR_RPT_GROUP_VT(X) ZR_RPT_VIEW_PERMS(X, k_rpt_temporal_view)
+#define ZR_RPT_GROUP_VS(X) ZR_RPT_VIEW_PERMS(X, k_rpt_stc_view)
+#define ZR_RPT_GROUPS_PRODUCT(X) ZR_RPT_GROUP_A(X) ZR_RPT_GROUP_B(X) ZR_RPT_GROUP_D(X) ZR_RPT_GROUP_E(X) ZR_RPT_GROUP_F(X) ZR_RPT_GROUP_G(X) ZR_RPT_GROUP_H(X) ZR_RPT_GROUP_I(X) ZR_RPT_GROUP_VP(X) ZR_RPT_GROUP_VT(X) ZR_RPT_GROUP_VS(X)

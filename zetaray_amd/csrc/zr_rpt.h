@@ -1606,8 +1606,53 @@ struct RptTex   // per-pass auxiliary planes
     uint8_t* neighbor;   // RG8_UINT
 };
 
+// Util.hlsli:69-139: the reconnection debug views (zetaray_amd.h zr_rpt_debug_view holds the colour tables).  A view replaces the radiance a
+// kernel is about to write to FINAL with a constant colour chosen from the pixel's reconnection; NONE (and a class no branch names) leaves it alone.
+enum RptDebugView : uint32_t { RPT_VIEW_NONE = 0, RPT_VIEW_K, RPT_VIEW_CASE, RPT_VIEW_FOUND_CONNECTION, RPT_VIEW_LOBE_K_MIN_1, RPT_VIEW_LOBE_K };
+ZR_HD void DebugColor(const Reconnection& rc, uint32_t view, V3& c)
+{
+    if (view == RPT_VIEW_NONE) return;
+    if (view == RPT_VIEW_K)
+    {
+        if (rc.Empty()) c = v3(0.0f, 0.0f, 0.0f);
+        else if (rc.k == 2) c = v3(0.1f, 0.25f, 0.88f);
+        else if (rc.k == 3) c = v3(0.13f, 0.55f, 0.14f);
+        else if (rc.k == 4) c = v3(0.69f, 0.45f, 0.1f);
+        else if (rc.k >= 5) c = v3(0.88f, 0.08f, 0.1f);
+    }
+    else if (view == RPT_VIEW_CASE)
+    {
+        if (rc.Empty()) c = v3(0.0f, 0.0f, 0.0f);
+        else if (rc.IsCase1()) c = v3(0.85f, 0.096f, 0.1f);
+        else if (rc.IsCase2()) c = v3(0.13f, 0.6f, 0.14f);
+        else if (rc.IsCase3()) c = v3(0.1f, 0.27f, 0.888f);
+    }
+    else if (view == RPT_VIEW_FOUND_CONNECTION) c = !rc.Empty() ? v3(0.234f, 0.12f, 0.2134f) : v3(0.0f, 0.0f, 0.0f);
+    else if (view == RPT_VIEW_LOBE_K_MIN_1)
+    {
+        if (rc.Empty()) c = v3(0.0f, 0.0f, 0.0f);
+        else if (rc.lobe_k_min_1 == LOBE_DIFFUSE_R) c = v3(0.384f, 0.12f, 0.2134f);
+        else if (rc.lobe_k_min_1 == LOBE_GLOSSY_R) c = v3(0.12f, 0.4284f, 0.2134f);
+        else if (rc.lobe_k_min_1 == LOBE_GLOSSY_T) c = v3(0.1134f, 0.12f, 0.634f);
+        else if (rc.lobe_k_min_1 == LOBE_DIFFUSE_T) c = v3(0.25f, 0.25f, 0.25f);
+        else c = v3(0.55f, 0.55f, 0.0f);
+    }
+    else if (view == RPT_VIEW_LOBE_K)
+    {
+        if (rc.Empty() || rc.IsCase3()) c = v3(0.0f, 0.0f, 0.0f);
+        else if (rc.lobe_k == LOBE_DIFFUSE_R) c = v3(0.384f, 0.12f, 0.2134f);
+        else if (rc.lobe_k == LOBE_GLOSSY_R) c = v3(0.12f, 0.284f, 0.2134f);
+        else if (rc.lobe_k == LOBE_GLOSSY_T) c = v3(0.1134f, 0.12f, 0.634f);
+        else if (rc.lobe_k == LOBE_DIFFUSE_T) c = v3(0.25f, 0.25f, 0.0f);
+        else c = v3(0.25f, 0.25f, 0.25f);
+    }
+}
+
 // main() epilogue (ReSTIR_PT_PathTrace.hlsl:526-559)
-ZR_HD void PtFinishLane(const GBuf& gb, const RptParams& prm, const ResPlanes& out, const RptTex& tex, float* finalRGBA, PTLane& P)
+// VIEW (here and in the reuse stages below): the kernel instantiation draws the debug view `view`.  A compile-time property, so that the
+// ordinary kernels (VIEW = false, view unused) compile to the code they had before the views existed (docs/NEGATIVE_RESULTS.md round 6).
+template<bool VIEW = false>
+ZR_HD void PtFinishLane(const GBuf& gb, const RptParams& prm, const ResPlanes& out, const RptTex& tex, float* finalRGBA, PTLane& P, uint32_t view = RPT_VIEW_NONE)
 {
     if (!P.valid) return;
     const size_t px = Pix(gb, P.x, P.y);
@@ -1620,6 +1665,7 @@ ZR_HD void PtFinishLane(const GBuf& gb, const RptParams& prm, const ResPlanes& o
     if (prm.doTemporal) tex.target[px] = f4(Sanitize3(r.target), 0.0f);
     else
     {
+        if (VIEW) DebugColor(r.rc, view, P.li);
         V3 li = any_nan(P.li) ? v3(0.0f) : P.li;
         float* o = finalRGBA + 4 * px;
         if (prm.accumulate) { o[0] += li.x; o[1] += li.y; o[2] += li.z; }
@@ -1627,9 +1673,11 @@ ZR_HD void PtFinishLane(const GBuf& gb, const RptParams& prm, const ResPlanes& o
     }
 }
 
-// Util.hlsli:141-159
-ZR_HD void WriteOutputColor(const zr_frame_constants& g, float* finalRGBA, size_t px, V3 li)
+// Util.hlsli:141-159 (toBlack = filterToBlackWhenDebugViewEnabled: the early writes of a frame drawn with a view store / add 0)
+template<bool VIEW = false>
+ZR_HD void WriteOutputColor(const zr_frame_constants& g, float* finalRGBA, size_t px, V3 li, uint32_t view = RPT_VIEW_NONE, bool toBlack = true)
 {
+    if (VIEW && toBlack && view != RPT_VIEW_NONE) li = v3(0.0f);
     li = any_nan(li) ? v3(0.0f) : li;
     float* o = finalRGBA + 4 * px;
     if (g.accumulate && g.camera_static && g.num_frames_camera_static > 1) { o[0] += li.x; o[1] += li.y; o[2] += li.z; }
@@ -2147,7 +2195,8 @@ ZR_HD void MoveXk(const SceneView& sc, Reconnection& rc, bool currToPrev, bool s
 // for one pixel.  The reference runs them as two dispatches; both only read/write this pixel's current reservoir (CtT
 // writes w_sum, TtC reads it back) and read the previous frame's set, so running them back to back per pixel gives the
 // same result and shares the G-buffer reconstruction and the temporal-pixel search.
-ZR_HD void ReconnectTemporalPixel(const RptFrame& F, const zr_frame_constants& g, uint32_t x, uint32_t y, TravStack stack, uint32_t* cnt)
+template<bool VIEW = false>
+ZR_HD void ReconnectTemporalPixel(const RptFrame& F, const zr_frame_constants& g, uint32_t x, uint32_t y, TravStack stack, uint32_t* cnt, uint32_t view = RPT_VIEW_NONE)
 {
     const size_t px = Pix(F.gb, x, y);
     GFlags flags = DecodeFlags(F.gb.mr[px]);
@@ -2196,7 +2245,7 @@ ZR_HD void ReconnectTemporalPixel(const RptFrame& F, const zr_frame_constants& g
     r_curr.target = xyz(F.tex.target[px]);
     if (!tp.ok)
     {
-        if (!doSpatial) WriteOutputColor(g, F.finalRGBA, px, r_curr.target * r_curr.W);
+        if (!doSpatial) WriteOutputColor<VIEW>(g, F.finalRGBA, px, r_curr.target * r_curr.W, view);
         return;
     }
     Reservoir r_prev = Load_NonReconnection(F.prev, pp);
@@ -2208,7 +2257,7 @@ ZR_HD void ReconnectTemporalPixel(const RptFrame& F, const zr_frame_constants& g
         r_curr.W = targetLum > 0 ? r_curr.w_sum / targetLum : 0;
         r_curr.M = M_new;
         r_curr.WriteReservoirData2(F.cur, px, M_max);
-        if (!doSpatial) WriteOutputColor(g, F.finalRGBA, px, r_curr.target * r_curr.W);
+        if (!doSpatial) WriteOutputColor<VIEW>(g, F.finalRGBA, px, r_curr.target * r_curr.W, view);
         return;
     }
     r_prev.Load_Reconnection(F.prev, pp, F.prm.emissive != 0);
@@ -2236,7 +2285,12 @@ ZR_HD void ReconnectTemporalPixel(const RptFrame& F, const zr_frame_constants& g
         if (doSpatial) F.tex.target[px] = f4(Sanitize3(r_curr.target), 0.0f);
     }
     else r_curr.WriteReservoirData(F.cur, px, M_max);
-    if (!doSpatial) WriteOutputColor(g, F.finalRGBA, px, r_curr.target * r_curr.W);
+    if (!doSpatial)
+    {
+        V3 li = r_curr.target * r_curr.W;
+        if (VIEW) DebugColor(r_curr.rc, view, li);
+        WriteOutputColor<VIEW>(g, F.finalRGBA, px, li, view, false);
+    }
 }
 
 // cheap predicates for the replay work lists (supersets of the pixels the replay passes act on; the passes re-check).  They return the replay
@@ -2539,7 +2593,8 @@ ZR_HD void StcPhase0(const RptFrame& F, const zr_frame_constants& g, uint32_t x,
     s2 = a.w_sum_loaded * (a.hasN ? 0.0f : 1.0f);
 }
 // phase 1: lanes without a neighbour finish; the others load the spatial reservoir; contributes sum3
-ZR_HD void StcPhase1(const RptFrame& F, const zr_frame_constants& g, StcLane& a, float sum1, float& s3)
+template<bool VIEW = false>
+ZR_HD void StcPhase1(const RptFrame& F, const zr_frame_constants& g, StcLane& a, float sum1, float& s3, uint32_t view = RPT_VIEW_NONE)
 {
     s3 = 0;
     if (!a.valid) return;
@@ -2551,7 +2606,7 @@ ZR_HD void StcPhase1(const RptFrame& F, const zr_frame_constants& g, StcLane& a,
     if (!a.hasN)
     {
         if (F.prm.boiling) StcSuppress(waveAvgExclusive, a.r_curr);
-        WriteOutputColor(g, F.finalRGBA, a.px, a.r_curr.target * a.r_curr.W);
+        WriteOutputColor<VIEW>(g, F.finalRGBA, a.px, a.r_curr.target * a.r_curr.W, view);
         StcCopyToNextFrame(F, a.px, a.r_curr, a.M_max);
         return;
     }
@@ -2562,7 +2617,8 @@ ZR_HD void StcPhase1(const RptFrame& F, const zr_frame_constants& g, StcLane& a,
     s3 = a.r_curr.w_sum * (a.spatialEmpty ? 1.0f : 0.0f);
 }
 // phase 2: lanes whose neighbour is empty finish; the others shift + resample; contributes sum4
-ZR_HD void StcPhase2(const RptFrame& F, const zr_frame_constants& g, StcLane& a, float sum1, TravStack stack, uint32_t* cnt, float& s4)
+template<bool VIEW = false>
+ZR_HD void StcPhase2(const RptFrame& F, const zr_frame_constants& g, StcLane& a, float sum1, TravStack stack, uint32_t* cnt, float& s4, uint32_t view = RPT_VIEW_NONE)
 {
     s4 = 0;
     if (!a.valid || !a.hasN) return;
@@ -2574,7 +2630,7 @@ ZR_HD void StcPhase2(const RptFrame& F, const zr_frame_constants& g, StcLane& a,
         a.r_curr.W = targetLum > 0 ? a.r_curr.w_sum / targetLum : 0;
         a.r_curr.M = a.M_new;
         StcCopyToNextFrame(F, a.px, a.r_curr, a.M_max);
-        WriteOutputColor(g, F.finalRGBA, a.px, a.r_curr.target * a.r_curr.W);
+        WriteOutputColor<VIEW>(g, F.finalRGBA, a.px, a.r_curr.target * a.r_curr.W, view);
         return;
     }
     a.resample = true;
@@ -2606,7 +2662,8 @@ ZR_HD void StcPhase2(const RptFrame& F, const zr_frame_constants& g, StcLane& a,
     s4 = a.r_curr.w_sum;
 }
 // phase 3: boiling suppression with the full wave sum, write
-ZR_HD void StcPhase3(const RptFrame& F, const zr_frame_constants& g, StcLane& a, float waveSum)
+template<bool VIEW = false>
+ZR_HD void StcPhase3(const RptFrame& F, const zr_frame_constants& g, StcLane& a, float waveSum, uint32_t view = RPT_VIEW_NONE)
 {
     if (!a.resample) return;
     if (F.prm.boiling)
@@ -2616,7 +2673,9 @@ ZR_HD void StcPhase3(const RptFrame& F, const zr_frame_constants& g, StcLane& a,
     }
     if (a.changed) a.r_curr.Write(F.prev, a.px, a.M_max, F.prm.emissive != 0);
     else StcCopyToNextFrame(F, a.px, a.r_curr, a.M_max);
-    WriteOutputColor(g, F.finalRGBA, a.px, a.r_curr.target * a.r_curr.W);
+    V3 li = a.r_curr.target * a.r_curr.W;
+    if (VIEW) DebugColor(a.r_curr.rc, view, li);
+    WriteOutputColor<VIEW>(g, F.finalRGBA, a.px, li, view, false);
 }
 
 // canonical 64-lane sum (xor butterfly, strides 1, 2, 4, 8, 16, 32): what the device computes with DPP / shuffles

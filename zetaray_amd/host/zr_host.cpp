@@ -517,6 +517,7 @@ void IndirectLighting::SetSortSpatial(bool b) { SetFlag(ZR_IND_SORT_SPATIAL, b);
 void IndirectLighting::SetTexFilter(uint32_t f) { m_params.tex_filter = f; ZR_CHECK(zr_pass_set_params(m_pass, &m_params)); }
 void IndirectLighting::SetBoilingSuppression(bool b) { SetFlag(ZR_IND_BOILING_SUPPRESSION, b); }
 void IndirectLighting::SetPathRegularization(bool b) { SetFlag(ZR_IND_PATH_REGULARIZATION, b); }
+void IndirectLighting::SetDebugView(RPT_DEBUG_VIEW v) { m_debugView = v; ZR_CHECK(zr_pass_set_rpt_debug_view(m_pass, (int)v)); }
 void IndirectLighting::SetAlphaMin(float a) { m_params.alpha_min = a * a; ZR_CHECK(zr_pass_set_params(m_pass, &m_params)); }
 void* IndirectLighting::GetOutput(SHADER_OUT_RES i) const
 {
@@ -608,6 +609,15 @@ int zrh_render_sequence_tuned(const zr_scene_desc* desc, const zr_frame_constant
     g_tuning = nullptr;
     return r;
 }
+// ... with a reconnection debug view selected on the indirect pass before the first frame (IndirectLighting::SetDebugView)
+static int g_debugView = 0;
+int zrh_render_sequence_debug_view(const zr_scene_desc* desc, const zr_frame_constants* cbs, uint32_t n, uint32_t w, uint32_t h, int integrator, int view, float* finalOut)
+{
+    g_debugView = view;
+    const int r = zrh_render_sequence3(desc, cbs, n, w, h, integrator, finalOut, nullptr, 0, 0);
+    g_debugView = 0;
+    return r;
+}
 int zrh_render_sequence2(const zr_scene_desc* desc, const zr_frame_constants* cbs, uint32_t n, uint32_t w, uint32_t h, int integrator, float* finalOut, float* directOut)
 { return zrh_render_sequence3(desc, cbs, n, w, h, integrator, finalOut, directOut, 0, 0); }
 
@@ -631,6 +641,7 @@ int zrh_render_sequence3(const zr_scene_desc* desc, const zr_frame_constants* cb
             ind.SetLightPresamplingParams(pre.IsPresamplingEnabled(), presampleSets, presampleSize);
             if (directOut) di.SetLightPresamplingParams(pre.IsPresamplingEnabled(), presampleSets, presampleSize);
         }
+        if (g_debugView) ind.SetDebugView((RenderPass::IndirectLighting::RPT_DEBUG_VIEW)g_debugView);
         if (const zrh_tuning* t = g_tuning)
         {   // what the reference's settings UI does between frames: one callback per knob (IndirectLighting.cpp:1468-1600, DirectLighting.cpp:374-410)
             if (t->max_non_tr >= 0) ind.SetMaxNonTrBounces(t->max_non_tr);

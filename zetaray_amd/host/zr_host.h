@@ -436,6 +436,10 @@ namespace RenderPass {
         void SetBoilingSuppression(bool b);
         void SetPathRegularization(bool b);
         void SetAlphaMin(float alphaMin);                 // "Alpha_min (Reconnection)"; the constant buffers hold its square (IndirectLighting.cpp:1593-1600)
+        // "Debug View" (DebugViewCallback, IndirectLighting.cpp:1543-1550): ReSTIR PT's reconnection views; only FINAL changes (zetaray_amd.h zr_pass_set_rpt_debug_view)
+        enum class RPT_DEBUG_VIEW { NONE, K, CASE, FOUND_CONNECTION, CONNECTION_LOBE_K_MIN_1, CONNECTION_LOBE_K, COUNT };
+        void SetDebugView(RPT_DEBUG_VIEW v);
+        RPT_DEBUG_VIEW DebugView() const { return m_debugView; }
         const zr_params& Params() const { return m_params; }
         // device pointer of the FINAL plane (RGBA32F)
         void* GetOutput(SHADER_OUT_RES i) const;
@@ -451,6 +455,7 @@ namespace RenderPass {
     private:
         void SetFlag(uint32_t bit, bool on);
         zr_params m_params{};
+        RPT_DEBUG_VIEW m_debugView = RPT_DEBUG_VIEW::NONE;
     };
 }
 

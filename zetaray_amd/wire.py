@@ -151,6 +151,8 @@ TONEMAP_NONE, TONEMAP_NEUTRAL, TONEMAP_AGX_DEFAULT, TONEMAP_AGX_GOLDEN, TONEMAP_
 (DISPLAY_DEFAULT, DISPLAY_BASE_COLOR, DISPLAY_NORMAL, DISPLAY_METALNESS_ROUGHNESS, DISPLAY_COAT_WEIGHT, DISPLAY_COAT_COLOR, DISPLAY_ROUGHNESS_TH,
  DISPLAY_EMISSIVE, DISPLAY_TRANSMISSION, DISPLAY_DEPTH, DISPLAY_COUNT) = range(11)
 DISPLAY_ROUGHNESS_TH_DEFAULT = 1.0
+# enum zr_rpt_debug_view (RPT_DEBUG_VIEW, IndirectLighting_Common.h:58-67): zr_pass_set_rpt_debug_view
+RPT_VIEW_NONE, RPT_VIEW_K, RPT_VIEW_CASE, RPT_VIEW_FOUND_CONNECTION, RPT_VIEW_LOBE_K_MIN_1, RPT_VIEW_LOBE_K, RPT_VIEW_COUNT = range(7)
 OUT_PICK_MASK = 50          # ZR_PASS_DISPLAY: R8, render size (zr_pass_set_picked_instances)
 
 
