@@ -453,7 +453,13 @@ int zr_device_synchronize(int device);
 /* The same protocol for the other passes with cross-pixel reuse (SURVEY 8(e) "Collective"): bytes per pixel of a halo transfer =
    the pass's reservoir planes back to back: ReSTIR PT 62, ReSTIR GI 40 (A, B, C), ReSTIR DI emissive 24 (A, B), sun + sky DI 13.
    DI passes: TEMPORAL stage -> exchange ZR_HALO_POST_TEMPORAL -> SPATIAL stage (the exchanged set is also the one the next
-   frame reprojects into, so no ZR_HALO_FINAL is needed).  ReSTIR GI renders in the TEMPORAL stage and needs ZR_HALO_FINAL only. */
+   frame reprojects into, so no ZR_HALO_FINAL is needed).  ReSTIR GI renders in the TEMPORAL stage and needs ZR_HALO_FINAL only.
+   With its spatial stage on (zr_pass_set_rgi_spatial) ReSTIR GI runs k_rgi in ZR_STAGE_TEMPORAL and k_rgi_spatial in ZR_STAGE_SPATIAL.  The spatial kernel
+   gathers from the set k_rgi has just written, which is also the set the next frame reads as "previous" -- the reservoir sets flip at the end of the TEMPORAL
+   stage -- so the same ZR_HALO_FINAL exchange (40 B/px), placed BETWEEN the two stages of every frame, serves both readers and nothing is exchanged after
+   the frame.  The setting may change between frames: the first frame rendered with the stage on after frames without it still needs the ZR_HALO_FINAL
+   exchange the previous frame did not make (before its TEMPORAL stage, as without the stage), besides its own between the stages.  Taps beyond the apron
+   are rejected like taps beyond the frame, so on a split frame the radius must keep them inside it: ceil(1.1707 radius_px + 0.5) <= the apron width. */
 int zr_pass_halo_bytes_per_pixel(zr_pass* pass, uint32_t* bytes);
 int zr_pass_render_stage(zr_pass* pass, void* hip_stream, const zr_frame_constants* cb, const zr_scene* scene,
                          zr_gbuffer* gbuffer, int stages);
@@ -558,6 +564,15 @@ typedef enum zr_rpt_debug_view
    value is stored and has no effect.  Works unchanged with zr_pass_set_owned_rect (a view is per pixel) and with zr_pass_set_frame_overlap.
    ZR_ERR_INVALID_ARG for a null pass, another pass kind or a value outside the enum. */
 int zr_pass_set_rpt_debug_view(zr_pass* pass, int view);
+/* ZR_PASS_INDIRECT, ReSTIR GI only: the spatial reuse stage (zetaray_amd/csrc/zr_rgi_spatial.h holds its contract; the reference's ReSTIR GI is
+   temporal-only -- ReSTIR_GI/PairwiseMIS.hlsli::SpatialResample is dead code there -- so this stage is defined by this library).  num_samples 0
+   (default) = off: the pass is exactly what it was.  1..2 = neighbours resampled per pixel; radius_px in (0, 64], 0 = default 16.  Takes effect with
+   the next frame.  While on, zr_pass_render launches k_rgi, then k_rgi_spatial on the same stream (timer "rgi_spatial", ray-counter slot "rgi_spatial");
+   zr_pass_render_stage runs k_rgi in ZR_STAGE_TEMPORAL and the spatial kernel in ZR_STAGE_SPATIAL.  ZR_OUT_FINAL gets the spatial stage's radiance,
+   one contribution per pixel and frame (k_rgi's own goes to a scratch plane); k_rgi writes its reservoirs every frame and the spatial stage writes
+   nothing back to them. ZR_IND_SPATIAL_RESAMPLE in zr_params stays ignored by ReSTIR GI.  With another integrator the value is stored and
+   has no effect.  ZR_ERR_INVALID_ARG for a null pass, another pass kind, num_samples > 2, a NaN / negative / > 64 radius. */
+int zr_pass_set_rgi_spatial(zr_pass* pass, uint32_t num_samples, float radius_px);
 /* ZR_PASS_DISPLAY: outline the picked instances (DisplayPass::DrawPicked, Display.cpp:293-400; DrawPicked.hlsl, Sobel.hlsl).  mesh_idx: n instance indices
    as zr_pass_read_pick returns them, kept until the next call; n = 0 clears.  They are checked against the scene passed to zr_pass_render
    (ZR_ERR_INVALID_ARG for an index that is not one of its instances).  After the display kernel, on the same stream, for each pick in order:

@@ -61,6 +61,7 @@ EXPORTS = [
     "zr_pass_set_inscattering", "zr_pass_bind_inscattering",
     "zr_pass_set_display_option", "zr_pass_set_picked_instances",
     "zr_pass_set_rpt_debug_view",
+    "zr_pass_set_rgi_spatial",
 ]
 STAGE_TEMPORAL, STAGE_SPATIAL, STAGE_ALL = 1, 2, 3
 STAGE_SPATIAL2 = 4          # ReSTIR PT, num_spatial_passes = 2 on tiles: the second round, behind one more HALO_POST_TEMPORAL exchange
@@ -134,6 +135,7 @@ def lib():
         L.zr_pass_set_display_option.argtypes = [vp, i32, C.c_float]
         L.zr_pass_set_picked_instances.argtypes = [vp, vp, u32]
         L.zr_pass_set_rpt_debug_view.argtypes = [vp, i32]
+        L.zr_pass_set_rgi_spatial.argtypes = [vp, u32, C.c_float]
         L.zr_pass_halo_pack_all.argtypes = [vp, vp, vp, i32, vp, u32, vp, C.c_size_t]
         L.zr_pass_halo_unpack_all.argtypes = [vp, vp, vp, i32, vp, u32, vp, C.c_size_t]
         L.zr_pass_set_owned_rect.argtypes = [vp, u32, u32, u32, u32]
@@ -399,6 +401,11 @@ class Pass:
     def set_rpt_debug_view(self, view):
         _check(lib().zr_pass_set_rpt_debug_view(self.h, int(view)))
 
+    # INDIRECT pass: ReSTIR GI's spatial reuse stage (zetaray_amd.h zr_pass_set_rgi_spatial): num_samples 0 = off, 1..2 neighbours per pixel within radius_px
+    # (0 = the default 16), from the next frame on
+    def set_rgi_spatial(self, num_samples, radius_px=0.0):
+        _check(lib().zr_pass_set_rgi_spatial(self.h, int(num_samples), float(radius_px)))
+
     # DISPLAY pass: outline these instances (zr_pass_read_pick values) after the display kernel; [] clears (zetaray_amd.h zr_pass_set_picked_instances)
     def set_picked_instances(self, mesh_idx):
         a = np.ascontiguousarray(mesh_idx, np.uint32).reshape(-1)
@@ -646,6 +653,10 @@ class Renderer:
             return
         self.scene.invalidate_alias_table()
         self._alias_ready = False
+
+    def set_rgi_spatial(self, num_samples, radius_px=0.0):
+        """ReSTIR GI: the spatial reuse stage of the indirect pass (Pass.set_rgi_spatial); stored without effect by the other integrators"""
+        self.p_indirect.set_rgi_spatial(num_samples, radius_px)
 
     _SKY_FIELDS = ("sun_dir", "sun_illuminance", "planet_radius", "atmosphere_altitude", "g", "rayleigh_sigma_s_color", "rayleigh_sigma_s_scale",
                    "ozone_sigma_a_color", "ozone_sigma_a_scale", "mie_sigma_s", "mie_sigma_a")

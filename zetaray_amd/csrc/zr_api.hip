@@ -18,6 +18,7 @@
 #include "zr_rdi.h"
 #include "zr_sdi.h"
 #include "zr_rgi.h"
+#include "zr_rgi_spatial.h"
 #include "zr_bvh.h"
 #include "zr_taa.h"
 #include "zr_svgf.h"
@@ -486,6 +487,8 @@ __global__ void __launch_bounds__(kBlock) k_trace_rays_any(SceneView sc, const F
 // threads per block (see kRptBlock in zr_kernels.h): one-wave blocks pay for the emissive DI kernels (K5 0.580 -> 0.568 ms
 // Cornell, 5.42 -> 5.12 ms atrium; K6 0.258 -> 0.241 / 2.99 -> 2.61 ms), not for the sun + sky ones (K7 / K8 within +-0.6 %)
 #include "zr_kernels_di.h"
+// the spatial reuse stage of ReSTIR GI: defined in zr_tu_rgi_spatial.hip, launched by RenderReSTIR_GI
+__global__ void k_rgi_spatial(rgi::GiFrame F, zr_frame_constants g, uint32_t tilesX, unsigned long long* counters, rgi::SpatialParams sp);
 ZR_DI_GROUP(extern template, false)
 ZR_DI_GROUP(extern template, true)
 static const uint16_t kRdiSampleSet[64] = {
@@ -814,7 +817,7 @@ static constexpr int kMaxTimers = 64;
 // ray-counter slots (pairs of u64 on the device): 0 = wavefront path tracer, 1.. = ReSTIR PT kernels in launch order
 static constexpr int kCounterSlots = 16;
 static const char* const kCounterNames[kCounterSlots] = {"trace", "rpt_pathtrace", "rpt_replay_ctt", "rpt_replay_ttc", "rpt_reconnect_temporal",
-    "rpt_replay_cts", "rpt_replay_stc", "rpt_reconnect_spatial", "rdi_temporal", "rdi_spatial", "rgi", "sdi_temporal", "sdi_spatial", "", "", ""};
+    "rpt_replay_cts", "rpt_replay_stc", "rpt_reconnect_spatial", "rdi_temporal", "rdi_spatial", "rgi", "sdi_temporal", "sdi_spatial", "rgi_spatial", "", ""};
 
 struct zr_pass
 {
@@ -889,6 +892,9 @@ struct zr_pass
     int displayOption = ZR_DISPLAY_DEFAULT; float roughnessTh = 1.0f;      // DISPLAY: zr_pass_set_display_option (Display.cpp:69-73)
     // INDIRECT: zr_pass_set_rpt_debug_view (IndirectLighting.cpp:1543-1550); rptViewFrame = the view of the frame being rendered (latched by its first stage)
     int rptView = ZR_RPT_VIEW_NONE, rptViewFrame = ZR_RPT_VIEW_NONE;
+    // INDIRECT: zr_pass_set_rgi_spatial (zr_rgi_spatial.h).  rgiSpatialFrame = the setting of the frame being rendered (latched by its first stage);
+    // rgiScratch = the plane k_rgi's own radiance goes to while the spatial stage writes FINAL (allocated by the first frame that needs it)
+    rgi::SpatialParams rgiSpatial{0u, rgi::kSpatialDefaultRadius}, rgiSpatialFrame{0u, rgi::kSpatialDefaultRadius}; DevBuf<float> rgiScratch;
     std::vector<uint32_t> picks; DevBuf<uint8_t> pickMask; DevBuf<int4> pickTris; DevBuf<uint32_t> pickCount;     // DISPLAY: zr_pass_set_picked_instances
     uint32_t pickMaskW = 0, pickMaskH = 0;
     uint32_t own[4] = {0, 0, 0, 0};                // owned rect (global pixels); w == 0 -> the whole G-buffer rect
@@ -2364,8 +2370,10 @@ static int RenderDirectSky(zr_pass* p, hipStream_t s, const zr_frame_constants* 
     return ZR_OK;
 }
 
-// IndirectLighting::RenderReSTIR_GI (IndirectLighting.cpp:277-368) + the Render() tail (:1006-1025)
-static int RenderReSTIR_GI(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, const zr_scene* sc, zr_gbuffer* gb)
+// IndirectLighting::RenderReSTIR_GI (IndirectLighting.cpp:277-368) + the Render() tail (:1006-1025).  ZR_STAGE_TEMPORAL: k_rgi (the reference's whole pass);
+// ZR_STAGE_SPATIAL: k_rgi_spatial when zr_pass_set_rgi_spatial has switched it on (zr_rgi_spatial.h; no reference counterpart), else nothing.  The reservoir
+// sets flip at the end of the TEMPORAL stage, so between the stages -- as after the frame -- the set k_rgi wrote is [1 - currIdx]: the set ZR_HALO_FINAL moves.
+static int RenderReSTIR_GI(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, const zr_scene* sc, zr_gbuffer* gb, int stages)
 {
     using namespace rgi;
     const zr_params& ip = p->params;
@@ -2373,26 +2381,51 @@ static int RenderReSTIR_GI(zr_pass* p, hipStream_t s, const zr_frame_constants* 
     F.sc = FrameView(sc, cb); F.gb = gb->View(); F.gbPrev = gb->PrevView();
     F.sc.texFilter = ip.tex_filter;
     if (int orc = ResolveOwnedRect(p, gb, cb, &F.ox0, &F.oy0, &F.ow, &F.oh)) return orc;
-    F.cur.A = p->giA[p->currIdx].p; F.cur.B = p->giB[p->currIdx].p; F.cur.C = p->giC[p->currIdx].p;
-    F.prev.A = p->giA[1 - p->currIdx].p; F.prev.B = p->giB[1 - p->currIdx].p; F.prev.C = p->giC[1 - p->currIdx].p;
-    F.finalRGBA = p->finalRGBA.p;
     GiParams& prm = F.prm;
     prm.flags = ip.flags; prm.maxNonTrBounces = ip.max_non_tr_bounces; prm.maxGlossyTrBounces = ip.max_glossy_tr_bounces;
     prm.numSampleSets = ip.presampling ? ip.num_sample_sets : 0u;
     prm.accumulate = (cb->accumulate && cb->camera_static) ? 1u : 0u;
-    prm.doTemporal = ((ip.flags & ZR_IND_TEMPORAL_RESAMPLE) && p->temporalValid && gb->numRendered >= 2) ? 1u : 0u;
-    prm.writeReservoirs = (prm.doTemporal || !p->temporalValid) ? 1u : 0u;
     prm.M_max = (float)ip.m_max_temporal;
     prm.useLVG = (ip.use_lvg && ip.presampling) ? 1u : 0u;
     prm.textured = sc->view.tex.count ? 1u : 0u;
-    if (prm.useLVG && !sc->view.lvg) return Fail(ZR_ERR_NOT_INITIALIZED, "light voxel grid missing: render the PRELIGHTING pass with use_lvg first");
     const uint32_t tilesX = (F.ow + 15) / 16, tilesY = (F.oh + 15) / 16;
-    TimerBegin(p, s, "rgi");
-    hipLaunchKernelGGL(sc->view.tex.count ? k_rgi_tex : PlainClass(sc, gb) ? k_rgi<true> : k_rgi<false>, dim3(tilesX * tilesY * (256 / kRgiBlock)), dim3(kRgiBlock), 0, s, F, *cb, tilesX, p->counters.p + 2 * 10);
-    TimerEnd(p, s);
-    HIP_TRY(hipGetLastError());
-    p->temporalValid = true;
-    p->currIdx = 1 - p->currIdx;
+    if (stages & ZR_STAGE_TEMPORAL)
+    {
+        p->rgiSpatialFrame = p->rgiSpatial;
+        const bool spatial = p->rgiSpatialFrame.numSamples != 0;
+        F.cur.A = p->giA[p->currIdx].p; F.cur.B = p->giB[p->currIdx].p; F.cur.C = p->giC[p->currIdx].p;
+        F.prev.A = p->giA[1 - p->currIdx].p; F.prev.B = p->giB[1 - p->currIdx].p; F.prev.C = p->giC[1 - p->currIdx].p;
+        F.finalRGBA = p->finalRGBA.p;
+        prm.doTemporal = ((ip.flags & ZR_IND_TEMPORAL_RESAMPLE) && p->temporalValid && gb->numRendered >= 2) ? 1u : 0u;
+        prm.writeReservoirs = (prm.doTemporal || !p->temporalValid) ? 1u : 0u;
+        if (spatial)
+        {   // FINAL gets one contribution per pixel and frame, from the spatial stage: k_rgi's own radiance is stored (never accumulated) in a scratch plane,
+            // and it writes the set the spatial kernel reads every frame
+            const size_t cap = (size_t)p->w * p->h * 4;
+            if (p->rgiScratch.n != cap) { int r; if ((r = p->rgiScratch.Alloc(cap))) return r; HIP_TRY(hipMemsetAsync(p->rgiScratch.p, 0, cap * sizeof(float), s)); }
+            F.finalRGBA = p->rgiScratch.p; prm.accumulate = 0u; prm.writeReservoirs = 1u;
+        }
+        if (prm.useLVG && !sc->view.lvg) return Fail(ZR_ERR_NOT_INITIALIZED, "light voxel grid missing: render the PRELIGHTING pass with use_lvg first");
+        TimerBegin(p, s, "rgi");
+        hipLaunchKernelGGL(sc->view.tex.count ? k_rgi_tex : PlainClass(sc, gb) ? k_rgi<true> : k_rgi<false>, dim3(tilesX * tilesY * (256 / kRgiBlock)), dim3(kRgiBlock), 0, s, F, *cb, tilesX, p->counters.p + 2 * 10);
+        TimerEnd(p, s);
+        HIP_TRY(hipGetLastError());
+        p->temporalValid = true;
+        p->currIdx = 1 - p->currIdx;
+    }
+    if ((stages & ZR_STAGE_SPATIAL) && p->rgiSpatialFrame.numSamples != 0)
+    {
+        if (!p->temporalValid) return Fail(ZR_ERR_NOT_INITIALIZED, "ReSTIR GI: ZR_STAGE_SPATIAL before the frame's ZR_STAGE_TEMPORAL");
+        const int set = 1 - p->currIdx;      // the set this frame's k_rgi wrote
+        F.cur.A = p->giA[set].p; F.cur.B = p->giB[set].p; F.cur.C = p->giC[set].p; F.prev = F.cur;
+        F.finalRGBA = p->finalRGBA.p;
+        prm.accumulate = (cb->accumulate && cb->camera_static) ? 1u : 0u;      // (the TEMPORAL stage above cleared it for k_rgi's scratch plane)
+        prm.doTemporal = 0u; prm.writeReservoirs = 0u; prm.textured = 0u;
+        TimerBegin(p, s, "rgi_spatial");
+        hipLaunchKernelGGL(k_rgi_spatial, dim3(tilesX * tilesY), dim3(kBlock), 0, s, F, *cb, tilesX, p->counters.p + 2 * 13, p->rgiSpatialFrame);
+        TimerEnd(p, s);
+        HIP_TRY(hipGetLastError());
+    }
     return ZR_OK;
 }
 
@@ -2683,8 +2716,8 @@ static int RenderIndirect(zr_pass* p, hipStream_t s, const zr_frame_constants* c
     if (p->params.presampling && (!sc->view.sampleSets || sc->numSampleSets != p->params.num_sample_sets || sc->view.sampleSetSize != p->params.sample_set_size))
         return Fail(ZR_ERR_NOT_INITIALIZED, "presampled light sets missing or of another size: render the PRELIGHTING pass with the same presampling params first");
     if (p->integrator == ZR_INTEGRATOR_RESTIR_PT) return RenderReSTIR_PT(p, s, cb, sc, gb, stages);
-    if (!(stages & ZR_STAGE_TEMPORAL)) return ZR_OK;
-    if (p->integrator == ZR_INTEGRATOR_RESTIR_GI) return RenderReSTIR_GI(p, s, cb, sc, gb);      // single-stage integrators render in the first stage
+    if (p->integrator == ZR_INTEGRATOR_RESTIR_GI) return RenderReSTIR_GI(p, s, cb, sc, gb, stages);
+    if (!(stages & ZR_STAGE_TEMPORAL)) return ZR_OK;      // the path tracer renders in the first stage
     PtParams prm;
     prm.maxNonTrBounces = p->params.max_non_tr_bounces; prm.maxGlossyTrBounces = p->params.max_glossy_tr_bounces;
     prm.russianRoulette = (p->params.flags & ZR_IND_RUSSIAN_ROULETTE) ? 1u : 0u;
@@ -2820,6 +2853,16 @@ extern "C" int zr_pass_set_rpt_debug_view(zr_pass* p, int view)
     if (!p || p->kind != ZR_PASS_INDIRECT) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_rpt_debug_view: needs an INDIRECT pass");
     if (view < ZR_RPT_VIEW_NONE || view >= ZR_RPT_VIEW_COUNT) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_rpt_debug_view: unknown view %d", view);
     p->rptView = view;      // read by ReSTIR PT only (the other integrators never look at it), from the next frame's first stage on
+    return ZR_OK;
+}
+
+extern "C" int zr_pass_set_rgi_spatial(zr_pass* p, uint32_t num_samples, float radius_px)
+{
+    if (!p || p->kind != ZR_PASS_INDIRECT) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_rgi_spatial: needs an INDIRECT pass");
+    if (num_samples > rgi::kSpatialMaxSamples) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_rgi_spatial: num_samples %u > %u", num_samples, rgi::kSpatialMaxSamples);
+    if (!(radius_px >= 0.0f && radius_px <= rgi::kSpatialMaxRadius)) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_rgi_spatial: radius_px %g outside [0, %g] (0 = the default)", (double)radius_px, (double)rgi::kSpatialMaxRadius);
+    // read by ReSTIR GI only (the other integrators never look at it), from the next frame's first stage on
+    p->rgiSpatial.numSamples = num_samples; p->rgiSpatial.radius = radius_px == 0.0f ? rgi::kSpatialDefaultRadius : radius_px;
     return ZR_OK;
 }
 

@@ -9,6 +9,7 @@
 //   zr_tu_rpt_d.hip  explicit instantiations of K16 (k_rpt_stc)
 //   zr_tu_rpt_view_{p,t,s}.hip  the reconnection-debug-view instantiations of K11 / K14 / K16 (k_rpt_*_view)
 //   zr_tu_di.hip     K5 - K8 and K10 (zr_kernels_di.h)
+//   zr_tu_rgi_spatial.hip  k_rgi_spatial, the opt-in spatial reuse stage of ReSTIR GI (zr_rgi_spatial.h)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "zr_stages.h"

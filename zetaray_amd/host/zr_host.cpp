@@ -518,6 +518,7 @@ void IndirectLighting::SetTexFilter(uint32_t f) { m_params.tex_filter = f; ZR_CH
 void IndirectLighting::SetBoilingSuppression(bool b) { SetFlag(ZR_IND_BOILING_SUPPRESSION, b); }
 void IndirectLighting::SetPathRegularization(bool b) { SetFlag(ZR_IND_PATH_REGULARIZATION, b); }
 void IndirectLighting::SetDebugView(RPT_DEBUG_VIEW v) { m_debugView = v; ZR_CHECK(zr_pass_set_rpt_debug_view(m_pass, (int)v)); }
+void IndirectLighting::SetGISpatialResampling(uint32_t numSamples, float radiusPx) { ZR_CHECK(zr_pass_set_rgi_spatial(m_pass, numSamples, radiusPx)); }
 void IndirectLighting::SetAlphaMin(float a) { m_params.alpha_min = a * a; ZR_CHECK(zr_pass_set_params(m_pass, &m_params)); }
 void* IndirectLighting::GetOutput(SHADER_OUT_RES i) const
 {

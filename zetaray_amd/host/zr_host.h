@@ -440,6 +440,9 @@ namespace RenderPass {
         enum class RPT_DEBUG_VIEW { NONE, K, CASE, FOUND_CONNECTION, CONNECTION_LOBE_K_MIN_1, CONNECTION_LOBE_K, COUNT };
         void SetDebugView(RPT_DEBUG_VIEW v);
         RPT_DEBUG_VIEW DebugView() const { return m_debugView; }
+        // ReSTIR GI's spatial reuse stage (zetaray_amd.h zr_pass_set_rgi_spatial; the reference's ReSTIR GI has none): numSamples 0 = off, 1..2 neighbours per
+        // pixel; radiusPx in (0, 64], 0 = the default 16.  From the next frame on; stored without effect by the other integrators
+        void SetGISpatialResampling(uint32_t numSamples, float radiusPx = 0.0f);
         const zr_params& Params() const { return m_params; }
         // device pointer of the FINAL plane (RGBA32F)
         void* GetOutput(SHADER_OUT_RES i) const;

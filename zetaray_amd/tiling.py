@@ -104,6 +104,17 @@ def choose_layout(w, h, n, cost, min_gain=1.15, uniform=0.3):
     return lay if grid > min_gain * bal else None
 
 
+def rgi_spatial_reach(radius_px):
+    """how many pixels, per axis, ReSTIR GI's spatial stage can reach from a pixel (zr_rgi_spatial.h, item 2): the longest point of the tap table,
+    (-0.875, 7/9), rotated onto an axis and scaled by the radius (0 = the 16-px default), then rounded to the nearest pixel (half a pixel at most)"""
+    import math
+    return math.ceil((float(radius_px) or 16.0) * math.hypot(0.875, 7.0 / 9.0) + 0.5)
+
+
+# the largest radius whose taps all stay inside the apron: (32 - 0.5) / 1.1707...
+RGI_SPATIAL_MAX_TILED_RADIUS = 26.9
+
+
 def extended_rect(w, h, rect, apron=APRON):
     x0, y0, tw, th = rect
     ex0, ey0 = max(0, x0 - apron), max(0, y0 - apron)
@@ -178,7 +189,8 @@ class TiledRestirPT:
     the halo exchange in between, through torch.distributed P2P (backend nccl == RCCL over xGMI on ROCm).
 
     kind = "restir_pt" (default; Indirect, 62 B/px, exchanges post-temporal and final reservoirs), "restir_gi" (Indirect, 40 B/px,
-    one stage, final exchange only), "di" (ReSTIR DI emissive, 24 B/px) or "sky_di" (sun + sky ReSTIR DI, 13 B/px): the DI
+    one stage, final exchange only; with set_rgi_spatial the spatial stage follows it, and the same ZR_HALO_FINAL exchange -- the set k_rgi
+    wrote is both what the spatial kernel gathers from and the next frame's "previous" -- moves BETWEEN the two stages, every frame), "di" (ReSTIR DI emissive, 24 B/px) or "sky_di" (sun + sky ReSTIR DI, 13 B/px): the DI
     passes exchange once, between their temporal and spatial stages."""
 
     def __init__(self, scene_host, width, height, world, rank, device=0, params=None, dist=None, kind="restir_pt", pass_params=None,
@@ -223,6 +235,8 @@ class TiledRestirPT:
         self._frames_rendered = 0
         self._scene_version_seen = self.r.scene.version
         self.exchanges_done = 0      # (statistics: how many halo exchanges this object has run)
+        self.rgi_spatial = False     # set_rgi_spatial: ReSTIR GI's spatial stage is on
+        self._final_in_apron = False # the last rendered frame exchanged ZR_HALO_FINAL between its stages: the apron holds the set the next frame reads as "previous"
         if transport == "rccl_cpp" and world > 1:
             # every rank must take the same branch (communicator creation is collective): agree on success before using it
             try:
@@ -387,6 +401,17 @@ class TiledRestirPT:
         assert self.kind == "restir_pt"
         self.r.enable_frame_overlap(on, carry)
 
+    def set_rgi_spatial(self, num_samples, radius_px=0.0):
+        """ReSTIR GI's spatial reuse stage on this tile (api.Pass.set_rgi_spatial); every tile of a frame must be given the same setting.
+        On a split frame the taps must stay inside the apron -- the kernel treats what lies beyond it like the frame border, and the owned pixels
+        would no longer equal the full frame's -- so a radius whose furthest tap (rgi_spatial_reach) exceeds it is a ValueError, as in denoise_schedule."""
+        if self.kind == "restir_gi" and self.world > 1 and int(num_samples) != 0:
+            need = rgi_spatial_reach(radius_px)
+            if need > APRON:
+                raise ValueError(f"ReSTIR GI spatial reuse on tiles: radius {float(radius_px) or 16.0:g} px reaches {need} px, beyond the {APRON}-px apron (at most {RGI_SPATIAL_MAX_TILED_RADIUS:g} px)")
+        self.r.set_rgi_spatial(num_samples, radius_px)
+        self.rgi_spatial = self.kind == "restir_gi" and int(num_samples) != 0
+
     def stage_spatial(self, cb, stream=None):
         self.hp.render_stage(cb, self.r.scene, self.r.gbuffer, self.api.STAGE_SPATIAL, stream)
 
@@ -405,11 +430,16 @@ class TiledRestirPT:
         between), and a frame whose reprojection cannot leave its tile (history_crosses_tiles) skips the exchange altogether: one exchange per
         frame instead of two while nothing moves.  exchange_final=False never exchanges it (the caller vouches for a static view)."""
         post, final = self.EXCHANGES[self.kind]
-        if final and exchange_final and self._frames_rendered > 0 and self.history_crosses_tiles(cb):
+        # (ReSTIR GI: a frame that ran its spatial stage moved the FINAL set between its stages, so the apron already holds it here.  That is a fact
+        # about the PREVIOUS frame -- _final_in_apron -- not about this one's setting: the first frame after set_rgi_spatial switches the stage on
+        # still needs the exchange, the first one after it is switched off does not.)
+        if final and exchange_final and self._frames_rendered > 0 and not self._final_in_apron and self.history_crosses_tiles(cb):
             self.exchange(self.api.HALO_FINAL)
         self.stage_temporal(cb)
         if post:
             self.exchange(self.api.HALO_POST_TEMPORAL)
+        if self.rgi_spatial:
+            self.exchange(self.api.HALO_FINAL)
         self.stage_spatial(cb)
         if self.two_spatial_rounds:
             self.exchange(self.api.HALO_POST_TEMPORAL)
@@ -417,6 +447,7 @@ class TiledRestirPT:
         if getattr(self, "p_denoise", None) is not None:
             self.denoise(cb)
         self._frames_rendered += 1
+        self._final_in_apron = self.rgi_spatial
         self._scene_version_seen = self.r.scene.version
 
     def owned_cost_cells(self):
@@ -517,12 +548,14 @@ def render_frame_in_process(ranks, cb, exchange_final=True):
     api = ranks[0].api
     post, final = ranks[0].EXCHANGES[ranks[0].kind]
     n = 0
-    if final and exchange_final and ranks[0]._frames_rendered > 0 and ranks[0].history_crosses_tiles(cb):
+    if final and exchange_final and ranks[0]._frames_rendered > 0 and not ranks[0]._final_in_apron and ranks[0].history_crosses_tiles(cb):
         exchange_in_process(ranks, api.HALO_FINAL); n += 1
     for r in ranks:
         r.stage_temporal(cb)
     if post:
         exchange_in_process(ranks, api.HALO_POST_TEMPORAL); n += 1
+    if ranks[0].rgi_spatial:
+        exchange_in_process(ranks, api.HALO_FINAL); n += 1
     for r in ranks:
         r.stage_spatial(cb)
     if ranks[0].two_spatial_rounds:
@@ -540,6 +573,7 @@ def render_frame_in_process(ranks, cb, exchange_final=True):
                     r.denoise_steps(cb, v)
     for r in ranks:
         r._frames_rendered += 1
+        r._final_in_apron = r.rgi_spatial
         r._scene_version_seen = r.r.scene.version
     return n
 

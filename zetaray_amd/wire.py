@@ -153,6 +153,8 @@ TONEMAP_NONE, TONEMAP_NEUTRAL, TONEMAP_AGX_DEFAULT, TONEMAP_AGX_GOLDEN, TONEMAP_
 DISPLAY_ROUGHNESS_TH_DEFAULT = 1.0
 # enum zr_rpt_debug_view (RPT_DEBUG_VIEW, IndirectLighting_Common.h:58-67): zr_pass_set_rpt_debug_view
 RPT_VIEW_NONE, RPT_VIEW_K, RPT_VIEW_CASE, RPT_VIEW_FOUND_CONNECTION, RPT_VIEW_LOBE_K_MIN_1, RPT_VIEW_LOBE_K, RPT_VIEW_COUNT = range(7)
+# zr_pass_set_rgi_spatial: ReSTIR GI's spatial reuse stage (zr_rgi_spatial.h): neighbours per pixel 0 (off) .. 2, radius in (0, 64] px, 0 = the default
+RGI_SPATIAL_MAX_SAMPLES, RGI_SPATIAL_DEFAULT_RADIUS, RGI_SPATIAL_MAX_RADIUS = 2, 16.0, 64.0
 OUT_PICK_MASK = 50          # ZR_PASS_DISPLAY: R8, render size (zr_pass_set_picked_instances)
 
 
