@@ -74,8 +74,6 @@ STAGE_DENOISE_TEMPORAL, STAGE_DENOISE_VARIANCE, STAGE_DENOISE_MASK = 1 << 8, 1 <
 def stage_denoise_atrous(i):
     return 1 << (10 + i)
 
-HALO_BYTES_PER_PIXEL = 62
-
 
 class ZetaRayError(RuntimeError):
     def __init__(self, code, msg):

@@ -500,10 +500,28 @@ template<typename T> struct DevBuf
 {
     T* p = nullptr; size_t n = 0;
     int Alloc(size_t count) { Free(); n = count; if (!count) return ZR_OK; hipError_t e = hipMalloc((void**)&p, count * sizeof(T)); if (e != hipSuccess) { p = nullptr; return Fail(ZR_ERR_OOM, "hipMalloc(%zu B) failed: %s", count * sizeof(T), hipGetErrorString(e)); } return ZR_OK; }
+    // ... and clears it on the null stream (asynchronous to the host: see zr_pass_init)
+    int AllocZero(size_t count) { int r = Alloc(count); if (r) return r; HIP_TRY(hipMemset(p, 0, count * sizeof(T))); return ZR_OK; }
     int Upload(const T* src, size_t count) { int r = Alloc(count); if (r) return r; if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice)); return ZR_OK; }
     void Free() { if (p) { (void)hipFree(p); p = nullptr; } n = 0; }
     ~DevBuf() { Free(); }
 };
+struct HaloPlane { void* base; size_t bpp; };
+// A per-pixel device plane: PER_PIXEL elements of T for every pixel.  This declaration is the one statement of the plane's layout -- allocation, the
+// clear, halo transfers and zr_pass_get_output all take its bytes per pixel from here.  Alloc / AllocZero count pixels; n goes on counting elements.
+template<typename T, size_t PER_PIXEL = 1> struct Plane : DevBuf<T>
+{
+    static constexpr size_t bpp = sizeof(T) * PER_PIXEL;
+    int Alloc(size_t pixels) { return DevBuf<T>::Alloc(pixels * PER_PIXEL); }
+    int AllocZero(size_t pixels) { return DevBuf<T>::AllocZero(pixels * PER_PIXEL); }
+    size_t Pixels() const { return this->n / PER_PIXEL; }
+    HaloPlane Halo() const { return {this->p, bpp}; }
+    void Output(void** dev, uint32_t* bytesPerPixel) const { *dev = this->p; if (bytesPerPixel) *bytesPerPixel = (uint32_t)bpp; }      // zr_pass_get_output
+};
+// ... and a set of planes (zr_pass::ResStorage / RBufStorage): S::Each(set, f) calls f on each plane in the set's order and stops at the first error
+template<typename S> static int PlanesAllocZero(S& set, size_t pixels) { return S::Each(set, [&](auto& pl) { return pl.AllocZero(pixels); }); }
+template<typename S> static int PlanesHalo(const S& set, HaloPlane* out) { int n = 0; S::Each(set, [&](const auto& pl) { out[n++] = pl.Halo(); return 0; }); return n; }
+template<typename S> static void PlanesOutput(const S& set, int i, void** dev, uint32_t* bpp) { S::Each(set, [&](const auto& pl) { if (i-- == 0) pl.Output(dev, bpp); return 0; }); }
 
 struct zr_scene
 {
@@ -831,35 +849,33 @@ struct zr_pass
     // ZR_PASS_SKY: the inscattering voxel grid (Sky::SetInscatteringEnablement, zr_pass_set_inscattering), numVoxelsX x numVoxelsY x 128 R11G11B10F texels
     bool inscatterOn = false; InscatterParams inscatter{}; DevBuf<uint32_t> inscatterGrid;
     const zr_pass* inscatterSky = nullptr;         // ZR_PASS_COMPOSITING: the SKY pass whose grid is composited (zr_pass_bind_inscattering), read at render time
-    DevBuf<float> finalRGBA; DevBuf<F4> firstBOP; DevBuf<uint32_t> counts; DevBuf<unsigned long long> counters;
+    Plane<float, 4> finalRGBA; Plane<F4> firstBOP; DevBuf<uint32_t> counts; DevBuf<unsigned long long> counters;
     DevBuf<uint32_t> groupMax;      // kMaxRounds x (8x8 groups of the tile): RR reduction keys
     zr_counters hostCounters{0, 0};
     // GBUFFER: GBufferRT::PickPixel (GBufferRT.h:36-46).  pickXY = x | y << 16, 0xffffffff = no pick pending; pickBuf[0] = the last picked mesh index
     uint32_t pickXY = 0xffffffffu; DevBuf<uint32_t> pickBuf; bool pickWritten = false;
-    // INDIRECT / ReSTIR PT: two reservoir sets (7 planes each), two r-buffers, target, spatial neighbour, sample set
+    // INDIRECT / ReSTIR PT: two reservoir sets, two r-buffers, target, spatial neighbour, sample set.  A set states its planes once: their layouts in
+    // the declaration, their order in Each (the order of zr_output and of a halo block), their kernel-side names in View; PlanesAllocZero / PlanesHalo /
+    // PlanesOutput below go through Each
     struct ResStorage
     {
-        DevBuf<uint32_t> A, G; DevBuf<float> B, F; DevBuf<U4> C, D; DevBuf<uint16_t> E;
-        int Alloc(size_t n)
-        {
-            int r;
-            if ((r = A.Alloc(n)) || (r = B.Alloc(2 * n)) || (r = C.Alloc(n)) || (r = D.Alloc(n)) || (r = E.Alloc(n)) || (r = F.Alloc(2 * n)) || (r = G.Alloc(2 * n))) return r;
-            return ZR_OK;
-        }
+        Plane<uint32_t> A; Plane<float, 2> B; Plane<U4> C, D; Plane<uint16_t> E; Plane<float, 2> F; Plane<uint32_t, 2> G;
+        template<typename S, typename Fn> static int Each(S& s, Fn f)
+        { int r; if ((r = f(s.A)) || (r = f(s.B)) || (r = f(s.C)) || (r = f(s.D)) || (r = f(s.E)) || (r = f(s.F)) || (r = f(s.G))) return r; return ZR_OK; }
         rpt::ResPlanes View() const { rpt::ResPlanes v; v.A = A.p; v.B = B.p; v.C = C.p; v.D = D.p; v.E = E.p; v.F = F.p; v.G = G.p; return v; }
     } res[3];      // [2]: allocated by zr_pass_set_frame_overlap (the set K11 of the next frame writes while this frame's reuse passes read the other two)
     struct RBufStorage
     {
-        DevBuf<uint16_t> A, D; DevBuf<U4> B, C;
-        int Alloc(size_t n) { int r; if ((r = A.Alloc(4 * n)) || (r = B.Alloc(n)) || (r = C.Alloc(n)) || (r = D.Alloc(n))) return r; return ZR_OK; }
+        Plane<uint16_t, 4> A; Plane<U4> B, C; Plane<uint16_t> D;
+        template<typename S, typename Fn> static int Each(S& s, Fn f) { int r; if ((r = f(s.A)) || (r = f(s.B)) || (r = f(s.C)) || (r = f(s.D))) return r; return ZR_OK; }
         rpt::RBuf View() const { rpt::RBuf v; v.A = A.p; v.B = B.p; v.C = C.p; v.D = D.p; return v; }
     } rb[2];
-    DevBuf<F4> rptTarget, rptTargetAlt; DevBuf<uint8_t> rptNeighbor; DevBuf<uint16_t> rptSampleSet;
+    Plane<F4> rptTarget, rptTargetAlt; Plane<uint8_t, 2> rptNeighbor; DevBuf<uint16_t> rptSampleSet;
     // Frame overlap (zr_pass_set_frame_overlap).  rptSet: which storage plays the two roles currIdx flips between ([0], [1]) and which one is free ([2]);
     // the CANDIDATES stage of an overlapped frame writes the free set and hands the set it replaces back.  tgtIdx / finIdx: the target / FINAL plane of
     // the frame whose CANDIDATES stage ran last; finOut: the FINAL plane of the last frame whose final stage has been enqueued (zr_pass_get_output)
     bool overlap = false, overlapCarry = false; int rptSet[3] = {0, 1, 2}; int tgtIdx = 0, finIdx = 0, finOut = 0;
-    DevBuf<float> finalAlt, finalAlt2;      // FINAL rotates over three planes: K11 of frame N + 2 (which clears the pixels without a surface) may run while frame N's is still being consumed
+    Plane<float, 4> finalAlt, finalAlt2;      // FINAL rotates over three planes: K11 of frame N + 2 (which clears the pixels without a surface) may run while frame N's is still being consumed
     // the last stage of the frame before the previous one done (depth-2 pipelining, product mode): evDone[k & 1] is recorded when frame k closes
     hipEvent_t evDone[2] = {nullptr, nullptr}; bool haveDone[2] = {false, false}; hipStream_t doneStream[2] = {nullptr, nullptr}; uint64_t ovFrame = 0;
     hipStream_t overlapStream = nullptr;                     // "stream A" for callers without streams of their own
@@ -868,33 +884,35 @@ struct zr_pass
     zr_pass::ResStorage& RptCur() { return res[rptSet[currIdx]]; }
     zr_pass::ResStorage& RptOth() { return res[rptSet[1 - currIdx]]; }
     const zr_pass::ResStorage& RptOth() const { return res[rptSet[1 - currIdx]]; }
-    F4* Target() const { return tgtIdx ? rptTargetAlt.p : rptTarget.p; }
-    float* Final(int i) const { return i == 0 ? finalRGBA.p : (i == 1 ? finalAlt.p : finalAlt2.p); }
-    DevBuf<uint16_t> rptMap[2];      // K12 thread maps: [0] CtN, [1] NtC
+    const Plane<F4>& TargetPlane() const { return tgtIdx ? rptTargetAlt : rptTarget; }
+    const Plane<float, 4>& FinalPlane(int i) const { return i == 0 ? finalRGBA : (i == 1 ? finalAlt : finalAlt2); }
+    F4* Target() const { return TargetPlane().p; }
+    float* Final(int i) const { return FinalPlane(i).p; }
+    Plane<uint16_t> rptMap[2];      // K12 thread maps: [0] CtN, [1] NtC
     DevBuf<uint32_t> trip; DevBuf<unsigned long long> tripStats;      // ZR_K11=trip diagnostic
     DevBuf<uint32_t> carry[2], carryCount;                             // K11 with per-bounce compaction: path-state planes (ping-pong), alive counts
     bool frameOpen = false;      // ReSTIR PT staged rendering: a frame's TEMPORAL stage has run, its last stage has not
     DevBuf<uint32_t> costMap; bool costOn = false, costRays = false;      // rays per 32 x 32-px cell (zr_pass_enable_cost_map)
     DevBuf<uint32_t> rptLists, rptListCounts;      // 4 replay work lists (pixel ids) + their device-side counts
     // DI_EMISSIVE: two reservoir sets (A RGBA32_UINT, B RG32F), target, sample set
-    DevBuf<U4> diA[2]; DevBuf<float> diB[2]; DevBuf<F4> diTarget; DevBuf<uint16_t> diSampleSet;
-    DevBuf<uint8_t> skyA[2]; DevBuf<uint16_t> skyB[2]; DevBuf<float> skyC[2];      // sun + sky DI reservoirs (R8_UINT, RG16_UINT, RG32F)
+    Plane<U4> diA[2]; Plane<float, 2> diB[2]; Plane<F4> diTarget; DevBuf<uint16_t> diSampleSet;
+    Plane<uint8_t> skyA[2]; Plane<uint16_t, 2> skyB[2]; Plane<float, 2> skyC[2];      // sun + sky DI reservoirs (R8_UINT, RG16_UINT, RG32F)
     // INDIRECT / ReSTIR GI: two reservoir sets (A RGBA32F, B RGBA16F, C RGBA32F)
-    DevBuf<F4> giA[2], giC[2]; DevBuf<uint16_t> giB[2];
+    Plane<F4> giA[2], giC[2]; Plane<uint16_t, 4> giB[2];
     bool temporalValid = false, doTemporal = false, doSpatial = false; int currIdx = 0;
     const F4* compIn[4] = {nullptr, nullptr, nullptr, nullptr};     // COMPOSITING inputs (emissive DI, indirect, sky DI); [3] = TAA signal
-    DevBuf<F4> svgfHist, svgfAccum, svgfPing, svgfPong; DevBuf<float> svgfMoments[2], svgfGuideFw; DevBuf<svgf::GuideN> svgfGuide; int svgfMomIdx = 0; const F4* svgfOut = nullptr; F4* svgfCur = nullptr; uint32_t svgfStepsDone = 0;      // DENOISE
-    DevBuf<uint16_t> taaOut[2]; int taaIdx = 0;            // TAA: ping-pong RGBA16F outputs; taaIdx = the one written last
+    Plane<F4> svgfHist, svgfAccum, svgfPing, svgfPong; Plane<float, 2> svgfMoments[2]; Plane<float> svgfGuideFw; Plane<svgf::GuideN> svgfGuide; int svgfMomIdx = 0; const F4* svgfOut = nullptr; F4* svgfCur = nullptr; uint32_t svgfStepsDone = 0;      // DENOISE
+    Plane<uint16_t, 4> taaOut[2]; int taaIdx = 0;            // TAA: ping-pong RGBA16F outputs; taaIdx = the one written last
     // AUTO_EXPOSURE / DISPLAY
     const uint16_t* postIn16 = nullptr; const F4* postIn32 = nullptr; const float* exposureIn = nullptr;
     DevBuf<uint32_t> aeHist; DevBuf<float> aeExposure;
-    DevBuf<uint32_t> tonemapLut; uint32_t tonemapLutDim = 0; DevBuf<F4> displayOut; DevBuf<uint32_t> displaySrgb;
+    DevBuf<uint32_t> tonemapLut; uint32_t tonemapLutDim = 0; Plane<F4> displayOut; Plane<uint32_t> displaySrgb;
     int displayOption = ZR_DISPLAY_DEFAULT; float roughnessTh = 1.0f;      // DISPLAY: zr_pass_set_display_option (Display.cpp:69-73)
     // INDIRECT: zr_pass_set_rpt_debug_view (IndirectLighting.cpp:1543-1550); rptViewFrame = the view of the frame being rendered (latched by its first stage)
     int rptView = ZR_RPT_VIEW_NONE, rptViewFrame = ZR_RPT_VIEW_NONE;
     // INDIRECT: zr_pass_set_rgi_spatial (zr_rgi_spatial.h).  rgiSpatialFrame = the setting of the frame being rendered (latched by its first stage);
     // rgiScratch = the plane k_rgi's own radiance goes to while the spatial stage writes FINAL (allocated by the first frame that needs it)
-    rgi::SpatialParams rgiSpatial{0u, rgi::kSpatialDefaultRadius}, rgiSpatialFrame{0u, rgi::kSpatialDefaultRadius}; DevBuf<float> rgiScratch;
+    rgi::SpatialParams rgiSpatial{0u, rgi::kSpatialDefaultRadius}, rgiSpatialFrame{0u, rgi::kSpatialDefaultRadius}; Plane<float, 4> rgiScratch;
     std::vector<uint32_t> picks; DevBuf<uint8_t> pickMask; DevBuf<int4> pickTris; DevBuf<uint32_t> pickCount;     // DISPLAY: zr_pass_set_picked_instances
     uint32_t pickMaskW = 0, pickMaskH = 0;
     uint32_t own[4] = {0, 0, 0, 0};                // owned rect (global pixels); w == 0 -> the whole G-buffer rect
@@ -1831,11 +1849,7 @@ int zr_gbuffer_create(int device, uint32_t w, uint32_t h, zr_gbuffer** out)
     g->device = device; g->w = w; g->h = h;
     for (int k = 0; k < 2; k++)
     for (int i = 0; i < ZR_GB_COUNT; i++)
-    {
-        if ((r = g->planeSets[k][i].Alloc((size_t)w * h * ZR_GB_PLANE_BYTES[i]))) { delete g; return r; }
-        hipError_t e = hipMemset(g->planeSets[k][i].p, 0, g->planeSets[k][i].n);
-        if (e != hipSuccess) { delete g; return Fail(ZR_ERR_HIP, "hipMemset failed: %s", hipGetErrorString(e)); }
-    }
+        if ((r = g->planeSets[k][i].AllocZero((size_t)w * h * ZR_GB_PLANE_BYTES[i]))) { delete g; return r; }
     { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) { delete g; return Fail(ZR_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e)); } }   // see zr_pass_init
     *out = g;
     return ZR_OK;
@@ -1897,123 +1911,80 @@ static int AllocOverlapPlanes(zr_pass* p)
 {
     const size_t cap = (size_t)p->w * p->h;
     int r;
-    zr_pass::ResStorage& R = p->res[2];
-    if ((r = R.Alloc(cap)) || (r = p->rptTargetAlt.Alloc(cap)) || (r = p->finalAlt.Alloc(cap * 4)) || (r = p->finalAlt2.Alloc(cap * 4))) return r;
-    HIP_TRY(hipMemset(R.A.p, 0, cap * 4)); HIP_TRY(hipMemset(R.B.p, 0, cap * 8)); HIP_TRY(hipMemset(R.C.p, 0, cap * 16));
-    HIP_TRY(hipMemset(R.D.p, 0, cap * 16)); HIP_TRY(hipMemset(R.E.p, 0, cap * 2)); HIP_TRY(hipMemset(R.F.p, 0, cap * 8)); HIP_TRY(hipMemset(R.G.p, 0, cap * 8));
-    HIP_TRY(hipMemset(p->rptTargetAlt.p, 0, cap * 16)); HIP_TRY(hipMemset(p->finalAlt.p, 0, cap * 4 * sizeof(float))); HIP_TRY(hipMemset(p->finalAlt2.p, 0, cap * 4 * sizeof(float)));
+    if ((r = PlanesAllocZero(p->res[2], cap)) || (r = p->rptTargetAlt.AllocZero(cap)) || (r = p->finalAlt.AllocZero(cap)) || (r = p->finalAlt2.AllocZero(cap))) return r;
     return ZR_OK;
 }
 static int AllocPass(zr_pass* p)
 {
     int r;
-    if (p->kind == ZR_PASS_SKY) { if ((r = p->skyLut.Alloc((size_t)p->w * p->h))) return r; }
+    const size_t cap = (size_t)p->w * p->h;
+    if (p->kind == ZR_PASS_SKY) { if ((r = p->skyLut.Alloc(cap))) return r; }
     if (p->kind == ZR_PASS_TAA)
     {
-        const size_t n = (size_t)p->w * p->h * 4;
-        for (int k = 0; k < 2; k++) { if ((r = p->taaOut[k].Alloc(n))) return r; HIP_TRY(hipMemset(p->taaOut[k].p, 0, n * sizeof(uint16_t))); }
+        for (auto& t : p->taaOut) if ((r = t.AllocZero(cap))) return r;
         p->taaIdx = 0; p->temporalValid = false;
     }
     if (p->kind == ZR_PASS_DENOISE)
     {
-        const size_t n = (size_t)p->w * p->h;
-        if ((r = p->svgfHist.Alloc(n)) || (r = p->svgfAccum.Alloc(n)) || (r = p->svgfPing.Alloc(n)) || (r = p->svgfPong.Alloc(n)) || (r = p->svgfGuide.Alloc(n)) || (r = p->svgfGuideFw.Alloc(n))) return r;
-        for (int k = 0; k < 2; k++) { if ((r = p->svgfMoments[k].Alloc(2 * n))) return r; HIP_TRY(hipMemset(p->svgfMoments[k].p, 0, 2 * n * sizeof(float))); }
-        HIP_TRY(hipMemset(p->svgfHist.p, 0, n * sizeof(F4))); HIP_TRY(hipMemset(p->svgfPing.p, 0, n * sizeof(F4))); HIP_TRY(hipMemset(p->svgfPong.p, 0, n * sizeof(F4)));
+        if ((r = p->svgfHist.AllocZero(cap)) || (r = p->svgfAccum.Alloc(cap)) || (r = p->svgfPing.AllocZero(cap)) || (r = p->svgfPong.AllocZero(cap)) || (r = p->svgfGuide.Alloc(cap)) || (r = p->svgfGuideFw.Alloc(cap))) return r;
+        for (auto& m : p->svgfMoments) if ((r = m.AllocZero(cap))) return r;
         p->svgfMomIdx = 0; p->svgfOut = p->svgfPing.p; p->svgfCur = p->svgfPing.p; p->temporalValid = false;
     }
     if (p->kind == ZR_PASS_AUTO_EXPOSURE)
     {
-        if ((r = p->aeHist.Alloc(post::kHistBins)) || (r = p->aeExposure.Alloc(2))) return r;
-        HIP_TRY(hipMemset(p->aeHist.p, 0, post::kHistBins * sizeof(uint32_t)));
-        HIP_TRY(hipMemset(p->aeExposure.p, 0, 2 * sizeof(float)));      // TEXTURE_FLAGS::INIT_TO_ZERO, AutoExposure.cpp:150-155
+        if ((r = p->aeHist.AllocZero(post::kHistBins)) || (r = p->aeExposure.AllocZero(2))) return r;      // TEXTURE_FLAGS::INIT_TO_ZERO, AutoExposure.cpp:150-155
     }
     if (p->kind == ZR_PASS_DISPLAY)
     {
-        const size_t cap = (size_t)p->w * p->h;
-        if ((r = p->displayOut.Alloc(cap)) || (r = p->displaySrgb.Alloc(cap))) return r;
-        HIP_TRY(hipMemset(p->displayOut.p, 0, cap * sizeof(F4))); HIP_TRY(hipMemset(p->displaySrgb.p, 0, cap * 4));
+        if ((r = p->displayOut.AllocZero(cap)) || (r = p->displaySrgb.AllocZero(cap))) return r;
     }
     if (p->kind == ZR_PASS_COMPOSITING)
     {
-        const size_t cap = (size_t)p->w * p->h;
-        if ((r = p->firstBOP.Alloc(cap))) return r;            // scratch plane of the firefly filter (composited, unfiltered)
-        HIP_TRY(hipMemset(p->firstBOP.p, 0, cap * sizeof(F4)));
-        if ((r = p->finalRGBA.Alloc(cap * 4))) return r;
-        HIP_TRY(hipMemset(p->finalRGBA.p, 0, cap * 4 * sizeof(float)));
+        if ((r = p->firstBOP.AllocZero(cap))) return r;            // scratch plane of the firefly filter (composited, unfiltered)
+        if ((r = p->finalRGBA.AllocZero(cap))) return r;
     }
     if (p->kind == ZR_PASS_DI_SKY)
     {
-        const size_t cap = (size_t)p->w * p->h;
-        if ((r = p->finalRGBA.Alloc(cap * 4))) return r;
-        if ((r = p->counters.Alloc(2 * kCounterSlots))) return r;
-        HIP_TRY(hipMemset(p->finalRGBA.p, 0, cap * 4 * sizeof(float)));
-        HIP_TRY(hipMemset(p->counters.p, 0, 2 * kCounterSlots * sizeof(unsigned long long)));
+        if ((r = p->finalRGBA.AllocZero(cap))) return r;
+        if ((r = p->counters.AllocZero(2 * kCounterSlots))) return r;
         for (int k = 0; k < 2; k++)
-        {
-            if ((r = p->skyA[k].Alloc(cap)) || (r = p->skyB[k].Alloc(2 * cap)) || (r = p->skyC[k].Alloc(2 * cap))) return r;
-            HIP_TRY(hipMemset(p->skyA[k].p, 0, cap)); HIP_TRY(hipMemset(p->skyB[k].p, 0, cap * 4)); HIP_TRY(hipMemset(p->skyC[k].p, 0, cap * 8));
-        }
-        if ((r = p->diTarget.Alloc(cap))) return r;
-        HIP_TRY(hipMemset(p->diTarget.p, 0, cap * 16));
+            if ((r = p->skyA[k].AllocZero(cap)) || (r = p->skyB[k].AllocZero(cap)) || (r = p->skyC[k].AllocZero(cap))) return r;
+        if ((r = p->diTarget.AllocZero(cap))) return r;
         p->temporalValid = false; p->currIdx = 0;
     }
     if (p->kind == ZR_PASS_DI_EMISSIVE)
     {
-        const size_t cap = (size_t)p->w * p->h;
-        if ((r = p->finalRGBA.Alloc(cap * 4))) return r;
-        if ((r = p->counters.Alloc(2 * kCounterSlots))) return r;
-        HIP_TRY(hipMemset(p->finalRGBA.p, 0, cap * 4 * sizeof(float)));
-        HIP_TRY(hipMemset(p->counters.p, 0, 2 * kCounterSlots * sizeof(unsigned long long)));
+        if ((r = p->finalRGBA.AllocZero(cap))) return r;
+        if ((r = p->counters.AllocZero(2 * kCounterSlots))) return r;
         for (int k = 0; k < 2; k++)
-        {
-            if ((r = p->diA[k].Alloc(cap)) || (r = p->diB[k].Alloc(2 * cap))) return r;
-            HIP_TRY(hipMemset(p->diA[k].p, 0, cap * 16)); HIP_TRY(hipMemset(p->diB[k].p, 0, cap * 8));
-        }
-        if ((r = p->diTarget.Alloc(cap))) return r;
-        HIP_TRY(hipMemset(p->diTarget.p, 0, cap * 16));
+            if ((r = p->diA[k].AllocZero(cap)) || (r = p->diB[k].AllocZero(cap))) return r;
+        if ((r = p->diTarget.AllocZero(cap))) return r;
         if ((r = p->diSampleSet.Upload(kRdiSampleSet, 64))) return r;
         p->temporalValid = false; p->currIdx = 0;
     }
     if (p->kind == ZR_PASS_INDIRECT)
     {
-        const size_t cap = (size_t)p->w * p->h;
         if ((r = p->q[0].Alloc(cap))) return r;
         if ((r = p->q[1].Alloc(cap))) return r;
-        if ((r = p->finalRGBA.Alloc(cap * 4))) return r;
+        if ((r = p->finalRGBA.AllocZero(cap))) return r;
         if ((r = p->firstBOP.Alloc(cap))) return r;
         if ((r = p->counts.Alloc(5 * (kMaxRounds + 2) * kCounterStride))) return r;   // per round: live paths, k_trace cursor, 3 ray counts
-        if ((r = p->counters.Alloc(2 * kCounterSlots))) return r;
+        if ((r = p->counters.AllocZero(2 * kCounterSlots))) return r;
         if ((r = p->groupMax.Alloc((size_t)kMaxRounds * ((p->w + 7) / 8) * ((p->h + 7) / 8)))) return r;
-        HIP_TRY(hipMemset(p->finalRGBA.p, 0, cap * 4 * sizeof(float)));
-        HIP_TRY(hipMemset(p->counters.p, 0, 2 * kCounterSlots * sizeof(unsigned long long)));
         if (p->integrator == ZR_INTEGRATOR_RESTIR_GI)
         {
             for (int k = 0; k < 2; k++)
-            {
-                if ((r = p->giA[k].Alloc(cap)) || (r = p->giB[k].Alloc(4 * cap)) || (r = p->giC[k].Alloc(cap))) return r;
-                HIP_TRY(hipMemset(p->giA[k].p, 0, cap * 16)); HIP_TRY(hipMemset(p->giB[k].p, 0, cap * 8)); HIP_TRY(hipMemset(p->giC[k].p, 0, cap * 16));
-            }
+                if ((r = p->giA[k].AllocZero(cap)) || (r = p->giB[k].AllocZero(cap)) || (r = p->giC[k].AllocZero(cap))) return r;
             p->temporalValid = false; p->currIdx = 0;
         }
         if (p->integrator == ZR_INTEGRATOR_RESTIR_PT)
         {
             for (int k = 0; k < 2; k++)
-            {
-                if ((r = p->res[k].Alloc(cap))) return r;
-                if ((r = p->rb[k].Alloc(cap))) return r;
-                zr_pass::ResStorage& R = p->res[k];
-                HIP_TRY(hipMemset(R.A.p, 0, cap * 4)); HIP_TRY(hipMemset(R.B.p, 0, cap * 8)); HIP_TRY(hipMemset(R.C.p, 0, cap * 16));
-                HIP_TRY(hipMemset(R.D.p, 0, cap * 16)); HIP_TRY(hipMemset(R.E.p, 0, cap * 2)); HIP_TRY(hipMemset(R.F.p, 0, cap * 8));
-                HIP_TRY(hipMemset(R.G.p, 0, cap * 8));
-                zr_pass::RBufStorage& B = p->rb[k];
-                HIP_TRY(hipMemset(B.A.p, 0, cap * 8)); HIP_TRY(hipMemset(B.B.p, 0, cap * 16)); HIP_TRY(hipMemset(B.C.p, 0, cap * 16)); HIP_TRY(hipMemset(B.D.p, 0, cap * 2));
-            }
-            if ((r = p->rptTarget.Alloc(cap))) return r;
-            if ((r = p->rptNeighbor.Alloc(2 * cap))) return r;
-            HIP_TRY(hipMemset(p->rptTarget.p, 0, cap * 16)); HIP_TRY(hipMemset(p->rptNeighbor.p, 0, cap * 2));
-            for (auto& m : p->rptMap) { if ((r = m.Alloc(cap))) return r; HIP_TRY(hipMemset(m.p, 0, cap * 2)); }
-            { const size_t cells = (size_t)((p->w + 31u) / 32u + 1u) * ((p->h + 31u) / 32u + 1u); if ((r = p->costMap.Alloc(cells))) return r; HIP_TRY(hipMemset(p->costMap.p, 0, cells * 4)); }
+                if ((r = PlanesAllocZero(p->res[k], cap)) || (r = PlanesAllocZero(p->rb[k], cap))) return r;
+            if ((r = p->rptTarget.AllocZero(cap))) return r;
+            if ((r = p->rptNeighbor.AllocZero(cap))) return r;
+            for (auto& m : p->rptMap) if ((r = m.AllocZero(cap))) return r;
+            if ((r = p->costMap.AllocZero((size_t)((p->w + 31u) / 32u + 1u) * ((p->h + 31u) / 32u + 1u)))) return r;
             if ((r = p->rptSampleSet.Upload(kRptSampleSet, 1024))) return r;
             if ((r = p->rptLists.Alloc(4 * cap))) return r;
             p->rptSet[0] = 0; p->rptSet[1] = 1; p->rptSet[2] = 2; p->tgtIdx = 0; p->finIdx = 0; p->finOut = 0; p->frameOpen = false; p->haveCand = false; p->haveTemporal = false; p->haveDone[0] = p->haveDone[1] = false;
@@ -2401,8 +2372,8 @@ static int RenderReSTIR_GI(zr_pass* p, hipStream_t s, const zr_frame_constants* 
         if (spatial)
         {   // FINAL gets one contribution per pixel and frame, from the spatial stage: k_rgi's own radiance is stored (never accumulated) in a scratch plane,
             // and it writes the set the spatial kernel reads every frame
-            const size_t cap = (size_t)p->w * p->h * 4;
-            if (p->rgiScratch.n != cap) { int r; if ((r = p->rgiScratch.Alloc(cap))) return r; HIP_TRY(hipMemsetAsync(p->rgiScratch.p, 0, cap * sizeof(float), s)); }
+            const size_t cap = (size_t)p->w * p->h;
+            if (p->rgiScratch.Pixels() != cap) { int r; if ((r = p->rgiScratch.Alloc(cap))) return r; HIP_TRY(hipMemsetAsync(p->rgiScratch.p, 0, cap * p->rgiScratch.bpp, s)); }
             F.finalRGBA = p->rgiScratch.p; prm.accumulate = 0u; prm.writeReservoirs = 1u;
         }
         if (prm.useLVG && !sc->view.lvg) return Fail(ZR_ERR_NOT_INITIALIZED, "light voxel grid missing: render the PRELIGHTING pass with use_lvg first");
@@ -3130,10 +3101,7 @@ int zr_pass_set_frame_overlap(zr_pass* p, zr_gbuffer* gb, int enable)
     if (enable && gb->numSets == 2)
     {   // the third plane set (never given back: the sets' roles rotate)
         for (int i = 0; i < ZR_GB_COUNT; i++)
-        {
-            if (int r = gb->planeSets[2][i].Alloc((size_t)gb->w * gb->h * ZR_GB_PLANE_BYTES[i])) return r;
-            HIP_TRY(hipMemset(gb->planeSets[2][i].p, 0, gb->planeSets[2][i].n));
-        }
+            if (int r = gb->planeSets[2][i].AllocZero((size_t)gb->w * gb->h * ZR_GB_PLANE_BYTES[i])) return r;
         HIP_TRY(hipDeviceSynchronize());
         // sets 0 / 1 hold the last two frames; the rotation continues from the current one: cur = 0 -> next 1 (two frames old), cur = 1 -> next 2 (fresh)
         gb->numSets = 3;
@@ -3166,7 +3134,14 @@ static zr_pass::ResStorage* HaloSet(zr_pass* p, int which)
     // frame reads as "previous" is res[1 - currIdx]
     return &p->res[p->rptSet[which == ZR_HALO_POST_TEMPORAL ? p->currIdx : 1 - p->currIdx]];
 }
-struct HaloPlane { void* base; size_t bpp; };
+// ZR_HALO_DENOISE_INPUT: what the temporal step of a tile reads in its apron -- this frame's signal (the bound input plane: its owner shaded it, in the
+// layout of the history; null while unbound) and the history the previous frame left (colour + length, moments)
+static int DenoiseInputPlanes(const zr_pass* p, HaloPlane* planes)
+{
+    planes[0] = {(void*)p->compIn[3], p->svgfHist.bpp}; planes[1] = p->svgfHist.Halo(); planes[2] = p->svgfMoments[p->svgfMomIdx].Halo();
+    return 3;
+}
+static size_t HaloBytes(const HaloPlane* planes, int n) { size_t b = 0; for (int i = 0; i < n; i++) b += planes[i].bpp; return b; }
 // the planes a halo transfer of this pass moves, and their bytes per pixel
 static int HaloPlanes(zr_pass* p, int which, HaloPlane* planes, size_t* bytesPerPixel)
 {
@@ -3174,34 +3149,25 @@ static int HaloPlanes(zr_pass* p, int which, HaloPlane* planes, size_t* bytesPer
     // "previous" is [1 - currIdx]
     const int set = which == ZR_HALO_POST_TEMPORAL ? p->currIdx : 1 - p->currIdx;
     int n = 0;
-    if (p->kind == ZR_PASS_INDIRECT && p->integrator == ZR_INTEGRATOR_RESTIR_PT)
-    {
-        zr_pass::ResStorage* R = &p->res[p->rptSet[set]];
-        const HaloPlane pl[7] = {{R->A.p, 4}, {R->B.p, 8}, {R->C.p, 16}, {R->D.p, 16}, {R->E.p, 2}, {R->F.p, 8}, {R->G.p, 8}};
-        for (auto& q : pl) planes[n++] = q;
-    }
+    if (p->kind == ZR_PASS_INDIRECT && p->integrator == ZR_INTEGRATOR_RESTIR_PT) n = PlanesHalo(p->res[p->rptSet[set]], planes);
     else if (p->kind == ZR_PASS_INDIRECT && p->integrator == ZR_INTEGRATOR_RESTIR_GI)
-    { planes[n++] = {p->giA[set].p, 16}; planes[n++] = {p->giB[set].p, 8}; planes[n++] = {p->giC[set].p, 16}; }
-    else if (p->kind == ZR_PASS_DI_EMISSIVE) { planes[n++] = {p->diA[set].p, 16}; planes[n++] = {p->diB[set].p, 8}; }
-    else if (p->kind == ZR_PASS_DI_SKY) { planes[n++] = {p->skyA[set].p, 1}; planes[n++] = {p->skyB[set].p, 4}; planes[n++] = {p->skyC[set].p, 8}; }
+    { planes[n++] = p->giA[set].Halo(); planes[n++] = p->giB[set].Halo(); planes[n++] = p->giC[set].Halo(); }
+    else if (p->kind == ZR_PASS_DI_EMISSIVE) { planes[n++] = p->diA[set].Halo(); planes[n++] = p->diB[set].Halo(); }
+    else if (p->kind == ZR_PASS_DI_SKY) { planes[n++] = p->skyA[set].Halo(); planes[n++] = p->skyB[set].Halo(); planes[n++] = p->skyC[set].Halo(); }
     else if (p->kind == ZR_PASS_DENOISE)
     {
-        // INPUT: what the temporal step of a tile reads in its apron -- this frame's signal (the bound input plane: its owner shaded it) and the
-        // history the previous frame left (colour + length, moments); ITER: the plane the next a-trous iteration reads
-        if (which == ZR_HALO_DENOISE_INPUT && p->compIn[3])
-        { planes[n++] = {(void*)p->compIn[3], 16}; planes[n++] = {p->svgfHist.p, 16}; planes[n++] = {p->svgfMoments[p->svgfMomIdx].p, 8}; }
-        else if (which == ZR_HALO_DENOISE_ITER) planes[n++] = {p->svgfCur, 16};
+        // ITER: the plane the next a-trous iteration reads (svgfPing or svgfPong)
+        if (which == ZR_HALO_DENOISE_INPUT && p->compIn[3]) n = DenoiseInputPlanes(p, planes);
+        else if (which == ZR_HALO_DENOISE_ITER) planes[n++] = {p->svgfCur, p->svgfPing.bpp};
     }
-    size_t b = 0;
-    for (int i = 0; i < n; i++) b += planes[i].bpp;
-    *bytesPerPixel = b;
+    *bytesPerPixel = HaloBytes(planes, n);
     return n;
 }
 int zr_pass_halo_bytes_per_pixel(zr_pass* p, uint32_t* bytes)
 {
     if (!p || !bytes) return Fail(ZR_ERR_INVALID_ARG, "null argument");
     HaloPlane pl[8]; size_t b = 0;
-    if (p->initialized && p->kind == ZR_PASS_DENOISE) { *bytes = 40; return ZR_OK; }      // the larger of its two exchanges (ZR_HALO_DENOISE_INPUT; _ITER moves 16)
+    if (p->initialized && p->kind == ZR_PASS_DENOISE) { *bytes = (uint32_t)HaloBytes(pl, DenoiseInputPlanes(p, pl)); return ZR_OK; }      // the larger of its two exchanges (_ITER moves one plane)
     if (!p->initialized || !HaloPlanes(p, ZR_HALO_FINAL, pl, &b)) return Fail(ZR_ERR_NOT_INITIALIZED, "pass has no reservoir planes to exchange (or is not initialised)");
     *bytes = (uint32_t)b;
     return ZR_OK;
@@ -3356,8 +3322,8 @@ int zr_pass_get_output(const zr_pass* p, int which, void** dev, uint32_t* w, uin
     }
     if (p->kind == ZR_PASS_DISPLAY)
     {
-        if (which == ZR_OUT_DISPLAY) { *dev = p->displayOut.p; if (w) *w = p->w; if (h) *h = p->h; if (bpp) *bpp = 16; return ZR_OK; }
-        if (which == ZR_OUT_DISPLAY_SRGB8) { *dev = p->displaySrgb.p; if (w) *w = p->w; if (h) *h = p->h; if (bpp) *bpp = 4; return ZR_OK; }
+        if (which == ZR_OUT_DISPLAY) { p->displayOut.Output(dev, bpp); if (w) *w = p->w; if (h) *h = p->h; return ZR_OK; }
+        if (which == ZR_OUT_DISPLAY_SRGB8) { p->displaySrgb.Output(dev, bpp); if (w) *w = p->w; if (h) *h = p->h; return ZR_OK; }
         if (which == ZR_OUT_PICK_MASK)
         {
             if (!p->pickMaskW) return Fail(ZR_ERR_INVALID_ARG, "DISPLAY: no picked instance has been rendered (zr_pass_set_picked_instances)");
@@ -3369,101 +3335,74 @@ int zr_pass_get_output(const zr_pass* p, int which, void** dev, uint32_t* w, uin
     {
         if (w) *w = p->w;
         if (h) *h = p->h;
-        if (which == ZR_OUT_DENOISED) { *dev = (void*)p->svgfOut; if (bpp) *bpp = 16; return ZR_OK; }
-        if (which == ZR_OUT_DENOISE_HISTORY) { *dev = p->svgfHist.p; if (bpp) *bpp = 16; return ZR_OK; }
-        if (which == ZR_OUT_DENOISE_MOMENTS) { *dev = p->svgfMoments[p->svgfMomIdx].p; if (bpp) *bpp = 8; return ZR_OK; }
+        if (which == ZR_OUT_DENOISED) { *dev = (void*)p->svgfOut; if (bpp) *bpp = (uint32_t)p->svgfPing.bpp; return ZR_OK; }      // svgfPing or svgfPong
+        if (which == ZR_OUT_DENOISE_HISTORY) { p->svgfHist.Output(dev, bpp); return ZR_OK; }
+        if (which == ZR_OUT_DENOISE_MOMENTS) { p->svgfMoments[p->svgfMomIdx].Output(dev, bpp); return ZR_OK; }
         return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
     }
     if (p->kind == ZR_PASS_TAA)
     {
         if (which != ZR_OUT_TAA) return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
-        *dev = p->taaOut[p->taaIdx].p;
+        p->taaOut[p->taaIdx].Output(dev, bpp);
         if (w) *w = p->w;
         if (h) *h = p->h;
-        if (bpp) *bpp = 8;
         return ZR_OK;
     }
     if (p->kind == ZR_PASS_COMPOSITING)
     {
         if (which != ZR_OUT_FINAL) return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
-        *dev = p->finalRGBA.p;
+        p->finalRGBA.Output(dev, bpp);
         if (w) *w = p->w;
         if (h) *h = p->h;
-        if (bpp) *bpp = 16;
         return ZR_OK;
     }
     if (p->kind == ZR_PASS_DI_SKY)
     {
-        uint32_t b = 16;
         const int last = 1 - p->currIdx;
-        if (which == ZR_OUT_FINAL) *dev = p->finalRGBA.p;
-        else if (which == ZR_OUT_SDI_RESERVOIR_A) { *dev = p->skyA[last].p; b = 1; }
-        else if (which == ZR_OUT_SDI_RESERVOIR_B) { *dev = p->skyB[last].p; b = 4; }
-        else if (which == ZR_OUT_SDI_RESERVOIR_C) { *dev = p->skyC[last].p; b = 8; }
-        else if (which == ZR_OUT_SDI_TARGET) *dev = p->diTarget.p;
+        if (which == ZR_OUT_FINAL) p->finalRGBA.Output(dev, bpp);
+        else if (which == ZR_OUT_SDI_RESERVOIR_A) p->skyA[last].Output(dev, bpp);
+        else if (which == ZR_OUT_SDI_RESERVOIR_B) p->skyB[last].Output(dev, bpp);
+        else if (which == ZR_OUT_SDI_RESERVOIR_C) p->skyC[last].Output(dev, bpp);
+        else if (which == ZR_OUT_SDI_TARGET) p->diTarget.Output(dev, bpp);
         else return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
         if (w) *w = p->w;
         if (h) *h = p->h;
-        if (bpp) *bpp = b;
         return ZR_OK;
     }
     if (p->kind == ZR_PASS_DI_EMISSIVE)
     {
-        uint32_t b = 16;
         const int last = 1 - p->currIdx;        // the reservoir set written by the last frame
-        if (which == ZR_OUT_FINAL) *dev = p->finalRGBA.p;
-        else if (which == ZR_OUT_RDI_RESERVOIR_A) *dev = p->diA[last].p;
-        else if (which == ZR_OUT_RDI_RESERVOIR_B) { *dev = p->diB[last].p; b = 8; }
-        else if (which == ZR_OUT_RDI_TARGET) *dev = p->diTarget.p;
+        if (which == ZR_OUT_FINAL) p->finalRGBA.Output(dev, bpp);
+        else if (which == ZR_OUT_RDI_RESERVOIR_A) p->diA[last].Output(dev, bpp);
+        else if (which == ZR_OUT_RDI_RESERVOIR_B) p->diB[last].Output(dev, bpp);
+        else if (which == ZR_OUT_RDI_TARGET) p->diTarget.Output(dev, bpp);
         else return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
         if (w) *w = p->w;
         if (h) *h = p->h;
-        if (bpp) *bpp = b;
         return ZR_OK;
     }
     if (p->kind != ZR_PASS_INDIRECT) return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
-    uint32_t bytes = 16;
-    if (which == ZR_OUT_FINAL) *dev = p->Final(p->finOut);
+    if (which == ZR_OUT_FINAL) p->FinalPlane(p->finOut).Output(dev, bpp);
     else if (which >= ZR_OUT_RGI_RESERVOIR_A && which <= ZR_OUT_RGI_RESERVOIR_C && p->integrator == ZR_INTEGRATOR_RESTIR_GI)
     {
         const int last = 1 - p->currIdx;
-        if (which == ZR_OUT_RGI_RESERVOIR_A) *dev = p->giA[last].p;
-        else if (which == ZR_OUT_RGI_RESERVOIR_B) { *dev = p->giB[last].p; bytes = 8; }
-        else *dev = p->giC[last].p;
+        if (which == ZR_OUT_RGI_RESERVOIR_A) p->giA[last].Output(dev, bpp);
+        else if (which == ZR_OUT_RGI_RESERVOIR_B) p->giB[last].Output(dev, bpp);
+        else p->giC[last].Output(dev, bpp);
     }
     else if (which >= ZR_OUT_RPT_RBUF_CTN_A && which <= ZR_OUT_RPT_RBUF_NTC_D && p->integrator == ZR_INTEGRATOR_RESTIR_PT)
-    {
-        const zr_pass::RBufStorage& B = p->rb[(which - ZR_OUT_RPT_RBUF_CTN_A) / 4];
-        switch ((which - ZR_OUT_RPT_RBUF_CTN_A) % 4)
-        {
-        case 0: *dev = B.A.p; bytes = 8; break;
-        case 1: *dev = B.B.p; bytes = 16; break;
-        case 2: *dev = B.C.p; bytes = 16; break;
-        default: *dev = B.D.p; bytes = 2; break;
-        }
-    }
+        PlanesOutput(p->rb[(which - ZR_OUT_RPT_RBUF_CTN_A) / 4], (which - ZR_OUT_RPT_RBUF_CTN_A) % 4, dev, bpp);
     else if ((which == ZR_OUT_RPT_THREAD_MAP_CTN || which == ZR_OUT_RPT_THREAD_MAP_NTC) && p->integrator == ZR_INTEGRATOR_RESTIR_PT)
-    { *dev = p->rptMap[which - ZR_OUT_RPT_THREAD_MAP_CTN].p; bytes = 2; }
+        p->rptMap[which - ZR_OUT_RPT_THREAD_MAP_CTN].Output(dev, bpp);
     else if (which >= ZR_OUT_RPT_RESERVOIR_A && which <= ZR_OUT_RPT_NEIGHBOR && p->integrator == ZR_INTEGRATOR_RESTIR_PT)
     {
-        const zr_pass::ResStorage& R = p->RptOth();      // the set the next frame reads as "previous"
-        switch (which)
-        {
-        case ZR_OUT_RPT_RESERVOIR_A: *dev = R.A.p; bytes = 4; break;
-        case ZR_OUT_RPT_RESERVOIR_B: *dev = R.B.p; bytes = 8; break;
-        case ZR_OUT_RPT_RESERVOIR_C: *dev = R.C.p; bytes = 16; break;
-        case ZR_OUT_RPT_RESERVOIR_D: *dev = R.D.p; bytes = 16; break;
-        case ZR_OUT_RPT_RESERVOIR_E: *dev = R.E.p; bytes = 2; break;
-        case ZR_OUT_RPT_RESERVOIR_F: *dev = R.F.p; bytes = 8; break;
-        case ZR_OUT_RPT_RESERVOIR_G: *dev = R.G.p; bytes = 8; break;
-        case ZR_OUT_RPT_TARGET: *dev = p->Target(); bytes = 16; break;
-        default: *dev = p->rptNeighbor.p; bytes = 2; break;
-        }
+        if (which <= ZR_OUT_RPT_RESERVOIR_G) PlanesOutput(p->RptOth(), which - ZR_OUT_RPT_RESERVOIR_A, dev, bpp);      // the set the next frame reads as "previous"
+        else if (which == ZR_OUT_RPT_TARGET) p->TargetPlane().Output(dev, bpp);
+        else p->rptNeighbor.Output(dev, bpp);
     }
     else return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
     if (w) *w = p->w;
     if (h) *h = p->h;
-    if (bpp) *bpp = bytes;
     return ZR_OK;
 }
 int zr_pass_download_output(const zr_pass* p, int which, void* stream, void* dst, size_t bytes)
