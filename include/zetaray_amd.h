@@ -338,6 +338,34 @@ int zr_scene_background_rebuild_stats(zr_scene* scene, uint64_t* started, uint64
 int zr_scene_update_emissives_async(zr_scene* scene, void* hip_stream, const zr_emissive_triangle* triangles, uint32_t first, uint32_t count);
 int zr_scene_update_materials_async(zr_scene* scene, void* hip_stream, const zr_material* materials, uint32_t first, uint32_t count);
 int zr_scene_set_alias_table_async(zr_scene* scene, void* hip_stream, const zr_alias_entry* entries, uint32_t n);
+/* The frame's scene update from matrices alone: "instance i now has world matrix M" (world_3x4: n_moved x 12 floats, the layout of
+ * zr_scene_desc.instance_to_world; instance_idx: the n_moved instances they belong to).  The MeshInstance records and the EmissiveTriangle records
+ * of the moved instances are computed on the device (include/zr_scene_math.h: the functions the host's zrh_scene_data_* compile), so
+ * only n_moved x 52 bytes cross the bus, through the staging ring.  zr_scene_move_instances_async is equivalent, in every device byte, to
+ *   1. zrh_scene_data_begin_frame,
+ *   2. zrh_scene_data_set_instance_world for each listed instance, in list order,
+ *   3. zr_scene_update_emissives_async on the dirty range (zrh_scene_data_dirty_emissives),
+ *   4. zr_scene_update_instances_async on all records
+ * (zetaray_amd/host/zr_scene_io.h): current and previous instance buffer, the object-to-world matrices, the emissive records, BVH triangles and
+ * nodes, the role swap, the ordering against renders and the background rebuild are those of that sequence.  n_moved == 0 is the static frame of
+ * a scene that has been updated before (previous := current).  zr_scene_set_object_emissives hands over, once per scene, the object-space light
+ * records the moved ones are derived from (zrh_scene_data_initial_emissives; n == the scene's emissive count); which instance carries which
+ * triangle follows from the instances' base_emissive_tri_offset and triangle counts.  A moved light's record keeps every non-geometric field of its
+ * object-space record (ID, emissive factor, strength, texture index, UVs): the texture indices of the object-space records are held to the
+ * descriptor-table bounds check of zr_pass_render like those of records handed to zr_scene_update_emissives.
+ * The caller guarantees what the loader does: positive scale, no light triangle with a zero-length edge (its record's bytes are unspecified, as on
+ * the host).  The byte equivalence holds for the contract build, not for the tolerance-mode one (-DZR_ARITH_FAST).
+ * Refused, with nothing changed: an index >= the scene's instance count or listed twice, a null pointer with n_moved > 0 (ZR_ERR_INVALID_ARG); a
+ * moved instance that carries lights before zr_scene_set_object_emissives (ZR_ERR_NOT_INITIALIZED); ZR_SCENE_UPDATE=rebuild / rebuild_host, which
+ * are host-synchronous by construction (ZR_ERR_UNSUPPORTED).  zr_scene_move_instances = _async on the null stream, then wait. */
+int zr_scene_set_object_emissives(zr_scene* scene, const zr_emissive_triangle* object_space, uint32_t n);
+int zr_scene_has_object_emissives(const zr_scene* scene);      /* 1 once zr_scene_set_object_emissives has succeeded on this scene, else 0 */
+int zr_scene_move_instances_async(zr_scene* scene, void* hip_stream, const uint32_t* instance_idx, const float* world_3x4, uint32_t n_moved);
+int zr_scene_move_instances(zr_scene* scene, const uint32_t* instance_idx, const float* world_3x4, uint32_t n_moved);
+/* Read-backs for tests and tools, after waiting for `hip_stream` (pass the stream of the last update).  which: 0 = the current instance buffer,
+ * 1 = the previous one (the current one while the scene has never been updated); to_world_or_null: n x 12 floats. */
+int zr_scene_get_instances(const zr_scene* scene, void* hip_stream, int which, zr_mesh_instance* out, float* to_world_or_null, uint32_t n);
+int zr_scene_get_emissives(const zr_scene* scene, void* hip_stream, zr_emissive_triangle* out, uint32_t first, uint32_t count);
 /* Emissive MATERIALS changed (SceneCore::UpdateEmissiveMaterial: factor / strength rewritten in the records handed to zr_scene_update_emissives;
  * Scene::AreEmissiveMaterialsStale, PreLighting.cpp:266): drops the alias table, so that the next ZR_PASS_PRELIGHTING render re-estimates the
  * triangle powers (K2) and rebuilds it. */

@@ -1,6 +1,12 @@
 """Latency of zr_scene_update_instances on the BASELINE config-4 stand-in (262k-triangle atrium): device refit (default) next to the host rebuild
 (ZR_SCENE_UPDATE=rebuild), and the ReSTIR PT frame time on the refit / rebuilt tree after the largest non-emissive clutter instance moved.
-Prints one JSON line; scripts/gpu_refit.sh [rounds 1-4: git history up to 31e92fa; today scripts/gpu.sh ab] runs it once per mode.  GPU only."""
+Prints one JSON line; scripts/gpu_refit.sh [rounds 1-4: git history up to 31e92fa; today scripts/gpu.sh ab] runs it once per mode.  GPU only.
+
+--device-records: one dynamic frame's SCENE UPDATE both ways on the same scene with its light instance moving every frame -- the host path
+(zrh_scene_data_begin_frame / _set_instance_world, zr_scene_update_emissives_async + zr_scene_update_instances_async) and the device form
+(zr_scene_move_instances_async) -- as host wall time from the first call to the last return and as stream time between two events, at two light
+counts a factor of 8 apart (--emissive N and N / 8).  Median and p10 / p90 of --frames frames after --warmup; one JSON line.  Exit status 1 when the
+device path's host time at the larger count exceeds that at the smaller by more than the smaller run's p10 - p90 spread."""
 import json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -47,5 +53,105 @@ def main():
                       "kernel_ms_static": kms["static"], "kernel_ms_moving": kms["moving"]}))
 
 
+def _stats(x):
+    x = np.asarray(x, np.float64)
+    return {"median": round(float(np.median(x)), 4), "p10": round(float(np.percentile(x, 10)), 4), "p90": round(float(np.percentile(x, 90)), 4)}
+
+
+def device_records(num_emissive, frames, warmup):
+    import ctypes as C
+    import torch
+    out = {"mode": "device_records", "frames": frames, "warmup": warmup, "library": os.path.basename(api.LIB_PATH), "sizes": []}
+    L = scene_io._sceneio_lib()
+    L.zrh_scene_data_begin_frame.argtypes = [C.c_void_p]
+    L.zrh_scene_data_set_instance_world.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    L.zrh_scene_data_dirty_emissives.argtypes = [C.c_void_p] * 3
+    L.zrh_scene_data_from_desc.argtypes = [C.c_void_p] * 3
+    raw = {}      # unrounded host wall times, for the requirement below
+    for ne in (num_emissive // 8, num_emissive):
+        # the same total triangle count at both sizes (the clutter takes what the lights give up): the refit's kernel launches, one per tree level,
+        # are host time of either path and would otherwise differ with the tree's depth, not with the light count
+        sc = scene_io.make_synthetic_scene(num_tris=262144 + num_emissive - ne, num_emissive=ne, layout="atrium")
+        light = [i for i in range(len(sc.instances)) if sc.instances["base_emissive_tri_offset"][i] != 0xFFFFFFFF][0]
+        base = np.array(sc.instance_to_world[light], np.float32).reshape(3, 4)
+        assert np.array_equal(base, np.eye(3, 4, dtype=np.float32)), "the light instance's records are object-space ones only under the identity"
+        desc, init = sc.desc(), np.ascontiguousarray(sc.emissives.copy())
+        h = C.c_void_p()
+        assert L.zrh_scene_data_from_desc(C.addressof(desc), init.ctypes.data, C.byref(h)) == 0
+        d = L.zrh_scene_data_desc(h).contents
+        n = d.num_instances
+        inst = np.ctypeslib.as_array(C.cast(d.instances, C.POINTER(C.c_uint8)), (n * wire.MESH_INSTANCE.itemsize,)).view(wire.MESH_INSTANCE)
+        world = np.ctypeslib.as_array(C.cast(d.instance_to_world, C.POINTER(C.c_float)), (n, 12))
+        ems = np.ctypeslib.as_array(C.cast(d.emissives, C.POINTER(C.c_uint8)), (ne * 48,)).view(wire.EMISSIVE_TRI)
+        A, B = api.Scene(sc), api.Scene(sc)
+        B.set_object_emissives(init)
+        st = torch.cuda.Stream()
+        idx = np.array([light], np.uint32)
+
+        def matrix(k):
+            a = 0.01 * k
+            M = np.zeros((3, 4), np.float32)
+            M[:, :3] = np.float32([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+            M[:, 3] = np.float32([0.002 * k, 0.0, 0.001 * k])
+            return M
+
+        def host_frame(M):
+            L.zrh_scene_data_begin_frame(h)
+            L.zrh_scene_data_set_instance_world(h, light, M.ctypes.data)
+            first, count = C.c_uint32(), C.c_uint32()
+            L.zrh_scene_data_dirty_emissives(h, C.byref(first), C.byref(count))
+            A.update_emissives(ems[first.value:first.value + count.value], first.value, stream=st.cuda_stream)
+            A.update_instances(inst, world, stream=st.cuda_stream)
+
+        def device_frame(M):
+            B.move_instances(idx, M.reshape(1, 12), stream=st.cuda_stream)
+
+        def static_frame(M):
+            B.move_instances(idx[:0], M.reshape(1, 12)[:0], stream=st.cuda_stream)
+
+        res = {"num_emissive": ne, "num_instances": int(n), "bvh": list(A.bvh_info())}
+        for name, fn in (("host_path", host_frame), ("device_path", device_frame), ("device_path_nothing_moved", static_frame)):
+            wall, stream_ms = [], []
+            for k in range(1, warmup + frames + 1):
+                M = matrix(k)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record(st)
+                a = time.perf_counter()
+                fn(M)
+                b = time.perf_counter()
+                e1.record(st)
+                torch.cuda.synchronize()
+                if k > warmup:
+                    wall.append((b - a) * 1e3); stream_ms.append(e0.elapsed_time(e1))
+            res[name] = {"host_wall_ms": _stats(wall), "stream_ms": _stats(stream_ms)}
+            raw[(ne, name)] = np.asarray(wall, np.float64)
+        res["host_wall_ratio_host_over_device"] = round(res["host_path"]["host_wall_ms"]["median"] / res["device_path"]["host_wall_ms"]["median"], 2)
+        # k_mark_moved + k_move_emissives + the 52-byte copy: the device path's stream time over the same update with nothing moved.  k_move_instances
+        # runs in both (every update rewrites the instance buffer), so its time stays inside device_path_nothing_moved's, next to the refit's
+        res["mark_and_emissive_kernels_stream_ms"] = round(res["device_path"]["stream_ms"]["median"] - res["device_path_nothing_moved"]["stream_ms"]["median"], 4)
+        same = (A.download_emissives().tobytes() == ems.tobytes())
+        res["host_path_records_on_device"] = bool(same)
+        out["sizes"].append(res)
+        A.close(); B.close(); L.zrh_scene_data_destroy(h)
+    # required: the device path's host time does not grow with the number of light triangles -- at the larger size it may exceed that at the
+    # smaller by no more than the p10 - p90 spread of the smaller (unrounded values)
+    small, large = raw[(num_emissive // 8, "device_path")], raw[(num_emissive, "device_path")]
+    growth, spread = float(np.median(large) - np.median(small)), float(np.percentile(small, 90) - np.percentile(small, 10))
+    out["device_host_wall_growth_ms"], out["small_p10_p90_spread_ms"], out["device_host_wall_flat"] = growth, spread, bool(growth <= spread)
+    print(json.dumps(out))
+    return 0 if out["device_host_wall_flat"] else 1
+
+
 if __name__ == "__main__":
-    main()
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--device-records", action="store_true")
+    ap.add_argument("--emissive", type=int, default=100000)
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--warmup", type=int, default=16)
+    a = ap.parse_args()
+    if a.device_records:
+        sys.exit(device_records(a.emissive, max(a.frames, 64), max(a.warmup, 16)))
+    else:
+        main()

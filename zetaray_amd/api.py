@@ -62,6 +62,7 @@ EXPORTS = [
     "zr_pass_set_display_option", "zr_pass_set_picked_instances",
     "zr_pass_set_rpt_debug_view",
     "zr_pass_set_rgi_spatial",
+    "zr_scene_set_object_emissives", "zr_scene_has_object_emissives", "zr_scene_move_instances", "zr_scene_move_instances_async", "zr_scene_get_instances", "zr_scene_get_emissives",
 ]
 STAGE_TEMPORAL, STAGE_SPATIAL, STAGE_ALL = 1, 2, 3
 STAGE_SPATIAL2 = 4          # ReSTIR PT, num_spatial_passes = 2 on tiles: the second round, behind one more HALO_POST_TEMPORAL exchange
@@ -205,6 +206,52 @@ class Scene:
         else:
             L.zr_scene_update_instances_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
             _check(L.zr_scene_update_instances_async(self.h, stream, i.ctypes.data, x.ctypes.data, len(i)))
+
+    def set_object_emissives(self, tris):
+        """once per scene, before move_instances moves an instance that carries lights: the OBJECT-space EmissiveTriangle records
+        (zrh_scene_data_initial_emissives / scene_io's emissives_initial), one per emissive triangle of the scene"""
+        L = lib()
+        t = np.ascontiguousarray(tris, wire.EMISSIVE_TRI)
+        L.zr_scene_set_object_emissives.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        _check(L.zr_scene_set_object_emissives(self.h, t.ctypes.data, len(t)))
+
+    def move_instances(self, idx, world, stream=False):
+        """the frame's scene update from matrices alone (zr_scene_move_instances): instance idx[j] now has the 3 x 4 object-to-world matrix world[j];
+        the MeshInstance and EmissiveTriangle records follow on the device.  Empty lists = a frame in which nothing moves.  stream as update_instances"""
+        L = lib()
+        i = np.ascontiguousarray(idx, np.uint32).reshape(-1)
+        x = np.ascontiguousarray(world, np.float32).reshape(-1, 12)
+        if len(i) != len(x):
+            raise ValueError(f"move_instances: {len(i)} indices, {len(x)} matrices")
+        ip, xp = (i.ctypes.data, x.ctypes.data) if len(i) else (None, None)
+        if stream is False:
+            L.zr_scene_move_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+            _check(L.zr_scene_move_instances(self.h, ip, xp, len(i)))
+        else:
+            L.zr_scene_move_instances_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+            _check(L.zr_scene_move_instances_async(self.h, stream, ip, xp, len(i)))
+        # (a refused call changes nothing, here either.)  The records describe motion in the frame something moved, and rest in a frame nothing did
+        self.version += 1
+        self.instances_in_motion = len(i) > 0
+
+    def download_instances(self, which=0, stream=None):
+        """(MeshInstance records, (n, 12) object-to-world matrices) as the device holds them; which: 0 current, 1 previous"""
+        L = lib()
+        n = len(self.host.instances)
+        out, xf = np.zeros(n, wire.MESH_INSTANCE), np.zeros((n, 12), np.float32)
+        L.zr_scene_get_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32]
+        _check(L.zr_scene_get_instances(self.h, stream, which, out.ctypes.data, xf.ctypes.data, n))
+        return out, xf
+
+    def download_emissives(self, first=0, count=None, stream=None):
+        """the EmissiveTriangle records [first, first + count) as the device holds them (count None: to the end)"""
+        L = lib()
+        if count is None:
+            count = len(self.host.emissives) - first
+        out = np.zeros(count, wire.EMISSIVE_TRI)
+        L.zr_scene_get_emissives.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        _check(L.zr_scene_get_emissives(self.h, stream, out.ctypes.data, first, count))
+        return out
 
     def set_background_rebuild(self, on=True):
         """dynamic scenes: rebuild the SAH tree on a host thread for the instances' current transforms and swap it in at a later update_instances
@@ -651,6 +698,10 @@ class Renderer:
             return
         self.scene.invalidate_alias_table()
         self._alias_ready = False
+
+    def move_instances(self, idx, world, stream=False):
+        """the frame's scene update from matrices alone (Scene.move_instances; lights: Scene.set_object_emissives once before)"""
+        self.scene.move_instances(idx, world, stream=stream)
 
     def set_rgi_spatial(self, num_samples, radius_px=0.0):
         """ReSTIR GI: the spatial reuse stage of the indirect pass (Pass.set_rgi_spatial); stored without effect by the other integrators"""

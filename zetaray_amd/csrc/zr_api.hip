@@ -67,6 +67,8 @@ namespace zr { hipError_t LaunchInscattering(hipStream_t s, const SceneView& sc,
 namespace zr { hipError_t LaunchDisplayView(hipStream_t s, int option, const GBuf& gb, uint32_t dw, uint32_t dh, float cameraNear, float roughnessTh, F4* out, uint32_t* outSrgb); }   // zr_tu_display.hip
 namespace zr { hipError_t LaunchPickOutline(hipStream_t s, const zr_vertex* vertices, const uint32_t* indices, const zr_mesh_instance* instances, uint32_t inst, uint32_t numTris,
     const post::PickWvp& m, uint32_t dw, uint32_t dh, uint32_t rw, uint32_t rh, int4* tris, uint32_t* count, uint8_t* mask, F4* out, uint32_t* outSrgb); }   // zr_tu_display.hip
+namespace zr { hipError_t LaunchMoveInstances(hipStream_t st, zr_mesh_instance* cur, const zr_mesh_instance* prev, float* toWorld, uint32_t n, uint32_t* slot,
+    const uint32_t* moved, uint32_t nMoved, zr_emissive_triangle* emissives, const zr_emissive_triangle* object, const uint32_t* owner, uint32_t emFirst, uint32_t emEnd); }   // zr_tu_scene_update.hip
 // the ReSTIR PT kernels are compiled in zr_tu_rpt_[a-i].hip (see zr_kernels.h)
 ZR_RPT_GROUPS_PRODUCT(extern template)
 #ifdef ZR_EXPERIMENTS
@@ -585,6 +587,12 @@ struct zr_scene
     DevBuf<uint32_t> bgDev;                      // device side of the package (children + slot triangles)
     // instances whose transform has ever changed: the background build gives each a subtree of its own (zr_bvh.h Build, ownSubtree)
     std::vector<float> hToWorld; std::vector<uint8_t> movedEver;
+    // ---- the device form of the update (zr_scene_move_instances; kernels in zr_tu_scene_update.hip): the object-space light records and the instance that
+    // carries each (zr_scene_set_object_emissives), the frame's moved list [n_moved x 12 floats | n_moved indices] and each instance's position in it
+    // (0xffffffff between updates).  hInstances: the records as the host last stated them -- their static fields (mesh offsets, first light triangle)
+    // are what the background builder and the dirty light range need when the caller hands over matrices only.  toWorldDev: `toWorld` holds hToWorld
+    std::vector<zr_mesh_instance> hInstances; bool toWorldDev = false;
+    DevBuf<zr_emissive_triangle> objectEmissives; DevBuf<uint32_t> emissiveOwner, movedDev, movedSlot;
     ~zr_scene()
     {
         if (bg.th.joinable()) bg.th.join();
@@ -1371,11 +1379,13 @@ int zr_scene_create(int device, const zr_scene_desc* d, zr_scene** out)
     s->hVertices.assign(d->vertices, d->vertices + d->num_vertices); s->hIndices.assign(d->indices, d->indices + d->num_indices);
     s->hMask.assign(d->instance_mask, d->instance_mask + d->num_instances); s->hNumTris.assign(d->instance_num_tris, d->instance_num_tris + d->num_instances);
     s->hToWorld.assign(d->instance_to_world, d->instance_to_world + 12 * (size_t)d->num_instances); s->movedEver.assign(d->num_instances, 0);
+    s->hInstances.assign(d->instances, d->instances + d->num_instances);
     BvhLevels(bvh.nodes4, s->hLevelOrder, s->levelOffsets);
     if (!s->hLevelOrder.empty() && (r = s->levelNodes.Upload(s->hLevelOrder.data(), s->hLevelOrder.size()))) { delete s; return r; }
     if (deviceBuild)
     {
         if ((r = s->toWorld.Upload(d->instance_to_world, 12 * (size_t)d->num_instances)) || (r = DeviceRebuild(s, nullptr))) { delete s; return r; }
+        s->toWorldDev = true;
     }
     // uploads from pageable memory return once staged; renders on non-blocking streams must not start before the DMA has landed
     { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) { delete s; return Fail(ZR_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e)); } }
@@ -1463,6 +1473,11 @@ int zr_scene_invalidate_alias_table_deferred(zr_scene* s)
     if (s->view.alias) s->aliasStale = true;      // without a table there is nothing to keep: the next PRELIGHTING render builds one (first-frame path)
     return ZR_OK;
 }
+// What a frame's update consists of when the caller hands over matrices only (zr_scene_move_instances_async): the moved instances, their new
+// matrices, and the range of light triangles they carry
+struct MovedList { const uint32_t* idx; const float* xf; uint32_t n, emFirst, emEnd; };
+static int SceneRefitUpdate(zr_scene* s, hipStream_t st, const zr_mesh_instance* instances, const float* instance_to_world, uint32_t n, const MovedList* moved);
+
 int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_instance* instances, const float* instance_to_world, uint32_t n)
 {
     if (!s || !instances || !instance_to_world) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_update_instances: null argument");
@@ -1476,6 +1491,7 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
     for (uint32_t i = 0; i < n; i++)      // the reference's static -> dynamic conversion of an instance that starts to move (SceneCore.cpp:1038)
         if (std::memcmp(s->hToWorld.data() + 12 * (size_t)i, instance_to_world + 12 * (size_t)i, 12 * sizeof(float))) { s->movedEver[i] = 1; s->bg.movedSinceBuild = true; }
     std::memcpy(s->hToWorld.data(), instance_to_world, 12 * (size_t)n * sizeof(float));
+    s->hInstances.assign(instances, instances + n);
     const bool rebuildHost = modeEnv && !std::strcmp(modeEnv, "rebuild_host");
     if (rebuild && s->meta.n > BvhBuilder::kTinyScene)
     {
@@ -1499,6 +1515,7 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
         s->numNodesPrev = s->view.numNodes; s->numTrisPrev = s->view.numTris; s->hasPrev = true;
         HIP_TRY(hipMemcpy(s->instances.p, instances, (size_t)n * sizeof(zr_mesh_instance), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(s->toWorld.p, instance_to_world, 12 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        s->toWorldDev = true;
         s->view.instances = s->instances.p; s->view.triMeta = s->meta.p;
         if ((r = DeviceRebuild(s, st)))
         {
@@ -1539,9 +1556,18 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
         BvhLevels(bvh.nodes4, s->hLevelOrder, s->levelOffsets);
         if ((r = s->levelNodes.Upload(s->hLevelOrder.data(), s->hLevelOrder.size()))) return r;
         s->refitReady = false;      // the two buffer sets no longer share a topology
+        s->toWorldDev = false;      // ... and the device matrices were not touched
         return ZR_OK;
     }
-    // ---- refit on the device, stream-ordered: nothing below waits on the host (the staging ring aside, when the host runs far ahead)
+    return SceneRefitUpdate(s, st, instances, instance_to_world, n, nullptr);
+}
+// ---- refit on the device, stream-ordered: nothing below waits on the host (the staging ring aside, when the host runs far ahead).  The shared tail of
+// the two forms of the update.  Host form (moved == null): the caller's records and matrices are uploaded.  Device form: `instances` /
+// `instance_to_world` are the scene's own host copies (hInstances / hToWorld; hToWorld takes the frame's matrices once everything is enqueued), only the moved list is uploaded
+// and the records are computed on the device from the buffer that becomes previous (zr_tu_scene_update.hip)
+static int SceneRefitUpdate(zr_scene* s, hipStream_t st, const zr_mesh_instance* instances, const float* instance_to_world, uint32_t n, const MovedList* moved)
+{
+    int r;
     // background SAH rebuild: is a finished tree waiting to be installed by this update?
     const bool install = s->bg.enabled && s->bg.state.load(std::memory_order_acquire) == 2 && s->bg.packed && s->bg.inst.size() == n &&
                          s->bg.numTris == s->view.numTris && s->bg.stackNeed + 1 <= (uint32_t)kTravStack;
@@ -1574,10 +1600,24 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
     const size_t nn = s->view.numNodes, nt = s->view.numTris;
     const size_t instBytes = (size_t)n * sizeof(zr_mesh_instance), xfBytes = 12 * (size_t)n * sizeof(float);
     zr_scene::StageSlot* t;
-    if ((r = StageAcquire(s, instBytes + xfBytes, &t))) return r;
-    memcpy(t->host, instances, instBytes); memcpy((char*)t->host + instBytes, instance_to_world, xfBytes);
+    // device form: [every matrix as it was, once -- while the device copy of the matrices is not current | the moved matrices | the moved indices]
+    const bool seedXf = moved && (!s->toWorldDev || s->toWorld.n != 12 * (size_t)n);
+    const size_t movedBytes = moved ? 13 * (size_t)moved->n * sizeof(uint32_t) : 0, seedBytes = seedXf ? xfBytes : 0;
+    if ((r = StageAcquire(s, moved ? seedBytes + movedBytes : instBytes + xfBytes, &t))) return r;
+    if (!moved) { memcpy(t->host, instances, instBytes); memcpy((char*)t->host + instBytes, instance_to_world, xfBytes); }
+    else
+    {
+        if (seedXf) memcpy(t->host, s->hToWorld.data(), xfBytes);
+        memcpy((char*)t->host + seedBytes, moved->xf, 12 * (size_t)moved->n * sizeof(float));
+        memcpy((char*)t->host + seedBytes + 12 * (size_t)moved->n * sizeof(float), moved->idx, (size_t)moved->n * sizeof(uint32_t));
+    }
     if ((r = SceneWaitUsers(s, st))) return r;         // renders of earlier frames on other streams still read the buffers that change roles below
     std::lock_guard<std::mutex> lock(s->mtx);
+    if (moved && (s->movedSlot.n != n || s->movedDev.n != 13 * (size_t)n))
+    {   // once per scene; the slots start out as "did not move", in stream order
+        if ((r = s->movedSlot.Alloc(n)) || (r = s->movedDev.Alloc(13 * (size_t)n))) return r;
+        HIP_TRY(hipMemsetAsync(s->movedSlot.p, 0xff, (size_t)n * sizeof(uint32_t), st));
+    }
     if (!s->refitReady)
     {
         // both buffer sets must hold the same tree: duplicate the current one (once, or after a rebuild)
@@ -1593,8 +1633,19 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
     }
     std::swap(s->instances.p, s->instancesPrev.p); std::swap(s->nodes.p, s->nodesPrev.p); std::swap(s->tris.p, s->trisPrev.p); std::swap(s->meta.p, s->metaPrev.p);
     s->numNodesPrev = (uint32_t)nn; s->numTrisPrev = (uint32_t)nt; s->hasPrev = true;
-    HIP_TRY(hipMemcpyAsync(s->instances.p, t->host, instBytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->toWorld.p, (char*)t->host + instBytes, xfBytes, hipMemcpyHostToDevice, st));
+    if (!moved)
+    {
+        HIP_TRY(hipMemcpyAsync(s->instances.p, t->host, instBytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s->toWorld.p, (char*)t->host + instBytes, xfBytes, hipMemcpyHostToDevice, st));
+    }
+    else
+    {
+        if (seedXf) HIP_TRY(hipMemcpyAsync(s->toWorld.p, t->host, xfBytes, hipMemcpyHostToDevice, st));
+        if (moved->n) HIP_TRY(hipMemcpyAsync(s->movedDev.p, (char*)t->host + seedBytes, movedBytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(zr::LaunchMoveInstances(st, s->instances.p, s->instancesPrev.p, s->toWorld.p, n, s->movedSlot.p, s->movedDev.p, moved->n,
+            s->emissives.p, s->objectEmissives.p, s->emissiveOwner.p, moved->emFirst, moved->emEnd));
+    }
+    s->toWorldDev = true;
     if ((r = StageCommit(t, st))) return r;
     uint32_t numNodesNow = (uint32_t)nn;
     if (install)
@@ -1625,6 +1676,15 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
         hipLaunchKernelGGL(k_refit_level, dim3((cnt + 63) / 64), dim3(64), 0, st, s->nodes.p, s->levelNodes.p + first, cnt, s->tris.p, s->nodeBounds.p);
     }
     HIP_TRY(hipGetLastError());
+    if (moved)
+    {   // everything is enqueued: the host's view of the matrices follows (what zr_scene_update_instances_async does from the caller's array up front)
+        for (uint32_t j = 0; j < moved->n; j++)
+        {
+            float* M = s->hToWorld.data() + 12 * (size_t)moved->idx[j];
+            if (std::memcmp(M, moved->xf + 12 * (size_t)j, 12 * sizeof(float))) { s->movedEver[moved->idx[j]] = 1; s->bg.movedSinceBuild = true; }
+            std::memcpy(M, moved->xf + 12 * (size_t)j, 12 * sizeof(float));
+        }
+    }
     SceneView& v = s->view;
     v.instances = s->instances.p; v.nodes = s->nodes.p; v.tris = s->tris.p; v.triMeta = s->meta.p; v.numNodes = numNodesNow;
     if (!s->updated) HIP_TRY(hipEventCreateWithFlags(&s->updated, hipEventDisableTiming));
@@ -1636,7 +1696,7 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
         zr_scene::Background& B = s->bg;
         B.movedSinceBuild = false;
         if (B.th.joinable()) B.th.join();
-        B.inst.assign(instances, instances + n); B.xf.assign(instance_to_world, instance_to_world + 12 * (size_t)n);
+        B.inst.assign(instances, instances + n); B.xf.assign(s->hToWorld.begin(), s->hToWorld.end());      // (hToWorld: this update's matrices in either form)
         { const char* e = ZR_EXP_ENV("ZR_BVH_GROUP"); if (e && !std::strcmp(e, "0")) B.own.clear(); else B.own = s->movedEver; }
         B.state.store(1, std::memory_order_release); B.started++;
         zr_scene* sp = s;
@@ -1705,6 +1765,93 @@ int zr_scene_update_instances(zr_scene* s, const zr_mesh_instance* instances, co
     int r = zr_scene_update_instances_async(s, nullptr, instances, instance_to_world, n);
     if (r) return r;
     HIP_TRY(hipDeviceSynchronize());
+    return ZR_OK;
+}
+
+// ---- the device form of the frame's update: the caller says "instance i now has world matrix M", the records follow on the stream
+int zr_scene_set_object_emissives(zr_scene* s, const zr_emissive_triangle* object_space, uint32_t n)
+{
+    if (!s || (!object_space && n)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_object_emissives: null argument");
+    if (n != s->emissives.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_object_emissives: %u records, the scene has %zu emissive triangles", n, s->emissives.n);
+    // the instance that carries each light triangle, from the instances' first light triangle and triangle counts
+    std::vector<uint32_t> owner(n, 0xffffffffu);
+    for (size_t i = 0; i < s->hInstances.size(); i++)
+    {
+        const uint32_t b = s->hInstances[i].base_emissive_tri_offset;
+        if (b == 0xffffffffu) continue;
+        if ((uint64_t)b + s->hNumTris[i] > n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_object_emissives: instance %zu carries light triangles [%u, %llu), the scene has %u", i, b, (unsigned long long)b + s->hNumTris[i], n);
+        std::fill(owner.begin() + b, owner.begin() + b + s->hNumTris[i], (uint32_t)i);
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());      // an update in flight may still read the records this call replaces
+    int r;
+    if ((r = s->objectEmissives.Upload(object_space, n)) || (r = s->emissiveOwner.Upload(owner.data(), n))) { s->objectEmissives.Free(); s->emissiveOwner.Free(); return r; }
+    HIP_TRY(hipDeviceSynchronize());
+    // k_move_emissives keeps every non-geometric field of the object-space record, its emissive texture index included: these records count for the
+    // descriptor-table bounds check of zr_pass_render like the ones zr_scene_update_emissives hands over
+    for (uint32_t i = 0; i < n; i++) RaiseMaxTex(s, 3, object_space[i].packed_b & 0xffffu);
+    return ZR_OK;
+}
+int zr_scene_has_object_emissives(const zr_scene* s) { return s && s->objectEmissives.p ? 1 : 0; }
+int zr_scene_move_instances_async(zr_scene* s, void* stream, const uint32_t* instance_idx, const float* world_3x4, uint32_t n_moved)
+{
+    if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_move_instances: null scene");
+    if (n_moved && (!instance_idx || !world_3x4)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_move_instances: null argument with %u moved instances", n_moved);
+    const char* modeEnv = std::getenv("ZR_SCENE_UPDATE");
+    if (modeEnv && (!std::strcmp(modeEnv, "rebuild") || !std::strcmp(modeEnv, "rebuild_host")))
+        return Fail(ZR_ERR_UNSUPPORTED, "zr_scene_move_instances: ZR_SCENE_UPDATE=%s is a host-synchronous path; the device form of the update needs the refit (default or refit_sah)", modeEnv);
+    const uint32_t n = (uint32_t)s->instances.n;
+    MovedList moved{instance_idx, world_3x4, n_moved, 0xffffffffu, 0u};
+    {
+        std::vector<uint8_t> listed(n, 0);
+        for (uint32_t j = 0; j < n_moved; j++)
+        {
+            const uint32_t i = instance_idx[j];
+            if (i >= n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_move_instances: instance %u (entry %u of the list), the scene has %u", i, j, n);
+            if (listed[i]) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_move_instances: instance %u is listed twice", i);
+            listed[i] = 1;
+            const uint32_t b = s->hInstances[i].base_emissive_tri_offset;
+            if (b == 0xffffffffu || !s->emissives.n) continue;
+            if (!s->objectEmissives.p) return Fail(ZR_ERR_NOT_INITIALIZED, "zr_scene_move_instances: instance %u carries lights: call zr_scene_set_object_emissives first", i);
+            moved.emFirst = std::min(moved.emFirst, b); moved.emEnd = std::max(moved.emEnd, b + s->hNumTris[i]);
+        }
+    }
+    if (moved.emEnd <= moved.emFirst) moved.emFirst = moved.emEnd = 0;
+    HIP_TRY(hipSetDevice(s->device));
+    return SceneRefitUpdate(s, (hipStream_t)stream, s->hInstances.data(), s->hToWorld.data(), n, &moved);
+}
+int zr_scene_move_instances(zr_scene* s, const uint32_t* instance_idx, const float* world_3x4, uint32_t n_moved)
+{
+    int r = zr_scene_move_instances_async(s, nullptr, instance_idx, world_3x4, n_moved);
+    if (r) return r;
+    HIP_TRY(hipDeviceSynchronize());
+    return ZR_OK;
+}
+int zr_scene_get_instances(const zr_scene* s, void* stream, int which, zr_mesh_instance* out, float* to_world_or_null, uint32_t n)
+{
+    if (!s || !out) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_instances: null argument");
+    if (which != 0 && which != 1) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_instances: which = %d (0 current, 1 previous)", which);
+    if (n != s->instances.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_instances: %u instances, the scene has %zu", n, s->instances.n);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    const zr_mesh_instance* src; bool xfDev;
+    { std::lock_guard<std::mutex> lock(s->mtx); src = which == 1 && s->hasPrev ? s->instancesPrev.p : s->instances.p; xfDev = s->toWorldDev && s->toWorld.n == 12 * (size_t)n; }
+    HIP_TRY(hipMemcpy(out, src, (size_t)n * sizeof(zr_mesh_instance), hipMemcpyDeviceToHost));
+    if (to_world_or_null)
+    {   // the matrices live on the device from the first refit update on; before that the scene has only the host's
+        if (xfDev) HIP_TRY(hipMemcpy(to_world_or_null, s->toWorld.p, 12 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+        else std::memcpy(to_world_or_null, s->hToWorld.data(), 12 * (size_t)n * sizeof(float));
+    }
+    return ZR_OK;
+}
+int zr_scene_get_emissives(const zr_scene* s, void* stream, zr_emissive_triangle* out, uint32_t first, uint32_t count)
+{
+    if (!s || (!out && count)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_emissives: null argument");
+    if ((uint64_t)first + count > s->emissives.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_emissives: [%u, %llu) exceeds the scene's %zu emissive triangles", first, (unsigned long long)first + count, s->emissives.n);
+    if (!count) return ZR_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(hipMemcpy(out, s->emissives.p + first, (size_t)count * sizeof(zr_emissive_triangle), hipMemcpyDeviceToHost));
     return ZR_OK;
 }
 

@@ -789,6 +789,15 @@ extern "C" int zrh_scene_apply_updates_on(zr_scene* scene, const zrh_scene_data*
 {
     if (!scene || !data) return -1;
     const zr_scene_desc* d = zrh_scene_data_desc(data);
+    if (zrh_scene_data_device_records(data))
+    {   // the device form: the moved instances and their matrices only; the records follow on the stream (zr_scene_move_instances_async)
+        // (the object-space light records once per device scene: whether they have arrived is the scene's to say, so one zrh_scene_data can drive several)
+        if (!zr_scene_has_object_emissives(scene) && zrh_scene_data_initial_emissives(data))
+        { const int r = zr_scene_set_object_emissives(scene, zrh_scene_data_initial_emissives(data), d->num_emissives); if (r) return r; }
+        const uint32_t* idx = nullptr; const float* world = nullptr;
+        const uint32_t nMoved = zrh_scene_data_moved(data, &idx, &world);
+        return zr_scene_move_instances_async(scene, stream, idx, world, nMoved);
+    }
     uint32_t first = 0, count = 0;
     zrh_scene_data_dirty_emissives(data, &first, &count);
     if (count) { const int r = zr_scene_update_emissives_async(scene, stream, d->emissives + first, first, count); if (r) return r; }

@@ -3,6 +3,8 @@
 // small enough for the JSON reader below).
 #include "zr_scene_io.h"
 #include "../../include/zr_detmath.h"
+#include "../../include/zr_scene_math.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -13,6 +15,9 @@
 #include <vector>
 
 namespace {
+
+// Mat43 / FromToWorld / DecomposeSRT / FillMeshInstance / the EmissiveTriangle encode, decode and transform: one statement for the host and the device
+using namespace zrsm;
 
 thread_local std::string g_err;
 struct Error { std::string what; };
@@ -108,21 +113,7 @@ std::string DirOf(const std::string& p) { size_t i = p.find_last_of('/'); return
 // ------------------------------------------------------------------------------------------------ packing helpers (Material.h, Vector.h)
 uint32_t Unorm8(float f) { f = f < 0.0f ? 0.0f : (f > 1.0f ? 1.0f : f); return (uint32_t)(f * 255.0f + 0.5f); }
 uint32_t Rgb8(const float* c) { return Unorm8(c[0]) | (Unorm8(c[1]) << 8) | (Unorm8(c[2]) << 16); }      // Float3ToRGB8
-// Math::encode_octahedral (VectorFuncs.h:134-153) + unorm2::FromNormalized (Vector.h:626-647), in the SSE code's operation order:
-// |x| + |z| first, then + |y| (hadd_float3); the fold's sign comes from the INPUT component (v >= 0, so -0.0 counts as positive);
-// [-1, 1] -> [0, 1] is one fma; cvtps_epi32 rounds to nearest even
-void EncodeOct32(const float* n, uint16_t out[2])
-{
-    const float denom = (std::fabs(n[0]) + std::fabs(n[2])) + std::fabs(n[1]);
-    const float p[2] = {n[0] / denom, n[1] / denom};
-    for (int k = 0; k < 2; k++)
-    {
-        const float sgn = n[k] >= 0.0f ? 1.0f : -1.0f;
-        const float folded = (1.0f - std::fabs(p[1 - k])) * sgn;
-        const float enc = n[2] <= 0.0f ? folded : p[k];
-        out[k] = (uint16_t)std::nearbyintf(std::fma(enc, 0.5f, 0.5f) * 65535.0f);
-    }
-}
+// (EncodeOct32 -- Math::encode_octahedral + unorm2::FromNormalized -- is in zr_scene_math.h)
 
 struct MaterialDesc      // glTF::Asset::MaterialDesc defaults (Material.h:66-95 via pack below)
 {
@@ -155,10 +146,7 @@ zr_material PackMaterial(const MaterialDesc& d)
 }
 
 // ------------------------------------------------------------------------------------------------ transforms (Math/MatrixFuncs.h)
-// Row-vector 4 x 4 as the reference stores it: rows 0-2 = images of the basis vectors, row 3 = translation.  Only [i][0..2] is kept.
-struct Mat43 { float m[4][3]; };
-Mat43 FromToWorld(const float* M)       // 3 x 4 row-major, column-vector convention -> reference layout
-{ Mat43 r; for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) r.m[i][j] = M[4 * j + i]; for (int j = 0; j < 3; j++) r.m[3][j] = M[4 * j + 3]; return r; }
+// Mat43 (zr_scene_math.h): row-vector 4 x 4 as the reference stores it, rows 0-2 = images of the basis vectors, row 3 = translation
 void ToToWorld(const Mat43& r, float* M) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) M[4 * j + i] = r.m[i][j]; for (int j = 0; j < 3; j++) M[4 * j + 3] = r.m[3][j]; }
 
 // rotationMatFromQuat, MatrixFuncs.h:356-405 (operation order of the SSE code)
@@ -197,92 +185,6 @@ Mat43 Mul(const Mat43& A, const Mat43& B)
         }
     }
     return C;
-}
-// decomposeSRT, MatrixFuncs.h:562-610 + quaternionFromRotationMat1, :410-437
-void DecomposeSRT(const Mat43& M, float s[3], float q[4], float t[3])
-{
-    for (int j = 0; j < 3; j++) t[j] = M.m[3][j];
-    float R[3][3];
-    for (int i = 0; i < 3; i++)
-    {
-        // diagonal of M M^T through mul(): (m0 m0 + m1 m1) + (m2 m2 + 0 0)
-        const float s2 = std::fma(M.m[i][1], M.m[i][1], M.m[i][0] * M.m[i][0]) + std::fma(0.0f, 0.0f, M.m[i][2] * M.m[i][2]);
-        s[i] = std::sqrt(s2);
-        const float inv = 1.0f / s[i];
-        for (int j = 0; j < 3; j++) R[i][j] = inv * M.m[i][j];
-    }
-    float tt[4], Q[4][4];
-    tt[0] = 1 + R[0][0] - R[1][1] - R[2][2];
-    tt[1] = 1 - R[0][0] + R[1][1] - R[2][2];
-    tt[2] = 1 - R[0][0] - R[1][1] + R[2][2];
-    tt[3] = 1 + R[0][0] + R[1][1] + R[2][2];
-    const float a = R[0][1] + R[1][0], b = R[2][0] + R[0][2], c = R[1][2] - R[2][1], d = R[1][2] + R[2][1], e = R[2][0] - R[0][2], f = R[0][1] - R[1][0];
-    const float q0[4] = {tt[0], a, b, c}, q1[4] = {a, tt[1], d, e}, q2[4] = {b, d, tt[2], f}, q3[4] = {c, e, f, tt[3]};
-    std::memcpy(Q[0], q0, 16); std::memcpy(Q[1], q1, 16); std::memcpy(Q[2], q2, 16); std::memcpy(Q[3], q3, 16);
-    const int i = (R[2][2] >= 0) * (2 + (R[0][0] >= -R[1][1])) + (R[2][2] < 0) * (R[1][1] >= R[0][0]);
-    const float k = 0.5f / std::sqrt(tt[i]);
-    for (int j = 0; j < 4; j++) q[j] = Q[i][j] * k;
-    // float4::normalize: _mm_dp_ps sums (x^2 + y^2) + (z^2 + w^2)
-    const float norm = std::sqrt((q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3]));
-    const float inv = 1.0f / norm;
-    for (int j = 0; j < 4; j++) q[j] *= inv;
-}
-// unorm4::FromNormalized (Vector.h:745-769): fma(v, 0.5, 0.5) * 65535, round to nearest even
-uint16_t Unorm16FromNormalized(float v) { return (uint16_t)std::nearbyintf(std::fma(v, 0.5f, 0.5f) * 65535.0f); }
-
-void FillMeshInstance(const float* toWorld, zr_mesh_instance& I)
-{
-    float s[3], q[4], t[3];
-    DecomposeSRT(FromToWorld(toWorld), s, q, t);
-    for (int k = 0; k < 4; k++) I.rotation[k] = I.prev_rotation[k] = Unorm16FromNormalized(q[k]);
-    for (int k = 0; k < 3; k++) { I.scale[k] = I.prev_scale[k] = zr_f32_to_f16(s[k]); I.translation[k] = t[k]; I.d_translation[k] = zr_f32_to_f16(0.0f); }
-}
-
-// RT::EmissiveTriangle::StoreVertices (RtCommon.h:141-198): vertex 0 + the two edges as 16-bit octahedral directions and half lengths
-void StoreEmissiveVertices(zr_emissive_triangle& e, const float* v0, const float* v1, const float* v2)
-{
-    float e0[3], e1[3];
-    for (int k = 0; k < 3; k++) { e.vtx0[k] = v0[k]; e0[k] = v1[k] - v0[k]; e1[k] = v2[k] - v0[k]; }
-    const float l0 = std::sqrt((e0[0] * e0[0] + e0[1] * e0[1]) + (e0[2] * e0[2] + 0.0f)), l1 = std::sqrt((e1[0] * e1[0] + e1[1] * e1[1]) + (e1[2] * e1[2] + 0.0f));
-    const float n0[3] = {e0[0] / l0, e0[1] / l0, e0[2] / l0}, n1[3] = {e1[0] / l1, e1[1] / l1, e1[2] / l1};
-    EncodeOct32(n0, e.v0v1); EncodeOct32(n1, e.v0v2);
-    e.edge_lengths[0] = zr_f32_to_f16(l0); e.edge_lengths[1] = zr_f32_to_f16(l1);
-}
-// RT::EmissiveTriangle::DecodeVertices (RtCommon.h:200-234) with Math::decode_octahedral (VectorFuncs.h:155-174) and normalize (:64-70: dpps sums
-// (x^2 + y^2) + (z^2 + 0)), in the SSE code's operation order
-void DecodeEmissiveVertices(const zr_emissive_triangle& e, float* v0, float* v1, float* v2)
-{
-    const uint16_t enc[4] = {e.v0v1[0], e.v0v1[1], e.v0v2[0], e.v0v2[1]};
-    float u[4];
-    for (int k = 0; k < 4; k++) u[k] = std::fma((float)(int32_t)enc[k] / 65535.0f, 2.0f, -1.0f);
-    const float len[2] = {zr_f16_to_f32(e.edge_lengths[0]), zr_f16_to_f32(e.edge_lengths[1])};
-    float* out[2] = {v1, v2};
-    for (int j = 0; j < 2; j++)
-    {
-        const float ux = u[2 * j], uy = u[2 * j + 1];
-        const float z = 1.0f - (std::fabs(ux) + std::fabs(uy));
-        const float nz = 0.0f - z, posT = nz < 0.0f ? 0.0f : (nz > 1.0f ? 1.0f : nz), negT = 0.0f - posT;      // saturate(negate(z)), negate
-        const float dx = ux + (ux >= 0.0f ? negT : posT), dy = uy + (uy >= 0.0f ? negT : posT);
-        const float n = std::sqrt((dx * dx + dy * dy) + (z * z + 0.0f));
-        const float d[3] = {dx / n, dy / n, z / n};
-        for (int k = 0; k < 3; k++) out[j][k] = std::fma(d[k], len[j], e.vtx0[k]);
-    }
-    for (int k = 0; k < 3; k++) v0[k] = e.vtx0[k];
-}
-// mul(v_float4x4, __m128) (MatrixFuncs.h:93-112) of a point (w = 1) with a 3 x 4 object-to-world matrix (column-vector convention, zr_scene_desc)
-void MulPoint(const float* M, const float* v, float* out)
-{
-    for (int r = 0; r < 3; r++) out[r] = std::fma(1.0f, M[4 * r + 3], std::fma(v[2], M[4 * r + 2], std::fma(v[1], M[4 * r + 1], v[0] * M[4 * r])));
-}
-// the emissive-triangle transform of SceneCore (SceneCore.cpp:196-236 on the first frame, UpdateEmissivePositions :913-955 for moving instances):
-// decode the stored (object-space) triangle, transform its vertices, encode again -- every other field is kept
-void EmissiveToWorld(const zr_emissive_triangle& in, const float* M, zr_emissive_triangle& out)
-{
-    float v0[3], v1[3], v2[3], w0[3], w1[3], w2[3];
-    DecodeEmissiveVertices(in, v0, v1, v2);
-    MulPoint(M, v0, w0); MulPoint(M, v1, w1); MulPoint(M, v2, w2);
-    out = in;
-    StoreEmissiveVertices(out, w0, w1, w2);
 }
 
 // RT::EmissiveTriangle ctor + StoreVertices (RtCommon.h:73-190)
@@ -430,6 +332,9 @@ struct zrh_scene_data
     std::vector<uint16_t> rho; uint32_t rhoDim[3] = {0, 0, 0};
     std::vector<zr_texture_desc> textures; std::vector<uint8_t> texels; uint32_t texOffsets[4] = {0, 0, 0, 0};
     std::vector<float> prevWorld; uint32_t dirtyFirst = 0xffffffffu, dirtyEnd = 0;      // per-frame maintenance (zrh_scene_data_begin_frame / _set_instance_world)
+    // the instances set_instance_world named this frame, each once, with their matrices; movedSlot[i] = where instance i stands in that list
+    std::vector<uint32_t> movedIdx, movedSlot; std::vector<float> movedWorld;
+    bool deviceRecords = false;      // zrh_scene_data_set_device_records (zr_host.h: zrh_scene_apply_updates)
     zr_scene_desc desc;
     void Finish()
     {
@@ -749,27 +654,22 @@ void zrh_scene_data_begin_frame(zrh_scene_data* s)
 {
     if (!s) return;
     s->prevWorld = s->toWorld;
-    for (zr_mesh_instance& I : s->instances)      // an instance that does not move this frame: Prev* = current, dTranslation = 0
-    {
-        for (int k = 0; k < 4; k++) I.prev_rotation[k] = I.rotation[k];
-        for (int k = 0; k < 3; k++) { I.prev_scale[k] = I.scale[k]; I.d_translation[k] = zr_f32_to_f16(0.0f); }
-    }
+    for (zr_mesh_instance& I : s->instances) InstanceBeginFrame(I);      // an instance that does not move this frame: Prev* = current, dTranslation = 0
     s->dirtyFirst = 0xffffffffu; s->dirtyEnd = 0;
+    for (uint32_t i : s->movedIdx) s->movedSlot[i] = 0xffffffffu;
+    s->movedIdx.clear(); s->movedWorld.clear();
 }
 int zrh_scene_data_set_instance_world(zrh_scene_data* s, uint32_t inst, const float* world)
 {
     if (!s || !world || inst >= s->instances.size()) { g_err = "zrh_scene_data_set_instance_world: bad argument"; return -1; }
     if (s->prevWorld.size() != s->toWorld.size()) s->prevWorld = s->toWorld;
     zr_mesh_instance& I = s->instances[inst];
-    // TLAS::FillMeshInstanceData, !staticMesh branch (RtAccelerationStructure.cpp:318-380): current and previous S / R / T by decomposeSRT of the two
-    // world matrices, dTranslation = half3(t - t_prev)
-    float sc[3], q[4], t[3], sp[3], qp[4], tp[3];
-    DecomposeSRT(FromToWorld(world), sc, q, t);
-    DecomposeSRT(FromToWorld(s->prevWorld.data() + 12 * (size_t)inst), sp, qp, tp);
-    for (int k = 0; k < 4; k++) { I.rotation[k] = Unorm16FromNormalized(q[k]); I.prev_rotation[k] = Unorm16FromNormalized(qp[k]); }
-    for (int k = 0; k < 3; k++)
-    { I.scale[k] = zr_f32_to_f16(sc[k]); I.prev_scale[k] = zr_f32_to_f16(sp[k]); I.translation[k] = t[k]; I.d_translation[k] = zr_f32_to_f16(t[k] - tp[k]); }
+    // TLAS::FillMeshInstanceData, !staticMesh branch: current and previous S / R / T by decomposeSRT of the two world matrices
+    InstanceSetWorld(I, world, s->prevWorld.data() + 12 * (size_t)inst);
     std::memcpy(s->toWorld.data() + 12 * (size_t)inst, world, 12 * sizeof(float));
+    if (s->movedSlot.size() != s->instances.size()) s->movedSlot.assign(s->instances.size(), 0xffffffffu);
+    if (s->movedSlot[inst] == 0xffffffffu) { s->movedSlot[inst] = (uint32_t)s->movedIdx.size(); s->movedIdx.push_back(inst); s->movedWorld.resize(12 * s->movedIdx.size()); }
+    std::memcpy(s->movedWorld.data() + 12 * (size_t)s->movedSlot[inst], world, 12 * sizeof(float));
     // SceneCore::UpdateEmissivePositions for an instance that carries lights
     if (I.base_emissive_tri_offset != 0xffffffffu && !s->emissivesInitial.empty())
     {
@@ -783,6 +683,34 @@ void zrh_scene_data_dirty_emissives(const zrh_scene_data* s, uint32_t* first, ui
 {
     const bool any = s && s->dirtyEnd > s->dirtyFirst;
     *first = any ? s->dirtyFirst : 0u; *count = any ? s->dirtyEnd - s->dirtyFirst : 0u;
+}
+uint32_t zrh_scene_data_moved(const zrh_scene_data* s, const uint32_t** idx, const float** world)
+{
+    if (!s) return 0;
+    if (idx) *idx = s->movedIdx.data();
+    if (world) *world = s->movedWorld.data();
+    return (uint32_t)s->movedIdx.size();
+}
+void zrh_scene_data_set_device_records(zrh_scene_data* s, int on) { if (s) s->deviceRecords = on != 0; }
+int zrh_scene_data_device_records(const zrh_scene_data* s) { return s && s->deviceRecords ? 1 : 0; }
+int zrh_scene_data_from_desc(const zr_scene_desc* d, const zr_emissive_triangle* object_space_emissives, zrh_scene_data** out)
+{
+    if (!d || !out || !d->vertices || !d->indices || !d->instances || !d->instance_to_world || !d->instance_mask || !d->instance_num_tris || !d->materials || !d->rho_lut ||
+        (d->num_emissives && !d->emissives))
+    { g_err = "zrh_scene_data_from_desc: incomplete scene description"; return -1; }
+    std::unique_ptr<zrh_scene_data> sc(new zrh_scene_data());
+    sc->vertices.assign(d->vertices, d->vertices + d->num_vertices); sc->indices.assign(d->indices, d->indices + d->num_indices);
+    sc->instances.assign(d->instances, d->instances + d->num_instances); sc->toWorld.assign(d->instance_to_world, d->instance_to_world + 12 * (size_t)d->num_instances);
+    sc->mask.assign(d->instance_mask, d->instance_mask + d->num_instances); sc->numTris.assign(d->instance_num_tris, d->instance_num_tris + d->num_instances);
+    sc->materials.assign(d->materials, d->materials + d->num_materials);
+    if (d->num_emissives) sc->emissives.assign(d->emissives, d->emissives + d->num_emissives);
+    if (d->num_emissives && object_space_emissives) sc->emissivesInitial.assign(object_space_emissives, object_space_emissives + d->num_emissives);
+    sc->rho.assign(d->rho_lut, d->rho_lut + (size_t)d->rho_dim[0] * d->rho_dim[1] * d->rho_dim[2]); for (int k = 0; k < 3; k++) sc->rhoDim[k] = d->rho_dim[k];
+    if (d->num_textures && d->textures) sc->textures.assign(d->textures, d->textures + d->num_textures);
+    if (d->texel_bytes && d->texels) sc->texels.assign(d->texels, d->texels + d->texel_bytes);
+    sc->Finish();
+    *out = sc.release();
+    return 0;
 }
 void zrh_emissive_to_world(const zr_emissive_triangle* in, const float* to_world_3x4, zr_emissive_triangle* out) { zr_emissive_triangle t; EmissiveToWorld(*in, to_world_3x4, t); *out = t; }
 const zr_emissive_triangle* zrh_scene_data_initial_emissives(const zrh_scene_data* s) { return s && !s->emissivesInitial.empty() ? s->emissivesInitial.data() : nullptr; }

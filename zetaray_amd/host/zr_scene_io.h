@@ -36,6 +36,17 @@ void zrh_scene_data_destroy(zrh_scene_data* s);
 void zrh_scene_data_begin_frame(zrh_scene_data* s);
 int zrh_scene_data_set_instance_world(zrh_scene_data* s, uint32_t instance, const float* world_3x4);
 void zrh_scene_data_dirty_emissives(const zrh_scene_data* s, uint32_t* first, uint32_t* count);
+// ... or, for the device form of the update (zr_scene_move_instances, include/zetaray_amd.h), which instances set_instance_world named since
+// begin_frame -- each once, in the order they were first named -- and their current matrices (n x 12 floats; valid until the next call on `s`).
+// zrh_scene_data_set_device_records(s, 1) makes zrh_scene_apply_updates (zr_host.h) hand over exactly that instead of records.  The host's own
+// records are maintained either way (set_instance_world still runs the record math: the device form saves the upload, and a caller that wants
+// to save the host math too calls zr_scene_move_instances itself and keeps no zrh_scene_data records)
+uint32_t zrh_scene_data_moved(const zrh_scene_data* s, const uint32_t** idx, const float** world_3x4);
+void zrh_scene_data_set_device_records(zrh_scene_data* s, int on);
+int zrh_scene_data_device_records(const zrh_scene_data* s);
+// the per-frame maintenance above for a scene that did not come from zrh_gltf_load: a deep copy of `desc`; object_space_emissives = desc->num_emissives
+// object-space light records (null: instances that carry lights keep their records when they move)
+int zrh_scene_data_from_desc(const zr_scene_desc* desc, const zr_emissive_triangle* object_space_emissives, zrh_scene_data** out);
 
 // ---- building blocks, exported for the parity pins (tests/test_scene_io.py) ----
 // decomposeSRT + quaternionFromRotationMat1 of a 3 x 4 row-major object-to-world matrix (column-vector convention, zr_scene_desc.instance_to_world)
