@@ -69,6 +69,8 @@ namespace zr { hipError_t LaunchPickOutline(hipStream_t s, const zr_vertex* vert
     const post::PickWvp& m, uint32_t dw, uint32_t dh, uint32_t rw, uint32_t rh, int4* tris, uint32_t* count, uint8_t* mask, F4* out, uint32_t* outSrgb); }   // zr_tu_display.hip
 namespace zr { hipError_t LaunchMoveInstances(hipStream_t st, zr_mesh_instance* cur, const zr_mesh_instance* prev, float* toWorld, uint32_t n, uint32_t* slot,
     const uint32_t* moved, uint32_t nMoved, zr_emissive_triangle* emissives, const zr_emissive_triangle* object, const uint32_t* owner, uint32_t emFirst, uint32_t emEnd); }   // zr_tu_scene_update.hip
+namespace zr { hipError_t LaunchFillInstRecs(hipStream_t st, InstRec* recs, const zr_mesh_instance* instances, uint32_t n);      // zr_tu_scene_update.hip
+               hipError_t LaunchFillVtxNormals(hipStream_t st, VtxDir* out, const zr_vertex* vertices, uint32_t n, bool tangent); }
 // the ReSTIR PT kernels are compiled in zr_tu_rpt_[a-i].hip (see zr_kernels.h)
 ZR_RPT_GROUPS_PRODUCT(extern template)
 #ifdef ZR_EXPERIMENTS
@@ -544,6 +546,12 @@ struct zr_scene
     std::vector<zr_vertex> hVertices; std::vector<uint32_t> hIndices; std::vector<uint8_t> hMask; std::vector<uint32_t> hNumTris;
     DevBuf<zr_mesh_instance> instancesPrev; DevBuf<Bvh4Node> nodesPrev; DevBuf<BvhTri> trisPrev; DevBuf<TriMeta> metaPrev;
     uint32_t numNodesPrev = 0, numTrisPrev = 0; bool hasPrev = false;
+    // what hit reconstruction decodes from an instance record / a vertex normal, stored once (zr_hit_tables.h).  instRecs belongs to `instances`, instRecsPrev
+    // to `instancesPrev`: they swap wherever those swap, and whatever writes an instance array refills its table on the same stream (SceneFillInstRecs)
+    DevBuf<InstRec> instRecs, instRecsPrev; DevBuf<VtxDir> vtxNormals;
+#if ZR_HIT_TANGENTS
+    DevBuf<VtxDir> vtxTangents;
+#endif
     // device refit: node indices grouped by tree level (deepest level first) + the offsets of the groups, per-node float bounds, object-to-world matrices
     DevBuf<uint32_t> levelNodes; std::vector<uint32_t> levelOffsets, hLevelOrder; DevBuf<float> nodeBounds, toWorld; bool refitReady = false;
     // device-side BVH build (zr_tu_bvh.hip): instance masks on the device, scratch buffers kept between builds
@@ -707,6 +715,7 @@ static SceneView FrameViewPrev(const zr_scene* sc, const zr_frame_constants* cb)
     if (sc->hasPrev)
     {
         v.instances = sc->instancesPrev.p; v.nodes = sc->nodesPrev.p; v.tris = sc->trisPrev.p; v.triMeta = sc->metaPrev.p;
+        v.instRecs = sc->instRecsPrev.p;
         v.numNodes = sc->numNodesPrev; v.numTris = sc->numTrisPrev;
     }
     return v;
@@ -1293,6 +1302,22 @@ static int DeviceRebuild(zr_scene* s, hipStream_t st)
     return ZR_OK;
 }
 
+// The instance array that has just been written on `st` (an upload, LaunchMoveInstances) gets its table of decoded records on the same stream
+static int SceneFillInstRecs(zr_scene* s, hipStream_t st)
+{
+    HIP_TRY(zr::LaunchFillInstRecs(st, s->instRecs.p, s->instances.p, (uint32_t)s->instances.n));
+    s->view.instRecs = s->instRecs.p;
+    return ZR_OK;
+}
+// instances <-> instancesPrev changed roles: so do their tables (the previous one is allocated on first use)
+static int SceneSwapInstRecs(zr_scene* s, size_t n)
+{
+    int r;
+    if (s->instRecsPrev.n != n && (r = s->instRecsPrev.Alloc(n))) return r;
+    std::swap(s->instRecs.p, s->instRecsPrev.p); std::swap(s->instRecs.n, s->instRecsPrev.n);
+    return ZR_OK;
+}
+
 // SceneView::plain: no material of the table is metallic, transmissive, thin-walled or coated (the fields GetMaterialData turns into those lobes, Material.h:268-427)
 static bool MaterialsArePlain(const std::vector<zr_material>& m)
 {
@@ -1354,6 +1379,18 @@ int zr_scene_create(int device, const zr_scene_desc* d, zr_scene** out)
     }
     UP(srgb, zr_srgb_to_linear_table, 256);
 #undef UP
+    // the decoded tables of zr_hit_tables.h, behind the uploads on the null stream (the synchronize below covers them)
+    if ((r = s->instRecs.Alloc(d->num_instances)) || (r = s->vtxNormals.Alloc(d->num_vertices))) { delete s; return r; }
+    if ((r = SceneFillInstRecs(s, nullptr))) { delete s; return r; }
+    { hipError_t e = zr::LaunchFillVtxNormals(nullptr, s->vtxNormals.p, s->vertices.p, d->num_vertices, false);
+      if (e != hipSuccess) { delete s; return Fail(ZR_ERR_HIP, "k_fill_vtx_normals failed: %s", hipGetErrorString(e)); } }
+    s->view.vtxNormals = s->vtxNormals.p;
+#if ZR_HIT_TANGENTS
+    if ((r = s->vtxTangents.Alloc(d->num_vertices))) { delete s; return r; }
+    { hipError_t e = zr::LaunchFillVtxNormals(nullptr, s->vtxTangents.p, s->vertices.p, d->num_vertices, true);
+      if (e != hipSuccess) { delete s; return Fail(ZR_ERR_HIP, "k_fill_vtx_normals failed: %s", hipGetErrorString(e)); } }
+    s->view.vtxTangents = s->vtxTangents.p;
+#endif
     SceneView& v = s->view;
     v.vertices = s->vertices.p; v.indices = s->indices.p; v.instances = s->instances.p; v.materials = s->materials.p;
     v.emissives = s->emissives.p; v.alias = nullptr; v.sampleSets = nullptr; v.sampleSetSize = 0; v.nodes = s->nodes.p; v.tris = s->tris.p; v.triMeta = s->meta.p;
@@ -1508,6 +1545,7 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
             (s->trisPrev.n < nt && (r = s->trisPrev.Alloc(nt))) || (s->metaPrev.n != s->meta.n && (r = s->metaPrev.Alloc(s->meta.n))) ||
             (s->toWorld.n != 12 * (size_t)n && (r = s->toWorld.Alloc(12 * (size_t)n)))) return r;
         if (!s->hasPrev && !s->refitReady) HIP_TRY(hipMemcpy(s->metaPrev.p, s->meta.p, s->meta.n * sizeof(TriMeta), hipMemcpyDeviceToDevice));
+        if ((r = SceneSwapInstRecs(s, n))) return r;
         std::swap(s->instances.p, s->instancesPrev.p); std::swap(s->instances.n, s->instancesPrev.n);
         std::swap(s->nodes.p, s->nodesPrev.p); std::swap(s->nodes.n, s->nodesPrev.n);
         std::swap(s->tris.p, s->trisPrev.p); std::swap(s->tris.n, s->trisPrev.n);
@@ -1517,12 +1555,14 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
         HIP_TRY(hipMemcpy(s->toWorld.p, instance_to_world, 12 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
         s->toWorldDev = true;
         s->view.instances = s->instances.p; s->view.triMeta = s->meta.p;
-        if ((r = DeviceRebuild(s, st)))
+        // (the new records' table first, behind the blocking upload above and on the build's stream: a failure of either takes the roll-back below)
+        if ((r = SceneFillInstRecs(s, st)) || (r = DeviceRebuild(s, st)))
         {
             // roll back: the buffers take their old roles again and the scene renders as before the call.  The "previous" set was used as the build
             // target, so there is no previous structure any more (hasPrev = false: the CtT / temporal passes bind the current one, as in frame 1).
             (void)hipDeviceSynchronize();
             std::swap(s->instances.p, s->instancesPrev.p); std::swap(s->instances.n, s->instancesPrev.n);
+            std::swap(s->instRecs.p, s->instRecsPrev.p); std::swap(s->instRecs.n, s->instRecsPrev.n);
             std::swap(s->nodes.p, s->nodesPrev.p); std::swap(s->nodes.n, s->nodesPrev.n);
             std::swap(s->tris.p, s->trisPrev.p); std::swap(s->tris.n, s->trisPrev.n);
             std::swap(s->meta.p, s->metaPrev.p); std::swap(s->meta.n, s->metaPrev.n);
@@ -1542,6 +1582,7 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
         if (bvh.stackNeed + 1 > (uint32_t)kTravStack) return Fail(ZR_ERR_UNSUPPORTED, "BVH needs %u traversal stack entries (limit %d)", bvh.stackNeed, kTravStack - 1);
         HIP_TRY(hipDeviceSynchronize());           // the host rebuild reallocates: a host-synchronous path by construction (ZR_SCENE_UPDATE=rebuild)
         std::lock_guard<std::mutex> lock(s->mtx);
+        if ((r = SceneSwapInstRecs(s, n))) return r;
         std::swap(s->instances.p, s->instancesPrev.p); std::swap(s->instances.n, s->instancesPrev.n);
         std::swap(s->nodes.p, s->nodesPrev.p); std::swap(s->nodes.n, s->nodesPrev.n);
         std::swap(s->tris.p, s->trisPrev.p); std::swap(s->tris.n, s->trisPrev.n);
@@ -1552,6 +1593,10 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
         SceneView& v = s->view;
         v.instances = s->instances.p; v.nodes = s->nodes.p; v.tris = s->tris.p; v.triMeta = s->meta.p;
         v.numNodes = (uint32_t)bvh.nodes4.size(); v.numTris = (uint32_t)bvh.tris.size();
+        // (SceneSwapInstRecs sized both tables.  Like the Uploads above, a failing fill returns with the roles already changed: this debug path -- ZR_SCENE_UPDATE=rebuild_host --
+        // has no roll-back, and the scene is not usable after an error from it)
+        if ((r = SceneFillInstRecs(s, nullptr))) return r;
+        HIP_TRY(hipStreamSynchronize(nullptr));      // host-synchronous like the uploads: renders on any stream may follow
         if (bvh.maxDepth > s->maxDepth) s->maxDepth = bvh.maxDepth;
         BvhLevels(bvh.nodes4, s->hLevelOrder, s->levelOffsets);
         if ((r = s->levelNodes.Upload(s->hLevelOrder.data(), s->hLevelOrder.size()))) return r;
@@ -1626,12 +1671,15 @@ static int SceneRefitUpdate(zr_scene* s, hipStream_t st, const zr_mesh_instance*
             (s->trisPrev.n != nt && (r = s->trisPrev.Alloc(nt))) || (s->metaPrev.n != s->meta.n && (r = s->metaPrev.Alloc(s->meta.n))) ||
             (nodeCap && s->nodeBounds.n < 6 * nodeCap && (r = s->nodeBounds.Alloc(6 * nodeCap))) || (s->toWorld.n != 12 * (size_t)n && (r = s->toWorld.Alloc(12 * (size_t)n)))) return r;
         HIP_TRY(hipMemcpyAsync(s->instancesPrev.p, s->instances.p, instBytes, hipMemcpyDeviceToDevice, st));
+        if (s->instRecsPrev.n != n && (r = s->instRecsPrev.Alloc(n))) return r;
+        HIP_TRY(hipMemcpyAsync(s->instRecsPrev.p, s->instRecs.p, (size_t)n * sizeof(InstRec), hipMemcpyDeviceToDevice, st));
         if (nn) HIP_TRY(hipMemcpyAsync(s->nodesPrev.p, s->nodes.p, nn * sizeof(Bvh4Node), hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(s->trisPrev.p, s->tris.p, nt * sizeof(BvhTri), hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(s->metaPrev.p, s->meta.p, s->meta.n * sizeof(TriMeta), hipMemcpyDeviceToDevice, st));
         s->refitReady = true;
     }
     std::swap(s->instances.p, s->instancesPrev.p); std::swap(s->nodes.p, s->nodesPrev.p); std::swap(s->tris.p, s->trisPrev.p); std::swap(s->meta.p, s->metaPrev.p);
+    std::swap(s->instRecs.p, s->instRecsPrev.p);
     s->numNodesPrev = (uint32_t)nn; s->numTrisPrev = (uint32_t)nt; s->hasPrev = true;
     if (!moved)
     {
@@ -1646,6 +1694,7 @@ static int SceneRefitUpdate(zr_scene* s, hipStream_t st, const zr_mesh_instance*
             s->emissives.p, s->objectEmissives.p, s->emissiveOwner.p, moved->emFirst, moved->emEnd));
     }
     s->toWorldDev = true;
+    if ((r = SceneFillInstRecs(s, st))) return r;      // the records just written, decoded for this frame's hits
     if ((r = StageCommit(t, st))) return r;
     uint32_t numNodesNow = (uint32_t)nn;
     if (install)

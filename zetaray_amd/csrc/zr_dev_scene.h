@@ -14,6 +14,7 @@
 //   triMeta : 8 B per *global* triangle = {meshIdx, primIdx} (hit reconstruction)
 #pragma once
 #include "zr_dev_bsdf.h"
+#include "zr_hit_tables.h"
 #include "zr_sky.h"
 #include "../../include/zr_texture.h"
 #include "../../include/zr_intersect.h"
@@ -71,6 +72,13 @@ struct SceneView
     uint32_t plain;
     uint32_t numNodes;       // 0 => single leaf covering tris[0 .. numTris)
     uint32_t numTris;
+    // decoded once (zr_hit_tables.h): instRecs[i] belongs to instances[i] and changes hands with it; vtxNormals[v] = DecodeOct32(vertices[v].normal).
+    // Device memory, bound by the product library only: host executors leave them null and every host compile decodes per hit.
+    const InstRec* instRecs = nullptr;
+    const VtxDir* vtxNormals = nullptr;
+#if ZR_HIT_TANGENTS
+    const VtxDir* vtxTangents = nullptr;     // vtxTangents[v] = DecodeOct32(vertices[v].tangent)
+#endif
 #ifdef ZR_PROF
     unsigned long long* prof;     // -DZR_PROF builds only (scripts/gpu.sh prof): wave-cycle counters per kernel / section
 #endif
@@ -605,23 +613,40 @@ ZR_HD void FillHit(const SceneView& sc, uint32_t meshIdx, uint32_t primIdx, floa
     ret.matIdx = md.mat_idx;
     ret.meshIdx = meshIdx;
     uint32_t tri = primIdx * 3 + md.base_idx_offset;
-    const zr_vertex& V0 = sc.vertices[sc.indices[tri] + md.base_vtx_offset];
-    const zr_vertex& V1 = sc.vertices[sc.indices[tri + 1] + md.base_vtx_offset];
-    const zr_vertex& V2_ = sc.vertices[sc.indices[tri + 2] + md.base_vtx_offset];
+    const uint32_t i0 = sc.indices[tri] + md.base_vtx_offset, i1 = sc.indices[tri + 1] + md.base_vtx_offset, i2 = sc.indices[tri + 2] + md.base_vtx_offset;
+    const zr_vertex& V0 = sc.vertices[i0];
+    const zr_vertex& V1 = sc.vertices[i1];
+    const zr_vertex& V2_ = sc.vertices[i2];
 
     // InCurrFrame == false: previous frame's instance transform (RayQuery.hlsli:75-90)
+#if ZR_HIT_TABLES_DEV
+    const InstRec& rec = sc.instRecs[meshIdx];
+    const InstXform& xf = currFrame ? rec.curr : rec.prev;
+    V4 q = XformQ(xf);
+    V3 s = XformScale(xf);
+#else
     V4 q = normalize(DecodeNormalized4(currFrame ? md.rotation : md.prev_rotation));
     const uint16_t* sh = currFrame ? md.scale : md.prev_scale;
     V3 s = v3(zr_f16_to_f32(sh[0]), zr_f16_to_f32(sh[1]), zr_f16_to_f32(sh[2]));
+#endif
 
     float tmp = 1 - bu - bv;
     V2 uv = v2(zr_fma(bv, V2_.uv[0], tmp * V0.uv[0]), zr_fma(bv, V2_.uv[1], tmp * V0.uv[1]));
     ret.uv = v2(zr_fma(bu, V1.uv[0], uv.x), zr_fma(bu, V1.uv[1], uv.y));
 
+#if ZR_HIT_VTX_NORMALS_DEV
+    const VtxDir vn0 = sc.vtxNormals[i0], vn1 = sc.vtxNormals[i1], vn2 = sc.vtxNormals[i2];
+    V3 v0_n = v3(vn0.x, vn0.y, vn0.z), v1_n = v3(vn1.x, vn1.y, vn1.z), v2_n = v3(vn2.x, vn2.y, vn2.z);
+#else
     V3 v0_n = DecodeOct32(V0.normal), v1_n = DecodeOct32(V1.normal), v2_n = DecodeOct32(V2_.normal);
+#endif
+#if ZR_HIT_TABLES_DEV
+    const V3 scaleInv = XformScaleInv(xf);
+#else
+    const V3 scaleInv = v3(1.0f / s.x, 1.0f / s.y, 1.0f / s.z);
+#endif
     V3 hn = mad(bv, v2_n, tmp * v0_n);
     hn = mad(bu, v1_n, hn);
-    const V3 scaleInv = v3(1.0f / s.x, 1.0f / s.y, 1.0f / s.z);
     hn = hn * scaleInv;
     hn = RotateVector(hn, q);
     ret.normal = normalize(hn);
@@ -629,7 +654,11 @@ ZR_HD void FillHit(const SceneView& sc, uint32_t meshIdx, uint32_t primIdx, floa
     if (WantDiffs)
     {
         V3 trn = v3p(md.translation);
+#if ZR_HIT_TABLES_DEV
+        if (!currFrame) trn = trn - RecDT(rec);
+#else
         if (!currFrame) trn = trn - v3(zr_f16_to_f32(md.d_translation[0]), zr_f16_to_f32(md.d_translation[1]), zr_f16_to_f32(md.d_translation[2]));
+#endif
         V3 v0W = TransformTRS(v3p(V0.pos), trn, q, s);
         V3 v1W = TransformTRS(v3p(V1.pos), trn, q, s);
         V3 v2W = TransformTRS(v3p(V2_.pos), trn, q, s);

@@ -760,7 +760,10 @@ __global__ void __launch_bounds__(kStcBlock) ZR_WAVES(ZR_WAVES_STC_N) k_rpt_stc_
 #define ZR_RPT_GROUP_E(X) \
     X __global__ void k_rpt_pathtrace<true, true> ZR_RPT_ARGS_TILE; X __global__ void k_rpt_pathtrace<false, true> ZR_RPT_ARGS_TILE; \
     X __global__ void k_rpt_pathtrace_w4<true, true> ZR_RPT_ARGS_TILE; X __global__ void k_rpt_pathtrace_w4<false, true> ZR_RPT_ARGS_TILE; \
-    X __global__ void k_rpt_temporal<true, false, true> ZR_RPT_ARGS_TILE; X __global__ void k_rpt_temporal<false, false, true> ZR_RPT_ARGS_TILE; \
+    X __global__ void k_rpt_temporal<true, false, true> ZR_RPT_ARGS_TILE; X __global__ void k_rpt_temporal<false, false, true> ZR_RPT_ARGS_TILE;
+// ... its K16, in a translation unit of its own: the one consumer of the hit tables (zr_hit_tables.h) that lost with them (register allocation: + 4 spilled VGPRs,
+// + 1.5 % of its time) is compiled with the per-hit decode (zr_tu_rpt_j.hip)
+#define ZR_RPT_GROUP_J(X) \
     X __global__ void k_rpt_stc<true, false, true> ZR_RPT_ARGS_TILE; X __global__ void k_rpt_stc<false, false, true> ZR_RPT_ARGS_TILE;
 // (experiments build only: zr_tu_rpt_c.hip)
 #define ZR_RPT_GROUP_C(X) \
@@ -785,4 +788,4 @@ __global__ void __launch_bounds__(kStcBlock) ZR_WAVES(ZR_WAVES_STC_N) k_rpt_stc_
 #define ZR_RPT_GROUP_VP(X) ZR_RPT_VIEW_PERMS(X, k_rpt_pathtrace_view)
 #define ZR_RPT_GROUP_VT(X) ZR_RPT_VIEW_PERMS(X, k_rpt_temporal_view)
 #define ZR_RPT_GROUP_VS(X) ZR_RPT_VIEW_PERMS(X, k_rpt_stc_view)
-#define ZR_RPT_GROUPS_PRODUCT(X) ZR_RPT_GROUP_A(X) ZR_RPT_GROUP_B(X) ZR_RPT_GROUP_D(X) ZR_RPT_GROUP_E(X) ZR_RPT_GROUP_F(X) ZR_RPT_GROUP_G(X) ZR_RPT_GROUP_H(X) ZR_RPT_GROUP_I(X) ZR_RPT_GROUP_VP(X) ZR_RPT_GROUP_VT(X) ZR_RPT_GROUP_VS(X)
+#define ZR_RPT_GROUPS_PRODUCT(X) ZR_RPT_GROUP_A(X) ZR_RPT_GROUP_B(X) ZR_RPT_GROUP_D(X) ZR_RPT_GROUP_E(X) ZR_RPT_GROUP_F(X) ZR_RPT_GROUP_G(X) ZR_RPT_GROUP_H(X) ZR_RPT_GROUP_I(X) ZR_RPT_GROUP_J(X) ZR_RPT_GROUP_VP(X) ZR_RPT_GROUP_VT(X) ZR_RPT_GROUP_VS(X)

@@ -2173,6 +2173,16 @@ ZR_HD_FLAT void ReplayTemporalPixel(const RptFrame& F, const zr_frame_constants&
 ZR_HD void MoveXk(const SceneView& sc, Reconnection& rc, bool currToPrev, bool setMotionFlag)
 {
     const zr_mesh_instance& md = sc.instances[rc.meshIdx];
+#if ZR_HIT_TABLES_DEV
+    // decoded once per instance (zr_hit_tables.h), the reciprocal scales of InverseTransformTRS included
+    const InstRec& rec = sc.instRecs[rc.meshIdx];
+    V4 q_curr = XformQ(rec.curr), q_prev = XformQ(rec.prev);
+    V3 s_curr = XformScale(rec.curr), s_prev = XformScale(rec.prev);
+    V3 dT = RecDT(rec);
+    V3 t_curr = v3p(md.translation), t_prev = t_curr - dT;
+    if (currToPrev) rc.x_k = TransformTRS(InverseTransformTRS_SInv(rc.x_k, t_curr, q_curr, XformScaleInv(rec.curr)), t_prev, q_prev, s_prev);
+    else rc.x_k = TransformTRS(InverseTransformTRS_SInv(rc.x_k, t_prev, q_prev, XformScaleInv(rec.prev)), t_curr, q_curr, s_curr);
+#else
     V4 q_curr = normalize(DecodeNormalized4(md.rotation));
     V4 q_prev = normalize(DecodeNormalized4(md.prev_rotation));
     V3 s_curr = v3(zr_f16_to_f32(md.scale[0]), zr_f16_to_f32(md.scale[1]), zr_f16_to_f32(md.scale[2]));
@@ -2181,6 +2191,7 @@ ZR_HD void MoveXk(const SceneView& sc, Reconnection& rc, bool currToPrev, bool s
     V3 t_curr = v3p(md.translation), t_prev = t_curr - dT;
     if (currToPrev) rc.x_k = TransformTRS(InverseTransformTRS(rc.x_k, t_curr, q_curr, s_curr), t_prev, q_prev, s_prev);
     else rc.x_k = TransformTRS(InverseTransformTRS(rc.x_k, t_prev, q_prev, s_prev), t_curr, q_curr, s_curr);
+#endif
     if (setMotionFlag)
     {
         V4 dRot = v4(q_prev.x - q_curr.x, q_prev.y - q_curr.y, q_prev.z - q_curr.z, q_prev.w - q_curr.w);

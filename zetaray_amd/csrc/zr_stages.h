@@ -163,23 +163,45 @@ ZR_HD void GBufferPixel(const SceneView& sc, const zr_frame_constants& g, const 
     if (picked) *picked = tm.mesh;
     const zr_mesh_instance& md = sc.instances[tm.mesh];
     uint32_t tri = tm.prim * 3 + md.base_idx_offset;
-    const zr_vertex& V0 = sc.vertices[sc.indices[tri] + md.base_vtx_offset];
-    const zr_vertex& V1 = sc.vertices[sc.indices[tri + 1] + md.base_vtx_offset];
-    const zr_vertex& V2_ = sc.vertices[sc.indices[tri + 2] + md.base_vtx_offset];
+    const uint32_t i0 = sc.indices[tri] + md.base_vtx_offset, i1 = sc.indices[tri + 1] + md.base_vtx_offset, i2 = sc.indices[tri + 2] + md.base_vtx_offset;
+    const zr_vertex& V0 = sc.vertices[i0];
+    const zr_vertex& V1 = sc.vertices[i1];
+    const zr_vertex& V2_ = sc.vertices[i2];
+    // the instance's decoded transforms and the vertices' decoded normals come from the tables of zr_hit_tables.h in device code
+#if ZR_HIT_TABLES_DEV
+    const InstRec& rec = sc.instRecs[tm.mesh];
+    V4 q = XformQ(rec.curr);
+    const V3 scale = XformScale(rec.curr);
+#else
     V4 q = normalize(DecodeNormalized4(md.rotation));
     const V3 scale = v3(zr_f16_to_f32(md.scale[0]), zr_f16_to_f32(md.scale[1]), zr_f16_to_f32(md.scale[2]));
+#endif
     const V3 trn = v3p(md.translation);
     const V2 uv0 = v2(V0.uv[0], V0.uv[1]), uv1 = v2(V1.uv[0], V1.uv[1]), uv2 = v2(V2_.uv[0], V2_.uv[1]);
 
+#if ZR_HIT_VTX_NORMALS_DEV
+    const VtxDir vn0 = sc.vtxNormals[i0], vn1 = sc.vtxNormals[i1], vn2 = sc.vtxNormals[i2];
+    V3 v0_n = v3(vn0.x, vn0.y, vn0.z), v1_n = v3(vn1.x, vn1.y, vn1.z), v2_n = v3(vn2.x, vn2.y, vn2.z);
+#else
     V3 v0_n = DecodeOct32(V0.normal), v1_n = DecodeOct32(V1.normal), v2_n = DecodeOct32(V2_.normal);
-    V3 normal = v0_n + h.u * (v1_n - v0_n) + h.v * (v2_n - v0_n);
+#endif
+#if ZR_HIT_TABLES_DEV
+    const V3 scaleInv = XformScaleInv(rec.curr);
+#else
     const V3 scaleInv = v3(1.0f / scale.x, 1.0f / scale.y, 1.0f / scale.z);
+#endif
+    V3 normal = v0_n + h.u * (v1_n - v0_n) + h.v * (v2_n - v0_n);
     normal = normalize(RotateVector(normal * scaleInv, q));
 
     const V2 uv = uv0 + h.u * (uv1 - uv0) + h.v * (uv2 - uv0);
 
     // tangent vector (GBufferRT_Inline.hlsl:147-155)
+#if ZR_HIT_TANGENTS_DEV
+    const VtxDir vt0 = sc.vtxTangents[i0], vt1 = sc.vtxTangents[i1], vt2 = sc.vtxTangents[i2];
+    const V3 v0_t = v3(vt0.x, vt0.y, vt0.z), v1_t = v3(vt1.x, vt1.y, vt1.z), v2_t = v3(vt2.x, vt2.y, vt2.z);
+#else
     const V3 v0_t = DecodeOct32(V0.tangent), v1_t = DecodeOct32(V1.tangent), v2_t = DecodeOct32(V2_.tangent);
+#endif
     V3 tangent = v0_t + h.u * (v1_t - v0_t) + h.v * (v2_t - v0_t);
     tangent = normalize(RotateVector(tangent * scale, q));
 
@@ -193,10 +215,17 @@ ZR_HD void GBufferPixel(const SceneView& sc, const zr_frame_constants& g, const 
 
     // motion vector
     V3 hitPos = mad(h.t, dir, origin);
+#if ZR_HIT_TABLES_DEV
+    V3 posL = InverseTransformTRS_SInv(hitPos, trn, q, scaleInv);
+    V3 prevT = trn - RecDT(rec);
+    V4 qp = XformQ(rec.prev);
+    V3 ps = XformScale(rec.prev);
+#else
     V3 posL = InverseTransformTRS(hitPos, trn, q, scale);
     V3 prevT = trn - v3(zr_f16_to_f32(md.d_translation[0]), zr_f16_to_f32(md.d_translation[1]), zr_f16_to_f32(md.d_translation[2]));
     V4 qp = normalize(DecodeNormalized4(md.prev_rotation));
     V3 ps = v3(zr_f16_to_f32(md.prev_scale[0]), zr_f16_to_f32(md.prev_scale[1]), zr_f16_to_f32(md.prev_scale[2]));
+#endif
     V3 posPrev = TransformTRS(posL, prevT, qp, ps);
     V3 pvPrev = Mul3x4(g.prev_view, posPrev);
     V2 ndcPrev = v2(pvPrev.x / (pvPrev.z * g.tan_half_fov), pvPrev.y / (pvPrev.z * g.tan_half_fov));

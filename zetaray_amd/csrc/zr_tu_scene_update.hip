@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include "../../include/zr_scene_math.h"
+#include "zr_hit_tables.h"
 
 namespace zr {
 
@@ -109,6 +110,38 @@ __global__ void __launch_bounds__(kBlock) k_move_instances(zr_mesh_instance* cur
         slot[i] = kNone;
     }
     StoreInstance(cur + i, I);
+}
+
+// ---- the tables of zr_hit_tables.h: what hit reconstruction decodes from an instance record / a vertex, stored once.  MakeInstRec and DecodeOct32 are
+// the inline functions the per-hit code calls, compiled with the library's flags, so the stored bits are the bits a hit would compute
+// one lane per instance
+__global__ void __launch_bounds__(kBlock) k_fill_inst_recs(InstRec* recs, const zr_mesh_instance* instances, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const zr_mesh_instance I = LoadInstance(instances + i);
+    StoreRecord(recs + i, MakeInstRec(I));
+}
+// one lane per vertex; tangent: decode vertex.tangent instead of vertex.normal (-DZR_HIT_TANGENTS builds)
+__global__ void __launch_bounds__(kBlock) k_fill_vtx_normals(VtxDir* out, const zr_vertex* vertices, uint32_t n, bool tangent)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(tangent ? vertices[i].tangent : vertices[i].normal);      // (4-byte aligned: offsets 20 / 24 of a 28-byte record)
+    const uint16_t e[2] = { Lo16(w), Hi16(w) };
+    const V3 d = DecodeOct32(e);
+    VtxDir r; r.x = d.x; r.y = d.y; r.z = d.z; r.w = 0.0f;
+    out[i] = r;
+}
+hipError_t LaunchFillInstRecs(hipStream_t st, InstRec* recs, const zr_mesh_instance* instances, uint32_t n)
+{
+    if (n) hipLaunchKernelGGL(k_fill_inst_recs, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, recs, instances, n);
+    return hipGetLastError();
+}
+hipError_t LaunchFillVtxNormals(hipStream_t st, VtxDir* out, const zr_vertex* vertices, uint32_t n, bool tangent)
+{
+    if (n) hipLaunchKernelGGL(k_fill_vtx_normals, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, out, vertices, n, tangent);
+    return hipGetLastError();
 }
 
 // moved: [nMoved x 12 floats | nMoved instance indices] in device memory, every index < n and listed once (checked by the caller);
