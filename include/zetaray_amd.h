@@ -362,6 +362,28 @@ int zr_scene_set_object_emissives(zr_scene* scene, const zr_emissive_triangle* o
 int zr_scene_has_object_emissives(const zr_scene* scene);      /* 1 once zr_scene_set_object_emissives has succeeded on this scene, else 0 */
 int zr_scene_move_instances_async(zr_scene* scene, void* hip_stream, const uint32_t* instance_idx, const float* world_3x4, uint32_t n_moved);
 int zr_scene_move_instances(zr_scene* scene, const uint32_t* instance_idx, const float* world_3x4, uint32_t n_moved);
+/* Keyframe animation of instances, sampled and applied on the device: only the time crosses the bus.  zr_scene_set_animation (a host call) takes the
+ * scene graph's DYNAMIC CLOSURE (zr_anim_desc, zr_wire.h): uploads the tables once, replaces an earlier set, a null or empty desc clears.  At set time it
+ * computes each node's level and the per-level node ranges, the local matrices of the non-animated nodes, the index half of the frame's moved list and
+ * the dirty light range of the listed instances, and marks those instances as moving for the background rebuild.
+ * zr_scene_animate_async(scene, stream, t) is then the frame's scene update: the arithmetic of include/zr_anim.h (SceneCore::UpdateAnimations, slerp and
+ * world = local x parent restated, with the three deviations that header states: exact 1 / sqrt where the reference's slerp uses rsqrtps; local time
+ * u = t - t0 throughout; the key interval clamped to the animation's last one) runs on the device, one lane per animated node, one launch per level, and
+ * feeds the kernels of zr_scene_move_instances.  In every device byte it equals zr_scene_move_instances_async called with the listed instances, in list
+ * order, and the matrices the header computes on the host for time t (zrh_scene_data_animate, zr_scene_io.h): current and previous instance buffer,
+ * object-to-world matrices, emissive records, BVH triangles and nodes, the role swap, the ordering against renders on other streams and the background
+ * rebuild.  The host's copies of the matrices (zr_scene_get_instances, the picked-instance outline, the background builder's snapshot) follow lazily:
+ * the time is kept and the header runs on the host where they are read.
+ * A frame is updated by exactly ONE of zr_scene_update_instances, zr_scene_move_instances or zr_scene_animate.
+ * Caller guarantees: unit rotations, positive scales, strictly increasing key times (the setter checks the last two and finiteness).
+ * zr_scene_set_animation refuses, with nothing changed: a parent that is not an earlier entry, a key range out of bounds, num_keys == 1, key times not
+ * strictly increasing or not finite, a scale <= 0, an instance >= the scene's count or listed twice, a node index >= num_nodes, more than
+ * ZR_ANIM_MAX_LEVELS levels (ZR_ERR_INVALID_ARG); a listed instance that carries lights before zr_scene_set_object_emissives (ZR_ERR_NOT_INITIALIZED).
+ * zr_scene_animate refuses, with nothing changed: no animation set (ZR_ERR_NOT_INITIALIZED); ZR_SCENE_UPDATE=rebuild / rebuild_host (ZR_ERR_UNSUPPORTED).
+ * zr_scene_animate = _async on the null stream, then wait.  The byte equivalence holds for the contract build, not for -DZR_ARITH_FAST. */
+int zr_scene_set_animation(zr_scene* scene, const zr_anim_desc* desc);
+int zr_scene_animate_async(zr_scene* scene, void* hip_stream, float t);
+int zr_scene_animate(zr_scene* scene, float t);
 /* Read-backs for tests and tools, after waiting for `hip_stream` (pass the stream of the last update).  which: 0 = the current instance buffer,
  * 1 = the previous one (the current one while the scene has never been updated); to_world_or_null: n x 12 floats. */
 int zr_scene_get_instances(const zr_scene* scene, void* hip_stream, int which, zr_mesh_instance* out, float* to_world_or_null, uint32_t n);

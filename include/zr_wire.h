@@ -240,6 +240,44 @@ typedef struct zr_scene_desc {
     const uint8_t*              texels;          uint64_t texel_bytes;
 } zr_scene_desc;
 
+/*
+ * Keyframe animation of instances (zr_scene_set_animation / zr_scene_animate, zetaray_amd.h; the arithmetic is include/zr_anim.h).
+ * zr_keyframe: SceneCore's Keyframe (AffineTransformation + Time).  zr_anim_node: one node of the DYNAMIC CLOSURE of the scene graph -- every
+ * animated node plus every descendant of one that carries, or leads to, an instance.  `parent` is an EARLIER entry of the table or ZR_ANIM_ROOT;
+ * num_keys is 0 (not animated: the local transform is rest_*) or >= 2, the node's keys are keys[first_key .. first_key + num_keys).  For
+ * ZR_ANIM_ROOT entries parent_world is the static world matrix above the node (3 x 4 row-major like instance_to_world; identity for a scene root).
+ * zr_anim_desc: instance instance_idx[j] has the world matrix of node instance_node[j] (the loader's rule: one instance per primitive of a node's mesh).
+ */
+#define ZR_ANIM_ROOT 0xffffffffu
+#define ZR_ANIM_MAX_LEVELS 32u
+typedef struct zr_keyframe {
+    float scale[3];
+    float rotation[4];
+    float translation[3];
+    float time;
+} zr_keyframe;
+typedef struct zr_anim_node {
+    uint32_t parent;
+    uint32_t first_key;
+    uint32_t num_keys;
+    uint32_t loop;
+    float    t0;
+    float    rest_scale[3];
+    float    rest_rotation[4];
+    float    rest_translation[3];
+    float    parent_world[12];
+} zr_anim_node;
+typedef struct zr_anim_desc {
+    const zr_anim_node* nodes;          uint32_t num_nodes;
+    const zr_keyframe*  keys;           uint32_t num_keys;
+    const uint32_t*     instance_idx;
+    const uint32_t*     instance_node;  uint32_t num_instances;
+} zr_anim_desc;
+#ifdef __cplusplus
+static_assert(sizeof(zr_keyframe) == 44, "zr_keyframe");
+static_assert(sizeof(zr_anim_node) == 108, "zr_anim_node");
+#endif
+
 #ifdef __cplusplus
 }
 #endif

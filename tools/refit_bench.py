@@ -6,7 +6,14 @@ Prints one JSON line; scripts/gpu_refit.sh [rounds 1-4: git history up to 31e92f
 (zrh_scene_data_begin_frame / _set_instance_world, zr_scene_update_emissives_async + zr_scene_update_instances_async) and the device form
 (zr_scene_move_instances_async) -- as host wall time from the first call to the last return and as stream time between two events, at two light
 counts a factor of 8 apart (--emissive N and N / 8).  Median and p10 / p90 of --frames frames after --warmup; one JSON line.  Exit status 1 when the
-device path's host time at the larger count exceeds that at the smaller by more than the smaller run's p10 - p90 spread."""
+device path's host time at the larger count exceeds that at the smaller by more than the smaller run's p10 - p90 spread.
+
+--animate: keyframe animation of N single-quad instances, all animated, two keys each, flat hierarchy (--instances N and 16 N; the smaller scene
+carries one static clutter instance that brings it to the larger one's triangle count, so that both refit trees are equally deep and the refit's one
+launch per level costs either size the same host time).  (A) the C++ mirror samples on the host (zrh_scene_data_begin_frame + zrh_scene_data_animate)
+and hands the moved list to zr_scene_move_instances_async; (B) zr_scene_animate_async.  Host wall time of the update and stream time between two events,
+median and p10 / p90 of --frames frames after --warmup; one JSON line with the device probes.  Exit status 1 when (B)'s host time at 16 N exceeds that
+at N by more than the smaller run's p10 - p90 spread, or (B)'s stream time is longer than (A)'s at either size."""
 import json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -143,15 +150,133 @@ def device_records(num_emissive, frames, warmup):
     return 0 if out["device_host_wall_flat"] else 1
 
 
+def _quad_scene(n_quads, clutter_tris, seed=3):
+    """n_quads instances of one shared unit quad on a jittered grid (+ one static instance of clutter_tris small triangles)"""
+    rng = np.random.default_rng(seed)
+    sc = scene_io.Scene()
+    sc.materials = np.array([scene_io.pack_material(metallic=0.0, roughness=0.3), scene_io.pack_material(base_color=(0.7, 0.6, 0.5, 1), roughness=0.6, double_sided=True)], wire.MATERIAL)
+    quad = np.float32([[-0.5, 0, -0.5], [0.5, 0, -0.5], [0.5, 0, 0.5], [-0.5, 0, 0.5]]) * np.float32(0.02)
+    P = [quad]
+    I = [np.uint32([0, 1, 2, 0, 2, 3])]
+    if clutter_tris:
+        c = rng.uniform(-3, 3, (clutter_tris, 1, 3)).astype(np.float32)
+        P.append((c + rng.uniform(-0.01, 0.01, (clutter_tris, 3, 3)).astype(np.float32)).reshape(-1, 3))
+        I.append(np.arange(3 * clutter_tris, dtype=np.uint32))
+    v = np.zeros(sum(len(p) for p in P), wire.VERTEX)
+    v["pos"] = np.concatenate(P)
+    v["normal"] = scene_io.encode_octahedral(np.tile(np.float32([0, 1, 0]), (len(v), 1)), sse_order=False)
+    sc.vertices, sc.indices = v, np.concatenate(I)
+    n = n_quads + (1 if clutter_tris else 0)
+    side = int(np.ceil(np.sqrt(n_quads)))
+    g = np.arange(n_quads)
+    pos = np.stack([(g % side) * 0.03 - side * 0.015, rng.uniform(-1, 1, n_quads), (g // side) * 0.03 - side * 0.015], 1).astype(np.float32)
+    xf = np.tile(np.float32([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]), (n, 1))
+    xf[:n_quads, 3], xf[:n_quads, 7], xf[:n_quads, 11] = pos[:, 0], pos[:, 1], pos[:, 2]
+    inst = np.zeros(n, wire.MESH_INSTANCE)
+    ident_q = np.rint((np.array([0, 0, 0, 1], np.float32) * np.float32(0.5) + np.float32(0.5)) * np.float32(65535.0)).astype(np.uint16)
+    inst["rotation"] = inst["prev_rotation"] = ident_q
+    inst["scale"] = inst["prev_scale"] = scene_io.f32_to_f16_bits([1, 1, 1])
+    inst["translation"][:n_quads] = pos
+    inst["mat_idx"], inst["base_emissive_tri_offset"], inst["base_color_tex"], inst["alpha_factor_cutoff"] = 1, 0xFFFFFFFF, 0xFFFF, 255 | (128 << 8)
+    ntris = np.full(n, 2, np.uint32)
+    if clutter_tris:
+        inst["base_vtx_offset"][-1], inst["base_idx_offset"][-1], ntris[-1] = 4, 6, clutter_tris
+    sc.instances, sc.instance_to_world, sc.instance_num_tris = inst, xf, ntris
+    sc.instance_mask = np.full(n, wire.SUBGROUP_NON_EMISSIVE, np.uint8)
+    sc.emissives = np.zeros(0, wire.EMISSIVE_TRI)
+    sc.rho, sc.rho_dim = scene_io.load_rho_default()
+    return sc, pos
+
+
+def animate(n_small, frames, warmup):
+    import ctypes as C
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import bench
+    out = {"mode": "animate", "frames": frames, "warmup": warmup, "library": os.path.basename(api.LIB_PATH), "device_state": bench.device_state(api, 0), "sizes": []}
+    L = scene_io._sceneio_lib()
+    vp = C.c_void_p
+    L.zrh_scene_data_begin_frame.argtypes = [vp]
+    L.zrh_scene_data_from_desc.argtypes = [vp] * 3
+    L.zrh_scene_data_set_animation.argtypes = [vp, vp]
+    L.zrh_scene_data_animate.argtypes = [vp, C.c_float]
+    L.zrh_scene_data_set_device_records.argtypes = [vp, C.c_int]
+    H = C.CDLL(os.path.join(os.path.dirname(api.LIB_PATH), "libzetaray_host.so"))
+    H.zrh_scene_apply_updates_on.argtypes = [vp, vp, vp]
+    n_large, raw = 16 * n_small, {}
+    for nq in (n_small, n_large):
+        sc, pos = _quad_scene(nq, 2 * (n_large - nq))
+        rng = np.random.default_rng(9)
+        nodes, keys = np.zeros(nq, wire.ANIM_NODE), np.zeros(2 * nq, wire.KEYFRAME)
+        nodes["parent"], nodes["first_key"], nodes["num_keys"], nodes["loop"] = wire.ANIM_ROOT, 2 * np.arange(nq), 2, 1
+        nodes["rest_scale"], nodes["rest_rotation"], nodes["rest_translation"], nodes["parent_world"] = 1, (0, 0, 0, 1), pos, np.float32([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0])
+        q = rng.normal(size=(2 * nq, 4))
+        keys["rotation"], keys["scale"], keys["time"] = q / np.linalg.norm(q, axis=1, keepdims=True), rng.uniform(0.8, 1.2, (2 * nq, 3)), np.tile(np.float32([0.0, 1.0]), nq)
+        keys["translation"] = np.repeat(pos, 2, axis=0) + rng.uniform(-0.01, 0.01, (2 * nq, 3)).astype(np.float32)
+        anim = wire.AnimDesc(nodes, keys, np.arange(nq), np.arange(nq))
+        desc, ad = sc.desc(), anim.c_desc()
+        h = vp()
+        assert L.zrh_scene_data_from_desc(C.addressof(desc), None, C.byref(h)) == 0
+        assert L.zrh_scene_data_set_animation(h, C.addressof(ad)) == 0, L.zrh_scene_io_last_error()
+        L.zrh_scene_data_set_device_records(h, 1)
+        A, B = api.Scene(sc), api.Scene(sc)
+        B.set_animation(anim)
+        st = torch.cuda.Stream()
+
+        def host_samples(t):
+            L.zrh_scene_data_begin_frame(h)
+            assert L.zrh_scene_data_animate(h, t) == 0
+            assert H.zrh_scene_apply_updates_on(A.h, h, st.cuda_stream) == 0
+
+        def device_animates(t):
+            B.animate(t, stream=st.cuda_stream)
+
+        res = {"animated_instances": nq, "num_instances": len(sc.instances), "num_tris": int(sc.num_tris), "bvh": list(A.bvh_info())}
+        for name, fn in (("A_host_samples_then_move_instances", host_samples), ("B_scene_animate", device_animates)):
+            wall, stream_ms = [], []
+            for k in range(1, warmup + frames + 1):
+                t = 0.013 * k
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record(st)
+                a = time.perf_counter()
+                fn(t)
+                b = time.perf_counter()
+                e1.record(st)
+                torch.cuda.synchronize()
+                if k > warmup:
+                    wall.append((b - a) * 1e3); stream_ms.append(e0.elapsed_time(e1))
+            res[name] = {"host_wall_ms": _stats(wall), "stream_ms": _stats(stream_ms)}
+            raw[(nq, name)] = (np.asarray(wall, np.float64), np.asarray(stream_ms, np.float64))
+        ia, xa = A.download_instances(0)
+        ib, xb = B.download_instances(0)
+        res["same_device_bytes"] = bool(ia.tobytes() == ib.tobytes() and xa.tobytes() == xb.tobytes())
+        res["host_wall_ratio_A_over_B"] = round(res["A_host_samples_then_move_instances"]["host_wall_ms"]["median"] / res["B_scene_animate"]["host_wall_ms"]["median"], 2)
+        out["sizes"].append(res)
+        A.close(); B.close(); L.zrh_scene_data_destroy(h)
+    small, large = raw[(n_small, "B_scene_animate")][0], raw[(n_large, "B_scene_animate")][0]
+    growth, spread = float(np.median(large) - np.median(small)), float(np.percentile(small, 90) - np.percentile(small, 10))
+    out["B_host_wall_growth_ms"], out["small_p10_p90_spread_ms"], out["B_host_wall_flat"] = growth, spread, bool(growth <= spread)
+    out["B_stream_not_longer_than_A"] = [bool(np.median(raw[(nq, "B_scene_animate")][1]) <= np.median(raw[(nq, "A_host_samples_then_move_instances")][1])) for nq in (n_small, n_large)]
+    out["B_faster_than_A_on_the_host_at_small_n"] = bool(np.median(small) < np.median(raw[(n_small, "A_host_samples_then_move_instances")][0]))
+    ok = out["B_host_wall_flat"] and all(out["B_stream_not_longer_than_A"]) and all(r["same_device_bytes"] for r in out["sizes"])
+    print(json.dumps(out))
+    return 0 if ok else 1
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--device-records", action="store_true")
+    ap.add_argument("--animate", action="store_true")
+    ap.add_argument("--instances", type=int, default=4096)
     ap.add_argument("--emissive", type=int, default=100000)
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=16)
     a = ap.parse_args()
-    if a.device_records:
+    if a.animate:
+        sys.exit(animate(a.instances, max(a.frames, 64), max(a.warmup, 16)))
+    elif a.device_records:
         sys.exit(device_records(a.emissive, max(a.frames, 64), max(a.warmup, 16)))
     else:
         main()

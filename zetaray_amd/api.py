@@ -63,6 +63,7 @@ EXPORTS = [
     "zr_pass_set_rpt_debug_view",
     "zr_pass_set_rgi_spatial",
     "zr_scene_set_object_emissives", "zr_scene_has_object_emissives", "zr_scene_move_instances", "zr_scene_move_instances_async", "zr_scene_get_instances", "zr_scene_get_emissives",
+    "zr_scene_set_animation", "zr_scene_animate", "zr_scene_animate_async",
 ]
 STAGE_TEMPORAL, STAGE_SPATIAL, STAGE_ALL = 1, 2, 3
 STAGE_SPATIAL2 = 4          # ReSTIR PT, num_spatial_passes = 2 on tiles: the second round, behind one more HALO_POST_TEMPORAL exchange
@@ -233,6 +234,33 @@ class Scene:
         # (a refused call changes nothing, here either.)  The records describe motion in the frame something moved, and rest in a frame nothing did
         self.version += 1
         self.instances_in_motion = len(i) > 0
+
+    def set_animation(self, desc):
+        """keyframe animation of instances (zr_scene_set_animation): a wire.AnimDesc -- the dynamic closure of the scene graph, its keys and the instances
+        that hang on its nodes -- uploaded once; None (or an empty one) clears.  Lights: set_object_emissives first"""
+        L = lib()
+        L.zr_scene_set_animation.argtypes = [C.c_void_p, C.c_void_p]
+        if desc is None:
+            _check(L.zr_scene_set_animation(self.h, None))
+            self._anim = None
+            return
+        d = desc.c_desc()
+        _check(L.zr_scene_set_animation(self.h, C.addressof(d)))
+        self._anim = desc
+
+    def animate(self, t, stream=False):
+        """the frame's scene update from the time alone (zr_scene_animate): the animation is sampled, composed down the hierarchy and applied on the
+        device.  stream as update_instances"""
+        L = lib()
+        if stream is False:
+            L.zr_scene_animate.argtypes = [C.c_void_p, C.c_float]
+            _check(L.zr_scene_animate(self.h, float(t)))
+        else:
+            L.zr_scene_animate_async.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
+            _check(L.zr_scene_animate_async(self.h, stream, float(t)))
+        self.version += 1
+        anim = getattr(self, "_anim", None)
+        self.instances_in_motion = anim is not None and len(anim.instance_idx) > 0
 
     def download_instances(self, which=0, stream=None):
         """(MeshInstance records, (n, 12) object-to-world matrices) as the device holds them; which: 0 current, 1 previous"""
@@ -702,6 +730,14 @@ class Renderer:
     def move_instances(self, idx, world, stream=False):
         """the frame's scene update from matrices alone (Scene.move_instances; lights: Scene.set_object_emissives once before)"""
         self.scene.move_instances(idx, world, stream=stream)
+
+    def set_animation(self, desc):
+        """keyframe animation of instances (Scene.set_animation)"""
+        self.scene.set_animation(desc)
+
+    def animate(self, t, stream=False):
+        """the frame's scene update from the time alone (Scene.animate)"""
+        self.scene.animate(t, stream=stream)
 
     def set_rgi_spatial(self, num_samples, radius_px=0.0):
         """ReSTIR GI: the spatial reuse stage of the indirect pass (Pass.set_rgi_spatial); stored without effect by the other integrators"""

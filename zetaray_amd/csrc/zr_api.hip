@@ -62,6 +62,8 @@ static int RequireDevice(int device)
 #define ZR_EXP_ENV(name) ((const char*)nullptr)
 #endif
 #include "zr_bvh_device.h"
+#include "../../include/zr_anim.h"
+#include <memory>
 namespace zr { int DeviceProbeRun(int device, float min_ms, zr_device_probe* out, std::string& err); }      // zr_tu_probe.hip
 namespace zr { hipError_t LaunchInscattering(hipStream_t s, const SceneView& sc, const zr_frame_constants& g, const InscatterParams& c, uint32_t* grid); }   // zr_tu_sky.hip
 namespace zr { hipError_t LaunchDisplayView(hipStream_t s, int option, const GBuf& gb, uint32_t dw, uint32_t dh, float cameraNear, float roughnessTh, F4* out, uint32_t* outSrgb); }   // zr_tu_display.hip
@@ -69,6 +71,8 @@ namespace zr { hipError_t LaunchPickOutline(hipStream_t s, const zr_vertex* vert
     const post::PickWvp& m, uint32_t dw, uint32_t dh, uint32_t rw, uint32_t rh, int4* tris, uint32_t* count, uint8_t* mask, F4* out, uint32_t* outSrgb); }   // zr_tu_display.hip
 namespace zr { hipError_t LaunchMoveInstances(hipStream_t st, zr_mesh_instance* cur, const zr_mesh_instance* prev, float* toWorld, uint32_t n, uint32_t* slot,
     const uint32_t* moved, uint32_t nMoved, zr_emissive_triangle* emissives, const zr_emissive_triangle* object, const uint32_t* owner, uint32_t emFirst, uint32_t emEnd); }   // zr_tu_scene_update.hip
+namespace zr { hipError_t LaunchAnimate(hipStream_t st, float t, const zr_anim_node* nodes, const zr_keyframe* keys, const uint32_t* animated, uint32_t nAnimated,
+    const uint32_t* levelNodes, const uint32_t* levelOffsets, uint32_t numLevels, float* nodeLocal, float* nodeWorld, const uint32_t* instNode, uint32_t nInst, uint32_t* moved); }   // zr_tu_anim.hip
 namespace zr { hipError_t LaunchFillInstRecs(hipStream_t st, InstRec* recs, const zr_mesh_instance* instances, uint32_t n);      // zr_tu_scene_update.hip
                hipError_t LaunchFillVtxNormals(hipStream_t st, VtxDir* out, const zr_vertex* vertices, uint32_t n, bool tangent); }
 // the ReSTIR PT kernels are compiled in zr_tu_rpt_[a-i].hip (see zr_kernels.h)
@@ -601,6 +605,20 @@ struct zr_scene
     // are what the background builder and the dirty light range need when the caller hands over matrices only.  toWorldDev: `toWorld` holds hToWorld
     std::vector<zr_mesh_instance> hInstances; bool toWorldDev = false;
     DevBuf<zr_emissive_triangle> objectEmissives; DevBuf<uint32_t> emissiveOwner, movedDev, movedSlot;
+    // ---- keyframe animation (zr_scene_set_animation / zr_scene_animate; kernels in zr_tu_anim.hip, arithmetic in include/zr_anim.h).  Host copies of the
+    // tables (desc points into them), what set_animation derives once -- the animated nodes, the nodes grouped by level (top level first) and the groups'
+    // offsets, the dirty light range of the listed instances -- and the device side: the tables, every node's local and world matrix (the non-animated
+    // nodes' local matrices written at set time) and the scene-owned moved list [n x 12 floats | n indices] with its index half written at set time.
+    // The host's view of the matrices (hToWorld) follows an animate LAZILY: lastT is kept, and SceneAnimSyncHost runs the header on the host for it at the
+    // places that read hToWorld.
+    struct Anim
+    {
+        std::vector<zr_anim_node> nodes; std::vector<zr_keyframe> keys; std::vector<uint32_t> instIdx, instNode, levelOffsets;
+        zr_anim_desc desc{}; uint32_t nAnimated = 0, emFirst = 0, emEnd = 0;
+        DevBuf<zr_anim_node> dNodes; DevBuf<zr_keyframe> dKeys; DevBuf<uint32_t> dAnimated, dLevelNodes, dInstNode, dMoved; DevBuf<float> dLocal, dWorld;
+        float lastT = 0; bool hasT = false, hostStale = false;
+    };
+    std::unique_ptr<Anim> anim; std::mutex animMtx;
     ~zr_scene()
     {
         if (bg.th.joinable()) bg.th.join();
@@ -1512,7 +1530,20 @@ int zr_scene_invalidate_alias_table_deferred(zr_scene* s)
 }
 // What a frame's update consists of when the caller hands over matrices only (zr_scene_move_instances_async): the moved instances, their new
 // matrices, and the range of light triangles they carry
-struct MovedList { const uint32_t* idx; const float* xf; uint32_t n, emFirst, emEnd; };
+// (animT: the list is the scene's own, written on the device by zr::LaunchAnimate for that time -- idx / xf are null, nothing goes through the staging ring)
+struct MovedList { const uint32_t* idx; const float* xf; uint32_t n, emFirst, emEnd; const float* animT = nullptr; };
+// the host's matrices after zr_scene_animate: brought up to date for the time of the last one, where they are read
+static void SceneAnimSyncHost(zr_scene* s)
+{
+    std::lock_guard<std::mutex> lock(s->animMtx);
+    if (!s->anim || !s->anim->hostStale) return;
+    zr_scene::Anim& A = *s->anim;
+    std::vector<float> world(12 * (size_t)A.desc.num_nodes);
+    zran::EvalNodeWorlds(A.desc, A.lastT, world.data());
+    for (uint32_t j = 0; j < A.desc.num_instances; j++)
+        std::memcpy(s->hToWorld.data() + 12 * (size_t)A.instIdx[j], world.data() + 12 * (size_t)A.instNode[j], 12 * sizeof(float));
+    A.hostStale = false;
+}
 static int SceneRefitUpdate(zr_scene* s, hipStream_t st, const zr_mesh_instance* instances, const float* instance_to_world, uint32_t n, const MovedList* moved);
 
 int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_instance* instances, const float* instance_to_world, uint32_t n)
@@ -1524,6 +1555,7 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
     const char* modeEnv = std::getenv("ZR_SCENE_UPDATE");
     bool rebuild = modeEnv && !std::strcmp(modeEnv, "rebuild");
     int r;
+    SceneAnimSyncHost(s);
     for (uint32_t i = 0; i < n; i++) RaiseMaxTex(s, 0, instances[i].base_color_tex);
     for (uint32_t i = 0; i < n; i++)      // the reference's static -> dynamic conversion of an instance that starts to move (SceneCore.cpp:1038)
         if (std::memcmp(s->hToWorld.data() + 12 * (size_t)i, instance_to_world + 12 * (size_t)i, 12 * sizeof(float))) { s->movedEver[i] = 1; s->bg.movedSinceBuild = true; }
@@ -1644,12 +1676,17 @@ static int SceneRefitUpdate(zr_scene* s, hipStream_t st, const zr_mesh_instance*
     }
     const size_t nn = s->view.numNodes, nt = s->view.numTris;
     const size_t instBytes = (size_t)n * sizeof(zr_mesh_instance), xfBytes = 12 * (size_t)n * sizeof(float);
-    zr_scene::StageSlot* t;
+    zr_scene::StageSlot* t = nullptr;
+    const bool animated = moved && moved->animT;
+    if (animated && (!s->toWorldDev || s->toWorld.n != 12 * (size_t)n)) SceneAnimSyncHost(s);      // (the seed below takes hToWorld)
     // device form: [every matrix as it was, once -- while the device copy of the matrices is not current | the moved matrices | the moved indices]
     const bool seedXf = moved && (!s->toWorldDev || s->toWorld.n != 12 * (size_t)n);
-    const size_t movedBytes = moved ? 13 * (size_t)moved->n * sizeof(uint32_t) : 0, seedBytes = seedXf ? xfBytes : 0;
-    if ((r = StageAcquire(s, moved ? seedBytes + movedBytes : instBytes + xfBytes, &t))) return r;
+    const size_t movedBytes = moved && !animated ? 13 * (size_t)moved->n * sizeof(uint32_t) : 0, seedBytes = seedXf ? xfBytes : 0;
+    const size_t stageBytes = moved ? seedBytes + movedBytes : instBytes + xfBytes;
+    // (an animated frame after the first stages nothing and takes no slot; every other form takes one as it always did, an empty moved list included)
+    if ((stageBytes || !animated) && (r = StageAcquire(s, stageBytes, &t))) return r;
     if (!moved) { memcpy(t->host, instances, instBytes); memcpy((char*)t->host + instBytes, instance_to_world, xfBytes); }
+    else if (animated) { if (seedXf) memcpy(t->host, s->hToWorld.data(), xfBytes); }
     else
     {
         if (seedXf) memcpy(t->host, s->hToWorld.data(), xfBytes);
@@ -1689,13 +1726,21 @@ static int SceneRefitUpdate(zr_scene* s, hipStream_t st, const zr_mesh_instance*
     else
     {
         if (seedXf) HIP_TRY(hipMemcpyAsync(s->toWorld.p, t->host, xfBytes, hipMemcpyHostToDevice, st));
-        if (moved->n) HIP_TRY(hipMemcpyAsync(s->movedDev.p, (char*)t->host + seedBytes, movedBytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(zr::LaunchMoveInstances(st, s->instances.p, s->instancesPrev.p, s->toWorld.p, n, s->movedSlot.p, s->movedDev.p, moved->n,
+        const uint32_t* movedList = s->movedDev.p;
+        if (animated)
+        {   // behind SceneWaitUsers: ordered after the previous update, whose kernels read the list this writes
+            zr_scene::Anim& A = *s->anim;
+            HIP_TRY(zr::LaunchAnimate(st, *moved->animT, A.dNodes.p, A.dKeys.p, A.dAnimated.p, A.nAnimated, A.dLevelNodes.p, A.levelOffsets.data(),
+                (uint32_t)A.levelOffsets.size() - 1, A.dLocal.p, A.dWorld.p, A.dInstNode.p, moved->n, A.dMoved.p));
+            movedList = A.dMoved.p;
+        }
+        else if (moved->n) HIP_TRY(hipMemcpyAsync(s->movedDev.p, (char*)t->host + seedBytes, movedBytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(zr::LaunchMoveInstances(st, s->instances.p, s->instancesPrev.p, s->toWorld.p, n, s->movedSlot.p, movedList, moved->n,
             s->emissives.p, s->objectEmissives.p, s->emissiveOwner.p, moved->emFirst, moved->emEnd));
     }
     s->toWorldDev = true;
     if ((r = SceneFillInstRecs(s, st))) return r;      // the records just written, decoded for this frame's hits
-    if ((r = StageCommit(t, st))) return r;
+    if (t && (r = StageCommit(t, st))) return r;
     uint32_t numNodesNow = (uint32_t)nn;
     if (install)
     {
@@ -1725,7 +1770,14 @@ static int SceneRefitUpdate(zr_scene* s, hipStream_t st, const zr_mesh_instance*
         hipLaunchKernelGGL(k_refit_level, dim3((cnt + 63) / 64), dim3(64), 0, st, s->nodes.p, s->levelNodes.p + first, cnt, s->tris.p, s->nodeBounds.p);
     }
     HIP_TRY(hipGetLastError());
-    if (moved)
+    if (animated)
+    {   // everything is enqueued: the host's view follows lazily (SceneAnimSyncHost), from the time alone
+        std::lock_guard<std::mutex> lockAnim(s->animMtx);
+        zr_scene::Anim& A = *s->anim;
+        if (!A.hasT || std::memcmp(&A.lastT, moved->animT, sizeof(float))) s->bg.movedSinceBuild = true;
+        A.lastT = *moved->animT; A.hasT = true; A.hostStale = true;
+    }
+    else if (moved)
     {   // everything is enqueued: the host's view of the matrices follows (what zr_scene_update_instances_async does from the caller's array up front)
         for (uint32_t j = 0; j < moved->n; j++)
         {
@@ -1745,6 +1797,7 @@ static int SceneRefitUpdate(zr_scene* s, hipStream_t st, const zr_mesh_instance*
         zr_scene::Background& B = s->bg;
         B.movedSinceBuild = false;
         if (B.th.joinable()) B.th.join();
+        SceneAnimSyncHost(s);
         B.inst.assign(instances, instances + n); B.xf.assign(s->hToWorld.begin(), s->hToWorld.end());      // (hToWorld: this update's matrices in either form)
         { const char* e = ZR_EXP_ENV("ZR_BVH_GROUP"); if (e && !std::strcmp(e, "0")) B.own.clear(); else B.own = s->movedEver; }
         B.state.store(1, std::memory_order_release); B.started++;
@@ -1867,7 +1920,87 @@ int zr_scene_move_instances_async(zr_scene* s, void* stream, const uint32_t* ins
     }
     if (moved.emEnd <= moved.emFirst) moved.emFirst = moved.emEnd = 0;
     HIP_TRY(hipSetDevice(s->device));
+    SceneAnimSyncHost(s);      // (a frame moved by hand between animated ones: the host's matrices are compared and replaced per moved instance)
     return SceneRefitUpdate(s, (hipStream_t)stream, s->hInstances.data(), s->hToWorld.data(), n, &moved);
+}
+// ---- keyframe animation: the tables once (zr_scene_set_animation), then one float per frame (zr_scene_animate_async)
+int zr_scene_set_animation(zr_scene* s, const zr_anim_desc* d)
+{
+    if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_animation: null scene");
+    HIP_TRY(hipSetDevice(s->device));
+    if (!d || (!d->num_nodes && !d->num_instances))
+    {
+        SceneAnimSyncHost(s);
+        HIP_TRY(hipDeviceSynchronize());      // an animate in flight still reads the tables
+        std::lock_guard<std::mutex> lock(s->animMtx);
+        s->anim.reset();
+        return ZR_OK;
+    }
+    const uint32_t n = (uint32_t)s->instances.n;
+    std::vector<uint32_t> level(d->num_nodes);
+    char msg[256];
+    if (zran::ValidateAnimation(*d, n, level.data(), msg, sizeof(msg))) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_animation: %s", msg);
+    std::unique_ptr<zr_scene::Anim> A(new zr_scene::Anim());
+    A->emFirst = 0xffffffffu; A->emEnd = 0;
+    for (uint32_t j = 0; j < d->num_instances; j++)
+    {
+        const uint32_t i = d->instance_idx[j], b = s->hInstances[i].base_emissive_tri_offset;
+        if (b == 0xffffffffu || !s->emissives.n) continue;
+        if (!s->objectEmissives.p) return Fail(ZR_ERR_NOT_INITIALIZED, "zr_scene_set_animation: instance %u carries lights: call zr_scene_set_object_emissives first", i);
+        A->emFirst = std::min(A->emFirst, b); A->emEnd = std::max(A->emEnd, b + s->hNumTris[i]);
+    }
+    if (A->emEnd <= A->emFirst) A->emFirst = A->emEnd = 0;
+    A->nodes.assign(d->nodes, d->nodes + d->num_nodes); A->keys.assign(d->keys, d->keys + d->num_keys);
+    A->instIdx.assign(d->instance_idx, d->instance_idx + d->num_instances); A->instNode.assign(d->instance_node, d->instance_node + d->num_instances);
+    A->desc.nodes = A->nodes.data(); A->desc.num_nodes = d->num_nodes; A->desc.keys = A->keys.data(); A->desc.num_keys = d->num_keys;
+    A->desc.instance_idx = A->instIdx.data(); A->desc.instance_node = A->instNode.data(); A->desc.num_instances = d->num_instances;
+    // the nodes grouped by level, top level first, table order within a level; the animated nodes; the local matrices of the others
+    uint32_t numLevels = 0;
+    for (uint32_t l : level) numLevels = std::max(numLevels, l + 1);
+    A->levelOffsets.assign(numLevels + 1, 0);
+    for (uint32_t l : level) A->levelOffsets[l + 1]++;
+    for (uint32_t l = 0; l < numLevels; l++) A->levelOffsets[l + 1] += A->levelOffsets[l];
+    std::vector<uint32_t> levelNodes(d->num_nodes), fill(A->levelOffsets.begin(), A->levelOffsets.end()), animatedNodes;
+    std::vector<float> local(12 * (size_t)d->num_nodes, 0.0f);
+    for (uint32_t i = 0; i < d->num_nodes; i++)
+    {
+        levelNodes[fill[level[i]]++] = i;
+        if (A->nodes[i].num_keys) animatedNodes.push_back(i);
+        else zran::NodeLocal(A->nodes[i], A->keys.data(), 0.0f, local.data() + 12 * (size_t)i);
+    }
+    A->nAnimated = (uint32_t)animatedNodes.size();
+    std::vector<uint32_t> movedInit(13 * (size_t)d->num_instances, 0u);
+    std::copy(A->instIdx.begin(), A->instIdx.end(), movedInit.begin() + 12 * (size_t)d->num_instances);
+    int r;
+    if ((r = A->dNodes.Upload(A->nodes.data(), A->nodes.size())) || (r = A->dKeys.Upload(A->keys.data(), A->keys.size())) ||
+        (r = A->dAnimated.Upload(animatedNodes.data(), animatedNodes.size())) || (r = A->dLevelNodes.Upload(levelNodes.data(), levelNodes.size())) ||
+        (r = A->dInstNode.Upload(A->instNode.data(), A->instNode.size())) || (r = A->dMoved.Upload(movedInit.data(), movedInit.size())) ||
+        (r = A->dLocal.Upload(local.data(), local.size())) || (r = A->dWorld.Alloc(local.size()))) return r;
+    // nothing of the scene has changed up to here.  The animation it replaces: its last frame reaches the host's matrices, its kernels finish
+    SceneAnimSyncHost(s);
+    HIP_TRY(hipDeviceSynchronize());
+    for (uint32_t i : A->instIdx) s->movedEver[i] = 1;      // the background builder gives each animated instance a subtree of its own
+    std::lock_guard<std::mutex> lock(s->animMtx);
+    s->anim = std::move(A);
+    return ZR_OK;
+}
+int zr_scene_animate_async(zr_scene* s, void* stream, float t)
+{
+    if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_animate: null scene");
+    if (!s->anim) return Fail(ZR_ERR_NOT_INITIALIZED, "zr_scene_animate: no animation set (zr_scene_set_animation)");
+    const char* modeEnv = std::getenv("ZR_SCENE_UPDATE");
+    if (modeEnv && (!std::strcmp(modeEnv, "rebuild") || !std::strcmp(modeEnv, "rebuild_host")))
+        return Fail(ZR_ERR_UNSUPPORTED, "zr_scene_animate: ZR_SCENE_UPDATE=%s is a host-synchronous path; the device form of the update needs the refit (default or refit_sah)", modeEnv);
+    MovedList moved{nullptr, nullptr, s->anim->desc.num_instances, s->anim->emFirst, s->anim->emEnd, &t};
+    HIP_TRY(hipSetDevice(s->device));
+    return SceneRefitUpdate(s, (hipStream_t)stream, s->hInstances.data(), s->hToWorld.data(), (uint32_t)s->instances.n, &moved);
+}
+int zr_scene_animate(zr_scene* s, float t)
+{
+    int r = zr_scene_animate_async(s, nullptr, t);
+    if (r) return r;
+    HIP_TRY(hipDeviceSynchronize());
+    return ZR_OK;
 }
 int zr_scene_move_instances(zr_scene* s, const uint32_t* instance_idx, const float* world_3x4, uint32_t n_moved)
 {
@@ -1883,6 +2016,7 @@ int zr_scene_get_instances(const zr_scene* s, void* stream, int which, zr_mesh_i
     if (n != s->instances.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_instances: %u instances, the scene has %zu", n, s->instances.n);
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    SceneAnimSyncHost(const_cast<zr_scene*>(s));
     const zr_mesh_instance* src; bool xfDev;
     { std::lock_guard<std::mutex> lock(s->mtx); src = which == 1 && s->hasPrev ? s->instancesPrev.p : s->instances.p; xfDev = s->toWorldDev && s->toWorld.n == 12 * (size_t)n; }
     HIP_TRY(hipMemcpy(out, src, (size_t)n * sizeof(zr_mesh_instance), hipMemcpyDeviceToHost));
@@ -3117,6 +3251,7 @@ static int RenderPickOutlines(zr_pass* p, hipStream_t s, const zr_frame_constant
     }
     if (!p->pickCount.p && (r = p->pickCount.Alloc(1))) return r;
     if (p->pickTris.n < 14 * (size_t)maxTris + 2 && (r = p->pickTris.Alloc(14 * (size_t)maxTris + 2))) return r;
+    SceneAnimSyncHost(const_cast<zr_scene*>(sc));
     for (uint32_t idx : p->picks)
     {
         // W: the 3x4 object-to-world matrix as the reference's float4x3 (row-vector convention); WVP[i][j] = ((W[i][0] VP[0][j] + W[i][1] VP[1][j]) + W[i][2] VP[2][j]) + W[i][3] VP[3][j]

@@ -805,6 +805,26 @@ extern "C" int zrh_scene_apply_updates_on(zr_scene* scene, const zrh_scene_data*
 }
 extern "C" int zrh_scene_apply_updates(zr_scene* scene, const zrh_scene_data* data) { return zrh_scene_apply_updates_on(scene, data, nullptr); }
 
+// A frame of a scene with keyframe animation (zrh_scene_data_set_animation or an animated glTF), enqueued on `stream`.  Host path: begin_frame,
+// zrh_scene_data_animate (include/zr_anim.h on the host), then the hand-over above.  After zrh_scene_data_set_device_animation(data, 1): the time alone
+// (zr_scene_animate_async); the tables -- and the object-space light records -- go to a device scene the first time it is asked to animate without any.
+extern "C" int zrh_scene_animate(zrh_scene_data* data, zr_scene* scene, void* stream, float t)
+{
+    if (!scene || !data || !zrh_scene_data_animation(data)) return -1;
+    if (!zrh_scene_data_device_animation(data))
+    {
+        zrh_scene_data_begin_frame(data);
+        if (zrh_scene_data_animate(data, t)) return -1;
+        return zrh_scene_apply_updates_on(scene, data, stream);
+    }
+    int r = zr_scene_animate_async(scene, stream, t);
+    if (r != ZR_ERR_NOT_INITIALIZED) return r;
+    if (!zr_scene_has_object_emissives(scene) && zrh_scene_data_initial_emissives(data) &&
+        (r = zr_scene_set_object_emissives(scene, zrh_scene_data_initial_emissives(data), zrh_scene_data_desc(data)->num_emissives))) return r;
+    if ((r = zr_scene_set_animation(scene, zrh_scene_data_animation(data)))) return r;
+    return zr_scene_animate_async(scene, stream, t);
+}
+
 int zrh_render_sequence_sky_display(const zr_scene_desc* desc, const zr_frame_constants* cbs, uint32_t n, uint32_t w, uint32_t h, int integrator, float* finalOut, float* skyDiOut,
     float* compositedOut, uint16_t* taaOut, const uint32_t* lutRGB9E5, uint32_t lutDim, int tonemapper, float* exposureOut, float* displayOut, uint8_t* displaySrgbOut);
 int zrh_render_sequence_sky_post(const zr_scene_desc* desc, const zr_frame_constants* cbs, uint32_t n, uint32_t w, uint32_t h, int integrator, float* finalOut, float* skyDiOut,

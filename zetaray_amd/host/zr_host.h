@@ -58,6 +58,12 @@ int zrh_scene_create_from_gltf(int device, const char* path, const uint16_t* rho
 // (zr_scene_set_object_emissives), then per frame the moved instances and their matrices alone (zr_scene_move_instances_async) -- the same device bytes
 int zrh_scene_apply_updates(zr_scene* scene, const struct zrh_scene_data* data);                       /* enqueued on the null stream, no host wait */
 int zrh_scene_apply_updates_on(zr_scene* scene, const struct zrh_scene_data* data, void* hip_stream); /* enqueued on `hip_stream` */
+// a frame of an animated scene at time t (zr_scene_io.h: zrh_scene_data_set_animation, or a glTF file with "animations"), enqueued on `hip_stream`.
+// Host path (the default): zrh_scene_data_begin_frame, zrh_scene_data_animate, then zrh_scene_apply_updates_on.  After
+// zrh_scene_data_set_device_animation(data, 1): zr_scene_animate_async -- only t crosses the bus; the tables (and the object-space light records) are
+// handed to a device scene that has none the first time.  The device path leaves data's own records and matrices where they were.  A table replaced
+// on `data` later reaches a device scene through zr_scene_set_animation.
+int zrh_scene_animate(struct zrh_scene_data* data, zr_scene* scene, void* hip_stream, float t);
 }
 
 namespace ZetaRayAMD {

@@ -4,6 +4,7 @@
 #include "zr_scene_io.h"
 #include "../../include/zr_detmath.h"
 #include "../../include/zr_scene_math.h"
+#include "../../include/zr_anim.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -18,6 +19,7 @@ namespace {
 
 // Mat43 / FromToWorld / DecomposeSRT / FillMeshInstance / the EmissiveTriangle encode, decode and transform: one statement for the host and the device
 using namespace zrsm;
+using namespace zran;
 
 thread_local std::string g_err;
 struct Error { std::string what; };
@@ -147,45 +149,7 @@ zr_material PackMaterial(const MaterialDesc& d)
 
 // ------------------------------------------------------------------------------------------------ transforms (Math/MatrixFuncs.h)
 // Mat43 (zr_scene_math.h): row-vector 4 x 4 as the reference stores it, rows 0-2 = images of the basis vectors, row 3 = translation
-void ToToWorld(const Mat43& r, float* M) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) M[4 * j + i] = r.m[i][j]; for (int j = 0; j < 3; j++) M[4 * j + 3] = r.m[3][j]; }
-
-// rotationMatFromQuat, MatrixFuncs.h:356-405 (operation order of the SSE code)
-void RotationMatFromQuat(const float q[4], float R[3][3])
-{
-    const float q1 = q[0], q2 = q[1], q3 = q[2], q4 = q[3];
-    const float q1s = q1 * q1, q2s = q2 * q2, q3s = q3 * q3;
-    const float d0 = std::fma(q1s + q3s, -2.0f, 1.0f), d1 = std::fma(q2s + q3s, -2.0f, 1.0f), d2 = std::fma(q1s + q2s, -2.0f, 1.0f);
-    const float q1q4 = (q1 * q4) * 2.0f, q2q4 = (q2 * q4) * 2.0f, q1q3 = (q3 * q1) * 2.0f, q3q4 = (q4 * q3) * 2.0f;
-    const float q1q2 = (q1 * q2) * 2.0f, q2q3 = (q2 * q3) * 2.0f;
-    R[0][0] = d1;          R[0][1] = q1q2 + q3q4; R[0][2] = q1q3 - q2q4;
-    R[1][0] = q1q2 - q3q4; R[1][1] = d0;          R[1][2] = q2q3 + q1q4;
-    R[2][0] = q1q3 + q2q4; R[2][1] = q2q3 - q1q4; R[2][2] = d2;
-}
-// affineTransformation(vS, vQ, vT), MatrixFuncs.h:488-503
-Mat43 AffineTransformation(const float s[3], const float q[4], const float t[3])
-{
-    float R[3][3]; RotationMatFromQuat(q, R);
-    Mat43 r;
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) r.m[i][j] = s[i] * R[i][j];
-    for (int j = 0; j < 3; j++) r.m[3][j] = t[j];
-    return r;
-}
-// mul(M1, M2), MatrixFuncs.h:114-163, for affine matrices (column 3 = (0, 0, 0, 1)): (a0 b0 + a1 b1) + (a2 b2 + a3 b3), fused as the AVX code
-Mat43 Mul(const Mat43& A, const Mat43& B)
-{
-    Mat43 C;
-    for (int i = 0; i < 4; i++)
-    {
-        const float a3 = i == 3 ? 1.0f : 0.0f;
-        for (int j = 0; j < 3; j++)
-        {
-            const float c2 = std::fma(A.m[i][1], B.m[1][j], A.m[i][0] * B.m[0][j]);
-            const float c6 = std::fma(a3, B.m[3][j], A.m[i][2] * B.m[2][j]);
-            C.m[i][j] = c2 + c6;
-        }
-    }
-    return C;
-}
+// ToToWorld, RotationMatFromQuat, AffineTransformation and Mul are include/zr_anim.h's (namespace zran): the device form of the animation compiles them too
 
 // RT::EmissiveTriangle ctor + StoreVertices (RtCommon.h:73-190)
 void PackEmissiveTriangle(const float* v0, const float* v1, const float* v2, const float* uv, uint32_t factorRGB8, uint32_t tex, uint16_t strengthH,
@@ -335,6 +299,9 @@ struct zrh_scene_data
     // the instances set_instance_world named this frame, each once, with their matrices; movedSlot[i] = where instance i stands in that list
     std::vector<uint32_t> movedIdx, movedSlot; std::vector<float> movedWorld;
     bool deviceRecords = false;      // zrh_scene_data_set_device_records (zr_host.h: zrh_scene_apply_updates)
+    // keyframe animation (zrh_scene_data_set_animation: a deep copy; anim points into the vectors) and the node matrices of the last zrh_scene_data_animate
+    std::vector<zr_anim_node> animNodes; std::vector<zr_keyframe> animKeys; std::vector<uint32_t> animInstIdx, animInstNode; std::vector<float> animWorld;
+    zr_anim_desc anim{}; bool hasAnim = false, deviceAnimation = false;      // deviceAnimation: zrh_scene_data_set_device_animation (zr_host.h: zrh_scene_animate)
     zr_scene_desc desc;
     void Finish()
     {
@@ -529,11 +496,58 @@ void Load(const std::string& path, zrh_scene_data& sc)
         if (const Json* ext = m.Find("extensions")) hasStrength = ext->Find("KHR_materials_emissive_strength") != nullptr;
         return sum > 0 || hasStrength || m.Find("emissiveTexture") != nullptr; };
     Mat43 identity; std::memset(&identity, 0, sizeof(identity)); for (int i = 0; i < 3; i++) identity.m[i][i] = 1.0f;
+    // ---- "animations": per animated node the input accessor its channels share and one output accessor per path (-1: the node's rest value at every
+    // key).  LINEAR samplers on translation / rotation / scale only; anything else fails the load with the animation and the node named
+    struct NodeAnim { int input = -1, out[3] = {-1, -1, -1}; std::string anim; };      // out: translation, rotation, scale
+    std::map<int, NodeAnim> nodeAnims;
+    if (const Json* anims = g.root.Find("animations"))
+        for (size_t ai = 0; ai < anims->Size(); ai++)
+        {
+            const Json& a = anims->arr[ai];
+            const std::string aname = "animation " + std::to_string(ai) + " ('" + a.StrOr("name", "") + "')";
+            const Json& samplers = a.At("samplers");
+            for (const Json& ch : a.At("channels").arr)
+            {
+                const Json& target = ch.At("target");
+                const int node = target.IntOr("node", -1);
+                if (node < 0) continue;      // (a channel without a target node is ignored, as the specification says)
+                const std::string where = "glTF: " + aname + ", node " + std::to_string(node) + ": ";
+                if ((size_t)node >= nodes.arr.size()) Throw(where + "node index out of range");
+                const std::string path = target.StrOr("path", "");
+                const int which = path == "translation" ? 0 : path == "rotation" ? 1 : path == "scale" ? 2 : -1;
+                if (which < 0) Throw(where + "target path '" + path + "' is not supported (translation, rotation and scale are)");
+                const Json& sm = samplers.arr.at((size_t)ch.At("sampler").num);
+                const std::string interp = sm.StrOr("interpolation", "LINEAR");
+                if (interp != "LINEAR") Throw(where + interp + " samplers are not supported (LINEAR is)");
+                NodeAnim& na = nodeAnims[node];
+                const int input = (int)sm.At("input").num;
+                if (na.input >= 0 && na.input != input) Throw(where + "its channels use different input accessors (per-channel key times are not supported)");
+                if (na.out[which] >= 0) Throw(where + "two channels target its " + path);
+                na.input = input; na.out[which] = (int)sm.At("output").num; na.anim = aname;
+                const Accessor in = g.Acc(input), out = g.Acc(na.out[which]);
+                if (in.count < 2) Throw(where + "fewer than 2 keys");
+                if (out.count < in.count || out.ncomp != (which == 1 ? 4 : 3) || in.ncomp != 1) Throw(where + "sampler accessors do not match the " + path + " path");
+            }
+        }
+    // does the subtree of a node hold a mesh?  (a descendant of an animated node joins the closure only if it carries, or leads to, an instance)
+    std::vector<int8_t> leadsToMesh(nodes.arr.size(), -1);
     struct Walker
     {
         Gltf& g; zrh_scene_data& sc; std::map<std::pair<int, int>, MeshPrim>& prims; std::vector<Em>& emissive; const Json& nodes; decltype(isEmissive)& isEm;
         std::vector<uint8_t> onPath;
-        void Visit(int nidx, const Mat43& parent)
+        std::map<int, NodeAnim>& nodeAnims; std::vector<int8_t>& leadsToMesh;
+        bool LeadsToMesh(int nidx, int depth = 0)
+        {
+            if (nidx < 0 || (size_t)nidx >= nodes.arr.size() || depth > 4096) return false;
+            if (leadsToMesh[nidx] >= 0) return leadsToMesh[nidx] != 0;
+            const Json& node = nodes.arr.at(nidx);
+            bool any = node.IntOr("mesh", -1) >= 0;
+            if (const Json* ch = node.Find("children")) for (const Json& c : ch->arr) any = LeadsToMesh((int)c.num, depth + 1) || any;
+            leadsToMesh[nidx] = any ? 1 : 0;
+            return any;
+        }
+        // closureParent: the node's parent in the closure table, ZR_ANIM_ROOT when no ancestor is animated
+        void Visit(int nidx, const Mat43& parent, uint32_t closureParent = ZR_ANIM_ROOT)
         {
             if (nidx < 0 || (size_t)nidx >= nodes.arr.size()) Throw("glTF: node index out of range");
             if (onPath.empty()) onPath.assign(nodes.arr.size(), 0);
@@ -557,6 +571,38 @@ void Load(const std::string& path, zrh_scene_data& sc)
                 if (const Json* a = node.Find("rotation")) { q[0] = -(float)a->arr.at(0).num; q[1] = -(float)a->arr.at(1).num; q[2] = (float)a->arr.at(2).num; q[3] = (float)a->arr.at(3).num; }
             }
             const Mat43 world = Mul(AffineTransformation(s, q, t), parent);
+            // ---- the dynamic closure, depth first (a parent precedes its children): the animated nodes and what hangs on them
+            uint32_t entry = ZR_ANIM_ROOT;
+            const auto anim = nodeAnims.find(nidx);
+            if (anim != nodeAnims.end() || (closureParent != ZR_ANIM_ROOT && LeadsToMesh(nidx)))
+            {
+                zr_anim_node an; std::memset(&an, 0, sizeof(an));
+                an.parent = closureParent;
+                for (int k = 0; k < 3; k++) { an.rest_scale[k] = s[k]; an.rest_translation[k] = t[k]; }
+                for (int k = 0; k < 4; k++) an.rest_rotation[k] = q[k];
+                if (closureParent == ZR_ANIM_ROOT) ToToWorld(parent, an.parent_world);      // the static world matrix above the node (unused below a closure node)
+                if (anim != nodeAnims.end())
+                {
+                    const NodeAnim& na = anim->second;
+                    const Accessor in = g.Acc(na.input);
+                    an.first_key = (uint32_t)sc.animKeys.size(); an.num_keys = (uint32_t)in.count; an.loop = 1; an.t0 = 0.0f;
+                    Accessor out[3]; for (int w = 0; w < 3; w++) if (na.out[w] >= 0) out[w] = g.Acc(na.out[w]);
+                    for (size_t k = 0; k < in.count; k++)
+                    {
+                        // the node's own handedness conversion: translation z negated, rotation x and y negated
+                        zr_keyframe key; std::memset(&key, 0, sizeof(key));
+                        key.time = Gltf::Comp(in, k, 0);
+                        for (int c = 0; c < 3; c++) { key.scale[c] = s[c]; key.translation[c] = t[c]; }
+                        for (int c = 0; c < 4; c++) key.rotation[c] = q[c];
+                        if (na.out[0] >= 0) { key.translation[0] = Gltf::Comp(out[0], k, 0); key.translation[1] = Gltf::Comp(out[0], k, 1); key.translation[2] = -Gltf::Comp(out[0], k, 2); }
+                        if (na.out[1] >= 0) { key.rotation[0] = -Gltf::Comp(out[1], k, 0); key.rotation[1] = -Gltf::Comp(out[1], k, 1); key.rotation[2] = Gltf::Comp(out[1], k, 2); key.rotation[3] = Gltf::Comp(out[1], k, 3); }
+                        if (na.out[2] >= 0) for (int c = 0; c < 3; c++) { key.scale[c] = Gltf::Comp(out[2], k, c); if (!(key.scale[c] > 0)) Throw("glTF: " + na.anim + ", node " + std::to_string(nidx) + ": negative scale factors are not supported"); }
+                        sc.animKeys.push_back(key);
+                    }
+                }
+                entry = (uint32_t)sc.animNodes.size();
+                sc.animNodes.push_back(an);
+            }
             const int mesh = node.IntOr("mesh", -1);
             if (mesh >= 0)
             {
@@ -577,18 +623,28 @@ void Load(const std::string& path, zrh_scene_data& sc)
                     const bool em = isEm(mp.mat);
                     const int alphaMode = (int)((mat.coat_color_flags >> 27) & 3u);
                     sc.instances.push_back(I);
+                    if (entry != ZR_ANIM_ROOT) { sc.animInstIdx.push_back((uint32_t)sc.instances.size() - 1); sc.animInstNode.push_back(entry); }
                     sc.toWorld.insert(sc.toWorld.end(), M, M + 12);
                     sc.mask.push_back((uint8_t)((em ? ZR_SUBGROUP_EMISSIVE : ZR_SUBGROUP_NON_EMISSIVE) | (alphaMode != 0 ? ZR_INSTANCE_NON_OPAQUE : 0u)));
                     sc.numTris.push_back(mp.nidx / 3);
                     if (em) emissive.push_back(Em{(uint32_t)sc.instances.size() - 1, mp});
                 }
             }
-            if (const Json* ch = node.Find("children")) for (const Json& c : ch->arr) Visit((int)c.num, world);
+            if (const Json* ch = node.Find("children")) for (const Json& c : ch->arr) Visit((int)c.num, world, entry);
         }
-    } walker{g, sc, prims, emissive, nodes, isEmissive, {}};
+    } walker{g, sc, prims, emissive, nodes, isEmissive, {}, nodeAnims, leadsToMesh};
     const Json& scenes = g.root.At("scenes");
     const Json& scene = scenes.arr.at((size_t)g.root.IntOr("scene", 0));
     for (const Json& n : scene.At("nodes").arr) walker.Visit((int)n.num, identity);
+    if (!sc.animNodes.empty())
+    {   // (an animated node outside the scene's node lists adds nothing.)  The tables are held to what zrh_scene_data_set_animation checks
+        zr_anim_desc d; std::memset(&d, 0, sizeof(d));
+        d.nodes = sc.animNodes.data(); d.num_nodes = (uint32_t)sc.animNodes.size(); d.keys = sc.animKeys.data(); d.num_keys = (uint32_t)sc.animKeys.size();
+        d.instance_idx = sc.animInstIdx.data(); d.instance_node = sc.animInstNode.data(); d.num_instances = (uint32_t)sc.animInstIdx.size();
+        char msg[256];
+        if (ValidateAnimation(d, (uint32_t)sc.instances.size(), nullptr, msg, sizeof(msg))) Throw(std::string("glTF: animations: ") + msg);
+        sc.anim = d; sc.hasAnim = true;
+    }
     // ---- emissive triangles in world space (glTF.cpp:692-767, SceneCore.cpp:196-236): ID = PCG3d(instance, 0, triangle).x
     for (const Em& em : emissive)
     {
@@ -691,6 +747,33 @@ uint32_t zrh_scene_data_moved(const zrh_scene_data* s, const uint32_t** idx, con
     if (world) *world = s->movedWorld.data();
     return (uint32_t)s->movedIdx.size();
 }
+// ---- keyframe animation: the host path (include/zr_anim.h on the host, then set_instance_world in list order)
+int zrh_scene_data_set_animation(zrh_scene_data* s, const zr_anim_desc* d)
+{
+    if (!s) { g_err = "zrh_scene_data_set_animation: null scene"; return -1; }
+    if (!d || (!d->num_nodes && !d->num_instances))
+    { s->hasAnim = false; s->animNodes.clear(); s->animKeys.clear(); s->animInstIdx.clear(); s->animInstNode.clear(); std::memset(&s->anim, 0, sizeof(s->anim)); return 0; }
+    char msg[256];
+    if (ValidateAnimation(*d, (uint32_t)s->instances.size(), nullptr, msg, sizeof(msg))) { g_err = std::string("zrh_scene_data_set_animation: ") + msg; return -1; }
+    s->animNodes.assign(d->nodes, d->nodes + d->num_nodes); s->animKeys.assign(d->keys, d->keys + d->num_keys);
+    s->animInstIdx.assign(d->instance_idx, d->instance_idx + d->num_instances); s->animInstNode.assign(d->instance_node, d->instance_node + d->num_instances);
+    s->anim.nodes = s->animNodes.data(); s->anim.num_nodes = d->num_nodes; s->anim.keys = s->animKeys.data(); s->anim.num_keys = d->num_keys;
+    s->anim.instance_idx = s->animInstIdx.data(); s->anim.instance_node = s->animInstNode.data(); s->anim.num_instances = d->num_instances;
+    s->hasAnim = true;
+    return 0;
+}
+const zr_anim_desc* zrh_scene_data_animation(const zrh_scene_data* s) { return s && s->hasAnim ? &s->anim : nullptr; }
+int zrh_scene_data_animate(zrh_scene_data* s, float t)
+{
+    if (!s || !s->hasAnim) { g_err = "zrh_scene_data_animate: no animation set"; return -1; }
+    s->animWorld.resize(12 * (size_t)s->anim.num_nodes);
+    EvalNodeWorlds(s->anim, t, s->animWorld.data());
+    for (uint32_t j = 0; j < s->anim.num_instances; j++)
+        if (zrh_scene_data_set_instance_world(s, s->animInstIdx[j], s->animWorld.data() + 12 * (size_t)s->animInstNode[j])) return -1;
+    return 0;
+}
+void zrh_scene_data_set_device_animation(zrh_scene_data* s, int on) { if (s) s->deviceAnimation = on != 0; }
+int zrh_scene_data_device_animation(const zrh_scene_data* s) { return s && s->deviceAnimation ? 1 : 0; }
 void zrh_scene_data_set_device_records(zrh_scene_data* s, int on) { if (s) s->deviceRecords = on != 0; }
 int zrh_scene_data_device_records(const zrh_scene_data* s) { return s && s->deviceRecords ? 1 : 0; }
 int zrh_scene_data_from_desc(const zr_scene_desc* d, const zr_emissive_triangle* object_space_emissives, zrh_scene_data** out)

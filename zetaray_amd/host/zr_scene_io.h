@@ -44,6 +44,17 @@ void zrh_scene_data_dirty_emissives(const zrh_scene_data* s, uint32_t* first, ui
 uint32_t zrh_scene_data_moved(const zrh_scene_data* s, const uint32_t** idx, const float** world_3x4);
 void zrh_scene_data_set_device_records(zrh_scene_data* s, int on);
 int zrh_scene_data_device_records(const zrh_scene_data* s);
+// ---- keyframe animation (include/zr_anim.h; zr_keyframe / zr_anim_node / zr_anim_desc: include/zr_wire.h).  set_animation deep-copies `desc` (null or
+// empty clears) and refuses what zr_scene_set_animation refuses as invalid (-1, zrh_scene_io_last_error(), nothing changed); zrh_scene_data_animation
+// returns the scene's copy, null when there is none.  zrh_scene_data_animate(s, t) is the HOST PATH of a frame's animation: the header on the host for
+// time t, then zrh_scene_data_set_instance_world for each listed instance in list order (the caller runs zrh_scene_data_begin_frame first, as for any
+// frame) -- the definition zr_scene_animate (zetaray_amd.h) is held to, byte for byte.
+int zrh_scene_data_set_animation(zrh_scene_data* s, const zr_anim_desc* desc);
+const zr_anim_desc* zrh_scene_data_animation(const zrh_scene_data* s);
+int zrh_scene_data_animate(zrh_scene_data* s, float t);
+// which of the two zrh_scene_animate (zr_host.h) takes: 0 (default) the host path above, 1 zr_scene_animate_async
+void zrh_scene_data_set_device_animation(zrh_scene_data* s, int on);
+int zrh_scene_data_device_animation(const zrh_scene_data* s);
 // the per-frame maintenance above for a scene that did not come from zrh_gltf_load: a deep copy of `desc`; object_space_emissives = desc->num_emissives
 // object-space light records (null: instances that carry lights keep their records when they move)
 int zrh_scene_data_from_desc(const zr_scene_desc* desc, const zr_emissive_triangle* object_space_emissives, zrh_scene_data** out);

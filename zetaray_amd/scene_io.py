@@ -256,6 +256,8 @@ def _accessor(g, bins, idx):
 
 
 def load_gltf(path, rho=None) -> Scene:
+    """glTF -> wire formats in Python (meshes, materials, node hierarchy).  It does not read "animations": an animated file loads as the still scene at
+    its nodes' rest transforms; load_gltf_native reads them (sc.animation)."""
     g = json.load(open(path))
     base = os.path.dirname(path)
     bins = [open(os.path.join(base, b["uri"]), "rb").read() for b in g["buffers"]]
@@ -444,7 +446,9 @@ def _sceneio_lib():
 
 def load_gltf_native(path, rho=None):
     """glTF -> wire formats through the C++ loader (MeshInstance quantisation by decomposeSRT of the world matrix, node hierarchies, matrix
-    nodes, DDS material textures decoded to the texel heap).  Returns (Scene, texture-table offsets dict for set_texture_heap_offsets)."""
+    nodes, DDS material textures decoded to the texel heap).  Returns (Scene, texture-table offsets dict for set_texture_heap_offsets).
+    A file with "animations" (LINEAR translation / rotation / scale channels) also gives sc.animation, a wire.AnimDesc over the dynamic closure of
+    its node hierarchy (Scene.set_animation / Scene.animate in api.py), and sc.emissives_initial, the object-space light records; None without."""
     import ctypes as C
     L = _sceneio_lib()
     rho_data, rho_dim = load_rho_default() if rho is None else rho
@@ -473,6 +477,17 @@ def load_gltf_native(path, rho=None):
         sc.textures = arr(d.textures, d.num_textures, wire.TEXTURE_DESC)
         sc.texels = arr(d.texels, d.texel_bytes, np.uint8)
         sc.rho, sc.rho_dim = rho_data, tuple(rho_dim)
+        sc.animation = None
+        L.zrh_scene_data_animation.argtypes = [C.c_void_p]
+        L.zrh_scene_data_animation.restype = C.POINTER(wire.AnimDescC)
+        a = L.zrh_scene_data_animation(h)
+        if a:
+            a = a.contents
+            sc.animation = wire.AnimDesc(arr(a.nodes, a.num_nodes, wire.ANIM_NODE), arr(a.keys, a.num_keys, wire.KEYFRAME),
+                                         arr(a.instance_idx, a.num_instances, np.uint32), arr(a.instance_node, a.num_instances, np.uint32))
+            L.zrh_scene_data_initial_emissives.restype = C.c_void_p
+            L.zrh_scene_data_initial_emissives.argtypes = [C.c_void_p]
+            sc.emissives_initial = arr(L.zrh_scene_data_initial_emissives(h), d.num_emissives, wire.EMISSIVE_TRI)
         offs = (C.c_uint32 * 4)()
         L.zrh_scene_data_tex_offsets(h, offs)
         return sc, dict(base_color=offs[0], normal=offs[1], metallic_roughness=offs[2], emissive=offs[3])

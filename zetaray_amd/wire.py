@@ -66,6 +66,12 @@ SUBGROUP_ALL = 3
 INSTANCE_NON_OPAQUE = 0x80      # extra bit of instance_mask: geometry without the OPAQUE flag (primary-ray alpha test)
 TEX_RGBA8_SRGB, TEX_RGBA8, TEX_RG8 = 0, 1, 2
 TEXTURE_DESC = np.dtype([("offset", "<u8"), ("width", "<u2"), ("height", "<u2"), ("num_mips", "u1"), ("format", "u1"), ("pad", "<u2")])
+# keyframe animation (zr_keyframe / zr_anim_node / zr_anim_desc, include/zr_wire.h)
+ANIM_ROOT = 0xFFFFFFFF
+KEYFRAME = np.dtype([("scale", "<f4", 3), ("rotation", "<f4", 4), ("translation", "<f4", 3), ("time", "<f4")])
+ANIM_NODE = np.dtype([("parent", "<u4"), ("first_key", "<u4"), ("num_keys", "<u4"), ("loop", "<u4"), ("t0", "<f4"), ("rest_scale", "<f4", 3),
+                      ("rest_rotation", "<f4", 4), ("rest_translation", "<f4", 3), ("parent_world", "<f4", 12)])
+assert KEYFRAME.itemsize == 44 and ANIM_NODE.itemsize == 108
 
 GB_PLANE_NAMES = ["base_color", "normal", "metallic_roughness", "motion_vector", "emissive_color", "ior", "coat",
                   "depth", "tri_diff_geo_a", "tri_diff_geo_b"]
@@ -89,6 +95,31 @@ class SceneDesc(C.Structure):
         ("textures", C.c_void_p), ("num_textures", C.c_uint32),
         ("texels", C.c_void_p), ("texel_bytes", C.c_uint64),
     ]
+
+
+class AnimDescC(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("num_nodes", C.c_uint32), ("keys", C.c_void_p), ("num_keys", C.c_uint32),
+                ("instance_idx", C.c_void_p), ("instance_node", C.c_void_p), ("num_instances", C.c_uint32)]
+
+
+class AnimDesc:
+    """zr_anim_desc over numpy arrays it keeps alive: nodes (ANIM_NODE; the dynamic closure, a parent before its children), keys (KEYFRAME),
+    instance_idx[j] = the instance that has the world matrix of node instance_node[j]"""
+
+    def __init__(self, nodes, keys, instance_idx, instance_node):
+        self.nodes = np.ascontiguousarray(nodes, ANIM_NODE)
+        self.keys = np.ascontiguousarray(keys, KEYFRAME)
+        self.instance_idx = np.ascontiguousarray(instance_idx, np.uint32).reshape(-1)
+        self.instance_node = np.ascontiguousarray(instance_node, np.uint32).reshape(-1)
+        if len(self.instance_idx) != len(self.instance_node):
+            raise ValueError(f"AnimDesc: {len(self.instance_idx)} instances, {len(self.instance_node)} nodes for them")
+
+    def c_desc(self):
+        d = AnimDescC()
+        d.nodes, d.num_nodes = self.nodes.ctypes.data, len(self.nodes)
+        d.keys, d.num_keys = self.keys.ctypes.data, len(self.keys)
+        d.instance_idx, d.instance_node, d.num_instances = self.instance_idx.ctypes.data, self.instance_node.ctypes.data, len(self.instance_idx)
+        return d
 
 
 class GBufferPlanes(C.Structure):
