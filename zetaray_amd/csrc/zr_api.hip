@@ -512,7 +512,17 @@ template<typename T> struct DevBuf
     int AllocZero(size_t count) { int r = Alloc(count); if (r) return r; HIP_TRY(hipMemset(p, 0, count * sizeof(T))); return ZR_OK; }
     int Upload(const T* src, size_t count) { int r = Alloc(count); if (r) return r; if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice)); return ZR_OK; }
     void Free() { if (p) { (void)hipFree(p); p = nullptr; } n = 0; }
+    void Swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); }
+    // at least `count` elements, the first `keep` of them kept (a blocking copy into a new allocation; nothing happens to a buffer that is large enough)
+    int Grow(size_t count, size_t keep) { if (n >= count) return ZR_OK; DevBuf nb; int r = nb.Alloc(count); if (r) return r; if (keep && p) HIP_TRY(hipMemcpy(nb.p, p, keep * sizeof(T), hipMemcpyDeviceToDevice)); Swap(nb); return ZR_OK; }
     ~DevBuf() { Free(); }
+};
+// What a trace binds that a frame's instance update replaces: the instance records and their decoded table (zr_hit_tables.h), the BVH4's nodes and triangle
+// slots, the global (mesh, primitive) table.  A buffer's n is its CAPACITY; numNodes / numTris say how much of nodes / tris the tree in them uses.
+struct AccelSet
+{
+    DevBuf<zr_mesh_instance> instances; DevBuf<InstRec> instRecs; DevBuf<Bvh4Node> nodes; DevBuf<BvhTri> tris; DevBuf<TriMeta> meta;
+    uint32_t numNodes = 0, numTris = 0;
 };
 struct HaloPlane { void* base; size_t bpp; };
 // A per-pixel device plane: PER_PIXEL elements of T for every pixel.  This declaration is the one statement of the plane's layout -- allocation, the
@@ -534,30 +544,35 @@ template<typename S> static void PlanesOutput(const S& set, int i, void** dev, u
 struct zr_scene
 {
     int device = 0;
-    DevBuf<zr_vertex> vertices; DevBuf<uint32_t> indices; DevBuf<zr_mesh_instance> instances; DevBuf<zr_material> materials;
-    DevBuf<zr_emissive_triangle> emissives; DevBuf<zr_alias_entry> alias; DevBuf<Bvh4Node> nodes; DevBuf<BvhTri> tris;
+    DevBuf<zr_vertex> vertices; DevBuf<uint32_t> indices; DevBuf<zr_material> materials;
+    DevBuf<zr_emissive_triangle> emissives; DevBuf<zr_alias_entry> alias;
+    // The current and the previous acceleration structure + instance buffer (RT_SCENE_BVH_PREV / RT_FRAME_MESH_INSTANCES_PREV of the temporal passes):
+    //  * they change roles in SceneFlip and nowhere else -- whole sets, capacities and counts with the pointers -- once per instance update of any form;
+    //    `prev` is bound only while hasPrev (FrameViewPrev: before the first update, and after a rolled-back rebuild, the temporal passes bind `cur`)
+    //  * `view` takes a set's buffers and counts through SceneBind only; view.numNodes / numTris are what kernels and zr_scene_bvh_info read,
+    //    cur.numNodes / numTris the host's statement of the same values
+    //  * refitReady: both sets hold the same topology (SceneDuplicate made `prev` a copy of `cur`, only refits followed), so the set that becomes current
+    //    is refit in place; a rebuild or the install of a background tree clears it, and the next refit duplicates first
+    AccelSet cur, prev; bool hasPrev = false, refitReady = false;
     // material class (SceneView::plain): host copy of the material table + "every material is an opaque uncoated non-metallic dielectric"; kept current by
     // zr_scene_create / zr_scene_update_materials on the calling thread, read by zr_pass_render when it picks a kernel permutation
     std::vector<zr_material> hMaterials; std::atomic<bool> plainMaterials{false};
     // identity of this scene for the G-buffers rendered from it (zr_gbuffer::sceneAt): never reused, unlike an address
     uint64_t uid = [] { static std::atomic<uint64_t> next{1}; return next.fetch_add(1); }();
-    DevBuf<TriMeta> meta; DevBuf<uint16_t> rho;
+    DevBuf<uint16_t> rho;
     DevBuf<zr_texture_desc> texDescs; DevBuf<uint8_t> texels; DevBuf<float> srgb;   // material texture heap (zr_texture.h)
     DevBuf<zr_presampled_tri> sampleSets; uint32_t numSampleSets = 0;      // K3 output, refreshed by every PRELIGHTING render
     DevBuf<zr_voxel_sample> lvg;                                           // K4 output, rebuilt by every PRELIGHTING render when use_lvg
     std::vector<zr_alias_entry> aliasHost;
-    // dynamic instances (zr_scene_update_instances): host copies of what a BVH rebuild needs, and the previous frame's instance buffer + BVH
+    // dynamic instances (zr_scene_update_instances): host copies of what a BVH rebuild needs
     std::vector<zr_vertex> hVertices; std::vector<uint32_t> hIndices; std::vector<uint8_t> hMask; std::vector<uint32_t> hNumTris;
-    DevBuf<zr_mesh_instance> instancesPrev; DevBuf<Bvh4Node> nodesPrev; DevBuf<BvhTri> trisPrev; DevBuf<TriMeta> metaPrev;
-    uint32_t numNodesPrev = 0, numTrisPrev = 0; bool hasPrev = false;
-    // what hit reconstruction decodes from an instance record / a vertex normal, stored once (zr_hit_tables.h).  instRecs belongs to `instances`, instRecsPrev
-    // to `instancesPrev`: they swap wherever those swap, and whatever writes an instance array refills its table on the same stream (SceneFillInstRecs)
-    DevBuf<InstRec> instRecs, instRecsPrev; DevBuf<VtxDir> vtxNormals;
+    // what hit reconstruction decodes from a vertex normal, stored once (zr_hit_tables.h; the instance records' table is part of each AccelSet)
+    DevBuf<VtxDir> vtxNormals;
 #if ZR_HIT_TANGENTS
     DevBuf<VtxDir> vtxTangents;
 #endif
-    // device refit: node indices grouped by tree level (deepest level first) + the offsets of the groups, per-node float bounds, object-to-world matrices
-    DevBuf<uint32_t> levelNodes; std::vector<uint32_t> levelOffsets, hLevelOrder; DevBuf<float> nodeBounds, toWorld; bool refitReady = false;
+    // device refit of `cur`: node indices grouped by tree level (deepest level first) + the offsets of the groups, per-node float bounds, object-to-world matrices
+    DevBuf<uint32_t> levelNodes; std::vector<uint32_t> levelOffsets, hLevelOrder; DevBuf<float> nodeBounds, toWorld;
     // device-side BVH build (zr_tu_bvh.hip): instance masks on the device, scratch buffers kept between builds
     DevBuf<uint8_t> dMask; DeviceBvhScratch bvhScratch; bool deviceBuilt = false;
     bool aliasStale = false;      // zr_scene_invalidate_alias_table_deferred: the old table stays bound until the rebuilt one has been uploaded
@@ -663,13 +678,26 @@ static int SceneWaitUsers(zr_scene* s, hipStream_t st)
     if (s->hasUpdate && s->updated && s->updatedOn != st) HIP_TRY(hipStreamWaitEvent(st, s->updated, 0));
     return ZR_OK;
 }
-static int SceneMarkUpdated(zr_scene* s, hipStream_t st)
+static int SceneMarkUpdatedLocked(zr_scene* s, hipStream_t st)      // (the caller holds mtx)
 {
-    std::lock_guard<std::mutex> lock(s->mtx);
     if (!s->updated) HIP_TRY(hipEventCreateWithFlags(&s->updated, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(s->updated, st));
     s->updatedOn = st; s->hasUpdate = true;
     return ZR_OK;
+}
+static int SceneMarkUpdated(zr_scene* s, hipStream_t st) { std::lock_guard<std::mutex> lock(s->mtx); return SceneMarkUpdatedLocked(s, st); }
+// cur <-> prev: the only place the two sets change roles (the caller holds mtx, and has ordered `st` behind the readers of both: SceneWaitUsers)
+static void SceneFlip(zr_scene* s)
+{
+    AccelSet &a = s->cur, &b = s->prev;
+    a.instances.Swap(b.instances); a.instRecs.Swap(b.instRecs); a.nodes.Swap(b.nodes); a.tris.Swap(b.tris); a.meta.Swap(b.meta);
+    std::swap(a.numNodes, b.numNodes); std::swap(a.numTris, b.numTris); s->hasPrev = true;
+}
+// ... and the only place a view takes a set's buffers and counts
+static void SceneBind(SceneView& v, const AccelSet& a)
+{
+    v.instances = a.instances.p; v.instRecs = a.instRecs.p; v.nodes = a.nodes.p; v.tris = a.tris.p; v.triMeta = a.meta.p;
+    v.numNodes = a.numNodes; v.numTris = a.numTris;
 }
 // a render on `st`: behind the last update if that ran on another stream ...
 static int SceneAcquireForRender(const zr_scene* sc, hipStream_t st)
@@ -730,12 +758,7 @@ static SceneView FrameViewPrev(const zr_scene* sc, const zr_frame_constants* cb)
 {
     SceneView v = FrameView(sc, cb);
     std::lock_guard<std::mutex> lock(sc->mtx);
-    if (sc->hasPrev)
-    {
-        v.instances = sc->instancesPrev.p; v.nodes = sc->nodesPrev.p; v.tris = sc->trisPrev.p; v.triMeta = sc->metaPrev.p;
-        v.instRecs = sc->instRecsPrev.p;
-        v.numNodes = sc->numNodesPrev; v.numTris = sc->numTrisPrev;
-    }
+    if (sc->hasPrev) SceneBind(v, sc->prev);
     return v;
 }
 
@@ -1282,59 +1305,52 @@ static void BvhLevels(const std::vector<Bvh4Node>& nodes, std::vector<uint32_t>&
     offsets.push_back((uint32_t)order.size());
 }
 
-// Builds the CURRENT acceleration structure on the device from the scene's current instance buffer + object-to-world matrices (both already
+// node boxes of the current set bottom-up: one k_refit_level launch per tree level (levelNodes / levelOffsets), deepest first
+static void LaunchRefitLevels(zr_scene* s, hipStream_t st)
+{
+    for (size_t l = 0; l + 1 < s->levelOffsets.size(); l++)
+    {
+        const uint32_t first = s->levelOffsets[l], cnt = s->levelOffsets[l + 1] - first;
+        hipLaunchKernelGGL(k_refit_level, dim3((cnt + 63) / 64), dim3(64), 0, st, s->cur.nodes.p, s->levelNodes.p + first, cnt, s->cur.tris.p, s->nodeBounds.p);
+    }
+}
+// Builds the CURRENT acceleration structure on the device from the current set's instance buffer + the object-to-world matrices (both already
 // on the device, or enqueued on `st`): LBVH topology (zr_tu_bvh.hip), then the level-by-level box computation + quantisation of the refit.
-// Host-synchronous (the level structure comes back).  The node / triangle buffers are grown to the build's capacity on first use.
+// Host-synchronous (the level structure comes back).  The node / triangle buffers are grown to the build's capacity on first use.  States the
+// tree's counts in the set; binding the set to `view` is the caller's, once everything else of the update has succeeded too.
 static int DeviceRebuild(zr_scene* s, hipStream_t st)
 {
-    const uint32_t nt = (uint32_t)s->meta.n;
+    AccelSet& a = s->cur;
+    const uint32_t nt = (uint32_t)a.meta.n;
     int r;
-    if (s->nodes.n < nt || s->tris.n < nt || s->nodeBounds.n < 6 * (size_t)nt)
+    if (a.nodes.n < nt || a.tris.n < nt || s->nodeBounds.n < 6 * (size_t)nt)
     {
         HIP_TRY(hipDeviceSynchronize());
-        if (s->nodes.n < nt && (r = s->nodes.Alloc(nt))) return r;
-        if (s->tris.n < nt && (r = s->tris.Alloc(nt))) return r;
+        if (a.nodes.n < nt && (r = a.nodes.Alloc(nt))) return r;
+        if (a.tris.n < nt && (r = a.tris.Alloc(nt))) return r;
         if (s->nodeBounds.n < 6 * (size_t)nt && (r = s->nodeBounds.Alloc(6 * (size_t)nt))) return r;
     }
     if (!s->dMask.p && (r = s->dMask.Upload(s->hMask.data(), s->hMask.size()))) return r;
-    DeviceBvhInputs in; in.numTris = nt; in.meta = s->meta.p; in.instances = s->instances.p; in.toWorld = s->toWorld.p; in.vertices = s->vertices.p;
+    DeviceBvhInputs in; in.numTris = nt; in.meta = a.meta.p; in.instances = a.instances.p; in.toWorld = s->toWorld.p; in.vertices = s->vertices.p;
     in.indices = s->indices.p; in.instanceMask = s->dMask.p;
-    DeviceBvhOutputs out; out.tris = s->tris.p; out.nodes = s->nodes.p; out.nodeCap = (uint32_t)s->nodes.n;
+    DeviceBvhOutputs out; out.tris = a.tris.p; out.nodes = a.nodes.p; out.nodeCap = (uint32_t)a.nodes.n;
     std::string err;
     if (DeviceBuildBvh4(st, s->bvhScratch, in, out, err)) return Fail(ZR_ERR_HIP, "device BVH build: %s", err.c_str());
     if (out.stackNeed + 1 > (uint32_t)kTravStack) return Fail(ZR_ERR_UNSUPPORTED, "device-built BVH has %u levels: needs %u traversal stack entries (limit %d); use the host builder", out.numLevels, out.stackNeed, kTravStack - 1);
     s->hLevelOrder = out.levelOrder; s->levelOffsets = out.levelOffsets;
     if (s->levelNodes.n < s->hLevelOrder.size()) { HIP_TRY(hipStreamSynchronize(st)); if ((r = s->levelNodes.Alloc(nt))) return r; }
     HIP_TRY(hipMemcpyAsync(s->levelNodes.p, s->hLevelOrder.data(), s->hLevelOrder.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    for (size_t l = 0; l + 1 < s->levelOffsets.size(); l++)
-    {
-        const uint32_t first = s->levelOffsets[l], cnt = s->levelOffsets[l + 1] - first;
-        hipLaunchKernelGGL(k_refit_level, dim3((cnt + 63) / 64), dim3(64), 0, st, s->nodes.p, s->levelNodes.p + first, cnt, s->tris.p, s->nodeBounds.p);
-    }
+    LaunchRefitLevels(s, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));          // hLevelOrder is pageable: its copy must have been staged and the kernels' errors seen
-    SceneView& v = s->view;
-    v.nodes = s->nodes.p; v.tris = s->tris.p; v.numNodes = out.numNodes; v.numTris = nt;
+    a.numNodes = out.numNodes; a.numTris = nt;
     if (out.numLevels > s->maxDepth) s->maxDepth = out.numLevels;
     s->deviceBuilt = true;
     return ZR_OK;
 }
 
-// The instance array that has just been written on `st` (an upload, LaunchMoveInstances) gets its table of decoded records on the same stream
-static int SceneFillInstRecs(zr_scene* s, hipStream_t st)
-{
-    HIP_TRY(zr::LaunchFillInstRecs(st, s->instRecs.p, s->instances.p, (uint32_t)s->instances.n));
-    s->view.instRecs = s->instRecs.p;
-    return ZR_OK;
-}
-// instances <-> instancesPrev changed roles: so do their tables (the previous one is allocated on first use)
-static int SceneSwapInstRecs(zr_scene* s, size_t n)
-{
-    int r;
-    if (s->instRecsPrev.n != n && (r = s->instRecsPrev.Alloc(n))) return r;
-    std::swap(s->instRecs.p, s->instRecsPrev.p); std::swap(s->instRecs.n, s->instRecsPrev.n);
-    return ZR_OK;
-}
+// The current instance array has just been written on `st` (an upload, LaunchMoveInstances): its table of decoded records follows on the same stream
+static int SceneFillInstRecs(zr_scene* s, hipStream_t st) { HIP_TRY(zr::LaunchFillInstRecs(st, s->cur.instRecs.p, s->cur.instances.p, (uint32_t)s->cur.instances.n)); return ZR_OK; }
 
 // SceneView::plain: no material of the table is metallic, transmissive, thin-walled or coated (the fields GetMaterialData turns into those lobes, Material.h:268-427)
 static bool MaterialsArePlain(const std::vector<zr_material>& m)
@@ -1343,6 +1359,32 @@ static bool MaterialsArePlain(const std::vector<zr_material>& m)
     for (const zr_material& x : m) if ((x.coat_color_flags & lobes) || ((x.base_color_tex_subsurf_coat_weight >> 24) & 0xffu)) return false;
     return !m.empty();
 }
+// Texture indices of created / updated records raise the per-table maxima that the descriptor-table bounds check of zr_pass_render relies on
+static void RaiseMaxTex(zr_scene* s, int table, uint32_t tex) { if (tex != ZR_INVALID_TEX && (int64_t)tex > s->maxTex[table]) s->maxTex[table] = tex; }
+// How zr_scene_update_instances makes the frame's tree (ZR_SCENE_UPDATE): the refit on the device (unset, "refit", "refit_sah"), a new LBVH on the device
+// ("rebuild"), the host's binned-SAH builder ("rebuild_host").  The two rebuilds are host-synchronous, and the device forms of the update refuse them.
+// "refit_sah" is the refit with the background rebuild on for every scene of the process; for one scene that is a flag (zr_scene_set_background_rebuild)
+enum class UpdateMode { Refit, RebuildDevice, RebuildHost };
+static UpdateMode SceneUpdateMode()
+{
+    const char* e = std::getenv("ZR_SCENE_UPDATE");
+    return !e ? UpdateMode::Refit : !std::strcmp(e, "rebuild") ? UpdateMode::RebuildDevice : !std::strcmp(e, "rebuild_host") ? UpdateMode::RebuildHost : UpdateMode::Refit;
+}
+static bool BackgroundRebuildByDefault() { const char* e = std::getenv("ZR_SCENE_UPDATE"); return e && !std::strcmp(e, "refit_sah"); }
+static int RefuseRebuildMode(const char* fn)
+{
+    const UpdateMode m = SceneUpdateMode();
+    return m == UpdateMode::Refit ? ZR_OK : Fail(ZR_ERR_UNSUPPORTED, "%s: ZR_SCENE_UPDATE=%s is a host-synchronous path; the device form of the update needs the refit (default or refit_sah)",
+        fn, m == UpdateMode::RebuildDevice ? "rebuild" : "rebuild_host");
+}
+// what the host's builder takes: the scene's host copies of the static arrays + the given instance records and matrices
+static zr_scene_desc SceneBuilderDesc(const zr_scene* s, const zr_mesh_instance* instances, uint32_t n, const float* toWorld)
+{
+    zr_scene_desc d; memset(&d, 0, sizeof(d));
+    d.vertices = s->hVertices.data(); d.num_vertices = (uint32_t)s->hVertices.size(); d.indices = s->hIndices.data(); d.num_indices = (uint32_t)s->hIndices.size();
+    d.instances = instances; d.num_instances = n; d.instance_to_world = toWorld; d.instance_mask = s->hMask.data(); d.instance_num_tris = s->hNumTris.data();
+    return d;
+}
 int zr_scene_create(int device, const zr_scene_desc* d, zr_scene** out)
 {
     if (!d || !out) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: null argument");
@@ -1350,7 +1392,7 @@ int zr_scene_create(int device, const zr_scene_desc* d, zr_scene** out)
         return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: incomplete scene description");
     int r = RequireDevice(device);
     if (r) return r;
-    zr_scene* s = new (std::nothrow) zr_scene();
+    std::unique_ptr<zr_scene> s(new (std::nothrow) zr_scene());      // (every early return below frees it)
     if (!s) return Fail(ZR_ERR_OOM, "out of host memory");
     s->device = device;
     // ZR_BVH_BUILD=device: the acceleration structure is built on the GPU (LBVH, zr_tu_bvh.hip) instead of by the host's binned-SAH builder
@@ -1364,56 +1406,46 @@ int zr_scene_create(int device, const zr_scene_desc* d, zr_scene** out)
         bvh.meta.reserve((size_t)totalTris);
         for (uint32_t i = 0; i < d->num_instances; i++) for (uint32_t p = 0; p < d->instance_num_tris[i]; p++) { TriMeta m; m.mesh = i; m.prim = p; bvh.meta.push_back(m); }
     }
-    else
-    {
-        BvhBuilder builder;
-        bvh = builder.Build(*d);
-    }
-    if (bvh.stackNeed + 1 > (uint32_t)kTravStack) { delete s; return Fail(ZR_ERR_UNSUPPORTED, "BVH needs %u traversal stack entries (limit %d)", bvh.stackNeed, kTravStack - 1); }
+    else bvh = BvhBuilder().Build(*d);
+    if (bvh.stackNeed + 1 > (uint32_t)kTravStack) return Fail(ZR_ERR_UNSUPPORTED, "BVH needs %u traversal stack entries (limit %d)", bvh.stackNeed, kTravStack - 1);
     s->maxDepth = bvh.maxDepth;
-#define UP(buf, ptr, cnt) if ((r = s->buf.Upload(ptr, cnt))) { delete s; return r; }
-    UP(vertices, d->vertices, d->num_vertices);
-    UP(indices, d->indices, d->num_indices);
-    UP(instances, d->instances, d->num_instances);
-    UP(materials, d->materials, d->num_materials);
-    UP(emissives, d->emissives, d->num_emissives);
-    UP(nodes, bvh.nodes4.data(), bvh.nodes4.size());
-    UP(tris, bvh.tris.data(), bvh.tris.size());
-    UP(meta, bvh.meta.data(), bvh.meta.size());
-    UP(rho, d->rho_lut, (size_t)d->rho_dim[0] * d->rho_dim[1] * d->rho_dim[2]);
+    AccelSet& a = s->cur;
+    if ((r = s->vertices.Upload(d->vertices, d->num_vertices)) || (r = s->indices.Upload(d->indices, d->num_indices)) ||
+        (r = a.instances.Upload(d->instances, d->num_instances)) || (r = s->materials.Upload(d->materials, d->num_materials)) ||
+        (r = s->emissives.Upload(d->emissives, d->num_emissives)) || (r = a.nodes.Upload(bvh.nodes4.data(), bvh.nodes4.size())) ||
+        (r = a.tris.Upload(bvh.tris.data(), bvh.tris.size())) || (r = a.meta.Upload(bvh.meta.data(), bvh.meta.size())) ||
+        (r = s->rho.Upload(d->rho_lut, (size_t)d->rho_dim[0] * d->rho_dim[1] * d->rho_dim[2]))) return r;
+    a.numNodes = (uint32_t)bvh.nodes4.size(); a.numTris = (uint32_t)bvh.tris.size();
     if (d->num_textures)
     {
-        if (!d->textures || !d->texels) { delete s; return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: num_textures > 0 without textures / texels"); }
+        if (!d->textures || !d->texels) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: num_textures > 0 without textures / texels");
         for (uint32_t i = 0; i < d->num_textures; i++)
         {
             const zr_texture_desc& t = d->textures[i];
             const zr_tex_mip last = zr_tex_mip_of(&t, t.num_mips ? t.num_mips - 1u : 0u);
             const uint64_t end = last.offset + (uint64_t)last.w * last.h * (t.format == ZR_TEX_RG8 ? 2u : 4u);
             if (!t.num_mips || !t.width || !t.height || t.format > ZR_TEX_RG8 || (t.offset & 3u) || end > d->texel_bytes)
-            { delete s; return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: texture %u is malformed or lies outside the texel blob", i); }
+                return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: texture %u is malformed or lies outside the texel blob", i);
         }
-        UP(texDescs, d->textures, d->num_textures);
-        UP(texels, d->texels, d->texel_bytes);
+        if ((r = s->texDescs.Upload(d->textures, d->num_textures)) || (r = s->texels.Upload(d->texels, d->texel_bytes))) return r;
     }
-    UP(srgb, zr_srgb_to_linear_table, 256);
-#undef UP
+    if ((r = s->srgb.Upload(zr_srgb_to_linear_table, 256))) return r;
     // the decoded tables of zr_hit_tables.h, behind the uploads on the null stream (the synchronize below covers them)
-    if ((r = s->instRecs.Alloc(d->num_instances)) || (r = s->vtxNormals.Alloc(d->num_vertices))) { delete s; return r; }
-    if ((r = SceneFillInstRecs(s, nullptr))) { delete s; return r; }
+    if ((r = a.instRecs.Alloc(d->num_instances)) || (r = s->vtxNormals.Alloc(d->num_vertices)) || (r = SceneFillInstRecs(s.get(), nullptr))) return r;
     { hipError_t e = zr::LaunchFillVtxNormals(nullptr, s->vtxNormals.p, s->vertices.p, d->num_vertices, false);
-      if (e != hipSuccess) { delete s; return Fail(ZR_ERR_HIP, "k_fill_vtx_normals failed: %s", hipGetErrorString(e)); } }
+      if (e != hipSuccess) return Fail(ZR_ERR_HIP, "k_fill_vtx_normals failed: %s", hipGetErrorString(e)); }
     s->view.vtxNormals = s->vtxNormals.p;
 #if ZR_HIT_TANGENTS
-    if ((r = s->vtxTangents.Alloc(d->num_vertices))) { delete s; return r; }
+    if ((r = s->vtxTangents.Alloc(d->num_vertices))) return r;
     { hipError_t e = zr::LaunchFillVtxNormals(nullptr, s->vtxTangents.p, s->vertices.p, d->num_vertices, true);
-      if (e != hipSuccess) { delete s; return Fail(ZR_ERR_HIP, "k_fill_vtx_normals failed: %s", hipGetErrorString(e)); } }
+      if (e != hipSuccess) return Fail(ZR_ERR_HIP, "k_fill_vtx_normals failed: %s", hipGetErrorString(e)); }
     s->view.vtxTangents = s->vtxTangents.p;
 #endif
     SceneView& v = s->view;
-    v.vertices = s->vertices.p; v.indices = s->indices.p; v.instances = s->instances.p; v.materials = s->materials.p;
-    v.emissives = s->emissives.p; v.alias = nullptr; v.sampleSets = nullptr; v.sampleSetSize = 0; v.nodes = s->nodes.p; v.tris = s->tris.p; v.triMeta = s->meta.p;
+    v.vertices = s->vertices.p; v.indices = s->indices.p; v.materials = s->materials.p;
+    v.emissives = s->emissives.p; v.alias = nullptr; v.sampleSets = nullptr; v.sampleSetSize = 0;
     v.rho.data = s->rho.p; v.rho.dx = d->rho_dim[0]; v.rho.dy = d->rho_dim[1]; v.rho.dz = d->rho_dim[2];
-    v.numEmissives = d->num_emissives; v.numNodes = (uint32_t)bvh.nodes4.size(); v.numTris = (uint32_t)bvh.tris.size();
+    v.numEmissives = d->num_emissives;
     s->hMaterials.assign(d->materials, d->materials + d->num_materials);
     s->plainMaterials = MaterialsArePlain(s->hMaterials) && d->num_textures == 0;
     v.tex.descs = s->texDescs.p; v.tex.texels = s->texels.p; v.tex.srgb = s->srgb.p; v.tex.count = d->num_textures;
@@ -1424,37 +1456,28 @@ int zr_scene_create(int device, const zr_scene_desc* d, zr_scene** out)
         const zr_material& m = d->materials[i];
         const uint32_t t[4] = { m.base_color_tex_subsurf_coat_weight & 0xffffu, m.normal_tex_tr_depth & 0xffffu,
                                 m.mr_tex_spec_roughness_coat_roughness & 0xffffu, m.emissive_tex_alpha_cutoff_coat_ior & 0xffffu };
-        for (int k = 0; k < 4; k++) if (t[k] != ZR_INVALID_TEX && (int64_t)t[k] > s->maxTex[k]) s->maxTex[k] = t[k];
+        for (int k = 0; k < 4; k++) RaiseMaxTex(s.get(), k, t[k]);
     }
-    for (uint32_t i = 0; i < d->num_instances; i++)
-        if (d->instances[i].base_color_tex != ZR_INVALID_TEX && (int64_t)d->instances[i].base_color_tex > s->maxTex[0]) s->maxTex[0] = d->instances[i].base_color_tex;
-    for (uint32_t i = 0; i < d->num_emissives; i++)
-    { const uint32_t t = d->emissives[i].packed_b & 0xffffu; if (t != ZR_INVALID_TEX && (int64_t)t > s->maxTex[3]) s->maxTex[3] = t; }
-    { const char* e = getenv("ZR_SCENE_UPDATE"); s->bg.enabled = e && !strcmp(e, "refit_sah"); }      // (zr_scene_set_background_rebuild for every scene of the process)
+    for (uint32_t i = 0; i < d->num_instances; i++) RaiseMaxTex(s.get(), 0, d->instances[i].base_color_tex);
+    for (uint32_t i = 0; i < d->num_emissives; i++) RaiseMaxTex(s.get(), 3, d->emissives[i].packed_b & 0xffffu);
+    s->bg.enabled = BackgroundRebuildByDefault();
     s->hVertices.assign(d->vertices, d->vertices + d->num_vertices); s->hIndices.assign(d->indices, d->indices + d->num_indices);
     s->hMask.assign(d->instance_mask, d->instance_mask + d->num_instances); s->hNumTris.assign(d->instance_num_tris, d->instance_num_tris + d->num_instances);
     s->hToWorld.assign(d->instance_to_world, d->instance_to_world + 12 * (size_t)d->num_instances); s->movedEver.assign(d->num_instances, 0);
     s->hInstances.assign(d->instances, d->instances + d->num_instances);
     BvhLevels(bvh.nodes4, s->hLevelOrder, s->levelOffsets);
-    if (!s->hLevelOrder.empty() && (r = s->levelNodes.Upload(s->hLevelOrder.data(), s->hLevelOrder.size()))) { delete s; return r; }
+    if (!s->hLevelOrder.empty() && (r = s->levelNodes.Upload(s->hLevelOrder.data(), s->hLevelOrder.size()))) return r;
     if (deviceBuild)
     {
-        if ((r = s->toWorld.Upload(d->instance_to_world, 12 * (size_t)d->num_instances)) || (r = DeviceRebuild(s, nullptr))) { delete s; return r; }
+        if ((r = s->toWorld.Upload(d->instance_to_world, 12 * (size_t)d->num_instances)) || (r = DeviceRebuild(s.get(), nullptr))) return r;
         s->toWorldDev = true;
     }
+    SceneBind(v, a);
     // uploads from pageable memory return once staged; renders on non-blocking streams must not start before the DMA has landed
-    { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) { delete s; return Fail(ZR_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e)); } }
-    *out = s;
+    { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) return Fail(ZR_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e)); }
+    *out = s.release();
     return ZR_OK;
 }
-
-// TLAS / instance-buffer update of a frame (RtAccelerationStructure.cpp:382-506, 708-787): the current instance buffer and acceleration
-// structure become the previous ones, the new ones follow the new object-to-world matrices.  Default: a **refit on the device** -- the BVH4 built
-// at zr_scene_create keeps its topology, k_refit_tris re-transforms the triangles and k_refit_level recomputes + re-quantises the node boxes
-// level by level (what a D3D12 TLAS / BLAS update with ALLOW_UPDATE does); ZR_SCENE_UPDATE=rebuild selects a full binned-SAH rebuild on the
-// host instead (better trees after large motion, three orders of magnitude slower).  Results do not depend on the tree (zr_intersect.h).
-// Texture indices of updated records raise the per-table maxima the descriptor-table bounds check of zr_pass_render relies on
-static void RaiseMaxTex(zr_scene* s, int table, uint32_t tex) { if (tex != ZR_INVALID_TEX && (int64_t)tex > s->maxTex[table]) s->maxTex[table] = tex; }
 
 int zr_scene_update_emissives_async(zr_scene* s, void* stream, const zr_emissive_triangle* triangles, uint32_t first, uint32_t count)
 {
@@ -1494,21 +1517,11 @@ int zr_scene_update_materials_async(zr_scene* s, void* stream, const zr_material
     if ((r = StageCommit(t, st))) return r;
     return SceneMarkUpdated(s, st);
 }
-// the original host-synchronous entry points: the update on the null stream, then wait for it (errors of the copies / refit kernels surface here)
-int zr_scene_update_emissives(zr_scene* s, const zr_emissive_triangle* triangles, uint32_t first, uint32_t count)
-{
-    int r = zr_scene_update_emissives_async(s, nullptr, triangles, first, count);
-    if (r || !count) return r;
-    HIP_TRY(hipDeviceSynchronize());
-    return ZR_OK;
-}
-int zr_scene_update_materials(zr_scene* s, const zr_material* materials, uint32_t first, uint32_t count)
-{
-    int r = zr_scene_update_materials_async(s, nullptr, materials, first, count);
-    if (r || !count) return r;
-    HIP_TRY(hipDeviceSynchronize());
-    return ZR_OK;
-}
+// the original host-synchronous entry points: the update on the null stream (r: what its _async form returned), then wait for it -- errors of the
+// copies / refit kernels surface here.  (An empty range enqueues nothing and waits for nothing.)
+static int ThenWait(int r) { if (r) return r; HIP_TRY(hipDeviceSynchronize()); return ZR_OK; }
+int zr_scene_update_emissives(zr_scene* s, const zr_emissive_triangle* t, uint32_t first, uint32_t count) { const int r = zr_scene_update_emissives_async(s, nullptr, t, first, count); return count ? ThenWait(r) : r; }
+int zr_scene_update_materials(zr_scene* s, const zr_material* m, uint32_t first, uint32_t count) { const int r = zr_scene_update_materials_async(s, nullptr, m, first, count); return count ? ThenWait(r) : r; }
 int zr_scene_invalidate_alias_table(zr_scene* s)
 {
     if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_invalidate_alias_table: null argument");
@@ -1528,10 +1541,26 @@ int zr_scene_invalidate_alias_table_deferred(zr_scene* s)
     if (s->view.alias) s->aliasStale = true;      // without a table there is nothing to keep: the next PRELIGHTING render builds one (first-frame path)
     return ZR_OK;
 }
-// What a frame's update consists of when the caller hands over matrices only (zr_scene_move_instances_async): the moved instances, their new
-// matrices, and the range of light triangles they carry
-// (animT: the list is the scene's own, written on the device by zr::LaunchAnimate for that time -- idx / xf are null, nothing goes through the staging ring)
-struct MovedList { const uint32_t* idx; const float* xf; uint32_t n, emFirst, emEnd; const float* animT = nullptr; };
+// One frame's instance update as the refit takes it, in one of three forms.  HostRecords: every record and matrix as the caller stated them, which the
+// scene's host copies (hInstances / hToWorld) hold by then.  MovedMatrices: "instance idx[j] now has world matrix xf[j]" (zr_scene_move_instances_async),
+// the records follow on the device.  Animated: the moved list is the scene's own, written on the device by zr::LaunchAnimate for time t -- nothing of it
+// goes through the staging ring.  Both device forms carry the list's length and the range of light triangles its instances carry
+enum class UpdateForm { HostRecords, MovedMatrices, Animated };
+struct FrameUpdate { UpdateForm form; const uint32_t* idx; const float* xf; uint32_t nMoved, emFirst, emEnd; float t; };
+// the range of light triangles the listed instances carry ([0, 0): none); a light that moves needs its object-space records first
+static int SceneDirtyLights(const zr_scene* s, const char* fn, const uint32_t* idx, uint32_t count, uint32_t* first, uint32_t* end)
+{
+    *first = 0xffffffffu; *end = 0u;
+    for (uint32_t j = 0; j < count; j++)
+    {
+        const uint32_t i = idx[j], b = s->hInstances[i].base_emissive_tri_offset;
+        if (b == 0xffffffffu || !s->emissives.n) continue;
+        if (!s->objectEmissives.p) return Fail(ZR_ERR_NOT_INITIALIZED, "%s: instance %u carries lights: call zr_scene_set_object_emissives first", fn, i);
+        *first = std::min(*first, b); *end = std::max(*end, b + s->hNumTris[i]);
+    }
+    if (*end <= *first) *first = *end = 0;
+    return ZR_OK;
+}
 // the host's matrices after zr_scene_animate: brought up to date for the time of the last one, where they are read
 static void SceneAnimSyncHost(zr_scene* s)
 {
@@ -1544,16 +1573,256 @@ static void SceneAnimSyncHost(zr_scene* s)
         std::memcpy(s->hToWorld.data() + 12 * (size_t)A.instIdx[j], world.data() + 12 * (size_t)A.instNode[j], 12 * sizeof(float));
     A.hostStale = false;
 }
-static int SceneRefitUpdate(zr_scene* s, hipStream_t st, const zr_mesh_instance* instances, const float* instance_to_world, uint32_t n, const MovedList* moved);
 
+// ---- the steps of SceneRefitUpdate (below), in its order
+// The frame's sizes and its layout in the staging slot, by form.  HostRecords: [n records | n matrices].  MovedMatrices: [seed | nMoved matrices |
+// nMoved indices].  Animated: [seed].  seed = every matrix as the host has it, once -- while the device copy of the matrices is not current.
+// (An animated frame without a seed stages nothing and takes no slot; every other form takes one as it always did, an empty moved list included.)
+struct RefitFrame { uint32_t n; size_t instBytes, xfBytes, seedBytes, listBytes, stageBytes; bool takesSlot; };
+static RefitFrame RefitFrameOf(const zr_scene* s, const FrameUpdate& u)
+{
+    RefitFrame F;
+    F.n = (uint32_t)s->cur.instances.n; F.instBytes = (size_t)F.n * sizeof(zr_mesh_instance); F.xfBytes = 12 * (size_t)F.n * sizeof(float);
+    const bool deviceForm = u.form != UpdateForm::HostRecords;
+    F.seedBytes = deviceForm && (!s->toWorldDev || s->toWorld.n != 12 * (size_t)F.n) ? F.xfBytes : 0;
+    F.listBytes = u.form == UpdateForm::MovedMatrices ? 13 * (size_t)u.nMoved * sizeof(uint32_t) : 0;
+    F.stageBytes = deviceForm ? F.seedBytes + F.listBytes : F.instBytes + F.xfBytes;
+    F.takesSlot = F.stageBytes || u.form != UpdateForm::Animated;
+    return F;
+}
+// background SAH rebuild: is a finished tree waiting to be installed by this update?  Its thread is joined either way; a tree that cannot be used
+// (the scene changed shape under it, or it is too deep for the traversal stack) is dropped
+static bool BgJoinFinished(zr_scene* s)
+{
+    zr_scene::Background& B = s->bg;
+    if (!B.enabled || B.state.load(std::memory_order_acquire) != 2) return false;
+    if (B.th.joinable()) B.th.join();
+    const bool usable = B.packed && B.inst.size() == s->cur.instances.n && B.numTris == s->cur.numTris && B.stackNeed + 1 <= (uint32_t)kTravStack;
+    if (!usable) B.state.store(0);
+    return usable;
+}
+// ... and with it on, both sets must be able to hold any topology over these triangles (a BVH4 over nt triangles has < nt nodes): grown once,
+// with their contents, behind a device-wide wait
+static int BgGrowBuffers(zr_scene* s)
+{
+    AccelSet &a = s->cur, &b = s->prev;
+    const size_t cap = a.numTris;
+    if (a.nodes.n >= cap && !(s->refitReady && b.nodes.n < cap) && s->levelNodes.n >= cap && s->nodeBounds.n >= 6 * cap && s->bgDev.n >= 5 * cap && s->dMask.p) return ZR_OK;
+    int r;
+    HIP_TRY(hipDeviceSynchronize());
+    if (!s->dMask.p && (r = s->dMask.Upload(s->hMask.data(), s->hMask.size()))) return r;
+    if (s->bgDev.n < 5 * cap && (r = s->bgDev.Alloc(5 * cap))) return r;      // 4 child words per node (< cap nodes) + one word per triangle slot
+    std::lock_guard<std::mutex> lock(s->mtx);
+    if ((r = a.nodes.Grow(cap, a.numNodes)) || (b.nodes.p && (r = b.nodes.Grow(cap, s->refitReady || s->hasPrev ? b.numNodes : 0))) ||
+        (r = s->levelNodes.Grow(cap, s->hLevelOrder.size())) || (r = s->nodeBounds.Grow(6 * cap, 0))) return r;
+    SceneBind(s->view, a);
+    return ZR_OK;
+}
+// the frame's input into a slot of the staging ring (RefitFrame: the layout)
+static int RefitStage(zr_scene* s, const FrameUpdate& u, const RefitFrame& F, zr_scene::StageSlot** out)
+{
+    *out = nullptr;
+    if (u.form == UpdateForm::Animated && F.seedBytes) SceneAnimSyncHost(s);      // (the seed takes hToWorld)
+    if (!F.takesSlot) return ZR_OK;
+    if (int r = StageAcquire(s, F.stageBytes, out)) return r;
+    char* h = (char*)(*out)->host;
+    if (u.form == UpdateForm::HostRecords) { memcpy(h, s->hInstances.data(), F.instBytes); memcpy(h + F.instBytes, s->hToWorld.data(), F.xfBytes); return ZR_OK; }
+    if (F.seedBytes) memcpy(h, s->hToWorld.data(), F.xfBytes);
+    const size_t matrixBytes = 12 * (size_t)u.nMoved * sizeof(float);
+    if (u.form == UpdateForm::MovedMatrices) { memcpy(h + F.seedBytes, u.xf, matrixBytes); memcpy(h + F.seedBytes + matrixBytes, u.idx, (size_t)u.nMoved * sizeof(uint32_t)); }
+    return ZR_OK;
+}
+// Both sets must hold the same tree before one is refit in place of the other: `prev` becomes a copy of `cur` on `st` (once, and again after a rebuild or an
+// install).  Also sizes what only the refit needs: node bounds, device matrices.  The conditions decide when a hipMalloc / hipFree makes the device wait
+static int SceneDuplicate(zr_scene* s, hipStream_t st)
+{
+    AccelSet &a = s->cur, &b = s->prev;
+    const size_t n = a.instances.n, nn = a.numNodes, nt = a.numTris, nodeCap = s->bg.enabled ? std::max(nn, nt) : nn;
+    int r;
+    if ((b.instances.n != n && (r = b.instances.Alloc(n))) || (nodeCap && b.nodes.n < nodeCap && (r = b.nodes.Alloc(nodeCap))) ||
+        (b.tris.n != nt && (r = b.tris.Alloc(nt))) || (b.meta.n != a.meta.n && (r = b.meta.Alloc(a.meta.n))) ||
+        (nodeCap && s->nodeBounds.n < 6 * nodeCap && (r = s->nodeBounds.Alloc(6 * nodeCap))) || (s->toWorld.n != 12 * n && (r = s->toWorld.Alloc(12 * n)))) return r;
+    HIP_TRY(hipMemcpyAsync(b.instances.p, a.instances.p, n * sizeof(zr_mesh_instance), hipMemcpyDeviceToDevice, st));
+    if (b.instRecs.n != n && (r = b.instRecs.Alloc(n))) return r;
+    HIP_TRY(hipMemcpyAsync(b.instRecs.p, a.instRecs.p, n * sizeof(InstRec), hipMemcpyDeviceToDevice, st));
+    if (nn) HIP_TRY(hipMemcpyAsync(b.nodes.p, a.nodes.p, nn * sizeof(Bvh4Node), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b.tris.p, a.tris.p, nt * sizeof(BvhTri), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b.meta.p, a.meta.p, a.meta.n * sizeof(TriMeta), hipMemcpyDeviceToDevice, st));
+    b.numNodes = a.numNodes; b.numTris = a.numTris;
+    s->refitReady = true;
+    return ZR_OK;
+}
+// the frame's records and matrices into the set that has just become current: uploaded, or computed on the device from the previous set's records
+// and the moved list (zr_tu_scene_update.hip; the animation writes its list first, zr_tu_anim.hip); then their decoded table
+static int RefitWriteRecords(zr_scene* s, hipStream_t st, const FrameUpdate& u, const RefitFrame& F, const zr_scene::StageSlot* t)
+{
+    const char* h = t ? (const char*)t->host : nullptr;
+    if (u.form == UpdateForm::HostRecords)
+    {
+        HIP_TRY(hipMemcpyAsync(s->cur.instances.p, h, F.instBytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s->toWorld.p, h + F.instBytes, F.xfBytes, hipMemcpyHostToDevice, st));
+    }
+    else
+    {
+        if (F.seedBytes) HIP_TRY(hipMemcpyAsync(s->toWorld.p, h, F.xfBytes, hipMemcpyHostToDevice, st));
+        const uint32_t* movedList = s->movedDev.p;
+        if (u.form == UpdateForm::Animated)
+        {   // behind SceneWaitUsers: ordered after the previous update, whose kernels read the list this writes
+            zr_scene::Anim& A = *s->anim;
+            HIP_TRY(zr::LaunchAnimate(st, u.t, A.dNodes.p, A.dKeys.p, A.dAnimated.p, A.nAnimated, A.dLevelNodes.p, A.levelOffsets.data(),
+                (uint32_t)A.levelOffsets.size() - 1, A.dLocal.p, A.dWorld.p, A.dInstNode.p, u.nMoved, A.dMoved.p));
+            movedList = A.dMoved.p;
+        }
+        else if (u.nMoved) HIP_TRY(hipMemcpyAsync(s->movedDev.p, h + F.seedBytes, F.listBytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(zr::LaunchMoveInstances(st, s->cur.instances.p, s->prev.instances.p, s->toWorld.p, F.n, s->movedSlot.p, movedList, u.nMoved,
+            s->emissives.p, s->objectEmissives.p, s->emissiveOwner.p, u.emFirst, u.emEnd));
+    }
+    s->toWorldDev = true;
+    return SceneFillInstRecs(s, st);
+}
+// The background build's topology goes into the set that has just become current (last frame's "previous": nobody needs it any more); its
+// triangles and boxes are then computed for THIS update's transforms by the refit kernels, like any other frame's
+static int BgInstall(zr_scene* s, hipStream_t st)
+{
+    zr_scene::Background& B = s->bg;
+    AccelSet& a = s->cur;
+    const size_t devWords = 4 * (size_t)B.numNodes + B.numTris;
+    if (!B.pkgCopied) HIP_TRY(hipEventCreateWithFlags(&B.pkgCopied, hipEventDisableTiming));
+    HIP_TRY(hipMemcpyAsync(s->bgDev.p, B.pkg, devWords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->levelNodes.p, B.pkg + devWords, (size_t)B.numNodes * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(B.pkgCopied, st)); B.pkgInFlight = true;      // the next build's thread waits for it before it overwrites the package
+    hipLaunchKernelGGL(k_install_topology, dim3((uint32_t)((std::max<size_t>(B.numNodes, B.numTris) + 255) / 256)), dim3(256), 0, st,
+        a.nodes.p, s->bgDev.p, B.numNodes, a.tris.p, s->bgDev.p + 4 * (size_t)B.numNodes, B.numTris, a.meta.p, s->dMask.p);
+    s->hLevelOrder.assign(B.pkg + devWords, B.pkg + devWords + B.numNodes); s->levelOffsets = B.levelOffsets;
+    a.numNodes = B.numNodes; s->deviceBuilt = false;
+    if (B.maxDepth > s->maxDepth) s->maxDepth = B.maxDepth;
+    s->refitReady = false;      // the two sets hold different topologies now: the next update duplicates this one first
+    B.installed++; B.refitsSince = 0; B.state.store(0, std::memory_order_release);
+    return ZR_OK;
+}
+// everything is enqueued: the host's view of the matrices follows.  HostRecords: zr_scene_update_instances_async did it from the caller's arrays up
+// front.  Animated: lazily (SceneAnimSyncHost), from the time alone
+static void RefitFollowOnHost(zr_scene* s, const FrameUpdate& u)
+{
+    if (u.form == UpdateForm::Animated)
+    {
+        std::lock_guard<std::mutex> lock(s->animMtx);
+        zr_scene::Anim& A = *s->anim;
+        if (!A.hasT || std::memcmp(&A.lastT, &u.t, sizeof(float))) s->bg.movedSinceBuild = true;
+        A.lastT = u.t; A.hasT = true; A.hostStale = true;
+    }
+    else if (u.form == UpdateForm::MovedMatrices)
+        for (uint32_t j = 0; j < u.nMoved; j++)
+        {
+            float* M = s->hToWorld.data() + 12 * (size_t)u.idx[j];
+            if (std::memcmp(M, u.xf + 12 * (size_t)j, 12 * sizeof(float))) { s->movedEver[u.idx[j]] = 1; s->bg.movedSinceBuild = true; }
+            std::memcpy(M, u.xf + 12 * (size_t)j, 12 * sizeof(float));
+        }
+}
+// The background builder's thread: the host's binned-SAH build over the snapshot (bg.inst / bg.xf / bg.own), then the topology packed into pinned
+// memory -- this thread's time, not the installing update's (zr_scene::Background: the package's layout)
+static void BgBuildThread(zr_scene* s)
+{
+    zr_scene::Background& Q = s->bg;
+    const auto t0 = std::chrono::steady_clock::now();
+    BuiltBvh bvh = BvhBuilder().Build(SceneBuilderDesc(s, Q.inst.data(), (uint32_t)Q.inst.size(), Q.xf.data()), Q.own.empty() ? nullptr : Q.own.data());
+    std::vector<uint32_t> levelOrder;
+    BvhLevels(bvh.nodes4, levelOrder, Q.levelOffsets);
+    const auto t1 = std::chrono::steady_clock::now();
+    const size_t nn = bvh.nodes4.size(), nt = bvh.tris.size(), words = 5 * nn + nt;
+    Q.packed = false;
+    if (hipSetDevice(s->device) == hipSuccess)
+    {
+        if (Q.pkgInFlight) { (void)hipEventSynchronize(Q.pkgCopied); Q.pkgInFlight = false; }      // the previous package's copies have left the buffer
+        if (Q.pkgCap < words)
+        {
+            if (Q.pkg) { (void)hipHostFree(Q.pkg); Q.pkg = nullptr; Q.pkgCap = 0; }
+            void* h = nullptr;
+            if (hipHostMalloc(&h, (words + words / 8) * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess) { Q.pkg = (uint32_t*)h; Q.pkgCap = words + words / 8; }
+            else (void)hipGetLastError();
+        }
+        if (Q.pkg)
+        {
+            uint32_t* w = Q.pkg;
+            for (size_t i = 0; i < nn; i++) for (int c = 0; c < 4; c++) *w++ = bvh.nodes4[i].child[c];
+            for (size_t i = 0; i < nt; i++) *w++ = bvh.tris[i].gidx;
+            std::memcpy(w, levelOrder.data(), nn * sizeof(uint32_t));
+            Q.packed = true;
+        }
+    }
+    Q.numNodes = (uint32_t)nn; Q.numTris = (uint32_t)nt; Q.stackNeed = bvh.stackNeed; Q.maxDepth = bvh.maxDepth;
+    Q.buildMs = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    Q.packMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    if (ZR_EXP_ENV("ZR_BVH_TIMING"))
+        std::fprintf(stderr, "[zr_scene] background tree: %zu nodes over %zu triangles, build %.1f ms, package (%.1f MB pinned) %.1f ms\n", nn, nt, Q.buildMs, words * 4e-6, Q.packMs);
+    Q.state.store(2, std::memory_order_release);
+}
+// ... started on this update's transforms when none is in flight and something has moved since the last one was (host copies: hInstances, and
+// hToWorld, which holds this update's matrices in every form)
+static void BgStartBuild(zr_scene* s)
+{
+    zr_scene::Background& B = s->bg;
+    if (!B.enabled || B.state.load(std::memory_order_acquire) != 0 || B.refitsSince < 1 || !B.movedSinceBuild || s->cur.meta.n <= BvhBuilder::kTinyScene) return;
+    B.movedSinceBuild = false;
+    if (B.th.joinable()) B.th.join();
+    SceneAnimSyncHost(s);
+    B.inst = s->hInstances; B.xf = s->hToWorld;
+    { const char* e = ZR_EXP_ENV("ZR_BVH_GROUP"); if (e && !std::strcmp(e, "0")) B.own.clear(); else B.own = s->movedEver; }
+    B.state.store(1, std::memory_order_release); B.started++;
+    B.th = std::thread(BgBuildThread, s);
+}
+
+// ---- refit on the device, stream-ordered: nothing below waits on the host (the staging ring aside, when the host runs far ahead, and the one-time growth
+// of the buffers under the background rebuild).  The shared tail of the three forms of the update.  What is enqueued on `st` or waited for, in order:
+//    1 StageAcquire (waits when the host is > 4 updates ahead)   6 SceneDuplicate's copies (first refit; after a rebuild / install)   11 the install's copies + k_install_topology
+//    2 the memcpy into the slot                                  7 SceneFlip                                                         12 k_refit_tris
+//    3 SceneWaitUsers (`st` behind readers on other streams)     8 the uploads, or LaunchAnimate + LaunchMoveInstances               13 k_refit_level, one launch per level
+//    4 lock mtx (held to the end: a render sees all or nothing)  9 LaunchFillInstRecs                                                14 the `updated` event
+//    5 the moved-slot memset (a scene's first device-form frame) 10 StageCommit                                                      15 the next background build's thread starts
+static int SceneRefitUpdate(zr_scene* s, hipStream_t st, const FrameUpdate& u)
+{
+    int r;
+    const bool install = BgJoinFinished(s);
+    if (s->bg.enabled && (r = BgGrowBuffers(s))) return r;
+    const RefitFrame F = RefitFrameOf(s, u);
+    zr_scene::StageSlot* t;
+    if ((r = RefitStage(s, u, F, &t))) return r;                                                    // 1, 2
+    if ((r = SceneWaitUsers(s, st))) return r;                                                      // 3
+    std::lock_guard<std::mutex> lock(s->mtx);                                                       // 4
+    if (u.form != UpdateForm::HostRecords && (s->movedSlot.n != F.n || s->movedDev.n != 13 * (size_t)F.n))
+    {   // once per scene: each instance's position in the frame's moved list, and the list; the slots start out as "did not move", in stream order
+        if ((r = s->movedSlot.Alloc(F.n)) || (r = s->movedDev.Alloc(13 * (size_t)F.n))) return r;
+        HIP_TRY(hipMemsetAsync(s->movedSlot.p, 0xff, (size_t)F.n * sizeof(uint32_t), st));         // 5
+    }
+    if (!s->refitReady && (r = SceneDuplicate(s, st))) return r;                                    // 6
+    SceneFlip(s);                                                                                   // 7: both sets hold the same tree, counts included
+    if ((r = RefitWriteRecords(s, st, u, F, t))) return r;                                          // 8, 9
+    if (t && (r = StageCommit(t, st))) return r;                                                    // 10
+    if (install) { if ((r = BgInstall(s, st))) return r; }                                          // 11
+    else if (s->bg.enabled) s->bg.refitsSince++;
+    const AccelSet& a = s->cur;
+    hipLaunchKernelGGL(k_refit_tris, dim3((a.numTris + 255) / 256), dim3(256), 0, st, a.tris.p, a.numTris, a.meta.p, a.instances.p, s->toWorld.p, s->vertices.p, s->indices.p);   // 12
+    LaunchRefitLevels(s, st);                                                                       // 13
+    HIP_TRY(hipGetLastError());
+    RefitFollowOnHost(s, u);
+    SceneBind(s->view, s->cur);
+    if ((r = SceneMarkUpdatedLocked(s, st))) return r;                                              // 14
+    BgStartBuild(s);                                                                                // 15
+    return ZR_OK;
+}
+
+// TLAS / instance-buffer update of a frame (RtAccelerationStructure.cpp:382-506, 708-787): the current instance buffer and acceleration
+// structure become the previous ones, the new ones follow the new object-to-world matrices.  Default: a **refit on the device** -- the BVH4 built
+// at zr_scene_create keeps its topology, k_refit_tris re-transforms the triangles and k_refit_level recomputes + re-quantises the node boxes
+// level by level (what a D3D12 TLAS / BLAS update with ALLOW_UPDATE does); ZR_SCENE_UPDATE=rebuild / rebuild_host select a new tree per frame
+// instead (UpdateMode; better trees after large motion, host-synchronous).  Results do not depend on the tree (zr_intersect.h).
 int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_instance* instances, const float* instance_to_world, uint32_t n)
 {
     if (!s || !instances || !instance_to_world) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_update_instances: null argument");
-    if (n != s->instances.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_update_instances: %u instances, the scene has %zu", n, s->instances.n);
+    if (n != s->cur.instances.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_update_instances: %u instances, the scene has %zu", n, s->cur.instances.n);
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    const char* modeEnv = std::getenv("ZR_SCENE_UPDATE");
-    bool rebuild = modeEnv && !std::strcmp(modeEnv, "rebuild");
+    const UpdateMode mode = SceneUpdateMode();
     int r;
     SceneAnimSyncHost(s);
     for (uint32_t i = 0; i < n; i++) RaiseMaxTex(s, 0, instances[i].base_color_tex);
@@ -1561,289 +1830,61 @@ int zr_scene_update_instances_async(zr_scene* s, void* stream, const zr_mesh_ins
         if (std::memcmp(s->hToWorld.data() + 12 * (size_t)i, instance_to_world + 12 * (size_t)i, 12 * sizeof(float))) { s->movedEver[i] = 1; s->bg.movedSinceBuild = true; }
     std::memcpy(s->hToWorld.data(), instance_to_world, 12 * (size_t)n * sizeof(float));
     s->hInstances.assign(instances, instances + n);
-    const bool rebuildHost = modeEnv && !std::strcmp(modeEnv, "rebuild_host");
-    if (rebuild && s->meta.n > BvhBuilder::kTinyScene)
+    if (mode == UpdateMode::RebuildDevice && s->cur.meta.n > BvhBuilder::kTinyScene)
     {
         // ---- a NEW tree on the device (ZR_SCENE_UPDATE=rebuild): LBVH over the moved triangles, ~1 ms for the 380k-triangle atrium against 192 ms
         // for the host's binned-SAH rebuild (ZR_SCENE_UPDATE=rebuild_host); what the reference's per-frame TLAS rebuild is (RtAccelerationStructure.cpp:708-789)
-        const size_t nt = s->meta.n;
+        const size_t nt = s->cur.meta.n;
         HIP_TRY(hipDeviceSynchronize());           // buffers change roles and may be reallocated below: a host-synchronous path
         std::lock_guard<std::mutex> lock(s->mtx);
-        // everything the failure path below must put back: a build that fails (allocation, a tree deeper than the traversal stack) must not leave
-        // view.nodes / view.tris pointing at buffers that were just demoted to "previous" next to the NEW instance records
-        const SceneView viewBefore = s->view;
-        const uint32_t numNodesPrevBefore = s->numNodesPrev, numTrisPrevBefore = s->numTrisPrev;
-        if ((r = (s->instancesPrev.n == n ? ZR_OK : s->instancesPrev.Alloc(n))) || (s->nodesPrev.n < nt && (r = s->nodesPrev.Alloc(nt))) ||
-            (s->trisPrev.n < nt && (r = s->trisPrev.Alloc(nt))) || (s->metaPrev.n != s->meta.n && (r = s->metaPrev.Alloc(s->meta.n))) ||
+        AccelSet& b = s->prev;                     // the build's target, sized here, current from the flip on
+        if ((b.instances.n != n && (r = b.instances.Alloc(n))) || (b.nodes.n < nt && (r = b.nodes.Alloc(nt))) ||
+            (b.tris.n < nt && (r = b.tris.Alloc(nt))) || (b.meta.n != nt && (r = b.meta.Alloc(nt))) ||
             (s->toWorld.n != 12 * (size_t)n && (r = s->toWorld.Alloc(12 * (size_t)n)))) return r;
-        if (!s->hasPrev && !s->refitReady) HIP_TRY(hipMemcpy(s->metaPrev.p, s->meta.p, s->meta.n * sizeof(TriMeta), hipMemcpyDeviceToDevice));
-        if ((r = SceneSwapInstRecs(s, n))) return r;
-        std::swap(s->instances.p, s->instancesPrev.p); std::swap(s->instances.n, s->instancesPrev.n);
-        std::swap(s->nodes.p, s->nodesPrev.p); std::swap(s->nodes.n, s->nodesPrev.n);
-        std::swap(s->tris.p, s->trisPrev.p); std::swap(s->tris.n, s->trisPrev.n);
-        std::swap(s->meta.p, s->metaPrev.p); std::swap(s->meta.n, s->metaPrev.n);
-        s->numNodesPrev = s->view.numNodes; s->numTrisPrev = s->view.numTris; s->hasPrev = true;
-        HIP_TRY(hipMemcpy(s->instances.p, instances, (size_t)n * sizeof(zr_mesh_instance), hipMemcpyHostToDevice));
+        if (!s->hasPrev && !s->refitReady) HIP_TRY(hipMemcpy(b.meta.p, s->cur.meta.p, nt * sizeof(TriMeta), hipMemcpyDeviceToDevice));
+        if (b.instRecs.n != n && (r = b.instRecs.Alloc(n))) return r;
+        SceneFlip(s);
+        HIP_TRY(hipMemcpy(s->cur.instances.p, instances, (size_t)n * sizeof(zr_mesh_instance), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(s->toWorld.p, instance_to_world, 12 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
         s->toWorldDev = true;
-        s->view.instances = s->instances.p; s->view.triMeta = s->meta.p;
         // (the new records' table first, behind the blocking upload above and on the build's stream: a failure of either takes the roll-back below)
         if ((r = SceneFillInstRecs(s, st)) || (r = DeviceRebuild(s, st)))
         {
-            // roll back: the buffers take their old roles again and the scene renders as before the call.  The "previous" set was used as the build
-            // target, so there is no previous structure any more (hasPrev = false: the CtT / temporal passes bind the current one, as in frame 1).
+            // roll back: a build that fails (allocation, a tree deeper than the traversal stack) must leave the scene rendering as before the call.  A second flip
+            // gives the sets their old roles and counts again (DeviceRebuild states a tree's counts only once it has succeeded); `view` has not been touched.  The
+            // "previous" set was the build's target, so there is no previous structure any more (the CtT / temporal passes bind the current one, as in frame 1).
             (void)hipDeviceSynchronize();
-            std::swap(s->instances.p, s->instancesPrev.p); std::swap(s->instances.n, s->instancesPrev.n);
-            std::swap(s->instRecs.p, s->instRecsPrev.p); std::swap(s->instRecs.n, s->instRecsPrev.n);
-            std::swap(s->nodes.p, s->nodesPrev.p); std::swap(s->nodes.n, s->nodesPrev.n);
-            std::swap(s->tris.p, s->trisPrev.p); std::swap(s->tris.n, s->trisPrev.n);
-            std::swap(s->meta.p, s->metaPrev.p); std::swap(s->meta.n, s->metaPrev.n);
-            s->view = viewBefore; s->numNodesPrev = numNodesPrevBefore; s->numTrisPrev = numTrisPrevBefore; s->hasPrev = false;
+            SceneFlip(s); s->hasPrev = false;
             return r;
         }
-        s->refitReady = false;      // the two buffer sets no longer share a topology
+        SceneBind(s->view, s->cur);
+        s->refitReady = false;      // the two sets no longer share a topology
         return ZR_OK;
     }
-    if (rebuild || rebuildHost)
+    if (mode != UpdateMode::Refit)
     {
-        zr_scene_desc d; memset(&d, 0, sizeof(d));
-        d.vertices = s->hVertices.data(); d.num_vertices = (uint32_t)s->hVertices.size(); d.indices = s->hIndices.data(); d.num_indices = (uint32_t)s->hIndices.size();
-        d.instances = instances; d.num_instances = n; d.instance_to_world = instance_to_world; d.instance_mask = s->hMask.data(); d.instance_num_tris = s->hNumTris.data();
-        BvhBuilder builder;
-        BuiltBvh bvh = builder.Build(d);
+        BuiltBvh bvh = BvhBuilder().Build(SceneBuilderDesc(s, instances, n, instance_to_world));
         if (bvh.stackNeed + 1 > (uint32_t)kTravStack) return Fail(ZR_ERR_UNSUPPORTED, "BVH needs %u traversal stack entries (limit %d)", bvh.stackNeed, kTravStack - 1);
-        HIP_TRY(hipDeviceSynchronize());           // the host rebuild reallocates: a host-synchronous path by construction (ZR_SCENE_UPDATE=rebuild)
+        HIP_TRY(hipDeviceSynchronize());           // the host rebuild reallocates: a host-synchronous path by construction (ZR_SCENE_UPDATE=rebuild_host)
         std::lock_guard<std::mutex> lock(s->mtx);
-        if ((r = SceneSwapInstRecs(s, n))) return r;
-        std::swap(s->instances.p, s->instancesPrev.p); std::swap(s->instances.n, s->instancesPrev.n);
-        std::swap(s->nodes.p, s->nodesPrev.p); std::swap(s->nodes.n, s->nodesPrev.n);
-        std::swap(s->tris.p, s->trisPrev.p); std::swap(s->tris.n, s->trisPrev.n);
-        std::swap(s->meta.p, s->metaPrev.p); std::swap(s->meta.n, s->metaPrev.n);
-        s->numNodesPrev = s->view.numNodes; s->numTrisPrev = s->view.numTris; s->hasPrev = true;
-        if ((r = s->instances.Upload(instances, n)) || (r = s->nodes.Upload(bvh.nodes4.data(), bvh.nodes4.size())) ||
-            (r = s->tris.Upload(bvh.tris.data(), bvh.tris.size())) || (r = s->meta.Upload(bvh.meta.data(), bvh.meta.size()))) return r;
-        SceneView& v = s->view;
-        v.instances = s->instances.p; v.nodes = s->nodes.p; v.tris = s->tris.p; v.triMeta = s->meta.p;
-        v.numNodes = (uint32_t)bvh.nodes4.size(); v.numTris = (uint32_t)bvh.tris.size();
-        // (SceneSwapInstRecs sized both tables.  Like the Uploads above, a failing fill returns with the roles already changed: this debug path -- ZR_SCENE_UPDATE=rebuild_host --
-        // has no roll-back, and the scene is not usable after an error from it)
+        if (s->prev.instRecs.n != n && (r = s->prev.instRecs.Alloc(n))) return r;
+        SceneFlip(s);
+        // (a failing upload or fill returns with the roles already changed: this debug path has no roll-back, and the scene is not usable after an error from it)
+        AccelSet& a = s->cur;
+        if ((r = a.instances.Upload(instances, n)) || (r = a.nodes.Upload(bvh.nodes4.data(), bvh.nodes4.size())) ||
+            (r = a.tris.Upload(bvh.tris.data(), bvh.tris.size())) || (r = a.meta.Upload(bvh.meta.data(), bvh.meta.size()))) return r;
+        a.numNodes = (uint32_t)bvh.nodes4.size(); a.numTris = (uint32_t)bvh.tris.size();
+        SceneBind(s->view, a);
         if ((r = SceneFillInstRecs(s, nullptr))) return r;
         HIP_TRY(hipStreamSynchronize(nullptr));      // host-synchronous like the uploads: renders on any stream may follow
         if (bvh.maxDepth > s->maxDepth) s->maxDepth = bvh.maxDepth;
         BvhLevels(bvh.nodes4, s->hLevelOrder, s->levelOffsets);
         if ((r = s->levelNodes.Upload(s->hLevelOrder.data(), s->hLevelOrder.size()))) return r;
-        s->refitReady = false;      // the two buffer sets no longer share a topology
+        s->refitReady = false;      // the two sets no longer share a topology
         s->toWorldDev = false;      // ... and the device matrices were not touched
         return ZR_OK;
     }
-    return SceneRefitUpdate(s, st, instances, instance_to_world, n, nullptr);
-}
-// ---- refit on the device, stream-ordered: nothing below waits on the host (the staging ring aside, when the host runs far ahead).  The shared tail of
-// the two forms of the update.  Host form (moved == null): the caller's records and matrices are uploaded.  Device form: `instances` /
-// `instance_to_world` are the scene's own host copies (hInstances / hToWorld; hToWorld takes the frame's matrices once everything is enqueued), only the moved list is uploaded
-// and the records are computed on the device from the buffer that becomes previous (zr_tu_scene_update.hip)
-static int SceneRefitUpdate(zr_scene* s, hipStream_t st, const zr_mesh_instance* instances, const float* instance_to_world, uint32_t n, const MovedList* moved)
-{
-    int r;
-    // background SAH rebuild: is a finished tree waiting to be installed by this update?
-    const bool install = s->bg.enabled && s->bg.state.load(std::memory_order_acquire) == 2 && s->bg.packed && s->bg.inst.size() == n &&
-                         s->bg.numTris == s->view.numTris && s->bg.stackNeed + 1 <= (uint32_t)kTravStack;
-    if (s->bg.enabled && s->bg.state.load(std::memory_order_acquire) == 2 && !install)
-    {   // a tree that cannot be used (the scene changed shape under it, or it is too deep for the traversal stack): drop it
-        if (s->bg.th.joinable()) s->bg.th.join();
-        s->bg.state.store(0);
-    }
-    if (install && s->bg.th.joinable()) s->bg.th.join();
-    if (s->bg.enabled)
-    {   // both buffer sets must be able to hold any topology over these triangles (a BVH4 over nt triangles has < nt nodes): grown once, with their contents
-        const size_t cap = s->view.numTris;
-        if (s->nodes.n < cap || (s->refitReady && s->nodesPrev.n < cap) || s->levelNodes.n < cap || s->nodeBounds.n < 6 * cap || s->bgDev.n < 5 * cap || !s->dMask.p)
-        {
-            HIP_TRY(hipDeviceSynchronize());
-            if (!s->dMask.p && (r = s->dMask.Upload(s->hMask.data(), s->hMask.size()))) return r;
-            if (s->bgDev.n < 5 * cap && (r = s->bgDev.Alloc(5 * cap))) return r;      // 4 child words per node (< cap nodes) + one word per triangle slot
-            auto grow = [&](auto& buf, size_t count, size_t keep) -> int {
-                if (buf.n >= count) return ZR_OK;
-                std::remove_reference_t<decltype(buf)> nb; int rr = nb.Alloc(count); if (rr) return rr;
-                if (keep && buf.p) HIP_TRY(hipMemcpy(nb.p, buf.p, keep * sizeof(*buf.p), hipMemcpyDeviceToDevice));
-                std::swap(buf.p, nb.p); std::swap(buf.n, nb.n);
-                return ZR_OK; };
-            std::lock_guard<std::mutex> lockGrow(s->mtx);
-            if ((r = grow(s->nodes, cap, s->view.numNodes)) || (s->nodesPrev.p && (r = grow(s->nodesPrev, cap, s->refitReady || s->hasPrev ? s->numNodesPrev : 0))) ||
-                (r = grow(s->levelNodes, cap, s->hLevelOrder.size())) || (r = grow(s->nodeBounds, 6 * cap, 0))) return r;
-            s->view.nodes = s->nodes.p;
-        }
-    }
-    const size_t nn = s->view.numNodes, nt = s->view.numTris;
-    const size_t instBytes = (size_t)n * sizeof(zr_mesh_instance), xfBytes = 12 * (size_t)n * sizeof(float);
-    zr_scene::StageSlot* t = nullptr;
-    const bool animated = moved && moved->animT;
-    if (animated && (!s->toWorldDev || s->toWorld.n != 12 * (size_t)n)) SceneAnimSyncHost(s);      // (the seed below takes hToWorld)
-    // device form: [every matrix as it was, once -- while the device copy of the matrices is not current | the moved matrices | the moved indices]
-    const bool seedXf = moved && (!s->toWorldDev || s->toWorld.n != 12 * (size_t)n);
-    const size_t movedBytes = moved && !animated ? 13 * (size_t)moved->n * sizeof(uint32_t) : 0, seedBytes = seedXf ? xfBytes : 0;
-    const size_t stageBytes = moved ? seedBytes + movedBytes : instBytes + xfBytes;
-    // (an animated frame after the first stages nothing and takes no slot; every other form takes one as it always did, an empty moved list included)
-    if ((stageBytes || !animated) && (r = StageAcquire(s, stageBytes, &t))) return r;
-    if (!moved) { memcpy(t->host, instances, instBytes); memcpy((char*)t->host + instBytes, instance_to_world, xfBytes); }
-    else if (animated) { if (seedXf) memcpy(t->host, s->hToWorld.data(), xfBytes); }
-    else
-    {
-        if (seedXf) memcpy(t->host, s->hToWorld.data(), xfBytes);
-        memcpy((char*)t->host + seedBytes, moved->xf, 12 * (size_t)moved->n * sizeof(float));
-        memcpy((char*)t->host + seedBytes + 12 * (size_t)moved->n * sizeof(float), moved->idx, (size_t)moved->n * sizeof(uint32_t));
-    }
-    if ((r = SceneWaitUsers(s, st))) return r;         // renders of earlier frames on other streams still read the buffers that change roles below
-    std::lock_guard<std::mutex> lock(s->mtx);
-    if (moved && (s->movedSlot.n != n || s->movedDev.n != 13 * (size_t)n))
-    {   // once per scene; the slots start out as "did not move", in stream order
-        if ((r = s->movedSlot.Alloc(n)) || (r = s->movedDev.Alloc(13 * (size_t)n))) return r;
-        HIP_TRY(hipMemsetAsync(s->movedSlot.p, 0xff, (size_t)n * sizeof(uint32_t), st));
-    }
-    if (!s->refitReady)
-    {
-        // both buffer sets must hold the same tree: duplicate the current one (once, or after a rebuild)
-        const size_t nodeCap = s->bg.enabled ? std::max(nn, nt) : nn;
-        if ((s->instancesPrev.n != n && (r = s->instancesPrev.Alloc(n))) || (nodeCap && s->nodesPrev.n < nodeCap && (r = s->nodesPrev.Alloc(nodeCap))) ||
-            (s->trisPrev.n != nt && (r = s->trisPrev.Alloc(nt))) || (s->metaPrev.n != s->meta.n && (r = s->metaPrev.Alloc(s->meta.n))) ||
-            (nodeCap && s->nodeBounds.n < 6 * nodeCap && (r = s->nodeBounds.Alloc(6 * nodeCap))) || (s->toWorld.n != 12 * (size_t)n && (r = s->toWorld.Alloc(12 * (size_t)n)))) return r;
-        HIP_TRY(hipMemcpyAsync(s->instancesPrev.p, s->instances.p, instBytes, hipMemcpyDeviceToDevice, st));
-        if (s->instRecsPrev.n != n && (r = s->instRecsPrev.Alloc(n))) return r;
-        HIP_TRY(hipMemcpyAsync(s->instRecsPrev.p, s->instRecs.p, (size_t)n * sizeof(InstRec), hipMemcpyDeviceToDevice, st));
-        if (nn) HIP_TRY(hipMemcpyAsync(s->nodesPrev.p, s->nodes.p, nn * sizeof(Bvh4Node), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(s->trisPrev.p, s->tris.p, nt * sizeof(BvhTri), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(s->metaPrev.p, s->meta.p, s->meta.n * sizeof(TriMeta), hipMemcpyDeviceToDevice, st));
-        s->refitReady = true;
-    }
-    std::swap(s->instances.p, s->instancesPrev.p); std::swap(s->nodes.p, s->nodesPrev.p); std::swap(s->tris.p, s->trisPrev.p); std::swap(s->meta.p, s->metaPrev.p);
-    std::swap(s->instRecs.p, s->instRecsPrev.p);
-    s->numNodesPrev = (uint32_t)nn; s->numTrisPrev = (uint32_t)nt; s->hasPrev = true;
-    if (!moved)
-    {
-        HIP_TRY(hipMemcpyAsync(s->instances.p, t->host, instBytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(s->toWorld.p, (char*)t->host + instBytes, xfBytes, hipMemcpyHostToDevice, st));
-    }
-    else
-    {
-        if (seedXf) HIP_TRY(hipMemcpyAsync(s->toWorld.p, t->host, xfBytes, hipMemcpyHostToDevice, st));
-        const uint32_t* movedList = s->movedDev.p;
-        if (animated)
-        {   // behind SceneWaitUsers: ordered after the previous update, whose kernels read the list this writes
-            zr_scene::Anim& A = *s->anim;
-            HIP_TRY(zr::LaunchAnimate(st, *moved->animT, A.dNodes.p, A.dKeys.p, A.dAnimated.p, A.nAnimated, A.dLevelNodes.p, A.levelOffsets.data(),
-                (uint32_t)A.levelOffsets.size() - 1, A.dLocal.p, A.dWorld.p, A.dInstNode.p, moved->n, A.dMoved.p));
-            movedList = A.dMoved.p;
-        }
-        else if (moved->n) HIP_TRY(hipMemcpyAsync(s->movedDev.p, (char*)t->host + seedBytes, movedBytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(zr::LaunchMoveInstances(st, s->instances.p, s->instancesPrev.p, s->toWorld.p, n, s->movedSlot.p, movedList, moved->n,
-            s->emissives.p, s->objectEmissives.p, s->emissiveOwner.p, moved->emFirst, moved->emEnd));
-    }
-    s->toWorldDev = true;
-    if ((r = SceneFillInstRecs(s, st))) return r;      // the records just written, decoded for this frame's hits
-    if (t && (r = StageCommit(t, st))) return r;
-    uint32_t numNodesNow = (uint32_t)nn;
-    if (install)
-    {
-        // the background build's topology goes into the set that has just become current (last frame's "previous": nobody needs it any more);
-        // its triangles and boxes are then computed for THIS update's transforms by the refit kernels below, like any other frame's
-        zr_scene::Background& B = s->bg;
-        const size_t devWords = 4 * (size_t)B.numNodes + B.numTris;
-        if (!B.pkgCopied) HIP_TRY(hipEventCreateWithFlags(&B.pkgCopied, hipEventDisableTiming));
-        HIP_TRY(hipMemcpyAsync(s->bgDev.p, B.pkg, devWords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(s->levelNodes.p, B.pkg + devWords, (size_t)B.numNodes * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(B.pkgCopied, st)); B.pkgInFlight = true;      // the next build's thread waits for it before it overwrites the package
-        hipLaunchKernelGGL(k_install_topology, dim3((uint32_t)((std::max<size_t>(B.numNodes, B.numTris) + 255) / 256)), dim3(256), 0, st,
-            s->nodes.p, s->bgDev.p, B.numNodes, s->tris.p, s->bgDev.p + 4 * (size_t)B.numNodes, B.numTris, s->meta.p, s->dMask.p);
-        s->hLevelOrder.assign(B.pkg + devWords, B.pkg + devWords + B.numNodes); s->levelOffsets = B.levelOffsets;
-        numNodesNow = B.numNodes;
-        if (B.maxDepth > s->maxDepth) s->maxDepth = B.maxDepth;
-        s->refitReady = false;      // the two sets hold different topologies now: the next update duplicates this one first
-        s->deviceBuilt = false;
-        B.installed++; B.refitsSince = 0;
-        B.state.store(0, std::memory_order_release);
-    }
-    else if (s->bg.enabled) s->bg.refitsSince++;
-    hipLaunchKernelGGL(k_refit_tris, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, st, s->tris.p, (uint32_t)nt, s->meta.p, s->instances.p, s->toWorld.p, s->vertices.p, s->indices.p);
-    for (size_t l = 0; l + 1 < s->levelOffsets.size(); l++)
-    {
-        const uint32_t first = s->levelOffsets[l], cnt = s->levelOffsets[l + 1] - first;
-        hipLaunchKernelGGL(k_refit_level, dim3((cnt + 63) / 64), dim3(64), 0, st, s->nodes.p, s->levelNodes.p + first, cnt, s->tris.p, s->nodeBounds.p);
-    }
-    HIP_TRY(hipGetLastError());
-    if (animated)
-    {   // everything is enqueued: the host's view follows lazily (SceneAnimSyncHost), from the time alone
-        std::lock_guard<std::mutex> lockAnim(s->animMtx);
-        zr_scene::Anim& A = *s->anim;
-        if (!A.hasT || std::memcmp(&A.lastT, moved->animT, sizeof(float))) s->bg.movedSinceBuild = true;
-        A.lastT = *moved->animT; A.hasT = true; A.hostStale = true;
-    }
-    else if (moved)
-    {   // everything is enqueued: the host's view of the matrices follows (what zr_scene_update_instances_async does from the caller's array up front)
-        for (uint32_t j = 0; j < moved->n; j++)
-        {
-            float* M = s->hToWorld.data() + 12 * (size_t)moved->idx[j];
-            if (std::memcmp(M, moved->xf + 12 * (size_t)j, 12 * sizeof(float))) { s->movedEver[moved->idx[j]] = 1; s->bg.movedSinceBuild = true; }
-            std::memcpy(M, moved->xf + 12 * (size_t)j, 12 * sizeof(float));
-        }
-    }
-    SceneView& v = s->view;
-    v.instances = s->instances.p; v.nodes = s->nodes.p; v.tris = s->tris.p; v.triMeta = s->meta.p; v.numNodes = numNodesNow;
-    if (!s->updated) HIP_TRY(hipEventCreateWithFlags(&s->updated, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(s->updated, st));
-    s->updatedOn = st; s->hasUpdate = true;
-    if (s->bg.enabled && s->bg.state.load(std::memory_order_acquire) == 0 && s->bg.refitsSince >= 1 && s->bg.movedSinceBuild && s->meta.n > BvhBuilder::kTinyScene)
-    {
-        // start the next build on these transforms (host copies: the caller's arrays are only valid during the call)
-        zr_scene::Background& B = s->bg;
-        B.movedSinceBuild = false;
-        if (B.th.joinable()) B.th.join();
-        SceneAnimSyncHost(s);
-        B.inst.assign(instances, instances + n); B.xf.assign(s->hToWorld.begin(), s->hToWorld.end());      // (hToWorld: this update's matrices in either form)
-        { const char* e = ZR_EXP_ENV("ZR_BVH_GROUP"); if (e && !std::strcmp(e, "0")) B.own.clear(); else B.own = s->movedEver; }
-        B.state.store(1, std::memory_order_release); B.started++;
-        zr_scene* sp = s;
-        B.th = std::thread([sp] {
-            zr_scene::Background& Q = sp->bg;
-            const auto t0 = std::chrono::steady_clock::now();
-            zr_scene_desc d; memset(&d, 0, sizeof(d));
-            d.vertices = sp->hVertices.data(); d.num_vertices = (uint32_t)sp->hVertices.size(); d.indices = sp->hIndices.data(); d.num_indices = (uint32_t)sp->hIndices.size();
-            d.instances = Q.inst.data(); d.num_instances = (uint32_t)Q.inst.size(); d.instance_to_world = Q.xf.data(); d.instance_mask = sp->hMask.data(); d.instance_num_tris = sp->hNumTris.data();
-            BvhBuilder builder;
-            BuiltBvh bvh = builder.Build(d, Q.own.empty() ? nullptr : Q.own.data());
-            std::vector<uint32_t> levelOrder;
-            BvhLevels(bvh.nodes4, levelOrder, Q.levelOffsets);
-            const auto t1 = std::chrono::steady_clock::now();
-            // pack the topology into pinned memory (this thread's time, not the installing update's)
-            const size_t nn = bvh.nodes4.size(), nt = bvh.tris.size(), words = 5 * nn + nt;
-            Q.packed = false;
-            if (hipSetDevice(sp->device) == hipSuccess)
-            {
-                if (Q.pkgInFlight) { (void)hipEventSynchronize(Q.pkgCopied); Q.pkgInFlight = false; }      // the previous package's copies have left the buffer
-                if (Q.pkgCap < words)
-                {
-                    if (Q.pkg) { (void)hipHostFree(Q.pkg); Q.pkg = nullptr; Q.pkgCap = 0; }
-                    void* h = nullptr;
-                    if (hipHostMalloc(&h, (words + words / 8) * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess) { Q.pkg = (uint32_t*)h; Q.pkgCap = words + words / 8; }
-                    else (void)hipGetLastError();
-                }
-                if (Q.pkg)
-                {
-                    uint32_t* w = Q.pkg;
-                    for (size_t i = 0; i < nn; i++) for (int c = 0; c < 4; c++) *w++ = bvh.nodes4[i].child[c];
-                    for (size_t i = 0; i < nt; i++) *w++ = bvh.tris[i].gidx;
-                    std::memcpy(w, levelOrder.data(), nn * sizeof(uint32_t));
-                    Q.packed = true;
-                }
-            }
-            Q.numNodes = (uint32_t)nn; Q.numTris = (uint32_t)nt; Q.stackNeed = bvh.stackNeed; Q.maxDepth = bvh.maxDepth;
-            Q.buildMs = std::chrono::duration<double, std::milli>(t1 - t0).count();
-            Q.packMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-            if (ZR_EXP_ENV("ZR_BVH_TIMING"))
-                std::fprintf(stderr, "[zr_scene] background tree: %zu nodes over %zu triangles, build %.1f ms, package (%.1f MB pinned) %.1f ms\n", nn, nt, Q.buildMs, words * 4e-6, Q.packMs);
-            Q.state.store(2, std::memory_order_release);
-        });
-    }
-    return ZR_OK;
+    return SceneRefitUpdate(s, st, FrameUpdate{UpdateForm::HostRecords, nullptr, nullptr, 0, 0, 0, 0.0f});
 }
 // A tree built for where the instances are NOW, in the background, swapped in by a later zr_scene_update_instances(_async) (see zr_scene::Background).
 int zr_scene_set_background_rebuild(zr_scene* s, int enable)
@@ -1861,14 +1902,7 @@ int zr_scene_background_rebuild_stats(zr_scene* s, uint64_t* started, uint64_t* 
     if (building) *building = s->bg.state.load(std::memory_order_acquire);
     return ZR_OK;
 }
-// host-synchronous form: the update on the null stream, then wait for the copies and the refit kernels (their errors surface here)
-int zr_scene_update_instances(zr_scene* s, const zr_mesh_instance* instances, const float* instance_to_world, uint32_t n)
-{
-    int r = zr_scene_update_instances_async(s, nullptr, instances, instance_to_world, n);
-    if (r) return r;
-    HIP_TRY(hipDeviceSynchronize());
-    return ZR_OK;
-}
+int zr_scene_update_instances(zr_scene* s, const zr_mesh_instance* instances, const float* to_world, uint32_t n) { return ThenWait(zr_scene_update_instances_async(s, nullptr, instances, to_world, n)); }
 
 // ---- the device form of the frame's update: the caller says "instance i now has world matrix M", the records follow on the stream
 int zr_scene_set_object_emissives(zr_scene* s, const zr_emissive_triangle* object_space, uint32_t n)
@@ -1899,29 +1933,21 @@ int zr_scene_move_instances_async(zr_scene* s, void* stream, const uint32_t* ins
 {
     if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_move_instances: null scene");
     if (n_moved && (!instance_idx || !world_3x4)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_move_instances: null argument with %u moved instances", n_moved);
-    const char* modeEnv = std::getenv("ZR_SCENE_UPDATE");
-    if (modeEnv && (!std::strcmp(modeEnv, "rebuild") || !std::strcmp(modeEnv, "rebuild_host")))
-        return Fail(ZR_ERR_UNSUPPORTED, "zr_scene_move_instances: ZR_SCENE_UPDATE=%s is a host-synchronous path; the device form of the update needs the refit (default or refit_sah)", modeEnv);
-    const uint32_t n = (uint32_t)s->instances.n;
-    MovedList moved{instance_idx, world_3x4, n_moved, 0xffffffffu, 0u};
+    if (int r = RefuseRebuildMode("zr_scene_move_instances")) return r;
+    const uint32_t n = (uint32_t)s->cur.instances.n;
+    FrameUpdate u{UpdateForm::MovedMatrices, instance_idx, world_3x4, n_moved, 0, 0, 0.0f};
+    std::vector<uint8_t> listed(n, 0);      // (the list as a whole first, then what its instances carry)
+    for (uint32_t j = 0; j < n_moved; j++)
     {
-        std::vector<uint8_t> listed(n, 0);
-        for (uint32_t j = 0; j < n_moved; j++)
-        {
-            const uint32_t i = instance_idx[j];
-            if (i >= n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_move_instances: instance %u (entry %u of the list), the scene has %u", i, j, n);
-            if (listed[i]) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_move_instances: instance %u is listed twice", i);
-            listed[i] = 1;
-            const uint32_t b = s->hInstances[i].base_emissive_tri_offset;
-            if (b == 0xffffffffu || !s->emissives.n) continue;
-            if (!s->objectEmissives.p) return Fail(ZR_ERR_NOT_INITIALIZED, "zr_scene_move_instances: instance %u carries lights: call zr_scene_set_object_emissives first", i);
-            moved.emFirst = std::min(moved.emFirst, b); moved.emEnd = std::max(moved.emEnd, b + s->hNumTris[i]);
-        }
+        const uint32_t i = instance_idx[j];
+        if (i >= n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_move_instances: instance %u (entry %u of the list), the scene has %u", i, j, n);
+        if (listed[i]) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_move_instances: instance %u is listed twice", i);
+        listed[i] = 1;
     }
-    if (moved.emEnd <= moved.emFirst) moved.emFirst = moved.emEnd = 0;
+    if (int r = SceneDirtyLights(s, "zr_scene_move_instances", instance_idx, n_moved, &u.emFirst, &u.emEnd)) return r;
     HIP_TRY(hipSetDevice(s->device));
     SceneAnimSyncHost(s);      // (a frame moved by hand between animated ones: the host's matrices are compared and replaced per moved instance)
-    return SceneRefitUpdate(s, (hipStream_t)stream, s->hInstances.data(), s->hToWorld.data(), n, &moved);
+    return SceneRefitUpdate(s, (hipStream_t)stream, u);
 }
 // ---- keyframe animation: the tables once (zr_scene_set_animation), then one float per frame (zr_scene_animate_async)
 int zr_scene_set_animation(zr_scene* s, const zr_anim_desc* d)
@@ -1936,20 +1962,12 @@ int zr_scene_set_animation(zr_scene* s, const zr_anim_desc* d)
         s->anim.reset();
         return ZR_OK;
     }
-    const uint32_t n = (uint32_t)s->instances.n;
+    const uint32_t n = (uint32_t)s->cur.instances.n;
     std::vector<uint32_t> level(d->num_nodes);
     char msg[256];
     if (zran::ValidateAnimation(*d, n, level.data(), msg, sizeof(msg))) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_animation: %s", msg);
     std::unique_ptr<zr_scene::Anim> A(new zr_scene::Anim());
-    A->emFirst = 0xffffffffu; A->emEnd = 0;
-    for (uint32_t j = 0; j < d->num_instances; j++)
-    {
-        const uint32_t i = d->instance_idx[j], b = s->hInstances[i].base_emissive_tri_offset;
-        if (b == 0xffffffffu || !s->emissives.n) continue;
-        if (!s->objectEmissives.p) return Fail(ZR_ERR_NOT_INITIALIZED, "zr_scene_set_animation: instance %u carries lights: call zr_scene_set_object_emissives first", i);
-        A->emFirst = std::min(A->emFirst, b); A->emEnd = std::max(A->emEnd, b + s->hNumTris[i]);
-    }
-    if (A->emEnd <= A->emFirst) A->emFirst = A->emEnd = 0;
+    if (int r = SceneDirtyLights(s, "zr_scene_set_animation", d->instance_idx, d->num_instances, &A->emFirst, &A->emEnd)) return r;
     A->nodes.assign(d->nodes, d->nodes + d->num_nodes); A->keys.assign(d->keys, d->keys + d->num_keys);
     A->instIdx.assign(d->instance_idx, d->instance_idx + d->num_instances); A->instNode.assign(d->instance_node, d->instance_node + d->num_instances);
     A->desc.nodes = A->nodes.data(); A->desc.num_nodes = d->num_nodes; A->desc.keys = A->keys.data(); A->desc.num_keys = d->num_keys;
@@ -1988,37 +2006,22 @@ int zr_scene_animate_async(zr_scene* s, void* stream, float t)
 {
     if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_animate: null scene");
     if (!s->anim) return Fail(ZR_ERR_NOT_INITIALIZED, "zr_scene_animate: no animation set (zr_scene_set_animation)");
-    const char* modeEnv = std::getenv("ZR_SCENE_UPDATE");
-    if (modeEnv && (!std::strcmp(modeEnv, "rebuild") || !std::strcmp(modeEnv, "rebuild_host")))
-        return Fail(ZR_ERR_UNSUPPORTED, "zr_scene_animate: ZR_SCENE_UPDATE=%s is a host-synchronous path; the device form of the update needs the refit (default or refit_sah)", modeEnv);
-    MovedList moved{nullptr, nullptr, s->anim->desc.num_instances, s->anim->emFirst, s->anim->emEnd, &t};
+    if (int r = RefuseRebuildMode("zr_scene_animate")) return r;
     HIP_TRY(hipSetDevice(s->device));
-    return SceneRefitUpdate(s, (hipStream_t)stream, s->hInstances.data(), s->hToWorld.data(), (uint32_t)s->instances.n, &moved);
+    return SceneRefitUpdate(s, (hipStream_t)stream, FrameUpdate{UpdateForm::Animated, nullptr, nullptr, s->anim->desc.num_instances, s->anim->emFirst, s->anim->emEnd, t});
 }
-int zr_scene_animate(zr_scene* s, float t)
-{
-    int r = zr_scene_animate_async(s, nullptr, t);
-    if (r) return r;
-    HIP_TRY(hipDeviceSynchronize());
-    return ZR_OK;
-}
-int zr_scene_move_instances(zr_scene* s, const uint32_t* instance_idx, const float* world_3x4, uint32_t n_moved)
-{
-    int r = zr_scene_move_instances_async(s, nullptr, instance_idx, world_3x4, n_moved);
-    if (r) return r;
-    HIP_TRY(hipDeviceSynchronize());
-    return ZR_OK;
-}
+int zr_scene_animate(zr_scene* s, float t) { return ThenWait(zr_scene_animate_async(s, nullptr, t)); }
+int zr_scene_move_instances(zr_scene* s, const uint32_t* idx, const float* world_3x4, uint32_t n_moved) { return ThenWait(zr_scene_move_instances_async(s, nullptr, idx, world_3x4, n_moved)); }
 int zr_scene_get_instances(const zr_scene* s, void* stream, int which, zr_mesh_instance* out, float* to_world_or_null, uint32_t n)
 {
     if (!s || !out) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_instances: null argument");
     if (which != 0 && which != 1) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_instances: which = %d (0 current, 1 previous)", which);
-    if (n != s->instances.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_instances: %u instances, the scene has %zu", n, s->instances.n);
+    if (n != s->cur.instances.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_instances: %u instances, the scene has %zu", n, s->cur.instances.n);
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     SceneAnimSyncHost(const_cast<zr_scene*>(s));
     const zr_mesh_instance* src; bool xfDev;
-    { std::lock_guard<std::mutex> lock(s->mtx); src = which == 1 && s->hasPrev ? s->instancesPrev.p : s->instances.p; xfDev = s->toWorldDev && s->toWorld.n == 12 * (size_t)n; }
+    { std::lock_guard<std::mutex> lock(s->mtx); src = (which == 1 && s->hasPrev ? s->prev : s->cur).instances.p; xfDev = s->toWorldDev && s->toWorld.n == 12 * (size_t)n; }
     HIP_TRY(hipMemcpy(out, src, (size_t)n * sizeof(zr_mesh_instance), hipMemcpyDeviceToHost));
     if (to_world_or_null)
     {   // the matrices live on the device from the first refit update on; before that the scene has only the host's
@@ -2122,13 +2125,7 @@ int zr_scene_set_alias_table_async(zr_scene* s, void* stream, const zr_alias_ent
     }
     return SceneMarkUpdated(s, st);
 }
-int zr_scene_set_alias_table(zr_scene* s, const zr_alias_entry* e, uint32_t n)
-{
-    int r = zr_scene_set_alias_table_async(s, nullptr, e, n);
-    if (r) return r;
-    HIP_TRY(hipDeviceSynchronize());
-    return ZR_OK;
-}
+int zr_scene_set_alias_table(zr_scene* s, const zr_alias_entry* e, uint32_t n) { return ThenWait(zr_scene_set_alias_table_async(s, nullptr, e, n)); }
 
 int zr_scene_get_alias_table(const zr_scene* s, zr_alias_entry* out, uint32_t n)
 {
@@ -3266,7 +3263,7 @@ static int RenderPickOutlines(zr_pass* p, hipStream_t s, const zr_frame_constant
             m.m[4 * i + j] = ((a + b) + c) + d;
         }
         TimerBegin(p, s, "pick_outline");
-        const hipError_t e = LaunchPickOutline(s, sc->vertices.p, sc->indices.p, sc->instances.p, idx, sc->hNumTris[idx], m, p->w, p->h, rw, rh, p->pickTris.p,
+        const hipError_t e = LaunchPickOutline(s, sc->vertices.p, sc->indices.p, sc->cur.instances.p, idx, sc->hNumTris[idx], m, p->w, p->h, rw, rh, p->pickTris.p,
             p->pickCount.p, p->pickMask.p, p->displayOut.p, p->displaySrgb.p);
         TimerEnd(p, s);
         HIP_TRY(e);
