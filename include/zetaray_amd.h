@@ -404,6 +404,21 @@ int zr_scene_set_alias_table(zr_scene* scene, const zr_alias_entry* entries, uin
 /* ... or build it from per-triangle power exactly like PreLighting.cpp:27-158 (host side, bit-exact) */
 int zr_alias_table_build(const float* power, uint32_t n, uint32_t align_phase, zr_alias_entry* out_entries);
 int zr_scene_get_alias_table(const zr_scene* scene, zr_alias_entry* out_entries, uint32_t n);
+/* Where a PRELIGHTING render builds the table.  ZR_ALIAS_BUILD_HOST (the default): the reference's path -- powers read back, Vose's method on the host
+ * (zr_alias_table_build), upload; its bytes are the reference's.  ZR_ALIAS_BUILD_DEVICE: a render that finds no table or a stale one (after either
+ * invalidate form) enqueues K2 and then the kernels of zr_tu_alias.hip on the pass stream, into the scene's table buffer, ahead of K3 / K4 and of the
+ * frame's sampling kernels: no device-to-host copy, no wait, no host build, and the new table is the one the SAME frame samples.  Renders on other
+ * streams are ordered by the scene's events as for zr_scene_set_alias_table_async.  That table is the one include/zr_alias.h defines -- a valid alias
+ * table for the same powers with the reference's cached_p_orig in every bit, but NOT Vose's assignment (its sequentially rounded residual chain has no
+ * parallel form); every byte is a function of the powers alone.  zr_scene_get_alias_table then reads the device buffer back (it waits for the device).
+ * Any other mode: ZR_ERR_INVALID_ARG, nothing changed.  The multi-device tiled renderer keeps the host build. */
+#define ZR_ALIAS_BUILD_HOST   0
+#define ZR_ALIAS_BUILD_DEVICE 1
+int zr_scene_set_alias_build(zr_scene* scene, int mode);
+/* The kernels of ZR_ALIAS_BUILD_DEVICE on caller buffers (tests and tools): d_power = n floats, d_out = n entries, both on `device`; enqueued on
+ * `hip_stream`, then waited for.  Equal to include/zr_alias.h run on the host in every byte (contract build).  Caller guarantee as for the host build:
+ * finite, non-negative powers with a positive sum; otherwise the bytes are unspecified, but every alias is < n and nothing is written out of bounds. */
+int zr_alias_table_build_device(int device, void* hip_stream, const float* d_power, uint32_t n, zr_alias_entry* d_out);
 /* K4 output (PreLighting::GetLightVoxelGrid, GlobalResource::LIGHT_VOXEL_GRID): dim.x * dim.y * dim.z * 64 samples, voxel-major */
 int zr_scene_get_light_voxel_grid(const zr_scene* scene, void* hip_stream, zr_voxel_sample* out_samples, uint32_t n);
 /* K3 output (GlobalResource::PRESAMPLED_EMISSIVE_SETS, PreLighting.cpp:300-315): num_sample_sets * sample_set_size records of the last PRELIGHTING render */
@@ -651,6 +666,9 @@ int zr_pass_set_picked_instances(zr_pass* pass, const uint32_t* mesh_idx, uint32
 #define ZR_OUT_PICK_MASK 50
 /* ray counters accumulated since the last call (device -> host copy; synchronises the stream) */
 int zr_pass_read_counters(zr_pass* pass, void* hip_stream, zr_counters* out, int reset);
+/* ZR_PASS_PRELIGHTING: K2's output (the per-triangle powers the alias table is built from) of the last render that estimated them, n = the scene's
+   emissive count; waits for `hip_stream`.  ZR_ERR_NOT_INITIALIZED before the first such render. */
+int zr_pass_get_emissive_powers(zr_pass* pass, void* hip_stream, float* out, uint32_t n);
 /* ReSTIR PT: GPU time per 32 x 32-pixel cell of the pass's planes ((w + 31) / 32 + 1 by (h + 31) / 32 + 1 cells, cell (0, 0) at the plane origin): the summed
  * lifetimes, in units of 16 shader cycles, of the waves of K11 / K14 / K16 that worked on the cell since the last reset: the load signal of the cost-balanced screen split over N devices (tiling.balanced_layout).  No
  * reference counterpart (the reference renders on one GPU).  Costs one atomic per wave while enabled.

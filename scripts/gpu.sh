@@ -10,6 +10,7 @@
 #                      (FETCH_SIZE, WRITE_SIZE, SQ sets A / B / C / E) of one bench command -> ${TAG}_pmc_<wl>.json, ${TAG}_kernel_stats_<wl>.csv
 #   stats [ARGS]       one rocprofv3 --kernel-trace --stats run of bench.py ARGS -> ${TAG}_kernel_stats.csv
 #   tiles              tools/tile_balance.py on Cornell + atrium (per-tile times of the 8-way split on one device)
+#   alias [ARGS]       tools/alias_bench.py: one stale-table PRELIGHTING render per frame, host / host-deferred / device build -> ${TAG}_alias_build.json
 #   prof LIB           section profiler (-DZR_PROF build LIB) on Cornell + atrium -> ${TAG}_section_profile_*.json
 R=${GRAFT_REPO_ROOT:-$PWD}; TAG=${TAG:-r06}; OUT=$R/gpurun_out; mkdir -p $OUT
 task=$1; shift
@@ -97,6 +98,10 @@ prof)
   for wl in ${WORKLOADS:-cornell atrium}; do
     timeout 600 python bench.py --gpus 1 --steps 16 --warmup 4 --frame-overlap 0 --full --no-device-state --no-general-kernels --no-cpu-baseline --no-extra-workloads $(wl_args $wl) 2> $OUT/${TAG}_prof_err.log | tail -1 | python -c "$P" > $OUT/${TAG}_section_profile_$wl.json || tail -5 $OUT/${TAG}_prof_err.log
   done
+  ;;
+alias)
+  cd $R; set -o pipefail
+  timeout 900 python tools/alias_bench.py "$@" 2> $OUT/${TAG}_alias_err.log | tail -1 | tee $OUT/${TAG}_alias_build.json || { echo "alias_bench: requirement missed or failed"; tail -5 $OUT/${TAG}_alias_err.log; exit 1; }
   ;;
 *) echo "unknown task $task"; exit 2;;
 esac

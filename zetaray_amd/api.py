@@ -64,7 +64,10 @@ EXPORTS = [
     "zr_pass_set_rgi_spatial",
     "zr_scene_set_object_emissives", "zr_scene_has_object_emissives", "zr_scene_move_instances", "zr_scene_move_instances_async", "zr_scene_get_instances", "zr_scene_get_emissives",
     "zr_scene_set_animation", "zr_scene_animate", "zr_scene_animate_async",
+    "zr_scene_set_alias_build", "zr_alias_table_build_device", "zr_pass_get_emissive_powers",
 ]
+ALIAS_BUILD_HOST, ALIAS_BUILD_DEVICE = 0, 1
+ALIAS_BUILD_MODES = {"host": ALIAS_BUILD_HOST, "device": ALIAS_BUILD_DEVICE}
 STAGE_TEMPORAL, STAGE_SPATIAL, STAGE_ALL = 1, 2, 3
 STAGE_SPATIAL2 = 4          # ReSTIR PT, num_spatial_passes = 2 on tiles: the second round, behind one more HALO_POST_TEMPORAL exchange
 STAGE_CANDIDATES, STAGE_TEMPORAL_REUSE = 8, 16      # ReSTIR PT: the TEMPORAL stage in its two halves (K11 / K12-K14): what frame overlap puts on two streams
@@ -109,6 +112,9 @@ def lib():
         L.zr_scene_set_alias_table.argtypes = [vp, vp, u32]
         L.zr_alias_table_build.argtypes = [vp, u32, u32, vp]
         L.zr_scene_get_alias_table.argtypes = [vp, vp, u32]
+        L.zr_scene_set_alias_build.argtypes = [vp, i32]
+        L.zr_alias_table_build_device.argtypes = [i32, vp, vp, u32, vp]
+        L.zr_pass_get_emissive_powers.argtypes = [vp, vp, vp, u32]
         L.zr_scene_get_light_voxel_grid.argtypes = [vp, vp, vp, u32]
         L.zr_scene_get_presampled_sets.argtypes = [vp, vp, vp, u32]
         L.zr_scene_bvh_info.argtypes = [vp, vp, vp, vp]
@@ -172,6 +178,17 @@ def alias_table_build(power, align_phase=0):
     out = np.zeros(len(power), wire.ALIAS_ENTRY)
     _check(lib().zr_alias_table_build(power.ctypes.data, len(power), align_phase, out.ctypes.data))
     return out
+
+
+def alias_table_build_device(power, device=0, stream=None):
+    """zr_alias_table_build_device: the kernels of ZR_ALIAS_BUILD_DEVICE (include/zr_alias.h's table) on a copy of `power` on the device; returns the entries"""
+    import torch
+    power = np.ascontiguousarray(power, np.float32)
+    d_power = torch.from_numpy(power).to(f"cuda:{device}")
+    d_out = torch.zeros(len(power) * wire.ALIAS_ENTRY.itemsize, dtype=torch.uint8, device=f"cuda:{device}")
+    torch.cuda.synchronize(device)
+    _check(lib().zr_alias_table_build_device(device, stream, d_power.data_ptr(), len(power), d_out.data_ptr()))
+    return d_out.cpu().numpy().view(wire.ALIAS_ENTRY).copy()
 
 
 class Scene:
@@ -334,6 +351,12 @@ class Scene:
         """emissive materials changed: the next PRELIGHTING render re-estimates the powers and rebuilds the alias table"""
         lib().zr_scene_invalidate_alias_table.argtypes = [C.c_void_p]
         _check(lib().zr_scene_invalidate_alias_table(self.h))
+
+    def set_alias_build(self, mode):
+        """"host" (the default: the reference's Vose build behind a read-back) or "device" (include/zr_alias.h's table, built on the PRELIGHTING render's
+        stream with nothing read back; zetaray_amd.h zr_scene_set_alias_build).  An integer is passed through as it is"""
+        mode = ALIAS_BUILD_MODES[mode] if isinstance(mode, str) else int(mode)
+        _check(lib().zr_scene_set_alias_build(self.h, mode))
 
     def set_alias_table(self, entries):
         entries = np.ascontiguousarray(entries)
@@ -568,6 +591,12 @@ class Pass:
         _check(lib().zr_pass_debug_trip_stats(self.h, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def get_emissive_powers(self, n, stream=None):
+        """PRELIGHTING pass: K2's per-triangle powers of the last render that estimated them (n = the scene's emissive count)"""
+        out = np.zeros(n, np.float32)
+        _check(lib().zr_pass_get_emissive_powers(self.h, stream, out.ctypes.data, n))
+        return out
+
     def read_counters(self, reset=True, stream=None):
         c = wire.Counters()
         _check(lib().zr_pass_read_counters(self.h, stream, C.addressof(c), int(reset)))
@@ -726,6 +755,10 @@ class Renderer:
             return
         self.scene.invalidate_alias_table()
         self._alias_ready = False
+
+    def set_alias_build(self, mode):
+        """where PRELIGHTING builds the alias table: "host" or "device" (Scene.set_alias_build)"""
+        self.scene.set_alias_build(mode)
 
     def move_instances(self, idx, world, stream=False):
         """the frame's scene update from matrices alone (Scene.move_instances; lights: Scene.set_object_emissives once before)"""

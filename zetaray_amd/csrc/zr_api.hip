@@ -75,6 +75,8 @@ namespace zr { hipError_t LaunchAnimate(hipStream_t st, float t, const zr_anim_n
     const uint32_t* levelNodes, const uint32_t* levelOffsets, uint32_t numLevels, float* nodeLocal, float* nodeWorld, const uint32_t* instNode, uint32_t nInst, uint32_t* moved); }   // zr_tu_anim.hip
 namespace zr { hipError_t LaunchFillInstRecs(hipStream_t st, InstRec* recs, const zr_mesh_instance* instances, uint32_t n);      // zr_tu_scene_update.hip
                hipError_t LaunchFillVtxNormals(hipStream_t st, VtxDir* out, const zr_vertex* vertices, uint32_t n, bool tangent); }
+namespace zr { size_t AliasScratchWords(uint32_t n);      // zr_tu_alias.hip
+               hipError_t LaunchAliasBuild(hipStream_t st, const float* power, uint32_t n, zr_alias_entry* out, uint64_t* scratch); }
 // the ReSTIR PT kernels are compiled in zr_tu_rpt_[a-i].hip (see zr_kernels.h)
 ZR_RPT_GROUPS_PRODUCT(extern template)
 #ifdef ZR_EXPERIMENTS
@@ -576,6 +578,10 @@ struct zr_scene
     // device-side BVH build (zr_tu_bvh.hip): instance masks on the device, scratch buffers kept between builds
     DevBuf<uint8_t> dMask; DeviceBvhScratch bvhScratch; bool deviceBuilt = false;
     bool aliasStale = false;      // zr_scene_invalidate_alias_table_deferred: the old table stays bound until the rebuilt one has been uploaded
+    // zr_scene_set_alias_build: ZR_ALIAS_BUILD_DEVICE builds the table in `alias` with the kernels of zr_tu_alias.hip on the PRELIGHTING render's stream.
+    // aliasScratch: their scratch words, sized once per emissive count.  aliasOnDevice: the bound table was built there, so aliasHost is empty and
+    // zr_scene_get_alias_table reads the device buffer back
+    int aliasBuild = ZR_ALIAS_BUILD_HOST; DevBuf<uint64_t> aliasScratch; bool aliasOnDevice = false;
     // `view` is what kernels receive by value.  Passes of one dependency level may record concurrently from several host threads
     // (RenderGraph.cpp:442-541) while Sky / PreLighting publish scene-owned state (sky LUT, alias table, presampled sets, LVG):
     // every reader takes a private copy through FrameView() and every writer updates `view` under `mtx`.
@@ -1528,7 +1534,15 @@ int zr_scene_invalidate_alias_table(zr_scene* s)
     // kernels of earlier frames keep sampling the old table through the pointer they were launched with; the device buffer is only
     // rewritten by zr_scene_set_alias_table, which orders itself behind them
     std::lock_guard<std::mutex> lock(s->mtx);
-    s->view.alias = nullptr; s->aliasHost.clear();
+    s->view.alias = nullptr; s->aliasHost.clear(); s->aliasOnDevice = false;
+    return ZR_OK;
+}
+int zr_scene_set_alias_build(zr_scene* s, int mode)
+{
+    if (mode != ZR_ALIAS_BUILD_HOST && mode != ZR_ALIAS_BUILD_DEVICE) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_alias_build: mode %d is neither ZR_ALIAS_BUILD_HOST nor ZR_ALIAS_BUILD_DEVICE", mode);
+    if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_alias_build: null argument");
+    std::lock_guard<std::mutex> lock(s->mtx);
+    s->aliasBuild = mode;
     return ZR_OK;
 }
 // The reference's steady-state behaviour (EmissiveTriangleAliasTable::Render, PreLighting.cpp:527-540: "fence hasn't passed, returning ..."): the
@@ -2120,7 +2134,7 @@ int zr_scene_set_alias_table_async(zr_scene* s, void* stream, const zr_alias_ent
     if ((r = StageCommit(t, st))) return r;
     {
         std::lock_guard<std::mutex> lock(s->mtx);
-        s->aliasHost.assign(e, e + n);
+        s->aliasHost.assign(e, e + n); s->aliasOnDevice = false;
         s->view.alias = s->alias.p;
     }
     return SceneMarkUpdated(s, st);
@@ -2130,8 +2144,27 @@ int zr_scene_set_alias_table(zr_scene* s, const zr_alias_entry* e, uint32_t n) {
 int zr_scene_get_alias_table(const zr_scene* s, zr_alias_entry* out, uint32_t n)
 {
     if (!s || !out) return Fail(ZR_ERR_INVALID_ARG, "null argument");
+    if (s->aliasOnDevice)
+    {   // a table built on the device has no host copy: a read-back for tests and tools, behind everything enqueued so far
+        if (n != s->alias.n) return Fail(ZR_ERR_INVALID_ARG, "alias table has %zu entries", s->alias.n);
+        HIP_TRY(hipSetDevice(s->device));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(out, s->alias.p, n * sizeof(zr_alias_entry), hipMemcpyDeviceToHost));
+        return ZR_OK;
+    }
     if (n != s->aliasHost.size()) return Fail(ZR_ERR_INVALID_ARG, "alias table has %zu entries", s->aliasHost.size());
     memcpy(out, s->aliasHost.data(), n * sizeof(zr_alias_entry));
+    return ZR_OK;
+}
+// the kernels of ZR_ALIAS_BUILD_DEVICE on caller buffers; waits for `stream` (the scratch words are the call's own)
+int zr_alias_table_build_device(int device, void* stream, const float* d_power, uint32_t n, zr_alias_entry* d_out)
+{
+    if (!d_power || !d_out || n == 0) return Fail(ZR_ERR_INVALID_ARG, "zr_alias_table_build_device: null/empty input");
+    if (hipSetDevice(device) != hipSuccess) return Fail(ZR_ERR_NO_DEVICE, "zr_alias_table_build_device: no usable HIP device %d", device);
+    DevBuf<uint64_t> scratch;
+    if (int r = scratch.Alloc(zr::AliasScratchWords(n))) return r;
+    HIP_TRY(zr::LaunchAliasBuild((hipStream_t)stream, d_power, n, d_out, scratch.p));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return ZR_OK;
 }
 
@@ -2500,10 +2533,41 @@ static int RenderPreLighting(zr_pass* p, hipStream_t s, const zr_frame_constants
     if (r || !p->params.use_lvg || sc->view.numEmissives == 0) return r;
     return RenderLVG(p, s, cb, sc);
 }
+// ZR_ALIAS_BUILD_DEVICE, no table or a stale one (either invalidate form): K2, then the table of include/zr_alias.h built by zr_tu_alias.hip, both
+// ENQUEUED on the pass stream into the scene's table buffer, ahead of K3 / K4 and of this frame's sampling kernels.  Nothing is read back, nothing
+// waits, no host build: the frame that finds the table stale samples the new one.  Ordering against other streams is that of
+// zr_scene_set_alias_table_async -- behind the renders that may still draw from the buffer, and an `updated` event behind the build.  (A table
+// buffer of a new size has no readers; the allocation itself is the one of the host path, once per emissive count.)
+static int RenderAliasTableDevice(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, zr_scene* sc)
+{
+    const uint32_t n = sc->view.numEmissives;
+    int r;
+    p->powerPending = false;      // a deferred host rebuild in flight when the mode changed is dropped: its powers must not feed a later host build
+    if (p->power.n != n && (r = p->power.Alloc(n))) return r;
+    const size_t words = zr::AliasScratchWords(n);
+    if (sc->aliasScratch.n != words && (r = sc->aliasScratch.Alloc(words))) return r;
+    if (sc->alias.n != n) { if ((r = sc->alias.Alloc(n))) return r; }
+    else if ((r = SceneWaitUsers(sc, s))) return r;
+    TimerBegin(p, s, "estimate_power");
+    hipLaunchKernelGGL(k_estimate_power, dim3((n + 255) / 256), dim3(256), 0, s, FrameView(sc, cb), n, p->power.p);
+    TimerEnd(p, s);
+    HIP_TRY(hipGetLastError());
+    TimerBegin(p, s, "alias_build");
+    HIP_TRY(zr::LaunchAliasBuild(s, p->power.p, n, sc->alias.p, sc->aliasScratch.p));
+    TimerEnd(p, s);
+    {
+        std::lock_guard<std::mutex> lock(sc->mtx);
+        sc->aliasHost.clear(); sc->aliasOnDevice = true; sc->aliasStale = false;
+        sc->view.alias = sc->alias.p;
+        if ((r = SceneMarkUpdatedLocked(sc, s))) return r;
+    }
+    return p->params.presampling ? RenderPresample(p, s, cb, sc) : ZR_OK;
+}
 static int RenderPreLightingInner(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, zr_scene* sc)
 {
     const uint32_t n = sc->view.numEmissives;
     if (n == 0) return ZR_OK;
+    if (sc->aliasBuild == ZR_ALIAS_BUILD_DEVICE && (!sc->view.alias || sc->aliasStale)) return RenderAliasTableDevice(p, s, cb, sc);
     // the alias table is built once per emissive set (EmissiveTriangleAliasTable is only re-run when emissive materials change):
     // zr_scene_invalidate_alias_table or a new scene forces a rebuild
     if (sc->view.alias && sc->aliasStale)
@@ -3785,6 +3849,19 @@ int zr_pass_read_cost_map(zr_pass* p, void* stream, uint32_t* out, uint32_t cell
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return ZR_OK;
 }
+// K2's output of the last PRELIGHTING render that estimated powers, after waiting for `stream` (tests and tools)
+int zr_pass_get_emissive_powers(zr_pass* p, void* stream, float* out, uint32_t n)
+{
+    if (!p || !out) return Fail(ZR_ERR_INVALID_ARG, "null argument");
+    if (p->kind != ZR_PASS_PRELIGHTING) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_get_emissive_powers: not a PRELIGHTING pass");
+    if (!p->power.p) return Fail(ZR_ERR_NOT_INITIALIZED, "no emissive powers: render the PRELIGHTING pass on a scene without a current alias table first");
+    if (n != p->power.n) return Fail(ZR_ERR_INVALID_ARG, "the pass holds the powers of %zu emissive triangles", p->power.n);
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(hipMemcpy(out, p->power.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    return ZR_OK;
+}
+
 int zr_pass_read_counters(zr_pass* p, void* stream, zr_counters* out, int reset)
 {
     if (!p || !out) return Fail(ZR_ERR_INVALID_ARG, "null argument");

@@ -229,6 +229,7 @@ void PreLighting::SetLightVoxelGridParams(bool enable, uint32_t dimX, uint32_t d
     m_params.lvg_offset_y = offsetY;
     ZR_CHECK(zr_pass_set_params(m_pass, &m_params));
 }
+void PreLighting::SetAliasTableBuild(int mode) { ZR_CHECK(zr_scene_set_alias_build(m_ctx->scene, mode)); }
 void PreLighting::Render(Core::CommandList& cl)
 {
     // The alias table only changes when the emissive set changes (EmissiveTriangleAliasTable::Update, PreLighting.cpp:455-510):

@@ -221,6 +221,9 @@ namespace RenderPass {
         // PreLighting.h:53-58 (dims / extents / y offset of the light voxel grid; needs presampling)
         void SetLightVoxelGridParams(bool enable, uint32_t dimX, uint32_t dimY, uint32_t dimZ, float extX, float extY, float extZ, float offsetY);
         bool IsPresamplingEnabled() const { return m_params.presampling != 0; }
+        // where the alias table is built (zr_scene_set_alias_build): ZR_ALIAS_BUILD_HOST, the reference's path and the default, or ZR_ALIAS_BUILD_DEVICE,
+        // on the command list's stream with nothing read back.  No counterpart in the reference
+        void SetAliasTableBuild(int mode);
         void Render(Core::CommandList& cmdList);
     private:
         zr_params m_params{};
