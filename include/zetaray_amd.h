@@ -298,6 +298,32 @@ int         zr_wire_layout(char* buf, size_t cap);
 /* ---- scene: device copies of VB/IB/MeshInstance/Material/Emissive/AliasTable + BVH ---- */
 int zr_scene_create(int device, const zr_scene_desc* desc, zr_scene** out);
 int zr_scene_destroy(zr_scene* scene);
+/* ---- block-compressed texture sources: the texel heap decoded on the device (include/zr_bcn.h states the decode; zr_tu_texdecode.hip runs it).
+ * The heap a scene holds is uncompressed either way (zr_wire.h); what changes is who decodes the BC7 / BC5 blocks the .dds files carry, and what crosses
+ * the bus: the blocks, a quarter (BC7) or half (BC5) of the bytes of the texels they decode to.
+ * zr_texture_source i belongs to zr_texture_desc i and names its WHOLE mip chain in `payload`: mips back to back in DDS order, mip m of
+ * max(1, w >> m) x max(1, h >> m) texels as ceil(w / 4) x ceil(h / 4) 16-byte blocks in row-major order (BC7, BC5), or as the uncompressed texels
+ * the heap holds (RAW).  BC7 decodes to 4 B / texel and needs format RGBA8 or RGBA8_SRGB, BC5 to 2 B / texel (r, g) and needs RG8.  `offset` must be a
+ * multiple of 16 for BC7 / BC5 and of 4 for RAW.  Not part of zr_wire_layout. */
+enum { ZR_TEX_SRC_RAW = 0, ZR_TEX_SRC_BC7 = 1, ZR_TEX_SRC_BC5 = 2 };
+typedef struct zr_texture_source { uint64_t offset; uint8_t encoding; uint8_t pad[7]; } zr_texture_source;
+typedef struct zr_texture_blocks { const zr_texture_source* sources; const uint8_t* payload; uint64_t payload_bytes; } zr_texture_blocks;
+/* zr_scene_create with the texel heap produced on the device: desc->texels must be NULL, desc->texel_bytes is the size of the decoded heap and
+ * desc->textures says where in it each chain goes, as for zr_scene_create.  The payload is uploaded once, decoded by one kernel launch (RAW chains:
+ * one device copy per texture) into a zero-filled heap, and released.  The heap then equals, in every byte, the one zr_scene_create holds when handed
+ * the host-decoded texels (zrh_bc7_decode / zrh_bc5_decode) with zeros between the chains.  ZR_ERR_INVALID_ARG, with nothing created and *out
+ * untouched, for: a null blocks / sources / payload; texels != NULL; an unknown encoding; BC7 on a format that is not RGBA8 / RGBA8_SRGB; BC5 on a
+ * format that is not RG8; a misaligned source offset; a chain that ends beyond payload_bytes; more than 2^32 - 1 blocks in all; and every
+ * zr_texture_desc zr_scene_create refuses.  A scene without textures takes no blocks argument checks beyond the null checks.
+ * Textures cannot be replaced after creation. */
+int zr_scene_create_compressed(int device, const zr_scene_desc* desc, const zr_texture_blocks* blocks, zr_scene** out);
+/* The decode alone, on caller buffers (tests and tools): n descs + sources as above (host pointers), d_payload (16-byte aligned) and d_texels
+ * (4-byte aligned) on `device`.  ENQUEUES on `hip_stream` and returns: the job table travels through a stream-ordered allocation.  Writes the texels of
+ * the n chains and nothing else.  Refuses what zr_scene_create_compressed refuses. */
+int zr_bcn_decode_device(int device, void* hip_stream, const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n,
+                         const void* d_payload, uint64_t payload_bytes, void* d_texels, uint64_t texel_bytes);
+/* read-back of bytes [first_byte, first_byte + count) of the scene's texel heap, for tests and tools; waits for `hip_stream` */
+int zr_scene_get_texels(const zr_scene* scene, void* hip_stream, uint8_t* out, uint64_t first_byte, uint64_t count);
 /* Per-frame update of dynamic instances (TLAS::FillMeshInstanceData + the TLAS rebuild, RtAccelerationStructure.cpp:318-506, 708-787;
  * what the reference publishes as RT_FRAME_MESH_INSTANCES_CURR / _PREV and RT_SCENE_BVH_CURR / _PREV): `instances` = the new
  * MeshInstance records (the caller fills PrevRotation / PrevScale / dTranslation like the reference does), `instance_to_world` = the new

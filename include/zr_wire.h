@@ -192,7 +192,9 @@ typedef struct zr_frame_constants {
  * hardware.  Neither block decompression nor hardware filtering is pinned by the reference, so this ABI takes the decoded
  * texels: every texture is a full mip chain of uncompressed texels (mip m is max(1, w >> m) x max(1, h >> m), rows
  * top-down, mips packed back to back from `offset`, which must be a multiple of 4), and zr_texture.h defines the
- * filtering.  Material / MeshInstance / EmissiveTriangle texture indices address `textures` exactly like the reference
+ * filtering.  The heap the kernels sample is always this uncompressed one; zr_scene_create_compressed (zetaray_amd.h)
+ * takes the BC7 / BC5 blocks instead of the texels and makes the same heap on the device, by the decode zr_bcn.h
+ * states.  Material / MeshInstance / EmissiveTriangle texture indices address `textures` exactly like the reference
  * addresses its descriptor heap: textures[frame_constants.<kind>_maps_desc_heap_offset + tex16].
  */
 #define ZR_TEX_RGBA8_SRGB  0u   /* 4 B/texel, RGB through the sRGB transfer function, A linear (base colour, emissive) */

@@ -65,6 +65,7 @@ EXPORTS = [
     "zr_scene_set_object_emissives", "zr_scene_has_object_emissives", "zr_scene_move_instances", "zr_scene_move_instances_async", "zr_scene_get_instances", "zr_scene_get_emissives",
     "zr_scene_set_animation", "zr_scene_animate", "zr_scene_animate_async",
     "zr_scene_set_alias_build", "zr_alias_table_build_device", "zr_pass_get_emissive_powers",
+    "zr_scene_create_compressed", "zr_bcn_decode_device", "zr_scene_get_texels",
 ]
 ALIAS_BUILD_HOST, ALIAS_BUILD_DEVICE = 0, 1
 ALIAS_BUILD_MODES = {"host": ALIAS_BUILD_HOST, "device": ALIAS_BUILD_DEVICE}
@@ -109,6 +110,9 @@ def lib():
         L.zr_device_count.argtypes = [vp]
         L.zr_scene_create.argtypes = [i32, vp, vp]
         L.zr_scene_destroy.argtypes = [vp]
+        L.zr_scene_create_compressed.argtypes = [i32, vp, vp, vp]
+        L.zr_bcn_decode_device.argtypes = [i32, vp, vp, vp, u32, vp, C.c_uint64, vp, C.c_uint64]
+        L.zr_scene_get_texels.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64]
         L.zr_scene_set_alias_table.argtypes = [vp, vp, u32]
         L.zr_alias_table_build.argtypes = [vp, u32, u32, vp]
         L.zr_scene_get_alias_table.argtypes = [vp, vp, u32]
@@ -191,6 +195,20 @@ def alias_table_build_device(power, device=0, stream=None):
     return d_out.cpu().numpy().view(wire.ALIAS_ENTRY).copy()
 
 
+def bcn_decode_device(descs, sources, payload, texel_bytes, fill=0, device=0, stream=None):
+    """zr_bcn_decode_device: the chains `sources` name in `payload` (wire.TEXTURE_SOURCE, uint8) decoded on the device into a heap of `texel_bytes` bytes
+    pre-filled with `fill`, at the places `descs` (wire.TEXTURE_DESC) name; returns the heap"""
+    import torch
+    descs, sources = np.ascontiguousarray(descs, wire.TEXTURE_DESC), np.ascontiguousarray(sources, wire.TEXTURE_SOURCE)
+    payload = np.ascontiguousarray(payload, np.uint8).reshape(-1)
+    d_payload = torch.from_numpy(payload.copy()).to(f"cuda:{device}")
+    d_out = torch.full((int(texel_bytes),), int(fill), dtype=torch.uint8, device=f"cuda:{device}")
+    torch.cuda.synchronize(device)
+    _check(lib().zr_bcn_decode_device(device, stream, descs.ctypes.data, sources.ctypes.data, len(descs), d_payload.data_ptr(), len(payload), d_out.data_ptr(), int(texel_bytes)))
+    torch.cuda.synchronize(device)
+    return d_out.cpu().numpy().copy()
+
+
 class Scene:
     def __init__(self, scene, device=0):
         self.host = scene
@@ -200,7 +218,22 @@ class Scene:
         # do the instance records now on the device describe motion (prev transform != current)?  They keep doing so in every later frame until
         # the host uploads records at rest, whether or not update_instances is called again -- the G-buffer's motion vectors come from them
         self.instances_in_motion = self._records_in_motion(getattr(scene, "instances", None))
-        _check(lib().zr_scene_create(device, C.addressof(self._desc), C.byref(self.h)))
+        # a host scene that carries block-compressed texture sources has its texel heap decoded on the device (zr_scene_create_compressed), whether or
+        # not decode_textures() also made the texels on the host
+        self._blocks = scene.texture_blocks() if len(getattr(scene, "texture_payload", ())) else None
+        if self._blocks is not None:
+            self._desc.texels, self._desc.texel_bytes = None, scene.texel_heap_bytes
+            _check(lib().zr_scene_create_compressed(device, C.addressof(self._desc), C.addressof(self._blocks), C.byref(self.h)))
+        else:
+            _check(lib().zr_scene_create(device, C.addressof(self._desc), C.byref(self.h)))
+
+    def get_texels(self, first=0, count=None, stream=None):
+        """zr_scene_get_texels: bytes [first, first + count) of the device texel heap (count None: to its end)"""
+        total = getattr(self.host, "texel_heap_bytes", 0) if self._blocks is not None else len(self.host.texels)
+        count = total - first if count is None else count
+        out = np.zeros(count, np.uint8)
+        _check(lib().zr_scene_get_texels(self.h, stream, out.ctypes.data, first, count))
+        return out
 
     @staticmethod
     def _records_in_motion(instances):

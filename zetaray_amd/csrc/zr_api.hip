@@ -77,6 +77,8 @@ namespace zr { hipError_t LaunchFillInstRecs(hipStream_t st, InstRec* recs, cons
                hipError_t LaunchFillVtxNormals(hipStream_t st, VtxDir* out, const zr_vertex* vertices, uint32_t n, bool tangent); }
 namespace zr { size_t AliasScratchWords(uint32_t n);      // zr_tu_alias.hip
                hipError_t LaunchAliasBuild(hipStream_t st, const float* power, uint32_t n, zr_alias_entry* out, uint64_t* scratch); }
+#include "../../include/zr_bcn.h"
+namespace zr { hipError_t LaunchBcnDecode(hipStream_t st, const zrbc::Job* jobs, uint32_t numJobs, uint32_t numBlocks, const uint8_t* payload, uint8_t* texels); }   // zr_tu_texdecode.hip
 // the ReSTIR PT kernels are compiled in zr_tu_rpt_[a-i].hip (see zr_kernels.h)
 ZR_RPT_GROUPS_PRODUCT(extern template)
 #ifdef ZR_EXPERIMENTS
@@ -1391,11 +1393,87 @@ static zr_scene_desc SceneBuilderDesc(const zr_scene* s, const zr_mesh_instance*
     d.instances = instances; d.num_instances = n; d.instance_to_world = toWorld; d.instance_mask = s->hMask.data(); d.instance_num_tris = s->hNumTris.data();
     return d;
 }
-int zr_scene_create(int device, const zr_scene_desc* d, zr_scene** out)
+// is texture i one zr_scene_create accepts?  (its chain inside the texel blob, its offset a multiple of 4)
+static bool TextureDescOk(const zr_texture_desc& t, uint64_t texelBytes)
 {
-    if (!d || !out) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: null argument");
+    const zr_tex_mip last = zr_tex_mip_of(&t, t.num_mips ? t.num_mips - 1u : 0u);
+    const uint64_t end = last.offset + (uint64_t)last.w * last.h * (t.format == ZR_TEX_RG8 ? 2u : 4u);
+    return t.num_mips && t.width && t.height && t.format <= ZR_TEX_RG8 && !(t.offset & 3u) && end <= texelBytes;
+}
+// What the device decode of n textures takes (zr_scene_create_compressed, zr_bcn_decode_device): one zrbc::Job per mip of every BC7 / BC5 chain, in
+// texture order, and one copy per RAW chain.  Everything either entry point refuses about descs and sources is refused here, before anything is allocated
+// chains: the bytes [first, second) of the heap each texture's chain fills, in texture order (everything else is what a caller sees as padding)
+struct BcnPlan { std::vector<zrbc::Job> jobs; struct Copy { uint64_t src, dst, bytes; }; std::vector<Copy> copies; uint32_t numBlocks = 0;
+                 std::vector<std::pair<uint64_t, uint64_t>> chains; };
+static int PlanBcnDecode(const char* fn, const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n, uint64_t payloadBytes, uint64_t texelBytes, BcnPlan& plan)
+{
+    uint64_t blocks = 0;
+    for (uint32_t i = 0; i < n; i++)
+    {
+        const zr_texture_desc& t = descs[i]; const zr_texture_source& src = sources[i];
+        if (!TextureDescOk(t, texelBytes)) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is malformed or lies outside the texel blob", fn, i);
+        if (src.encoding > ZR_TEX_SRC_BC5) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u has the unknown source encoding %u", fn, i, (unsigned)src.encoding);
+        if (src.encoding == ZR_TEX_SRC_BC7 && t.format != ZR_TEX_RGBA8 && t.format != ZR_TEX_RGBA8_SRGB) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is BC7 but its format is not RGBA8 / RGBA8_SRGB", fn, i);
+        if (src.encoding == ZR_TEX_SRC_BC5 && t.format != ZR_TEX_RG8) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is BC5 but its format is not RG8", fn, i);
+        if (src.offset & (src.encoding == ZR_TEX_SRC_RAW ? 3u : 15u)) return Fail(ZR_ERR_INVALID_ARG, "%s: the source offset of texture %u is not a multiple of %u", fn, i, src.encoding == ZR_TEX_SRC_RAW ? 4u : 16u);
+        const uint32_t bpp = t.format == ZR_TEX_RG8 ? 2u : 4u;
+        uint64_t at = src.offset;      // (a chain is < 2^37 bytes, so `at` cannot wrap before it is compared)
+        if (at > payloadBytes) return Fail(ZR_ERR_INVALID_ARG, "%s: the chain of texture %u starts beyond the payload", fn, i);
+        for (uint32_t m = 0; m < t.num_mips; m++)
+        {
+            const zr_tex_mip mip = zr_tex_mip_of(&t, m);
+            if (src.encoding == ZR_TEX_SRC_RAW) { at += (uint64_t)mip.w * mip.h * bpp; continue; }
+            zrbc::Job j; j.src = at; j.dst = mip.offset; j.w = mip.w; j.h = mip.h; j.first_block = (uint32_t)blocks; j.encoding = src.encoding;
+            const uint64_t nb = (uint64_t)((mip.w + 3u) >> 2) * ((mip.h + 3u) >> 2);
+            blocks += nb; at += 16u * nb;
+            if (blocks > 0xffffffffull) return Fail(ZR_ERR_INVALID_ARG, "%s: more than 2^32 - 1 blocks", fn);
+            plan.jobs.push_back(j);
+        }
+        if (at > payloadBytes) return Fail(ZR_ERR_INVALID_ARG, "%s: the chain of texture %u ends beyond the payload (%llu > %llu bytes)", fn, i, (unsigned long long)at, (unsigned long long)payloadBytes);
+        if (src.encoding == ZR_TEX_SRC_RAW) plan.copies.push_back({src.offset, t.offset, at - src.offset});
+        const zr_tex_mip last = zr_tex_mip_of(&t, t.num_mips - 1u);
+        plan.chains.push_back({t.offset, last.offset + (uint64_t)last.w * last.h * bpp});
+    }
+    plan.numBlocks = (uint32_t)blocks;
+    return ZR_OK;
+}
+// enqueues the plan on `st`: dJobs = the plan's jobs on the device (unused without jobs)
+static int RunBcnPlan(hipStream_t st, const BcnPlan& plan, const zrbc::Job* dJobs, const uint8_t* dPayload, uint8_t* dTexels)
+{
+    if (!plan.jobs.empty()) HIP_TRY(zr::LaunchBcnDecode(st, dJobs, (uint32_t)plan.jobs.size(), plan.numBlocks, dPayload, dTexels));
+    for (const BcnPlan::Copy& c : plan.copies) if (c.bytes) HIP_TRY(hipMemcpyAsync(dTexels + c.dst, dPayload + c.src, c.bytes, hipMemcpyDeviceToDevice, st));
+    return ZR_OK;
+}
+// zero-fills what no chain of the plan covers in a heap of `bytes` bytes (the decode and the copies write every byte of a chain): the padding between
+// chains, a few bytes each for a loader's heap, instead of the whole heap twice.  On the null stream
+static int ClearHeapGaps(const BcnPlan& plan, uint8_t* dTexels, uint64_t bytes)
+{
+    std::vector<std::pair<uint64_t, uint64_t>> c = plan.chains;
+    std::sort(c.begin(), c.end());
+    uint64_t at = 0;
+    for (const auto& r : c)
+    {
+        if (r.first > at) HIP_TRY(hipMemset(dTexels + at, 0, r.first - at));
+        if (r.second > at) at = r.second;
+    }
+    if (bytes > at) HIP_TRY(hipMemset(dTexels + at, 0, bytes - at));
+    return ZR_OK;
+}
+// zr_scene_create (blocks == nullptr) and zr_scene_create_compressed: the same scene, the texel heap uploaded or decoded on the device
+static int SceneCreate(const char* fn, int device, const zr_scene_desc* d, const zr_texture_blocks* blocks, zr_scene** out)
+{
+    if (!d || !out) return Fail(ZR_ERR_INVALID_ARG, "%s: null argument", fn);
     if (!d->vertices || !d->indices || !d->instances || !d->materials || !d->rho_lut || !d->instance_to_world || !d->instance_mask || !d->instance_num_tris)
-        return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: incomplete scene description");
+        return Fail(ZR_ERR_INVALID_ARG, "%s: incomplete scene description", fn);
+    BcnPlan plan;
+    if (blocks)
+    {   // refused before the acceleration structure is built
+        if (!blocks->sources || !blocks->payload) return Fail(ZR_ERR_INVALID_ARG, "%s: null sources / payload", fn);
+        if (d->texels) return Fail(ZR_ERR_INVALID_ARG, "%s: desc->texels must be null: the heap is decoded from the blocks", fn);
+        if (d->num_textures && !d->textures) return Fail(ZR_ERR_INVALID_ARG, "%s: num_textures > 0 without textures", fn);
+        if (int pr = PlanBcnDecode(fn, d->textures, blocks->sources, d->num_textures, blocks->payload_bytes, d->texel_bytes, plan)) return pr;
+    }
+    DevBuf<uint8_t> payload; DevBuf<zrbc::Job> jobs;      // (live until the synchronize at the end)
     int r = RequireDevice(device);
     if (r) return r;
     std::unique_ptr<zr_scene> s(new (std::nothrow) zr_scene());      // (every early return below frees it)
@@ -1422,17 +1500,17 @@ int zr_scene_create(int device, const zr_scene_desc* d, zr_scene** out)
         (r = a.tris.Upload(bvh.tris.data(), bvh.tris.size())) || (r = a.meta.Upload(bvh.meta.data(), bvh.meta.size())) ||
         (r = s->rho.Upload(d->rho_lut, (size_t)d->rho_dim[0] * d->rho_dim[1] * d->rho_dim[2]))) return r;
     a.numNodes = (uint32_t)bvh.nodes4.size(); a.numTris = (uint32_t)bvh.tris.size();
-    if (d->num_textures)
+    if (d->num_textures && blocks)
+    {   // the blocks cross the bus once; the heap's padding is zero-filled, its chains decoded into, on the null stream like the uploads around it
+        if ((r = s->texDescs.Upload(d->textures, d->num_textures)) || (r = payload.Upload(blocks->payload, blocks->payload_bytes)) ||
+            (r = s->texels.Alloc(d->texel_bytes)) || (r = ClearHeapGaps(plan, s->texels.p, d->texel_bytes)) || (r = jobs.Upload(plan.jobs.data(), plan.jobs.size())) ||
+            (r = RunBcnPlan(nullptr, plan, jobs.p, payload.p, s->texels.p))) return r;
+    }
+    else if (d->num_textures)
     {
         if (!d->textures || !d->texels) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: num_textures > 0 without textures / texels");
         for (uint32_t i = 0; i < d->num_textures; i++)
-        {
-            const zr_texture_desc& t = d->textures[i];
-            const zr_tex_mip last = zr_tex_mip_of(&t, t.num_mips ? t.num_mips - 1u : 0u);
-            const uint64_t end = last.offset + (uint64_t)last.w * last.h * (t.format == ZR_TEX_RG8 ? 2u : 4u);
-            if (!t.num_mips || !t.width || !t.height || t.format > ZR_TEX_RG8 || (t.offset & 3u) || end > d->texel_bytes)
-                return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: texture %u is malformed or lies outside the texel blob", i);
-        }
+            if (!TextureDescOk(d->textures[i], d->texel_bytes)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: texture %u is malformed or lies outside the texel blob", i);
         if ((r = s->texDescs.Upload(d->textures, d->num_textures)) || (r = s->texels.Upload(d->texels, d->texel_bytes))) return r;
     }
     if ((r = s->srgb.Upload(zr_srgb_to_linear_table, 256))) return r;
@@ -1482,6 +1560,52 @@ int zr_scene_create(int device, const zr_scene_desc* d, zr_scene** out)
     // uploads from pageable memory return once staged; renders on non-blocking streams must not start before the DMA has landed
     { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) return Fail(ZR_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e)); }
     *out = s.release();
+    return ZR_OK;
+}
+int zr_scene_create(int device, const zr_scene_desc* d, zr_scene** out) { return SceneCreate("zr_scene_create", device, d, nullptr, out); }
+int zr_scene_create_compressed(int device, const zr_scene_desc* d, const zr_texture_blocks* blocks, zr_scene** out)
+{
+    if (!blocks) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create_compressed: null blocks");
+    return SceneCreate("zr_scene_create_compressed", device, d, blocks, out);
+}
+// the decode of zr_scene_create_compressed on caller buffers.  Nothing here waits for the stream's earlier work: the job table lives in a stream-ordered
+// allocation freed behind the kernel; its copy from the host is synchronous towards the host buffer only (below)
+int zr_bcn_decode_device(int device, void* stream, const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n, const void* d_payload, uint64_t payload_bytes,
+    void* d_texels, uint64_t texel_bytes)
+{
+    const char* fn = "zr_bcn_decode_device";
+    if (!descs || !sources || !d_payload || !d_texels || n == 0) return Fail(ZR_ERR_INVALID_ARG, "%s: null/empty input", fn);
+    if (((uintptr_t)d_payload & 15u) || ((uintptr_t)d_texels & 3u)) return Fail(ZR_ERR_INVALID_ARG, "%s: d_payload must be 16-byte and d_texels 4-byte aligned", fn);
+    BcnPlan plan;
+    if (int r = PlanBcnDecode(fn, descs, sources, n, payload_bytes, texel_bytes, plan)) return r;
+    if (hipSetDevice(device) != hipSuccess) return Fail(ZR_ERR_NO_DEVICE, "%s: no usable HIP device %d", fn, device);
+    hipStream_t st = (hipStream_t)stream;
+    zrbc::Job* dJobs = nullptr;
+    if (!plan.jobs.empty())
+    {
+        // the table is copied from the plan's pageable vector, which this call destroys on return: hipMemcpyAsync from pageable memory is synchronous
+        // towards the host buffer (the runtime has staged or sent it when it returns), so the vector may go; it is no wait for earlier work of the stream
+        const size_t bytes = plan.jobs.size() * sizeof(zrbc::Job);
+        HIP_TRY(hipMallocAsync((void**)&dJobs, bytes, st));
+        const hipError_t e = hipMemcpyAsync(dJobs, plan.jobs.data(), bytes, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) { (void)hipFreeAsync(dJobs, st); return Fail(ZR_ERR_HIP, "%s: the copy of the job table failed: %s", fn, hipGetErrorString(e)); }
+    }
+    const int r = RunBcnPlan(st, plan, dJobs, (const uint8_t*)d_payload, (uint8_t*)d_texels);
+    if (dJobs)
+    {   // freed behind whatever was enqueued, on the error path too
+        const hipError_t e = hipFreeAsync(dJobs, st);
+        if (e != hipSuccess && !r) return Fail(ZR_ERR_HIP, "%s: hipFreeAsync failed: %s", fn, hipGetErrorString(e));
+    }
+    return r;
+}
+int zr_scene_get_texels(const zr_scene* s, void* stream, uint8_t* out, uint64_t first, uint64_t count)
+{
+    if (!s || (!out && count)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_texels: null argument");
+    if (first > s->texels.n || count > s->texels.n - first) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_texels: [%llu, +%llu) exceeds the heap's %zu bytes", (unsigned long long)first, (unsigned long long)count, s->texels.n);
+    if (!count) return ZR_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(hipMemcpy(out, s->texels.p + first, count, hipMemcpyDeviceToHost));
     return ZR_OK;
 }
 

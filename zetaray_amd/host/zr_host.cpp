@@ -772,11 +772,21 @@ int zrh_render_sequence_overlap(const zr_scene_desc* desc, const zr_frame_consta
 // Copies the FINAL planes of the last frame: Indirect to `finalOut`, SkyDI to `skyDiOut`.
 // Scene ingestion on the host (zr_scene_io.cpp) straight into a device scene: Model::glTF::Load + SceneCore + TLAS build of the reference
 // collapsed into one call.  tex_offsets4 = the descriptor-table offsets to put into cbFrameConstants (base colour, normal, MR, emissive).
+extern "C" int zrh_scene_create_from_data(int device, const zrh_scene_data* data, zr_scene** out)
+{
+    if (!data) return -1;
+    const zr_texture_blocks* blocks = zrh_scene_data_texture_blocks(data);
+    return blocks ? zr_scene_create_compressed(device, zrh_scene_data_desc(data), blocks, out) : zr_scene_create(device, zrh_scene_data_desc(data), out);
+}
 extern "C" int zrh_scene_create_from_gltf(int device, const char* path, const uint16_t* rho_lut, const uint32_t* rho_dim3, zr_scene** out, uint32_t* tex_offsets4)
 {
+    return zrh_scene_create_from_gltf_ex(device, path, rho_lut, rho_dim3, 0u, out, tex_offsets4);
+}
+extern "C" int zrh_scene_create_from_gltf_ex(int device, const char* path, const uint16_t* rho_lut, const uint32_t* rho_dim3, uint32_t load_flags, zr_scene** out, uint32_t* tex_offsets4)
+{
     zrh_scene_data* data = nullptr;
-    if (zrh_gltf_load(path, rho_lut, rho_dim3, &data) != 0) { std::fprintf(stderr, "zrh_scene_create_from_gltf: %s\n", zrh_scene_io_last_error()); return -1; }
-    const int r = zr_scene_create(device, zrh_scene_data_desc(data), out);
+    if (zrh_gltf_load_ex(path, rho_lut, rho_dim3, load_flags, &data) != 0) { std::fprintf(stderr, "zrh_scene_create_from_gltf: %s\n", zrh_scene_io_last_error()); return -1; }
+    const int r = zrh_scene_create_from_data(device, data, out);
     if (tex_offsets4) zrh_scene_data_tex_offsets(data, tex_offsets4);
     zrh_scene_data_destroy(data);
     return r;

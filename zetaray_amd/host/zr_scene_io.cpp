@@ -5,6 +5,8 @@
 #include "../../include/zr_detmath.h"
 #include "../../include/zr_scene_math.h"
 #include "../../include/zr_anim.h"
+#include "../../include/zr_bcn.h"
+#include "../../include/zr_texture.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -164,98 +166,14 @@ void PackEmissiveTriangle(const float* v0, const float* v1, const float* v2, con
 }
 
 // ------------------------------------------------------------------------------------------------ block decompression
-// BC7 (BPTC), the 8 modes of the D3D11 functional spec / Khronos data format spec section 18.3.
-const uint8_t kBc7Part2[64][16] = {
- {0,0,1,1,0,0,1,1,0,0,1,1,0,0,1,1},{0,0,0,1,0,0,0,1,0,0,0,1,0,0,0,1},{0,1,1,1,0,1,1,1,0,1,1,1,0,1,1,1},{0,0,0,1,0,0,1,1,0,0,1,1,0,1,1,1},
- {0,0,0,0,0,0,0,1,0,0,0,1,0,0,1,1},{0,0,1,1,0,1,1,1,0,1,1,1,1,1,1,1},{0,0,0,1,0,0,1,1,0,1,1,1,1,1,1,1},{0,0,0,0,0,0,0,1,0,0,1,1,0,1,1,1},
- {0,0,0,0,0,0,0,0,0,0,0,1,0,0,1,1},{0,0,1,1,0,1,1,1,1,1,1,1,1,1,1,1},{0,0,0,0,0,0,0,1,0,1,1,1,1,1,1,1},{0,0,0,0,0,0,0,0,0,0,0,1,0,1,1,1},
- {0,0,0,1,0,1,1,1,1,1,1,1,1,1,1,1},{0,0,0,0,0,0,0,0,1,1,1,1,1,1,1,1},{0,0,0,0,1,1,1,1,1,1,1,1,1,1,1,1},{0,0,0,0,0,0,0,0,0,0,0,0,1,1,1,1},
- {0,0,0,0,1,0,0,0,1,1,1,0,1,1,1,1},{0,1,1,1,0,0,0,1,0,0,0,0,0,0,0,0},{0,0,0,0,0,0,0,0,1,0,0,0,1,1,1,0},{0,1,1,1,0,0,1,1,0,0,0,1,0,0,0,0},
- {0,0,1,1,0,0,0,1,0,0,0,0,0,0,0,0},{0,0,0,0,1,0,0,0,1,1,0,0,1,1,1,0},{0,0,0,0,0,0,0,0,1,0,0,0,1,1,0,0},{0,1,1,1,0,0,1,1,0,0,1,1,0,0,0,1},
- {0,0,1,1,0,0,0,1,0,0,0,1,0,0,0,0},{0,0,0,0,1,0,0,0,1,0,0,0,1,1,0,0},{0,1,1,0,0,1,1,0,0,1,1,0,0,1,1,0},{0,0,1,1,0,1,1,0,0,1,1,0,1,1,0,0},
- {0,0,0,1,0,1,1,1,1,1,1,0,1,0,0,0},{0,0,0,0,1,1,1,1,1,1,1,1,0,0,0,0},{0,1,1,1,0,0,0,1,1,0,0,0,1,1,1,0},{0,0,1,1,1,0,0,1,1,0,0,1,1,1,0,0},
- {0,1,0,1,0,1,0,1,0,1,0,1,0,1,0,1},{0,0,0,0,1,1,1,1,0,0,0,0,1,1,1,1},{0,1,0,1,1,0,1,0,0,1,0,1,1,0,1,0},{0,0,1,1,0,0,1,1,1,1,0,0,1,1,0,0},
- {0,0,1,1,1,1,0,0,0,0,1,1,1,1,0,0},{0,1,0,1,0,1,0,1,1,0,1,0,1,0,1,0},{0,1,1,0,1,0,0,1,0,1,1,0,1,0,0,1},{0,1,0,1,1,0,1,0,1,0,1,0,0,1,0,1},
- {0,1,1,1,0,0,1,1,1,1,0,0,1,1,1,0},{0,0,0,1,0,0,1,1,1,1,0,0,1,0,0,0},{0,0,1,1,0,0,1,0,0,1,0,0,1,1,0,0},{0,0,1,1,1,0,1,1,1,1,0,1,1,1,0,0},
- {0,1,1,0,1,0,0,1,1,0,0,1,0,1,1,0},{0,0,1,1,1,1,0,0,1,1,0,0,0,0,1,1},{0,1,1,0,0,1,1,0,1,0,0,1,1,0,0,1},{0,0,0,0,0,1,1,0,0,1,1,0,0,0,0,0},
- {0,1,0,0,1,1,1,0,0,1,0,0,0,0,0,0},{0,0,1,0,0,1,1,1,0,0,1,0,0,0,0,0},{0,0,0,0,0,0,1,0,0,1,1,1,0,0,1,0},{0,0,0,0,0,1,0,0,1,1,1,0,0,1,0,0},
- {0,1,1,0,1,1,0,0,1,0,0,1,0,0,1,1},{0,0,1,1,0,1,1,0,1,1,0,0,1,0,0,1},{0,1,1,0,0,0,1,1,1,0,0,1,1,1,0,0},{0,0,1,1,1,0,0,1,1,1,0,0,0,1,1,0},
- {0,1,1,0,1,1,0,0,1,1,0,0,1,0,0,1},{0,1,1,0,0,0,1,1,0,0,1,1,1,0,0,1},{0,1,1,1,1,1,1,0,1,0,0,0,0,0,0,1},{0,0,0,1,1,0,0,0,1,1,1,0,0,1,1,1},
- {0,0,0,0,1,1,1,1,0,0,1,1,0,0,1,1},{0,0,1,1,0,0,1,1,1,1,1,1,0,0,0,0},{0,0,1,0,0,0,1,0,1,1,1,0,1,1,1,0},{0,1,0,0,0,1,0,0,0,1,1,1,0,1,1,1} };
-const uint8_t kBc7Part3[64][16] = {
- {0,0,1,1,0,0,1,1,0,2,2,1,2,2,2,2},{0,0,0,1,0,0,1,1,2,2,1,1,2,2,2,1},{0,0,0,0,2,0,0,1,2,2,1,1,2,2,1,1},{0,2,2,2,0,0,2,2,0,0,1,1,0,1,1,1},
- {0,0,0,0,0,0,0,0,1,1,2,2,1,1,2,2},{0,0,1,1,0,0,1,1,0,0,2,2,0,0,2,2},{0,0,2,2,0,0,2,2,1,1,1,1,1,1,1,1},{0,0,1,1,0,0,1,1,2,2,1,1,2,2,1,1},
- {0,0,0,0,0,0,0,0,1,1,1,1,2,2,2,2},{0,0,0,0,1,1,1,1,1,1,1,1,2,2,2,2},{0,0,0,0,1,1,1,1,2,2,2,2,2,2,2,2},{0,0,1,2,0,0,1,2,0,0,1,2,0,0,1,2},
- {0,1,1,2,0,1,1,2,0,1,1,2,0,1,1,2},{0,1,2,2,0,1,2,2,0,1,2,2,0,1,2,2},{0,0,1,1,0,1,1,2,1,1,2,2,1,2,2,2},{0,0,1,1,2,0,0,1,2,2,0,0,2,2,2,0},
- {0,0,0,1,0,0,1,1,0,1,1,2,1,1,2,2},{0,1,1,1,0,0,1,1,2,0,0,1,2,2,0,0},{0,0,0,0,1,1,2,2,1,1,2,2,1,1,2,2},{0,0,2,2,0,0,2,2,0,0,2,2,1,1,1,1},
- {0,1,1,1,0,1,1,1,0,2,2,2,0,2,2,2},{0,0,0,1,0,0,0,1,2,2,2,1,2,2,2,1},{0,0,0,0,0,0,1,1,0,1,2,2,0,1,2,2},{0,0,0,0,1,1,0,0,2,2,1,0,2,2,1,0},
- {0,1,2,2,0,1,2,2,0,0,1,1,0,0,0,0},{0,0,1,2,0,0,1,2,1,1,2,2,2,2,2,2},{0,1,1,0,1,2,2,1,1,2,2,1,0,1,1,0},{0,0,0,0,0,1,1,0,1,2,2,1,1,2,2,1},
- {0,0,2,2,1,1,0,2,1,1,0,2,0,0,2,2},{0,1,1,0,0,1,1,0,2,0,0,2,2,2,2,2},{0,0,1,1,0,1,2,2,0,1,2,2,0,0,1,1},{0,0,0,0,2,0,0,0,2,2,1,1,2,2,2,1},
- {0,0,0,0,0,0,0,2,1,1,2,2,1,2,2,2},{0,2,2,2,0,0,2,2,0,0,1,2,0,0,1,1},{0,0,1,1,0,0,1,2,0,0,2,2,0,2,2,2},{0,1,2,0,0,1,2,0,0,1,2,0,0,1,2,0},
- {0,0,0,0,1,1,1,1,2,2,2,2,0,0,0,0},{0,1,2,0,1,2,0,1,2,0,1,2,0,1,2,0},{0,1,2,0,2,0,1,2,1,2,0,1,0,1,2,0},{0,0,1,1,2,2,0,0,1,1,2,2,0,0,1,1},
- {0,0,1,1,1,1,2,2,2,2,0,0,0,0,1,1},{0,1,0,1,0,1,0,1,2,2,2,2,2,2,2,2},{0,0,0,0,0,0,0,0,2,1,2,1,2,1,2,1},{0,0,2,2,1,1,2,2,0,0,2,2,1,1,2,2},
- {0,0,2,2,0,0,1,1,0,0,2,2,0,0,1,1},{0,2,2,0,1,2,2,1,0,2,2,0,1,2,2,1},{0,1,0,1,2,2,2,2,2,2,2,2,0,1,0,1},{0,0,0,0,2,1,2,1,2,1,2,1,2,1,2,1},
- {0,1,0,1,0,1,0,1,0,1,0,1,2,2,2,2},{0,2,2,2,0,1,1,1,0,2,2,2,0,1,1,1},{0,0,0,2,1,1,1,2,0,0,0,2,1,1,1,2},{0,0,0,0,2,1,1,2,2,1,1,2,2,1,1,2},
- {0,2,2,2,0,1,1,1,0,1,1,1,0,2,2,2},{0,0,0,2,1,1,1,2,1,1,1,2,0,0,0,2},{0,1,1,0,0,1,1,0,0,1,1,0,2,2,2,2},{0,0,0,0,0,0,0,0,2,1,1,2,2,1,1,2},
- {0,1,1,0,0,1,1,0,2,2,2,2,2,2,2,2},{0,0,2,2,0,0,1,1,0,0,1,1,0,0,2,2},{0,0,2,2,1,1,2,2,1,1,2,2,0,0,2,2},{0,0,0,0,0,0,0,0,0,0,0,0,2,1,1,2},
- {0,0,0,2,0,0,0,1,0,0,0,2,0,0,0,1},{0,2,2,2,1,2,2,2,0,2,2,2,1,2,2,2},{0,1,0,1,2,2,2,2,2,2,2,2,2,2,2,2},{0,1,1,1,2,0,1,1,2,2,0,1,2,2,2,0} };
-const uint8_t kAnchor2[64] = {15,15,15,15,15,15,15,15,15,15,15,15,15,15,15,15,15,2,8,2,2,8,8,15,2,8,2,2,8,8,2,2,15,15,6,8,2,8,15,15,2,8,2,2,2,15,15,6,6,2,6,8,15,15,2,2,15,15,15,15,15,2,2,15};
-const uint8_t kAnchor3a[64] = {3,3,15,15,8,3,15,15,8,8,6,6,6,5,3,3,3,3,8,15,3,3,6,10,5,8,8,6,8,5,15,15,8,15,3,5,6,10,8,15,15,3,15,5,15,15,15,15,3,15,5,5,5,8,5,10,5,10,8,13,15,12,3,3};
-const uint8_t kAnchor3b[64] = {15,8,8,3,15,15,3,8,15,15,15,15,15,15,15,8,15,8,15,3,15,8,15,8,3,15,6,10,15,15,10,8,15,3,15,10,10,8,9,10,6,15,8,15,3,6,6,8,15,3,15,15,15,15,15,15,15,15,15,15,3,15,15,8};
-const uint8_t kW2[4] = {0, 21, 43, 64}, kW3[8] = {0, 9, 18, 27, 37, 46, 55, 64}, kW4[16] = {0, 4, 9, 13, 17, 21, 26, 30, 34, 38, 43, 47, 51, 55, 60, 64};
-struct Bits { const uint8_t* p; uint32_t pos = 0; uint32_t Get(uint32_t n) { uint32_t v = 0; for (uint32_t i = 0; i < n; i++, pos++) v |= (uint32_t)((p[pos >> 3] >> (pos & 7)) & 1u) << i; return v; } };
-uint8_t Interp(uint32_t a, uint32_t b, uint32_t w) { return (uint8_t)((a * (64 - w) + b * w + 32) >> 6); }
-void Bc7Block(const uint8_t* blk, uint8_t out[16][4])
-{
-    uint32_t mode = 0; while (mode < 8 && !((blk[0] >> mode) & 1)) mode++;
-    if (mode >= 8) { std::memset(out, 0, 64); return; }
-    static const uint8_t NS[8] = {3, 2, 3, 2, 1, 1, 1, 2}, PB[8] = {4, 6, 6, 6, 0, 0, 0, 6}, RB[8] = {0, 0, 0, 0, 2, 2, 0, 0}, ISB[8] = {0, 0, 0, 0, 1, 0, 0, 0};
-    static const uint8_t CB[8] = {4, 6, 5, 7, 5, 7, 7, 5}, AB[8] = {0, 0, 0, 0, 6, 8, 7, 5}, EPB[8] = {1, 0, 0, 1, 0, 0, 1, 1}, SPB[8] = {0, 1, 0, 0, 0, 0, 0, 0};
-    static const uint8_t IB[8] = {3, 3, 2, 2, 2, 2, 4, 2}, IB2[8] = {0, 0, 0, 0, 3, 2, 0, 0};
-    Bits bs{blk, mode + 1};
-    const uint32_t ns = NS[mode], part = bs.Get(PB[mode]), rot = bs.Get(RB[mode]), isel = bs.Get(ISB[mode]);
-    uint32_t ep[6][4];
-    for (int c = 0; c < 3; c++) for (uint32_t e = 0; e < 2 * ns; e++) ep[e][c] = bs.Get(CB[mode]);
-    for (uint32_t e = 0; e < 2 * ns; e++) ep[e][3] = AB[mode] ? bs.Get(AB[mode]) : 255u;
-    uint32_t cbits = CB[mode], abits = AB[mode];
-    if (EPB[mode]) { for (uint32_t e = 0; e < 2 * ns; e++) { const uint32_t pbit = bs.Get(1); for (int c = 0; c < 3; c++) ep[e][c] = (ep[e][c] << 1) | pbit; if (abits) ep[e][3] = (ep[e][3] << 1) | pbit; } cbits++; if (abits) abits++; }
-    else if (SPB[mode]) { for (uint32_t s = 0; s < ns; s++) { const uint32_t pbit = bs.Get(1); for (uint32_t e = 2 * s; e < 2 * s + 2; e++) for (int c = 0; c < 3; c++) ep[e][c] = (ep[e][c] << 1) | pbit; } cbits++; }
-    for (uint32_t e = 0; e < 2 * ns; e++)
-    {
-        for (int c = 0; c < 3; c++) { ep[e][c] <<= (8 - cbits); ep[e][c] |= ep[e][c] >> cbits; }
-        if (abits) { ep[e][3] <<= (8 - abits); ep[e][3] |= ep[e][3] >> abits; }
-    }
-    auto subsetOf = [&](int i) -> uint32_t { return ns == 1 ? 0u : (ns == 2 ? kBc7Part2[part][i] : kBc7Part3[part][i]); };
-    auto isAnchor = [&](int i) { if (i == 0) return true; if (ns == 2) return i == kAnchor2[part]; if (ns == 3) return i == kAnchor3a[part] || i == kAnchor3b[part]; return false; };
-    uint32_t idx[16], idx2[16];
-    for (int i = 0; i < 16; i++) idx[i] = bs.Get(IB[mode] - (isAnchor(i) ? 1u : 0u));
-    if (IB2[mode]) for (int i = 0; i < 16; i++) idx2[i] = bs.Get(IB2[mode] - (i == 0 ? 1u : 0u));
-    auto weight = [](uint32_t bits, uint32_t i) -> uint32_t { return bits == 2 ? kW2[i] : (bits == 3 ? kW3[i] : kW4[i]); };
-    for (int i = 0; i < 16; i++)
-    {
-        const uint32_t s = subsetOf(i);
-        uint32_t cw, aw;
-        if (IB2[mode]) { const uint32_t w1 = weight(IB[mode], idx[i]), w2 = weight(IB2[mode], idx2[i]); cw = isel ? w2 : w1; aw = isel ? w1 : w2; }
-        else cw = aw = weight(IB[mode], idx[i]);
-        uint8_t px[4];
-        for (int c = 0; c < 3; c++) px[c] = Interp(ep[2 * s][c], ep[2 * s + 1][c], cw);
-        px[3] = Interp(ep[2 * s][3], ep[2 * s + 1][3], aw);
-        if (rot) { const uint8_t t = px[3]; px[3] = px[rot - 1]; px[rot - 1] = t; }
-        std::memcpy(out[i], px, 4);
-    }
-}
-void Bc4Block(const uint8_t* b, uint8_t out[16])
-{
-    uint32_t r[8]; r[0] = b[0]; r[1] = b[1];
-    if (r[0] > r[1]) for (int i = 1; i < 7; i++) r[1 + i] = ((7 - i) * r[0] + i * r[1]) / 7;
-    else { for (int i = 1; i < 5; i++) r[1 + i] = ((5 - i) * r[0] + i * r[1]) / 5; r[6] = 0; r[7] = 255; }
-    uint64_t bits = 0; for (int i = 0; i < 6; i++) bits |= (uint64_t)b[2 + i] << (8 * i);
-    for (int i = 0; i < 16; i++) out[i] = (uint8_t)r[(bits >> (3 * i)) & 7];
-}
+// BC7 (BPTC) and BC5: include/zr_bcn.h, the header the device form of the decode (zr_tu_texdecode.hip) compiles too
+using zrbc::Bc7Block; using zrbc::Bc4Block;
 
 // ------------------------------------------------------------------------------------------------ DDS -> texel heap entry
-struct Image { uint32_t w = 0, h = 0, mips = 0; int channels = 4; bool srgbFormat = false; std::vector<std::vector<uint8_t>> mip; };
-Image LoadDDS(const std::string& path)
+// keep: ZR_TEX_SRC_BC7 / ZR_TEX_SRC_BC5 -- a file of that encoding is NOT decoded: `chain` gets its blocks, every mip back to back as the file stores them,
+// and `mip` stays empty (ZRH_LOAD_KEEP_COMPRESSED); ZR_TEX_SRC_RAW decodes everything, as zrh_gltf_load does
+struct Image { uint32_t w = 0, h = 0, mips = 0; int channels = 4; bool srgbFormat = false; std::vector<std::vector<uint8_t>> mip; std::vector<uint8_t> chain; };
+Image LoadDDS(const std::string& path, int keep = ZR_TEX_SRC_RAW)
 {
     const std::vector<uint8_t> d = ReadFile(path);
     if (d.size() < 128 || std::memcmp(d.data(), "DDS ", 4)) Throw(path + ": not a DDS file");
@@ -272,12 +190,14 @@ Image LoadDDS(const std::string& path)
     if (fmt != 28 && fmt != 29 && fmt != 83 && fmt != 98 && fmt != 99) Throw(path + ": unsupported DXGI format " + std::to_string(fmt));
     img.channels = fmt == 83 ? 2 : 4; img.srgbFormat = (fmt == 29 || fmt == 99);
     uint32_t w = img.w, h = img.h;
+    const bool kept = (keep == ZR_TEX_SRC_BC7 && (fmt == 98 || fmt == 99)) || (keep == ZR_TEX_SRC_BC5 && fmt == 83);
     for (uint32_t m = 0; m < img.mips; m++)
     {
-        std::vector<uint8_t> px((size_t)w * h * img.channels);
         const uint32_t bw = (w + 3) / 4, bh = (h + 3) / 4;
         const size_t bytes = fmt == 28 || fmt == 29 ? (size_t)w * h * 4 : (size_t)bw * bh * 16;
         if (off + bytes > d.size()) Throw(path + ": truncated");
+        if (kept) { img.chain.insert(img.chain.end(), d.begin() + off, d.begin() + off + bytes); off += bytes; w = w > 1 ? w >> 1 : 1; h = h > 1 ? h >> 1 : 1; continue; }
+        std::vector<uint8_t> px((size_t)w * h * img.channels);
         if (fmt == 28 || fmt == 29) std::memcpy(px.data(), d.data() + off, bytes);
         else if (fmt == 83) zrh_bc5_decode(d.data() + off, w, h, px.data());
         else zrh_bc7_decode(d.data() + off, w, h, px.data());
@@ -295,6 +215,8 @@ struct zrh_scene_data
     std::vector<uint8_t> mask; std::vector<uint32_t> numTris; std::vector<zr_material> materials; std::vector<zr_emissive_triangle> emissives, emissivesInitial;
     std::vector<uint16_t> rho; uint32_t rhoDim[3] = {0, 0, 0};
     std::vector<zr_texture_desc> textures; std::vector<uint8_t> texels; uint32_t texOffsets[4] = {0, 0, 0, 0};
+    // ZRH_LOAD_KEEP_COMPRESSED: `texels` stays empty; texSources[i] names the chain of textures[i] in texPayload, heapBytes is the size of the heap they decode to
+    bool keepCompressed = false; std::vector<zr_texture_source> texSources; std::vector<uint8_t> texPayload; uint64_t heapBytes = 0; zr_texture_blocks blocks{};
     std::vector<float> prevWorld; uint32_t dirtyFirst = 0xffffffffu, dirtyEnd = 0;      // per-frame maintenance (zrh_scene_data_begin_frame / _set_instance_world)
     // the instances set_instance_world named this frame, each once, with their matrices; movedSlot[i] = where instance i stands in that list
     std::vector<uint32_t> movedIdx, movedSlot; std::vector<float> movedWorld;
@@ -313,6 +235,7 @@ struct zrh_scene_data
         desc.rho_lut = rho.data(); for (int k = 0; k < 3; k++) desc.rho_dim[k] = rhoDim[k];
         desc.textures = textures.empty() ? nullptr : textures.data(); desc.num_textures = (uint32_t)textures.size();
         desc.texels = texels.empty() ? nullptr : texels.data(); desc.texel_bytes = texels.size();
+        if (keepCompressed && !texSources.empty()) { desc.texel_bytes = heapBytes; blocks.sources = texSources.data(); blocks.payload = texPayload.data(); blocks.payload_bytes = texPayload.size(); }
     }
 };
 
@@ -420,17 +343,33 @@ void Load(const std::string& path, zrh_scene_data& sc)
         {
             const std::string uri = g.root.At("images").arr.at(image).StrOr("uri", "");
             if (uri.size() < 4 || uri.compare(uri.size() - 4, 4, ".dds")) Throw("glTF: image '" + uri + "': only .dds images are supported (the reference converts its assets with Tools/BCnCompressglTF)");
-            const Image img = LoadDDS(g.dir + "/" + uri);
             const bool colour = (kind == 0 || kind == 3);
+            // a colour map keeps its BC7 blocks and an RG map its BC5 blocks: those decode straight to the heap's format.  Anything else (an RGBA8 file, a
+            // 4-channel file in an RG slot) is decoded here as in the default mode and travels as a RAW chain
+            const Image img = LoadDDS(g.dir + "/" + uri, !sc.keepCompressed ? ZR_TEX_SRC_RAW : (colour ? ZR_TEX_SRC_BC7 : ZR_TEX_SRC_BC5));
             if (colour && img.channels != 4) Throw(uri + ": base colour / emissive maps must be 4-channel");
             zr_texture_desc td; std::memset(&td, 0, sizeof(td));
-            while (sc.texels.size() & 3) sc.texels.push_back(0);
-            td.offset = sc.texels.size(); td.width = (uint16_t)img.w; td.height = (uint16_t)img.h; td.num_mips = (uint8_t)img.mips;
+            // (in the compressed mode the heap's texels are written here too, into a scratch vector that becomes the RAW chain)
+            std::vector<uint8_t> raw; std::vector<uint8_t>& texels = sc.keepCompressed ? raw : sc.texels;
+            if (!sc.keepCompressed) while (sc.texels.size() & 3) sc.texels.push_back(0);
+            else sc.heapBytes = (sc.heapBytes + 3u) & ~(uint64_t)3u;
+            td.offset = sc.keepCompressed ? sc.heapBytes : (uint64_t)sc.texels.size(); td.width = (uint16_t)img.w; td.height = (uint16_t)img.h; td.num_mips = (uint8_t)img.mips;
             td.format = colour ? ZR_TEX_RGBA8_SRGB : ZR_TEX_RG8;
             for (const auto& mp : img.mip)
             {
-                if (!colour && img.channels == 4) { for (size_t i = 0; i < mp.size(); i += 4) { sc.texels.push_back(mp[i]); sc.texels.push_back(mp[i + 1]); } }      // RGBA8 normal / MR map: keep RG
-                else sc.texels.insert(sc.texels.end(), mp.begin(), mp.end());
+                if (!colour && img.channels == 4) { for (size_t i = 0; i < mp.size(); i += 4) { texels.push_back(mp[i]); texels.push_back(mp[i + 1]); } }      // RGBA8 normal / MR map: keep RG
+                else texels.insert(texels.end(), mp.begin(), mp.end());
+            }
+            if (sc.keepCompressed)
+            {
+                zr_texture_source src; std::memset(&src, 0, sizeof(src));
+                while (sc.texPayload.size() & 15) sc.texPayload.push_back(0);
+                src.offset = sc.texPayload.size(); src.encoding = img.chain.empty() ? (uint8_t)ZR_TEX_SRC_RAW : (uint8_t)(colour ? ZR_TEX_SRC_BC7 : ZR_TEX_SRC_BC5);
+                const std::vector<uint8_t>& chain = img.chain.empty() ? raw : img.chain;
+                sc.texPayload.insert(sc.texPayload.end(), chain.begin(), chain.end());
+                const zr_tex_mip last = zr_tex_mip_of(&td, td.num_mips - 1u);
+                sc.heapBytes = last.offset + (uint64_t)last.w * last.h * (colour ? 4u : 2u);
+                sc.texSources.push_back(src);
             }
             sc.textures.push_back(td);
         }
@@ -681,10 +620,15 @@ extern "C" {
 
 const char* zrh_scene_io_last_error(void) { return g_err.c_str(); }
 
-int zrh_gltf_load(const char* path, const uint16_t* rho, const uint32_t* rhoDim, zrh_scene_data** out)
+int zrh_gltf_load(const char* path, const uint16_t* rho, const uint32_t* rhoDim, zrh_scene_data** out) { return zrh_gltf_load_ex(path, rho, rhoDim, 0u, out); }
+// (a scene without textures has no blocks in either mode: its desc is the default mode's, and zr_scene_create takes it)
+const zr_texture_blocks* zrh_scene_data_texture_blocks(const zrh_scene_data* s) { return s && s->keepCompressed && !s->texSources.empty() ? &s->blocks : nullptr; }
+int zrh_gltf_load_ex(const char* path, const uint16_t* rho, const uint32_t* rhoDim, uint32_t flags, zrh_scene_data** out)
 {
     if (!path || !out) { g_err = "null argument"; return -1; }
+    if (flags & ~(uint32_t)ZRH_LOAD_KEEP_COMPRESSED) { g_err = "zrh_gltf_load_ex: unknown flag"; return -1; }
     std::unique_ptr<zrh_scene_data> sc(new zrh_scene_data());
+    sc->keepCompressed = (flags & ZRH_LOAD_KEEP_COMPRESSED) != 0;
     try { Load(path, *sc); }
     catch (const Error& e) { g_err = e.what; return -1; }
     catch (const std::exception& e) { g_err = std::string("glTF: malformed file (") + e.what() + ")"; return -1; }

@@ -8,12 +8,14 @@
 //   Source/ZetaCore/RayTracing/RtAccelerationStructure.cpp:318-380   MeshInstance quantisation: decomposeSRT (Math/MatrixFuncs.h:562-610) of
 //       the world matrix -> unorm4 rotation, half3 scale, float3 translation
 //   Assets.cpp / Tools/BCnCompressglTF       DDS material textures; here BC7 / BC5 / RGBA8 DDS files are decoded once at load to the texel
-//       heap of zr_scene_desc (zr_wire.h: the ABI takes decoded texels and defines the filtering)
+//       heap of zr_scene_desc (zr_wire.h: the ABI takes decoded texels and defines the filtering), by include/zr_bcn.h -- or kept as blocks
+//       for zr_scene_create_compressed, which runs the same header on the device (ZRH_LOAD_KEEP_COMPRESSED)
 // No HIP dependency: the library loads on machines without a GPU.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include "../../include/zr_wire.h"
+#include "../../include/zetaray_amd.h"      // zr_texture_source / zr_texture_blocks (declarations only: this library links no HIP)
 
 extern "C" {
 typedef struct zrh_scene_data zrh_scene_data;      // owns every array its zr_scene_desc points to
@@ -21,6 +23,15 @@ typedef struct zrh_scene_data zrh_scene_data;      // owns every array its zr_sc
 // Loads <path>.gltf (+ its external .bin buffers and .dds images).  rho_lut / rho_dim: the GGX reflectance LUT to attach (Assets/LUT/rho.dds
 // payload; copied).  Returns 0 and a handle, or -1 (zrh_scene_io_last_error()).
 int zrh_gltf_load(const char* path, const uint16_t* rho_lut, const uint32_t* rho_dim3, zrh_scene_data** out);
+// ... with flags.  ZRH_LOAD_KEEP_COMPRESSED: the .dds payloads are not decoded.  A BC7 file bound as a base colour / emissive map and a BC5 file bound
+// as a normal / metallic-roughness map keep their blocks (the whole mip chain as the file stores it, copied 16-byte aligned into one payload); any other
+// file is decoded as in the default mode and carried as a RAW chain.  zr_scene_desc.texels is then null and texel_bytes the size of the heap the chains
+// decode to -- the desc zr_scene_create_compressed takes together with zrh_scene_data_texture_blocks (null in the default mode, and for a file
+// without textures, whose desc zr_scene_create takes in either mode).  The zr_texture_desc
+// records, and the heap once decoded (include/zr_bcn.h), equal the default mode's in every byte.
+enum { ZRH_LOAD_KEEP_COMPRESSED = 1u };
+int zrh_gltf_load_ex(const char* path, const uint16_t* rho_lut, const uint32_t* rho_dim3, uint32_t flags, zrh_scene_data** out);
+const zr_texture_blocks* zrh_scene_data_texture_blocks(const zrh_scene_data* s);
 const char* zrh_scene_io_last_error(void);
 const zr_scene_desc* zrh_scene_data_desc(const zrh_scene_data* s);
 // the four descriptor-table offsets for cbFrameConstants (base colour, normal, metallic-roughness, emissive maps) of the scene's texture heap

@@ -140,13 +140,83 @@ class Scene:
         self.rho_dim = (0, 0, 0)
         self.textures = np.zeros(0, wire.TEXTURE_DESC)     # material texture heap (include/zr_wire.h zr_texture_desc)
         self.texels = np.zeros(0, np.uint8)
+        # block-compressed sources (add_texture_blocks, load_gltf_native(textures="compressed")): texture_sources[i] names the chain of textures[i] in
+        # texture_payload, texel_heap_bytes is the size of the heap the chains decode to.  api.Scene hands them to zr_scene_create_compressed, which
+        # decodes on the device; decode_textures() fills `texels` on the host for the oracle and the host executor
+        self.texture_sources = np.zeros(0, wire.TEXTURE_SOURCE)
+        self.texture_payload = np.zeros(0, np.uint8)
+        self.texel_heap_bytes = 0
         self._desc = None
+
+    @staticmethod
+    def _chain_layout(width, height, num_mips, fmt, encoding):
+        """(source bytes, texel bytes) of each mip of a chain"""
+        bpp = 2 if fmt == wire.TEX_RG8 else 4
+        out = []
+        for m in range(num_mips):
+            w, h = max(1, width >> m), max(1, height >> m)
+            out.append((w, h, w * h * bpp if encoding == wire.TEX_SRC_RAW else ((w + 3) // 4) * ((h + 3) // 4) * 16, w * h * bpp))
+        return out
+
+    def add_texture_blocks(self, blocks, width, height, num_mips, fmt, encoding):
+        """Appends one texture from its stored chain -- BC7 / BC5 blocks (wire.TEX_SRC_BC7 needs an RGBA8 format, TEX_SRC_BC5 RG8), or uncompressed texels
+        (TEX_SRC_RAW) -- mips back to back in DDS order, mip m of max(1, w >> m) x max(1, h >> m) texels.  Nothing is decoded.  Returns its heap index."""
+        blocks = np.ascontiguousarray(blocks, np.uint8).reshape(-1)
+        if len(self.textures) != len(self.texture_sources):
+            raise ValueError("the scene already holds decoded textures: a heap is either all sources or all texels")
+        if encoding not in (wire.TEX_SRC_RAW, wire.TEX_SRC_BC7, wire.TEX_SRC_BC5) or (encoding == wire.TEX_SRC_BC7 and fmt == wire.TEX_RG8) or \
+                (encoding == wire.TEX_SRC_BC5 and fmt != wire.TEX_RG8):
+            raise ValueError("encoding %r does not decode to format %r" % (encoding, fmt))
+        layout = self._chain_layout(width, height, num_mips, fmt, encoding)
+        if num_mips < 1 or len(blocks) != sum(l[2] for l in layout):
+            raise ValueError("a %d x %d chain of %d mips is %d bytes, not %d" % (width, height, num_mips, sum(l[2] for l in layout), len(blocks)))
+        src = np.zeros(1, wire.TEXTURE_SOURCE)
+        src["offset"], src["encoding"] = (len(self.texture_payload) + 15) // 16 * 16, encoding
+        self.texture_payload = np.concatenate([self.texture_payload, np.zeros(int(src["offset"][0]) - len(self.texture_payload), np.uint8), blocks])
+        d = np.zeros(1, wire.TEXTURE_DESC)
+        off = (self.texel_heap_bytes + 3) // 4 * 4
+        d["offset"], d["width"], d["height"], d["num_mips"], d["format"] = off, width, height, num_mips, fmt
+        self.texel_heap_bytes = off + sum(l[3] for l in layout)
+        self.textures = np.concatenate([self.textures, d])
+        self.texture_sources = np.concatenate([self.texture_sources, src])
+        return len(self.textures) - 1
+
+    def decode_textures(self):
+        """Fills `texels` from the sources on the host, with the loader's decoder (zrh_bc7_decode / zrh_bc5_decode): the heap zr_scene_create_compressed
+        produces on the device.  The sources stay."""
+        import ctypes as C
+        L = _sceneio_lib()
+        for f in (L.zrh_bc7_decode, L.zrh_bc5_decode):
+            f.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        self.texture_payload = np.ascontiguousarray(self.texture_payload, np.uint8)
+        heap = np.zeros(self.texel_heap_bytes, np.uint8)
+        for t, s in zip(self.textures, self.texture_sources):
+            enc, at, to = int(s["encoding"]), int(s["offset"]), int(t["offset"])
+            for w, h, nsrc, ndst in self._chain_layout(int(t["width"]), int(t["height"]), int(t["num_mips"]), int(t["format"]), enc):
+                if enc == wire.TEX_SRC_RAW:
+                    heap[to:to + ndst] = self.texture_payload[at:at + nsrc]
+                else:
+                    (L.zrh_bc7_decode if enc == wire.TEX_SRC_BC7 else L.zrh_bc5_decode)(self.texture_payload.ctypes.data + at, w, h, heap.ctypes.data + to)
+                at, to = at + nsrc, to + ndst
+        self.texels = heap
+
+    def texture_blocks(self):
+        """wire.TextureBlocks (zr_texture_blocks) over the sources and the payload; None for a scene without sources"""
+        if len(self.texture_sources) == 0:
+            return None
+        self.texture_sources = np.ascontiguousarray(self.texture_sources)
+        self.texture_payload = np.ascontiguousarray(self.texture_payload, np.uint8)
+        b = wire.TextureBlocks()
+        b.sources, b.payload, b.payload_bytes = self.texture_sources.ctypes.data, self.texture_payload.ctypes.data, len(self.texture_payload)
+        return b
 
     def add_texture(self, image, fmt=wire.TEX_RGBA8_SRGB, mips=True):
         """Appends one texture (H x W x C uint8, C = 4 for RGBA8 formats, 2 for RG8) with its full mip chain and returns
         its index in the heap.  Mips are 2x2 box filtered on the stored bytes (round half up; an odd size drops its last
         row / column -- floor convention, as the reference's offline texconv does); the reference ships them inside the
         .dds (Tools/BCnCompressglTF), here they are the caller's data like any other texel."""
+        if len(self.texture_sources):
+            raise ValueError("the scene holds block-compressed texture sources: a heap is either all sources or all texels")
         img = np.ascontiguousarray(image, np.uint8)
         ch = 2 if fmt == wire.TEX_RG8 else 4
         assert img.ndim == 3 and img.shape[2] == ch
@@ -194,7 +264,7 @@ class Scene:
         d.textures = self.textures.ctypes.data if len(self.textures) else None
         d.num_textures = len(self.textures)
         d.texels = self.texels.ctypes.data if len(self.texels) else None
-        d.texel_bytes = len(self.texels)
+        d.texel_bytes = len(self.texels) if len(self.texels) or not len(self.texture_sources) else self.texel_heap_bytes
         self._desc = d
         return d
 
@@ -434,6 +504,9 @@ def _sceneio_lib():
     if "_SCENEIO" not in globals() or _SCENEIO is None:
         L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libzetaray_sceneio.so"))
         L.zrh_gltf_load.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.zrh_gltf_load_ex.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.zrh_scene_data_texture_blocks.restype = C.POINTER(wire.TextureBlocks)
+        L.zrh_scene_data_texture_blocks.argtypes = [C.c_void_p]
         L.zrh_scene_io_last_error.restype = C.c_char_p
         L.zrh_scene_data_desc.restype = C.POINTER(wire.SceneDesc)
         L.zrh_scene_data_desc.argtypes = [C.c_void_p]
@@ -444,18 +517,25 @@ def _sceneio_lib():
     return _SCENEIO
 
 
-def load_gltf_native(path, rho=None):
+LOAD_KEEP_COMPRESSED = 1      # ZRH_LOAD_KEEP_COMPRESSED
+
+
+def load_gltf_native(path, rho=None, textures="decoded"):
     """glTF -> wire formats through the C++ loader (MeshInstance quantisation by decomposeSRT of the world matrix, node hierarchies, matrix
     nodes, DDS material textures decoded to the texel heap).  Returns (Scene, texture-table offsets dict for set_texture_heap_offsets).
     A file with "animations" (LINEAR translation / rotation / scale channels) also gives sc.animation, a wire.AnimDesc over the dynamic closure of
-    its node hierarchy (Scene.set_animation / Scene.animate in api.py), and sc.emissives_initial, the object-space light records; None without."""
+    its node hierarchy (Scene.set_animation / Scene.animate in api.py), and sc.emissives_initial, the object-space light records; None without.
+    textures="compressed": the .dds payloads are not decoded (ZRH_LOAD_KEEP_COMPRESSED): sc.texels stays empty, sc.texture_sources / sc.texture_payload
+    carry the blocks and api.Scene decodes them on the device (zr_scene_create_compressed); sc.decode_textures() makes the texels on the host."""
     import ctypes as C
+    if textures not in ("decoded", "compressed"):
+        raise ValueError("textures must be 'decoded' or 'compressed', not %r" % (textures,))
     L = _sceneio_lib()
     rho_data, rho_dim = load_rho_default() if rho is None else rho
     rho_data = np.ascontiguousarray(rho_data, np.uint16)
     dims = (C.c_uint32 * 3)(*rho_dim)
     h = C.c_void_p()
-    if L.zrh_gltf_load(os.fsencode(path), rho_data.ctypes.data, dims, C.byref(h)) != 0:
+    if L.zrh_gltf_load_ex(os.fsencode(path), rho_data.ctypes.data, dims, LOAD_KEEP_COMPRESSED if textures == "compressed" else 0, C.byref(h)) != 0:
         raise RuntimeError(L.zrh_scene_io_last_error().decode())
     try:
         d = L.zrh_scene_data_desc(h).contents
@@ -476,6 +556,11 @@ def load_gltf_native(path, rho=None):
         sc.emissives = arr(d.emissives, d.num_emissives, wire.EMISSIVE_TRI)
         sc.textures = arr(d.textures, d.num_textures, wire.TEXTURE_DESC)
         sc.texels = arr(d.texels, d.texel_bytes, np.uint8)
+        tb = L.zrh_scene_data_texture_blocks(h)
+        if tb:
+            sc.texture_sources = arr(tb.contents.sources, d.num_textures, wire.TEXTURE_SOURCE)
+            sc.texture_payload = arr(tb.contents.payload, tb.contents.payload_bytes, np.uint8)
+            sc.texel_heap_bytes = int(d.texel_bytes)
         sc.rho, sc.rho_dim = rho_data, tuple(rho_dim)
         sc.animation = None
         L.zrh_scene_data_animation.argtypes = [C.c_void_p]
@@ -496,7 +581,10 @@ def load_gltf_native(path, rho=None):
 
 
 def save_npz(sc: Scene, path):
-    """Wire-format fixture (tests/golden/*.npz); the rho LUT is not stored (it ships in zetaray_amd/assets)."""
+    """Wire-format fixture (tests/golden/*.npz); the rho LUT is not stored (it ships in zetaray_amd/assets).  The fixture holds texels, not texture
+    sources: a scene with block-compressed sources must have run decode_textures() first."""
+    if len(sc.textures) and len(getattr(sc, "texture_sources", ())) and len(sc.texels) != sc.texel_heap_bytes:
+        raise ValueError("save_npz: the scene's textures are block-compressed sources; call decode_textures() first")
     np.savez_compressed(path, vertices=sc.vertices, indices=sc.indices, instances=sc.instances,
                         instance_to_world=sc.instance_to_world, instance_mask=sc.instance_mask,
                         instance_num_tris=sc.instance_num_tris, materials=sc.materials, emissives=sc.emissives,

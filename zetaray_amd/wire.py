@@ -66,6 +66,9 @@ SUBGROUP_ALL = 3
 INSTANCE_NON_OPAQUE = 0x80      # extra bit of instance_mask: geometry without the OPAQUE flag (primary-ray alpha test)
 TEX_RGBA8_SRGB, TEX_RGBA8, TEX_RG8 = 0, 1, 2
 TEXTURE_DESC = np.dtype([("offset", "<u8"), ("width", "<u2"), ("height", "<u2"), ("num_mips", "u1"), ("format", "u1"), ("pad", "<u2")])
+# block-compressed texture sources (zr_texture_source / zr_texture_blocks, include/zetaray_amd.h; the decode is include/zr_bcn.h)
+TEX_SRC_RAW, TEX_SRC_BC7, TEX_SRC_BC5 = 0, 1, 2
+TEXTURE_SOURCE = np.dtype([("offset", "<u8"), ("encoding", "u1"), ("pad", "u1", 7)])
 # keyframe animation (zr_keyframe / zr_anim_node / zr_anim_desc, include/zr_wire.h)
 ANIM_ROOT = 0xFFFFFFFF
 KEYFRAME = np.dtype([("scale", "<f4", 3), ("rotation", "<f4", 4), ("translation", "<f4", 3), ("time", "<f4")])
@@ -95,6 +98,10 @@ class SceneDesc(C.Structure):
         ("textures", C.c_void_p), ("num_textures", C.c_uint32),
         ("texels", C.c_void_p), ("texel_bytes", C.c_uint64),
     ]
+
+
+class TextureBlocks(C.Structure):
+    _fields_ = [("sources", C.c_void_p), ("payload", C.c_void_p), ("payload_bytes", C.c_uint64)]
 
 
 class AnimDescC(C.Structure):
