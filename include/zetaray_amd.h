@@ -303,9 +303,14 @@ int zr_scene_destroy(zr_scene* scene);
  * the bus: the blocks, a quarter (BC7) or half (BC5) of the bytes of the texels they decode to.
  * zr_texture_source i belongs to zr_texture_desc i and names its WHOLE mip chain in `payload`: mips back to back in DDS order, mip m of
  * max(1, w >> m) x max(1, h >> m) texels as ceil(w / 4) x ceil(h / 4) 16-byte blocks in row-major order (BC7, BC5), or as the uncompressed texels
- * the heap holds (RAW).  BC7 decodes to 4 B / texel and needs format RGBA8 or RGBA8_SRGB, BC5 to 2 B / texel (r, g) and needs RG8.  `offset` must be a
- * multiple of 16 for BC7 / BC5 and of 4 for RAW.  Not part of zr_wire_layout. */
-enum { ZR_TEX_SRC_RAW = 0, ZR_TEX_SRC_BC7 = 1, ZR_TEX_SRC_BC5 = 2 };
+ * the heap holds (RAW); a RAW_MIP0 source names level 0 only (below).  BC7 decodes to 4 B / texel and needs format RGBA8 or RGBA8_SRGB, BC5 to 2 B / texel (r, g) and needs RG8.  `offset` must be a
+ * multiple of 16 for BC7 / BC5 and of 4 for RAW / RAW_MIP0.  Not part of zr_wire_layout. */
+enum { ZR_TEX_SRC_RAW = 0, ZR_TEX_SRC_BC7 = 1, ZR_TEX_SRC_BC5 = 2,
+       /* level 0 ALONE, as the uncompressed texels the heap holds (what a PNG image of a glTF decodes to); `offset` a multiple of 4.  Levels
+        * 1 .. num_mips - 1 are generated on the device, each from the stored bytes of the level above it, by the box filter include/zr_mipgen.h states
+        * (zr_tu_mipgen.hip: one launch per level for all such textures of the scene, behind the block decode).  num_mips == 1 generates nothing.
+        * More than 2^32 - 1 texels in one generated level of all such textures together are refused like the other malformed inputs. */
+       ZR_TEX_SRC_RAW_MIP0 = 8 };
 typedef struct zr_texture_source { uint64_t offset; uint8_t encoding; uint8_t pad[7]; } zr_texture_source;
 typedef struct zr_texture_blocks { const zr_texture_source* sources; const uint8_t* payload; uint64_t payload_bytes; } zr_texture_blocks;
 /* zr_scene_create with the texel heap produced on the device: desc->texels must be NULL, desc->texel_bytes is the size of the decoded heap and
@@ -313,7 +318,7 @@ typedef struct zr_texture_blocks { const zr_texture_source* sources; const uint8
  * one device copy per texture) into a zero-filled heap, and released.  The heap then equals, in every byte, the one zr_scene_create holds when handed
  * the host-decoded texels (zrh_bc7_decode / zrh_bc5_decode) with zeros between the chains.  ZR_ERR_INVALID_ARG, with nothing created and *out
  * untouched, for: a null blocks / sources / payload; texels != NULL; an unknown encoding; BC7 on a format that is not RGBA8 / RGBA8_SRGB; BC5 on a
- * format that is not RG8; a misaligned source offset; a chain that ends beyond payload_bytes; more than 2^32 - 1 blocks in all; and every
+ * format that is not RG8; a misaligned source offset; a chain (RAW_MIP0: a level 0) that ends beyond payload_bytes; more than 2^32 - 1 blocks in all; and every
  * zr_texture_desc zr_scene_create refuses.  A scene without textures takes no blocks argument checks beyond the null checks.
  * Textures cannot be replaced after creation. */
 int zr_scene_create_compressed(int device, const zr_scene_desc* desc, const zr_texture_blocks* blocks, zr_scene** out);
@@ -322,6 +327,12 @@ int zr_scene_create_compressed(int device, const zr_scene_desc* desc, const zr_t
  * the n chains and nothing else.  Refuses what zr_scene_create_compressed refuses. */
 int zr_bcn_decode_device(int device, void* hip_stream, const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n,
                          const void* d_payload, uint64_t payload_bytes, void* d_texels, uint64_t texel_bytes);
+/* The mip generation alone, on caller buffers (tests and tools): levels 1 .. num_mips - 1 of the n chains `descs` (host pointer) names in d_texels
+ * (4-byte aligned, on `device`), in place, from their level 0.  ENQUEUES on `hip_stream` and returns: one launch per level, the job table in a
+ * stream-ordered allocation.  Writes the generated levels and nothing else.  ZR_ERR_INVALID_ARG for null pointers with n > 0 and for every
+ * zr_texture_desc zr_scene_create refuses (an unknown format, a zero dimension, no mips, an offset that is no multiple of 4, a chain that ends
+ * beyond texel_bytes).  zr_bcn_decode_device does not take ZR_TEX_SRC_RAW_MIP0 sources: their level 0 is the caller's copy, the rest is this call. */
+int zr_mipgen_device(int device, void* hip_stream, const zr_texture_desc* descs, uint32_t n, void* d_texels, uint64_t texel_bytes);
 /* read-back of bytes [first_byte, first_byte + count) of the scene's texel heap, for tests and tools; waits for `hip_stream` */
 int zr_scene_get_texels(const zr_scene* scene, void* hip_stream, uint8_t* out, uint64_t first_byte, uint64_t count);
 /* Per-frame update of dynamic instances (TLAS::FillMeshInstanceData + the TLAS rebuild, RtAccelerationStructure.cpp:318-506, 708-787;

@@ -12,6 +12,7 @@
 #   tiles              tools/tile_balance.py on Cornell + atrium (per-tile times of the 8-way split on one device)
 #   alias [ARGS]       tools/alias_bench.py: one stale-table PRELIGHTING render per frame, host / host-deferred / device build -> ${TAG}_alias_build.json
 #   texdecode [ARGS]   tools/texture_decode_bench.py: scene creation with host-decoded texels against zr_scene_create_compressed -> ${TAG}_texture_decode.json
+#   mipgen [ARGS]      tools/mipgen_bench.py: zr_scene_create_compressed with full RAW chains against RAW_MIP0 sources (mips generated on the device) -> ${TAG}_mipgen.json
 #   prof LIB           section profiler (-DZR_PROF build LIB) on Cornell + atrium -> ${TAG}_section_profile_*.json
 R=${GRAFT_REPO_ROOT:-$PWD}; TAG=${TAG:-r06}; OUT=$R/gpurun_out; mkdir -p $OUT
 task=$1; shift
@@ -107,6 +108,10 @@ alias)
 texdecode)
   cd $R; set -o pipefail
   timeout 1100 python tools/texture_decode_bench.py "$@" 2> $OUT/${TAG}_texdecode_err.log | tail -1 | tee $OUT/${TAG}_texture_decode.json || { echo "texture_decode_bench: requirement missed or failed"; tail -5 $OUT/${TAG}_texdecode_err.log; exit 1; }
+  ;;
+mipgen)
+  cd $R; set -o pipefail
+  timeout 1100 python tools/mipgen_bench.py "$@" 2> $OUT/${TAG}_mipgen_err.log | tail -1 | tee $OUT/${TAG}_mipgen.json || { echo "mipgen_bench: requirement missed or failed"; tail -5 $OUT/${TAG}_mipgen_err.log; exit 1; }
   ;;
 *) echo "unknown task $task"; exit 2;;
 esac

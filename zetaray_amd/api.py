@@ -65,7 +65,7 @@ EXPORTS = [
     "zr_scene_set_object_emissives", "zr_scene_has_object_emissives", "zr_scene_move_instances", "zr_scene_move_instances_async", "zr_scene_get_instances", "zr_scene_get_emissives",
     "zr_scene_set_animation", "zr_scene_animate", "zr_scene_animate_async",
     "zr_scene_set_alias_build", "zr_alias_table_build_device", "zr_pass_get_emissive_powers",
-    "zr_scene_create_compressed", "zr_bcn_decode_device", "zr_scene_get_texels",
+    "zr_scene_create_compressed", "zr_bcn_decode_device", "zr_scene_get_texels", "zr_mipgen_device",
 ]
 ALIAS_BUILD_HOST, ALIAS_BUILD_DEVICE = 0, 1
 ALIAS_BUILD_MODES = {"host": ALIAS_BUILD_HOST, "device": ALIAS_BUILD_DEVICE}
@@ -113,6 +113,7 @@ def lib():
         L.zr_scene_create_compressed.argtypes = [i32, vp, vp, vp]
         L.zr_bcn_decode_device.argtypes = [i32, vp, vp, vp, u32, vp, C.c_uint64, vp, C.c_uint64]
         L.zr_scene_get_texels.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64]
+        L.zr_mipgen_device.argtypes = [i32, vp, vp, u32, vp, C.c_uint64]
         L.zr_scene_set_alias_table.argtypes = [vp, vp, u32]
         L.zr_alias_table_build.argtypes = [vp, u32, u32, vp]
         L.zr_scene_get_alias_table.argtypes = [vp, vp, u32]
@@ -207,6 +208,22 @@ def bcn_decode_device(descs, sources, payload, texel_bytes, fill=0, device=0, st
     _check(lib().zr_bcn_decode_device(device, stream, descs.ctypes.data, sources.ctypes.data, len(descs), d_payload.data_ptr(), len(payload), d_out.data_ptr(), int(texel_bytes)))
     torch.cuda.synchronize(device)
     return d_out.cpu().numpy().copy()
+
+
+def mipgen_device(descs, texels, device=0, stream=None):
+    """zr_mipgen_device: levels 1 .. of the chains `descs` (wire.TEXTURE_DESC) names, generated on the device in a copy of the heap `texels` (uint8) from
+    their level 0; returns the heap.  stream: a torch.cuda.Stream (None: the null stream); read back after that stream's synchronize"""
+    import torch
+    descs = np.ascontiguousarray(descs, wire.TEXTURE_DESC)
+    texels = np.ascontiguousarray(texels, np.uint8).reshape(-1)
+    d_heap = torch.from_numpy(texels.copy()).to(f"cuda:{device}")
+    torch.cuda.synchronize(device)
+    _check(lib().zr_mipgen_device(device, stream.cuda_stream if stream is not None else None, descs.ctypes.data, len(descs), d_heap.data_ptr(), len(texels)))
+    if stream is not None:
+        stream.synchronize()
+    else:
+        torch.cuda.synchronize(device)
+    return d_heap.cpu().numpy().copy()
 
 
 class Scene:

@@ -79,6 +79,8 @@ namespace zr { size_t AliasScratchWords(uint32_t n);      // zr_tu_alias.hip
                hipError_t LaunchAliasBuild(hipStream_t st, const float* power, uint32_t n, zr_alias_entry* out, uint64_t* scratch); }
 #include "../../include/zr_bcn.h"
 namespace zr { hipError_t LaunchBcnDecode(hipStream_t st, const zrbc::Job* jobs, uint32_t numJobs, uint32_t numBlocks, const uint8_t* payload, uint8_t* texels); }   // zr_tu_texdecode.hip
+#include "../../include/zr_mipgen.h"
+namespace zr { hipError_t LaunchMipLevel(hipStream_t st, const zrmg::Job* jobs, uint32_t numJobs, uint32_t numItems, uint8_t* texels); }   // zr_tu_mipgen.hip
 // the ReSTIR PT kernels are compiled in zr_tu_rpt_[a-i].hip (see zr_kernels.h)
 ZR_RPT_GROUPS_PRODUCT(extern template)
 #ifdef ZR_EXPERIMENTS
@@ -1404,25 +1406,29 @@ static bool TextureDescOk(const zr_texture_desc& t, uint64_t texelBytes)
 // texture order, and one copy per RAW chain.  Everything either entry point refuses about descs and sources is refused here, before anything is allocated
 // chains: the bytes [first, second) of the heap each texture's chain fills, in texture order (everything else is what a caller sees as padding)
 struct BcnPlan { std::vector<zrbc::Job> jobs; struct Copy { uint64_t src, dst, bytes; }; std::vector<Copy> copies; uint32_t numBlocks = 0;
+                 std::vector<uint32_t> mip0;      // the textures whose source is level 0 alone (ZR_TEX_SRC_RAW_MIP0): their other levels are generated (MipPlan)
                  std::vector<std::pair<uint64_t, uint64_t>> chains; };
-static int PlanBcnDecode(const char* fn, const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n, uint64_t payloadBytes, uint64_t texelBytes, BcnPlan& plan)
+static int PlanBcnDecode(const char* fn, const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n, uint64_t payloadBytes, uint64_t texelBytes, BcnPlan& plan,
+    bool allowMip0)
 {
     uint64_t blocks = 0;
     for (uint32_t i = 0; i < n; i++)
     {
         const zr_texture_desc& t = descs[i]; const zr_texture_source& src = sources[i];
         if (!TextureDescOk(t, texelBytes)) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is malformed or lies outside the texel blob", fn, i);
-        if (src.encoding > ZR_TEX_SRC_BC5) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u has the unknown source encoding %u", fn, i, (unsigned)src.encoding);
+        const bool mip0 = allowMip0 && src.encoding == ZR_TEX_SRC_RAW_MIP0, raw = src.encoding == ZR_TEX_SRC_RAW || mip0;
+        if (src.encoding > ZR_TEX_SRC_BC5 && !mip0) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u has the unknown source encoding %u", fn, i, (unsigned)src.encoding);
         if (src.encoding == ZR_TEX_SRC_BC7 && t.format != ZR_TEX_RGBA8 && t.format != ZR_TEX_RGBA8_SRGB) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is BC7 but its format is not RGBA8 / RGBA8_SRGB", fn, i);
         if (src.encoding == ZR_TEX_SRC_BC5 && t.format != ZR_TEX_RG8) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is BC5 but its format is not RG8", fn, i);
-        if (src.offset & (src.encoding == ZR_TEX_SRC_RAW ? 3u : 15u)) return Fail(ZR_ERR_INVALID_ARG, "%s: the source offset of texture %u is not a multiple of %u", fn, i, src.encoding == ZR_TEX_SRC_RAW ? 4u : 16u);
+        if (src.offset & (raw ? 3u : 15u)) return Fail(ZR_ERR_INVALID_ARG, "%s: the source offset of texture %u is not a multiple of %u", fn, i, raw ? 4u : 16u);
         const uint32_t bpp = t.format == ZR_TEX_RG8 ? 2u : 4u;
         uint64_t at = src.offset;      // (a chain is < 2^37 bytes, so `at` cannot wrap before it is compared)
         if (at > payloadBytes) return Fail(ZR_ERR_INVALID_ARG, "%s: the chain of texture %u starts beyond the payload", fn, i);
         for (uint32_t m = 0; m < t.num_mips; m++)
         {
             const zr_tex_mip mip = zr_tex_mip_of(&t, m);
-            if (src.encoding == ZR_TEX_SRC_RAW) { at += (uint64_t)mip.w * mip.h * bpp; continue; }
+            if (mip0 && m) break;      // (the source ends with level 0)
+            if (raw) { at += (uint64_t)mip.w * mip.h * bpp; continue; }
             zrbc::Job j; j.src = at; j.dst = mip.offset; j.w = mip.w; j.h = mip.h; j.first_block = (uint32_t)blocks; j.encoding = src.encoding;
             const uint64_t nb = (uint64_t)((mip.w + 3u) >> 2) * ((mip.h + 3u) >> 2);
             blocks += nb; at += 16u * nb;
@@ -1430,7 +1436,8 @@ static int PlanBcnDecode(const char* fn, const zr_texture_desc* descs, const zr_
             plan.jobs.push_back(j);
         }
         if (at > payloadBytes) return Fail(ZR_ERR_INVALID_ARG, "%s: the chain of texture %u ends beyond the payload (%llu > %llu bytes)", fn, i, (unsigned long long)at, (unsigned long long)payloadBytes);
-        if (src.encoding == ZR_TEX_SRC_RAW) plan.copies.push_back({src.offset, t.offset, at - src.offset});
+        if (raw) plan.copies.push_back({src.offset, t.offset, at - src.offset});
+        if (mip0 && t.num_mips > 1u) plan.mip0.push_back(i);
         const zr_tex_mip last = zr_tex_mip_of(&t, t.num_mips - 1u);
         plan.chains.push_back({t.offset, last.offset + (uint64_t)last.w * last.h * bpp});
     }
@@ -1442,6 +1449,39 @@ static int RunBcnPlan(hipStream_t st, const BcnPlan& plan, const zrbc::Job* dJob
 {
     if (!plan.jobs.empty()) HIP_TRY(zr::LaunchBcnDecode(st, dJobs, (uint32_t)plan.jobs.size(), plan.numBlocks, dPayload, dTexels));
     for (const BcnPlan::Copy& c : plan.copies) if (c.bytes) HIP_TRY(hipMemcpyAsync(dTexels + c.dst, dPayload + c.src, c.bytes, hipMemcpyDeviceToDevice, st));
+    return ZR_OK;
+}
+// What the mip generation of n textures takes (zr_scene_create_compressed for its RAW_MIP0 sources, zr_mipgen_device): one zrmg::Job per generated level of
+// every texture, grouped by level -- levels[k - 1] names the jobs of the launch that writes level k -- each group in texture order.
+// which: the indices into descs of the n textures (null: 0 .. n - 1); the descs passed TextureDescOk
+struct MipPlan { std::vector<zrmg::Job> jobs; struct Level { uint32_t firstJob, numJobs, numItems; }; std::vector<Level> levels; };
+static int PlanMipGen(const char* fn, const zr_texture_desc* descs, const uint32_t* which, uint32_t n, MipPlan& plan)
+{
+    uint32_t maxMips = 0;
+    for (uint32_t i = 0; i < n; i++) maxMips = std::max<uint32_t>(maxMips, descs[which ? which[i] : i].num_mips);
+    for (uint32_t k = 1; k < maxMips; k++)
+    {
+        MipPlan::Level lv = {(uint32_t)plan.jobs.size(), 0u, 0u};
+        uint64_t items = 0;
+        for (uint32_t i = 0; i < n; i++)
+        {
+            const zr_texture_desc& t = descs[which ? which[i] : i];
+            if (t.num_mips <= k) continue;
+            const zr_tex_mip s = zr_tex_mip_of(&t, k - 1u), d = zr_tex_mip_of(&t, k);
+            zrmg::Job j; j.src = s.offset; j.dst = d.offset; j.sw = s.w; j.sh = s.h; j.dw = d.w; j.dh = d.h; j.format = t.format; j.first_item = (uint32_t)items;
+            items += (uint64_t)d.w * d.h;
+            if (items > 0xffffffffull) return Fail(ZR_ERR_INVALID_ARG, "%s: more than 2^32 - 1 texels in mip level %u", fn, k);
+            plan.jobs.push_back(j);
+        }
+        lv.numJobs = (uint32_t)plan.jobs.size() - lv.firstJob; lv.numItems = (uint32_t)items;
+        plan.levels.push_back(lv);
+    }
+    return ZR_OK;
+}
+// enqueues the plan's launches on `st`, top down: dJobs = the plan's jobs on the device
+static int RunMipPlan(hipStream_t st, const MipPlan& plan, const zrmg::Job* dJobs, uint8_t* dTexels)
+{
+    for (const MipPlan::Level& lv : plan.levels) if (lv.numItems) HIP_TRY(zr::LaunchMipLevel(st, dJobs + lv.firstJob, lv.numJobs, lv.numItems, dTexels));
     return ZR_OK;
 }
 // zero-fills what no chain of the plan covers in a heap of `bytes` bytes (the decode and the copies write every byte of a chain): the padding between
@@ -1465,15 +1505,16 @@ static int SceneCreate(const char* fn, int device, const zr_scene_desc* d, const
     if (!d || !out) return Fail(ZR_ERR_INVALID_ARG, "%s: null argument", fn);
     if (!d->vertices || !d->indices || !d->instances || !d->materials || !d->rho_lut || !d->instance_to_world || !d->instance_mask || !d->instance_num_tris)
         return Fail(ZR_ERR_INVALID_ARG, "%s: incomplete scene description", fn);
-    BcnPlan plan;
+    BcnPlan plan; MipPlan mipPlan;
     if (blocks)
     {   // refused before the acceleration structure is built
         if (!blocks->sources || !blocks->payload) return Fail(ZR_ERR_INVALID_ARG, "%s: null sources / payload", fn);
         if (d->texels) return Fail(ZR_ERR_INVALID_ARG, "%s: desc->texels must be null: the heap is decoded from the blocks", fn);
         if (d->num_textures && !d->textures) return Fail(ZR_ERR_INVALID_ARG, "%s: num_textures > 0 without textures", fn);
-        if (int pr = PlanBcnDecode(fn, d->textures, blocks->sources, d->num_textures, blocks->payload_bytes, d->texel_bytes, plan)) return pr;
+        if (int pr = PlanBcnDecode(fn, d->textures, blocks->sources, d->num_textures, blocks->payload_bytes, d->texel_bytes, plan, true)) return pr;
+        if (int pr = PlanMipGen(fn, d->textures, plan.mip0.data(), (uint32_t)plan.mip0.size(), mipPlan)) return pr;
     }
-    DevBuf<uint8_t> payload; DevBuf<zrbc::Job> jobs;      // (live until the synchronize at the end)
+    DevBuf<uint8_t> payload; DevBuf<zrbc::Job> jobs; DevBuf<zrmg::Job> mipJobs;      // (live until the synchronize at the end)
     int r = RequireDevice(device);
     if (r) return r;
     std::unique_ptr<zr_scene> s(new (std::nothrow) zr_scene());      // (every early return below frees it)
@@ -1505,6 +1546,8 @@ static int SceneCreate(const char* fn, int device, const zr_scene_desc* d, const
         if ((r = s->texDescs.Upload(d->textures, d->num_textures)) || (r = payload.Upload(blocks->payload, blocks->payload_bytes)) ||
             (r = s->texels.Alloc(d->texel_bytes)) || (r = ClearHeapGaps(plan, s->texels.p, d->texel_bytes)) || (r = jobs.Upload(plan.jobs.data(), plan.jobs.size())) ||
             (r = RunBcnPlan(nullptr, plan, jobs.p, payload.p, s->texels.p))) return r;
+        // ... and behind the decode and the copies of level 0, the other levels of the RAW_MIP0 chains: one launch per level
+        if (!mipPlan.jobs.empty() && ((r = mipJobs.Upload(mipPlan.jobs.data(), mipPlan.jobs.size())) || (r = RunMipPlan(nullptr, mipPlan, mipJobs.p, s->texels.p)))) return r;
     }
     else if (d->num_textures)
     {
@@ -1577,7 +1620,7 @@ int zr_bcn_decode_device(int device, void* stream, const zr_texture_desc* descs,
     if (!descs || !sources || !d_payload || !d_texels || n == 0) return Fail(ZR_ERR_INVALID_ARG, "%s: null/empty input", fn);
     if (((uintptr_t)d_payload & 15u) || ((uintptr_t)d_texels & 3u)) return Fail(ZR_ERR_INVALID_ARG, "%s: d_payload must be 16-byte and d_texels 4-byte aligned", fn);
     BcnPlan plan;
-    if (int r = PlanBcnDecode(fn, descs, sources, n, payload_bytes, texel_bytes, plan)) return r;
+    if (int r = PlanBcnDecode(fn, descs, sources, n, payload_bytes, texel_bytes, plan, false)) return r;
     if (hipSetDevice(device) != hipSuccess) return Fail(ZR_ERR_NO_DEVICE, "%s: no usable HIP device %d", fn, device);
     hipStream_t st = (hipStream_t)stream;
     zrbc::Job* dJobs = nullptr;
@@ -1596,6 +1639,30 @@ int zr_bcn_decode_device(int device, void* stream, const zr_texture_desc* descs,
         const hipError_t e = hipFreeAsync(dJobs, st);
         if (e != hipSuccess && !r) return Fail(ZR_ERR_HIP, "%s: hipFreeAsync failed: %s", fn, hipGetErrorString(e));
     }
+    return r;
+}
+// the level launches of zr_scene_create_compressed on caller buffers; enqueues only, like zr_bcn_decode_device
+int zr_mipgen_device(int device, void* stream, const zr_texture_desc* descs, uint32_t n, void* d_texels, uint64_t texel_bytes)
+{
+    const char* fn = "zr_mipgen_device";
+    if (n == 0) return ZR_OK;
+    if (!descs || !d_texels) return Fail(ZR_ERR_INVALID_ARG, "%s: null argument", fn);
+    if ((uintptr_t)d_texels & 3u) return Fail(ZR_ERR_INVALID_ARG, "%s: d_texels must be 4-byte aligned", fn);
+    for (uint32_t i = 0; i < n; i++) if (!TextureDescOk(descs[i], texel_bytes)) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is malformed or lies outside the texel blob", fn, i);
+    MipPlan plan;
+    if (int r = PlanMipGen(fn, descs, nullptr, n, plan)) return r;
+    if (plan.jobs.empty()) return ZR_OK;
+    if (hipSetDevice(device) != hipSuccess) return Fail(ZR_ERR_NO_DEVICE, "%s: no usable HIP device %d", fn, device);
+    hipStream_t st = (hipStream_t)stream;
+    // (the table's copy from the plan's pageable vector: see zr_bcn_decode_device)
+    zrmg::Job* dJobs = nullptr;
+    const size_t bytes = plan.jobs.size() * sizeof(zrmg::Job);
+    HIP_TRY(hipMallocAsync((void**)&dJobs, bytes, st));
+    hipError_t e = hipMemcpyAsync(dJobs, plan.jobs.data(), bytes, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) { (void)hipFreeAsync(dJobs, st); return Fail(ZR_ERR_HIP, "%s: the copy of the job table failed: %s", fn, hipGetErrorString(e)); }
+    const int r = RunMipPlan(st, plan, dJobs, (uint8_t*)d_texels);
+    e = hipFreeAsync(dJobs, st);      // freed behind whatever was enqueued, on the error path too
+    if (e != hipSuccess && !r) return Fail(ZR_ERR_HIP, "%s: hipFreeAsync failed: %s", fn, hipGetErrorString(e));
     return r;
 }
 int zr_scene_get_texels(const zr_scene* s, void* stream, uint8_t* out, uint64_t first, uint64_t count)

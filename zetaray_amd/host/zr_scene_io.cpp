@@ -7,6 +7,7 @@
 #include "../../include/zr_anim.h"
 #include "../../include/zr_bcn.h"
 #include "../../include/zr_texture.h"
+#include "../../include/zr_mipgen.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -207,6 +208,271 @@ Image LoadDDS(const std::string& path, int keep = ZR_TEX_SRC_RAW)
     return img;
 }
 
+// ------------------------------------------------------------------------------------------------ PNG -> RGBA8
+// What a stock glTF carries.  No link dependency: inflate (RFC 1951: stored, fixed and dynamic Huffman blocks), the zlib wrapper with its Adler-32
+// (RFC 1950) and the chunk CRC-32 are written here.  Every read is bounds-checked: a corrupted file is refused or decoded within the buffers.
+uint32_t Crc32(const uint8_t* p, size_t n)
+{
+    struct Table { uint32_t t[256]; Table() { for (uint32_t i = 0; i < 256u; i++) { uint32_t c = i; for (int k = 0; k < 8; k++) c = (c & 1u) ? 0xedb88320u ^ (c >> 1) : c >> 1; t[i] = c; } } };
+    static const Table table;
+    uint32_t c = 0xffffffffu;
+    for (size_t i = 0; i < n; i++) c = table.t[(c ^ p[i]) & 0xffu] ^ (c >> 8);
+    return c ^ 0xffffffffu;
+}
+uint32_t Adler32(const uint8_t* p, size_t n)
+{
+    uint32_t a = 1u, b = 0u;
+    while (n)
+    {
+        const size_t k = n < 5552u ? n : 5552u;      // the longest run whose sums stay below 2^32
+        for (size_t i = 0; i < k; i++) { a += p[i]; b += a; }
+        a %= 65521u; b %= 65521u; p += k; n -= k;
+    }
+    return (b << 16) | a;
+}
+// a zlib stream -> `out`, which must come to exactly `expect` bytes
+struct Inflater
+{
+    const std::string& name; const uint8_t* in; size_t inLen; std::vector<uint8_t>& out; size_t expect;
+    size_t inPos = 0; uint32_t bitBuf = 0; int bitCnt = 0;
+    struct Huff { uint16_t count[16]; uint16_t symbol[288]; };
+    [[noreturn]] void Bad(const char* why) { Throw(name + ": " + why); }
+    uint32_t Bits(int need)      // need <= 16; fewer than 8 bits are ever left in bitBuf
+    {
+        uint32_t v = bitBuf;
+        while (bitCnt < need) { if (inPos >= inLen) Bad("truncated: the compressed data ends early"); v |= (uint32_t)in[inPos++] << bitCnt; bitCnt += 8; }
+        bitBuf = v >> need; bitCnt -= need;
+        return v & ((1u << need) - 1u);
+    }
+    void Build(Huff& h, const uint8_t* lengths, int n)
+    {
+        std::memset(&h, 0, sizeof(h));
+        for (int i = 0; i < n; i++) h.count[lengths[i]]++;
+        int left = 1;
+        for (int len = 1; len < 16; len++) { left <<= 1; left -= h.count[len]; if (left < 0) Bad("invalid deflate data: over-subscribed Huffman code"); }
+        uint16_t offs[16]; offs[1] = 0;
+        for (int len = 1; len < 15; len++) offs[len + 1] = (uint16_t)(offs[len] + h.count[len]);
+        for (int i = 0; i < n; i++) if (lengths[i]) h.symbol[offs[lengths[i]]++] = (uint16_t)i;
+    }
+    int Decode(const Huff& h)
+    {
+        int code = 0, first = 0, index = 0;
+        for (int len = 1; len < 16; len++)
+        {
+            code |= (int)Bits(1);
+            const int count = h.count[len];
+            if (code - count < first) return h.symbol[index + (code - first)];
+            index += count; first += count; first <<= 1; code <<= 1;
+        }
+        Bad("invalid deflate data: no such Huffman code");
+    }
+    void Put(uint8_t b) { if (out.size() >= expect) Bad("the compressed data holds more than the image"); out.push_back(b); }
+    void Codes(const Huff& lencode, const Huff& distcode)
+    {
+        static const uint16_t lens[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
+        static const uint8_t lext[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
+        static const uint16_t dists[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
+        static const uint8_t dext[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
+        for (;;)
+        {
+            int sym = Decode(lencode);
+            if (sym < 256) { Put((uint8_t)sym); continue; }
+            if (sym == 256) return;
+            sym -= 257;
+            if (sym >= 29) Bad("invalid deflate data: bad length symbol");
+            const size_t len = lens[sym] + Bits(lext[sym]);
+            const int ds = Decode(distcode);
+            if (ds >= 30) Bad("invalid deflate data: bad distance symbol");
+            const size_t dist = dists[ds] + Bits(dext[ds]);
+            if (dist > out.size()) Bad("invalid deflate data: distance beyond the start");
+            if (len > expect - out.size()) Bad("the compressed data holds more than the image");
+            for (size_t i = 0; i < len; i++) out.push_back(out[out.size() - dist]);
+        }
+    }
+    void Run()
+    {
+        if (inLen < 2) Bad("truncated: no zlib header");
+        const uint32_t cmf = in[0], flg = in[1];
+        if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u || (flg & 32u)) Bad("invalid zlib header");
+        inPos = 2;
+        for (uint32_t last = 0; !last;)
+        {
+            last = Bits(1);
+            const uint32_t type = Bits(2);
+            if (type == 0)
+            {
+                bitBuf = 0; bitCnt = 0;
+                if (inLen - inPos < 4) Bad("truncated: the compressed data ends early");
+                const uint32_t len = in[inPos] | (in[inPos + 1] << 8), nlen = in[inPos + 2] | (in[inPos + 3] << 8);
+                inPos += 4;
+                if ((len ^ 0xffffu) != nlen) Bad("invalid deflate data: stored block length");
+                if (len > inLen - inPos) Bad("truncated: the compressed data ends early");
+                if (len > expect - out.size()) Bad("the compressed data holds more than the image");
+                out.insert(out.end(), in + inPos, in + inPos + len); inPos += len;
+            }
+            else if (type == 1)
+            {
+                uint8_t l[288 + 30];
+                for (int i = 0; i < 288; i++) l[i] = i < 144 ? 8 : (i < 256 ? 9 : (i < 280 ? 7 : 8));
+                for (int i = 0; i < 30; i++) l[288 + i] = 5;
+                Huff lencode, distcode; Build(lencode, l, 288); Build(distcode, l + 288, 30);
+                Codes(lencode, distcode);
+            }
+            else if (type == 2)
+            {
+                static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+                const int nlen = (int)Bits(5) + 257, ndist = (int)Bits(5) + 1, ncode = (int)Bits(4) + 4;
+                if (nlen > 286 || ndist > 30) Bad("invalid deflate data: too many codes");
+                uint8_t l[286 + 30]; std::memset(l, 0, sizeof(l));
+                for (int i = 0; i < ncode; i++) l[order[i]] = (uint8_t)Bits(3);
+                Huff lencode, distcode; Build(lencode, l, 19);
+                std::memset(l, 0, sizeof(l));
+                for (int i = 0; i < nlen + ndist;)
+                {
+                    const int sym = Decode(lencode);
+                    if (sym < 16) { l[i++] = (uint8_t)sym; continue; }
+                    uint8_t v = 0; int rep;
+                    if (sym == 16) { if (i == 0) Bad("invalid deflate data: repeat without a length"); v = l[i - 1]; rep = 3 + (int)Bits(2); }
+                    else if (sym == 17) rep = 3 + (int)Bits(3);
+                    else rep = 11 + (int)Bits(7);
+                    if (i + rep > nlen + ndist) Bad("invalid deflate data: too many lengths");
+                    while (rep--) l[i++] = v;
+                }
+                if (!l[256]) Bad("invalid deflate data: no end-of-block code");
+                uint8_t dl[30]; std::memcpy(dl, l + nlen, (size_t)ndist);
+                Build(lencode, l, nlen); Build(distcode, dl, ndist);
+                Codes(lencode, distcode);
+            }
+            else Bad("invalid deflate data: block type 3");
+        }
+        if (out.size() != expect) Bad("truncated: the compressed data holds less than the image");
+        if (inLen - inPos < 4) Bad("truncated: no Adler-32");
+        const uint32_t want = ((uint32_t)in[inPos] << 24) | ((uint32_t)in[inPos + 1] << 16) | ((uint32_t)in[inPos + 2] << 8) | in[inPos + 3];
+        if (Adler32(out.data(), out.size()) != want) Bad("bad Adler-32");
+    }
+};
+
+// bit depth 8 and 16 (the high byte is kept), colour types 0, 2, 3 (with tRNS), 4 and 6, the five row filters; no interlacing
+struct Png { uint32_t w = 0, h = 0; std::vector<uint8_t> rgba; };
+Png DecodePng(const std::string& name, const uint8_t* d, size_t n)
+{
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    if (n < 8 || std::memcmp(d, sig, 8)) Throw(name + ": not a PNG file");
+    auto be32 = [&](size_t off) { return ((uint32_t)d[off] << 24) | ((uint32_t)d[off + 1] << 16) | ((uint32_t)d[off + 2] << 8) | (uint32_t)d[off + 3]; };
+    Png png; uint32_t depth = 0, ctype = 0; bool haveHdr = false, end = false;
+    std::vector<uint8_t> idat, plte, trns;
+    for (size_t at = 8; !end;)
+    {
+        if (n - at < 12) Throw(name + ": truncated: the file ends without IEND");
+        const uint32_t len = be32(at);
+        if (len > n - at - 12) Throw(name + ": truncated: a chunk is longer than the file");
+        const uint8_t* type = d + at + 4; const uint8_t* body = d + at + 8;
+        if (Crc32(type, 4u + len) != be32(at + 8 + len)) Throw(name + ": bad CRC in chunk " + std::string((const char*)type, 4));
+        const bool is = haveHdr || !std::memcmp(type, "IHDR", 4);
+        if (!is) Throw(name + ": the first chunk is not IHDR");
+        if (!std::memcmp(type, "IHDR", 4))
+        {
+            if (haveHdr || len != 13) Throw(name + ": invalid IHDR");
+            png.w = be32(at + 8); png.h = be32(at + 12); depth = body[8]; ctype = body[9];
+            if (png.w == 0 || png.h == 0 || png.w > 65535u || png.h > 65535u) Throw(name + ": texture dimensions must be in [1, 65535]");
+            if (depth == 1 || depth == 2 || depth == 4) Throw(name + ": bit depths below 8 are not supported");
+            if ((depth != 8 && depth != 16) || (ctype != 0 && ctype != 2 && ctype != 3 && ctype != 4 && ctype != 6) || (ctype == 3 && depth != 8)) Throw(name + ": invalid bit depth / colour type");
+            if (body[10] != 0 || body[11] != 0) Throw(name + ": invalid compression / filter method");
+            if (body[12] == 1) Throw(name + ": interlaced PNG files are not supported");
+            if (body[12] != 0) Throw(name + ": invalid interlace method");
+            haveHdr = true;
+        }
+        else if (!std::memcmp(type, "PLTE", 4)) { if (len % 3u || len > 768u || len == 0) Throw(name + ": invalid PLTE"); plte.assign(body, body + len); }
+        else if (!std::memcmp(type, "tRNS", 4)) trns.assign(body, body + len);
+        else if (!std::memcmp(type, "IDAT", 4)) idat.insert(idat.end(), body, body + len);
+        else if (!std::memcmp(type, "IEND", 4)) end = true;
+        at += 12u + (size_t)len;
+    }
+    if (!haveHdr || idat.empty()) Throw(name + ": truncated: no image data");
+    const uint32_t channels = ctype == 0 ? 1u : (ctype == 2 ? 3u : (ctype == 3 ? 1u : (ctype == 4 ? 2u : 4u))), bps = depth / 8u, bpp = channels * bps;
+    const size_t stride = (size_t)png.w * bpp, expect = (size_t)png.h * (stride + 1u);
+    // (deflate expands by at most 1032 : 1: a header that promises more than the data can hold is refused before anything is allocated)
+    if (expect / 1032u > idat.size()) Throw(name + ": truncated: the compressed data holds less than the image");
+    if (ctype == 3 && plte.empty()) Throw(name + ": palette image without PLTE");
+    if ((ctype == 0 && !trns.empty() && trns.size() != 2) || (ctype == 2 && !trns.empty() && trns.size() != 6) || (ctype == 3 && trns.size() > plte.size() / 3u)) Throw(name + ": invalid tRNS");
+    std::vector<uint8_t> raw;
+    Inflater inf{name, idat.data(), idat.size(), raw, expect};
+    inf.Run();
+    // the row filters, in place
+    for (uint32_t y = 0; y < png.h; y++)
+    {
+        uint8_t* cur = raw.data() + (size_t)y * (stride + 1u) + 1u; const uint8_t* prev = y ? cur - (stride + 1u) : nullptr;
+        const uint8_t f = cur[-1];
+        if (f > 4) Throw(name + ": invalid row filter");
+        for (size_t i = 0; i < stride; i++)
+        {
+            const int a = i >= bpp ? cur[i - bpp] : 0, b = prev ? prev[i] : 0, c = (prev && i >= bpp) ? prev[i - bpp] : 0;
+            int pred = 0;
+            if (f == 1) pred = a;
+            else if (f == 2) pred = b;
+            else if (f == 3) pred = (a + b) >> 1;
+            else if (f == 4) { const int p = a + b - c, pa = std::abs(p - a), pb = std::abs(p - b), pc = std::abs(p - c); pred = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c); }
+            cur[i] = (uint8_t)(cur[i] + pred);
+        }
+    }
+    png.rgba.resize((size_t)png.w * png.h * 4u);
+    for (uint32_t y = 0; y < png.h; y++)
+    {
+        const uint8_t* row = raw.data() + (size_t)y * (stride + 1u) + 1u; uint8_t* o = png.rgba.data() + (size_t)y * png.w * 4u;
+        for (uint32_t x = 0; x < png.w; x++, o += 4)
+        {
+            const uint8_t* s = row + (size_t)x * bpp;      // sample k is s[k bps]: the high byte of a 16-bit sample comes first
+            if (ctype == 3)
+            {
+                const uint32_t idx = s[0];
+                if (idx >= plte.size() / 3u) Throw(name + ": palette index out of range");
+                o[0] = plte[3u * idx]; o[1] = plte[3u * idx + 1u]; o[2] = plte[3u * idx + 2u]; o[3] = idx < trns.size() ? trns[idx] : 255;
+            }
+            else if (ctype == 0 || ctype == 4)
+            {
+                o[0] = o[1] = o[2] = s[0];
+                if (ctype == 4) o[3] = s[bps];
+                else o[3] = (!trns.empty() && (bps == 2 ? (s[0] == trns[0] && s[1] == trns[1]) : s[0] == trns[1])) ? 0 : 255;
+            }
+            else
+            {
+                o[0] = s[0]; o[1] = s[bps]; o[2] = s[2u * bps];
+                if (ctype == 6) o[3] = s[3u * bps];
+                else
+                {
+                    bool key = !trns.empty();
+                    for (uint32_t k = 0; key && k < 3u; k++) key = bps == 2 ? (s[2u * k] == trns[2u * k] && s[2u * k + 1u] == trns[2u * k + 1u]) : s[k] == trns[2u * k + 1u];
+                    o[3] = key ? 0 : 255;
+                }
+            }
+        }
+    }
+    return png;
+}
+bool EndsWith(const std::string& s, const char* ext)      // ASCII case-insensitive
+{
+    const size_t n = std::strlen(ext);
+    if (s.size() < n) return false;
+    for (size_t i = 0; i < n; i++) { char c = s[s.size() - n + i]; if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a'); if (c != ext[i]) return false; }
+    return true;
+}
+// a .png image as the one-level Image of its slot: RGBA8 as decoded, or the two channels an RG8 slot keeps (r0, r1 of the file's R, G, B, A)
+Image LoadPNG(const std::string& path, bool colour, uint32_t r0, uint32_t r1)
+{
+    const std::vector<uint8_t> d = ReadFile(path);
+    Png png = DecodePng(path, d.data(), d.size());
+    Image img; img.w = png.w; img.h = png.h; img.channels = colour ? 4 : 2; img.srgbFormat = colour;
+    img.mips = 1; for (uint32_t m = png.w > png.h ? png.w : png.h; m > 1u; m >>= 1) img.mips++;      // 1 + floor(log2(max(w, h)))
+    if (colour) img.mip.push_back(std::move(png.rgba));
+    else
+    {
+        std::vector<uint8_t> rg((size_t)png.w * png.h * 2u);
+        for (size_t i = 0; i < (size_t)png.w * png.h; i++) { rg[2u * i] = png.rgba[4u * i + r0]; rg[2u * i + 1u] = png.rgba[4u * i + r1]; }
+        img.mip.push_back(std::move(rg));
+    }
+    return img;
+}
+
 } // namespace
 
 struct zrh_scene_data
@@ -342,11 +608,17 @@ void Load(const std::string& path, zrh_scene_data& sc)
         for (int image : table[kind])
         {
             const std::string uri = g.root.At("images").arr.at(image).StrOr("uri", "");
-            if (uri.size() < 4 || uri.compare(uri.size() - 4, 4, ".dds")) Throw("glTF: image '" + uri + "': only .dds images are supported (the reference converts its assets with Tools/BCnCompressglTF)");
+            const bool png = EndsWith(uri, ".png");
+            if (EndsWith(uri, ".jpg") || EndsWith(uri, ".jpeg")) Throw("glTF: image '" + uri + "': JPEG images are not supported (.dds and .png are)");
+            if (!png && !EndsWith(uri, ".dds")) Throw("glTF: image '" + uri + "': only .dds and .png images are supported");
             const bool colour = (kind == 0 || kind == 3);
             // a colour map keeps its BC7 blocks and an RG map its BC5 blocks: those decode straight to the heap's format.  Anything else (an RGBA8 file, a
-            // 4-channel file in an RG slot) is decoded here as in the default mode and travels as a RAW chain
-            const Image img = LoadDDS(g.dir + "/" + uri, !sc.keepCompressed ? ZR_TEX_SRC_RAW : (colour ? ZR_TEX_SRC_BC7 : ZR_TEX_SRC_BC5));
+            // 4-channel file in an RG slot) is decoded here as in the default mode and travels as a RAW chain.
+            // A .png is level 0 alone: RGBA8 for a colour map, the file's (R, G) for a normal map and its (B, G) for a metallic-roughness map (glTF keeps
+            // roughness in G and metalness in B; the reference's converter moves them to (metalness, roughness) with -swizzle bg).  Its full chain,
+            // 1 + floor(log2(max(w, h))) levels, is generated by include/zr_mipgen.h: here (default mode), or on the device from a RAW_MIP0 source
+            const Image img = png ? LoadPNG(g.dir + "/" + uri, colour, kind == 2 ? 2u : 0u, 1u)
+                                  : LoadDDS(g.dir + "/" + uri, !sc.keepCompressed ? ZR_TEX_SRC_RAW : (colour ? ZR_TEX_SRC_BC7 : ZR_TEX_SRC_BC5));
             if (colour && img.channels != 4) Throw(uri + ": base colour / emissive maps must be 4-channel");
             zr_texture_desc td; std::memset(&td, 0, sizeof(td));
             // (in the compressed mode the heap's texels are written here too, into a scratch vector that becomes the RAW chain)
@@ -360,11 +632,17 @@ void Load(const std::string& path, zrh_scene_data& sc)
                 if (!colour && img.channels == 4) { for (size_t i = 0; i < mp.size(); i += 4) { texels.push_back(mp[i]); texels.push_back(mp[i + 1]); } }      // RGBA8 normal / MR map: keep RG
                 else texels.insert(texels.end(), mp.begin(), mp.end());
             }
+            if (png && !sc.keepCompressed)
+            {   // the other levels, from level 0 in place
+                const zr_tex_mip last = zr_tex_mip_of(&td, td.num_mips - 1u);
+                sc.texels.resize(last.offset + (size_t)last.w * last.h * (colour ? 4u : 2u));
+                zrmg::GenerateChain(&td, sc.texels.data());
+            }
             if (sc.keepCompressed)
             {
                 zr_texture_source src; std::memset(&src, 0, sizeof(src));
                 while (sc.texPayload.size() & 15) sc.texPayload.push_back(0);
-                src.offset = sc.texPayload.size(); src.encoding = img.chain.empty() ? (uint8_t)ZR_TEX_SRC_RAW : (uint8_t)(colour ? ZR_TEX_SRC_BC7 : ZR_TEX_SRC_BC5);
+                src.offset = sc.texPayload.size(); src.encoding = png ? (uint8_t)ZR_TEX_SRC_RAW_MIP0 : img.chain.empty() ? (uint8_t)ZR_TEX_SRC_RAW : (uint8_t)(colour ? ZR_TEX_SRC_BC7 : ZR_TEX_SRC_BC5);
                 const std::vector<uint8_t>& chain = img.chain.empty() ? raw : img.chain;
                 sc.texPayload.insert(sc.texPayload.end(), chain.begin(), chain.end());
                 const zr_tex_mip last = zr_tex_mip_of(&td, td.num_mips - 1u);
@@ -744,6 +1022,33 @@ const zr_emissive_triangle* zrh_scene_data_initial_emissives(const zrh_scene_dat
 void zrh_pack_emissive_triangle(const float* v0, const float* v1, const float* v2, const float* uv6, uint32_t factor, uint32_t tex, uint16_t strength, uint32_t id,
     int doubleSided, zr_emissive_triangle* out) { PackEmissiveTriangle(v0, v1, v2, uv6, factor, tex, strength, id, doubleSided != 0, *out); }
 
+int zrh_png_decode(const char* name, const uint8_t* data, size_t bytes, uint32_t* w, uint32_t* h, uint8_t* rgba8, size_t capacity)
+{
+    if (!data || !w || !h) { g_err = "zrh_png_decode: null argument"; return -1; }
+    try
+    {
+        const Png png = DecodePng(name ? name : "<memory>", data, bytes);
+        *w = png.w; *h = png.h;
+        if (rgba8)
+        {
+            if (capacity < png.rgba.size()) Throw(std::string(name ? name : "<memory>") + ": the output buffer is smaller than the image");
+            std::memcpy(rgba8, png.rgba.data(), png.rgba.size());
+        }
+    }
+    catch (const Error& e) { g_err = e.what; return -1; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+    return 0;
+}
+int zrh_mip_generate(const zr_texture_desc* descs, uint32_t n, uint8_t* texels)
+{
+    if (n && (!descs || !texels)) { g_err = "zrh_mip_generate: null argument"; return -1; }
+    for (uint32_t i = 0; i < n; i++)
+    {
+        if (!descs[i].num_mips || !descs[i].width || !descs[i].height || descs[i].format > ZR_TEX_RG8) { g_err = "zrh_mip_generate: texture " + std::to_string(i) + " is malformed"; return -1; }
+        zrmg::GenerateChain(&descs[i], texels);
+    }
+    return 0;
+}
 int zrh_bc7_decode(const uint8_t* blocks, uint32_t w, uint32_t h, uint8_t* rgba)
 {
     const uint32_t bw = (w + 3) / 4, bh = (h + 3) / 4;

@@ -29,6 +29,10 @@ int zrh_gltf_load(const char* path, const uint16_t* rho_lut, const uint32_t* rho
 // decode to -- the desc zr_scene_create_compressed takes together with zrh_scene_data_texture_blocks (null in the default mode, and for a file
 // without textures, whose desc zr_scene_create takes in either mode).  The zr_texture_desc
 // records, and the heap once decoded (include/zr_bcn.h), equal the default mode's in every byte.
+// A .png image (what stock glTF files carry; a file may mix .dds and .png) is level 0 alone: RGBA8 in a base colour / emissive slot (RGBA8_SRGB), the
+// file's (R, G) in a normal slot and its (B, G) in a metallic-roughness slot (RG8; the reference converter's -swizzle bg), with
+// num_mips = 1 + floor(log2(max(w, h))).  The default mode generates the chain here, by include/zr_mipgen.h; ZRH_LOAD_KEEP_COMPRESSED hands level 0 over
+// as a ZR_TEX_SRC_RAW_MIP0 source and the same header runs on the device.  .jpg / .jpeg images are refused: JPEG is not supported.
 enum { ZRH_LOAD_KEEP_COMPRESSED = 1u };
 int zrh_gltf_load_ex(const char* path, const uint16_t* rho_lut, const uint32_t* rho_dim3, uint32_t flags, zrh_scene_data** out);
 const zr_texture_blocks* zrh_scene_data_texture_blocks(const zrh_scene_data* s);
@@ -89,4 +93,12 @@ const zr_emissive_triangle* zrh_scene_data_initial_emissives(const zrh_scene_dat
 // BC7 / BC5 block decompression: w x h texels (multiples of 4 not required) -> RGBA8 / RG8 rows top-down
 int zrh_bc7_decode(const uint8_t* blocks, uint32_t w, uint32_t h, uint8_t* rgba8);
 int zrh_bc5_decode(const uint8_t* blocks, uint32_t w, uint32_t h, uint8_t* rg8);
+// A PNG file in memory -> *w x *h RGBA8 texels, rows top-down (rgba8 null: the size alone; else capacity >= 4 w h bytes).  Bit depth 8, and 16 keeping
+// the high byte; colour types 0, 2, 3 (with tRNS), 4 and 6 (grey becomes r = g = b, a missing alpha 255); the five row filters.  Inflate, Adler-32 and
+// CRC-32 are the loader's own: no link dependency.  -1 with a message that starts with `name` (zrh_scene_io_last_error()) for an interlaced file, a bit
+// depth below 8, a bad CRC or Adler-32, truncated data, and dimensions outside [1, 65535].
+int zrh_png_decode(const char* name, const uint8_t* data, size_t bytes, uint32_t* w, uint32_t* h, uint8_t* rgba8, size_t capacity);
+// levels 1 .. num_mips - 1 of the n chains `descs` names in `texels`, in place, from their level 0: include/zr_mipgen.h on the host, the bytes
+// zr_mipgen_device and zr_scene_create_compressed (ZR_TEX_SRC_RAW_MIP0) produce on the device
+int zrh_mip_generate(const zr_texture_desc* descs, uint32_t n, uint8_t* texels);
 }

@@ -150,21 +150,26 @@ class Scene:
 
     @staticmethod
     def _chain_layout(width, height, num_mips, fmt, encoding):
-        """(source bytes, texel bytes) of each mip of a chain"""
+        """(w, h, source bytes, texel bytes) of each mip of a chain; a TEX_SRC_RAW_MIP0 source holds level 0 alone"""
         bpp = 2 if fmt == wire.TEX_RG8 else 4
         out = []
         for m in range(num_mips):
             w, h = max(1, width >> m), max(1, height >> m)
-            out.append((w, h, w * h * bpp if encoding == wire.TEX_SRC_RAW else ((w + 3) // 4) * ((h + 3) // 4) * 16, w * h * bpp))
+            if encoding == wire.TEX_SRC_RAW_MIP0:
+                nsrc = w * h * bpp if m == 0 else 0
+            else:
+                nsrc = w * h * bpp if encoding == wire.TEX_SRC_RAW else ((w + 3) // 4) * ((h + 3) // 4) * 16
+            out.append((w, h, nsrc, w * h * bpp))
         return out
 
     def add_texture_blocks(self, blocks, width, height, num_mips, fmt, encoding):
         """Appends one texture from its stored chain -- BC7 / BC5 blocks (wire.TEX_SRC_BC7 needs an RGBA8 format, TEX_SRC_BC5 RG8), or uncompressed texels
-        (TEX_SRC_RAW) -- mips back to back in DDS order, mip m of max(1, w >> m) x max(1, h >> m) texels.  Nothing is decoded.  Returns its heap index."""
+        (TEX_SRC_RAW) -- mips back to back in DDS order, mip m of max(1, w >> m) x max(1, h >> m) texels -- or from its uncompressed level 0 alone
+        (TEX_SRC_RAW_MIP0: levels 1 .. num_mips - 1 are generated, include/zr_mipgen.h).  Nothing is decoded.  Returns its heap index."""
         blocks = np.ascontiguousarray(blocks, np.uint8).reshape(-1)
         if len(self.textures) != len(self.texture_sources):
             raise ValueError("the scene already holds decoded textures: a heap is either all sources or all texels")
-        if encoding not in (wire.TEX_SRC_RAW, wire.TEX_SRC_BC7, wire.TEX_SRC_BC5) or (encoding == wire.TEX_SRC_BC7 and fmt == wire.TEX_RG8) or \
+        if encoding not in (wire.TEX_SRC_RAW, wire.TEX_SRC_BC7, wire.TEX_SRC_BC5, wire.TEX_SRC_RAW_MIP0) or (encoding == wire.TEX_SRC_BC7 and fmt == wire.TEX_RG8) or \
                 (encoding == wire.TEX_SRC_BC5 and fmt != wire.TEX_RG8):
             raise ValueError("encoding %r does not decode to format %r" % (encoding, fmt))
         layout = self._chain_layout(width, height, num_mips, fmt, encoding)
@@ -182,8 +187,8 @@ class Scene:
         return len(self.textures) - 1
 
     def decode_textures(self):
-        """Fills `texels` from the sources on the host, with the loader's decoder (zrh_bc7_decode / zrh_bc5_decode): the heap zr_scene_create_compressed
-        produces on the device.  The sources stay."""
+        """Fills `texels` from the sources on the host, with the loader's decoder (zrh_bc7_decode / zrh_bc5_decode) and, for TEX_SRC_RAW_MIP0 sources, its
+        mip generation (zrh_mip_generate): the heap zr_scene_create_compressed produces on the device.  The sources stay."""
         import ctypes as C
         L = _sceneio_lib()
         for f in (L.zrh_bc7_decode, L.zrh_bc5_decode):
@@ -193,11 +198,14 @@ class Scene:
         for t, s in zip(self.textures, self.texture_sources):
             enc, at, to = int(s["encoding"]), int(s["offset"]), int(t["offset"])
             for w, h, nsrc, ndst in self._chain_layout(int(t["width"]), int(t["height"]), int(t["num_mips"]), int(t["format"]), enc):
-                if enc == wire.TEX_SRC_RAW:
-                    heap[to:to + ndst] = self.texture_payload[at:at + nsrc]
+                if enc in (wire.TEX_SRC_RAW, wire.TEX_SRC_RAW_MIP0):
+                    heap[to:to + nsrc] = self.texture_payload[at:at + nsrc]
                 else:
                     (L.zrh_bc7_decode if enc == wire.TEX_SRC_BC7 else L.zrh_bc5_decode)(self.texture_payload.ctypes.data + at, w, h, heap.ctypes.data + to)
                 at, to = at + nsrc, to + ndst
+        gen = np.ascontiguousarray(self.textures[self.texture_sources["encoding"] == wire.TEX_SRC_RAW_MIP0])
+        if len(gen):
+            mip_generate(gen, heap)
         self.texels = heap
 
     def texture_blocks(self):
@@ -520,13 +528,45 @@ def _sceneio_lib():
 LOAD_KEEP_COMPRESSED = 1      # ZRH_LOAD_KEEP_COMPRESSED
 
 
+def mip_generate(descs, texels):
+    """zrh_mip_generate: levels 1 .. of the chains `descs` (wire.TEXTURE_DESC) names in `texels` (uint8, contiguous), in place, from their level 0"""
+    import ctypes as C
+    L = _sceneio_lib()
+    L.zrh_mip_generate.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    descs = np.ascontiguousarray(descs, wire.TEXTURE_DESC)
+    assert texels.dtype == np.uint8 and texels.flags["C_CONTIGUOUS"]
+    for t in descs:
+        last = Scene._chain_layout(int(t["width"]), int(t["height"]), int(t["num_mips"]), int(t["format"]), wire.TEX_SRC_RAW)
+        if int(t["offset"]) + sum(l[3] for l in last) > len(texels):
+            raise ValueError("a chain ends beyond the %d texel bytes" % len(texels))
+    if L.zrh_mip_generate(descs.ctypes.data, len(descs), texels.ctypes.data) != 0:
+        raise RuntimeError(L.zrh_scene_io_last_error().decode())
+    return texels
+
+
+def png_decode(data, name="<memory>"):
+    """zrh_png_decode: the bytes of a PNG file -> (h, w, 4) uint8 RGBA"""
+    import ctypes as C
+    L = _sceneio_lib()
+    L.zrh_png_decode.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    data = bytes(data)
+    w, h = C.c_uint32(), C.c_uint32()
+    if L.zrh_png_decode(os.fsencode(name), data, len(data), C.byref(w), C.byref(h), None, 0) != 0:
+        raise RuntimeError(L.zrh_scene_io_last_error().decode())
+    out = np.zeros((h.value, w.value, 4), np.uint8)
+    if L.zrh_png_decode(os.fsencode(name), data, len(data), C.byref(w), C.byref(h), out.ctypes.data, out.nbytes) != 0:
+        raise RuntimeError(L.zrh_scene_io_last_error().decode())
+    return out
+
+
 def load_gltf_native(path, rho=None, textures="decoded"):
     """glTF -> wire formats through the C++ loader (MeshInstance quantisation by decomposeSRT of the world matrix, node hierarchies, matrix
-    nodes, DDS material textures decoded to the texel heap).  Returns (Scene, texture-table offsets dict for set_texture_heap_offsets).
+    nodes, DDS material textures decoded to the texel heap, PNG ones with their mip chain generated by include/zr_mipgen.h).  Returns (Scene, texture-table offsets dict for set_texture_heap_offsets).
     A file with "animations" (LINEAR translation / rotation / scale channels) also gives sc.animation, a wire.AnimDesc over the dynamic closure of
     its node hierarchy (Scene.set_animation / Scene.animate in api.py), and sc.emissives_initial, the object-space light records; None without.
     textures="compressed": the .dds payloads are not decoded (ZRH_LOAD_KEEP_COMPRESSED): sc.texels stays empty, sc.texture_sources / sc.texture_payload
-    carry the blocks and api.Scene decodes them on the device (zr_scene_create_compressed); sc.decode_textures() makes the texels on the host."""
+    carry the blocks and api.Scene decodes them on the device (zr_scene_create_compressed); sc.decode_textures() makes the texels on the host.
+    A .png image travels as its level 0 (wire.TEX_SRC_RAW_MIP0) and its other levels are generated on the device."""
     import ctypes as C
     if textures not in ("decoded", "compressed"):
         raise ValueError("textures must be 'decoded' or 'compressed', not %r" % (textures,))

@@ -68,6 +68,7 @@ TEX_RGBA8_SRGB, TEX_RGBA8, TEX_RG8 = 0, 1, 2
 TEXTURE_DESC = np.dtype([("offset", "<u8"), ("width", "<u2"), ("height", "<u2"), ("num_mips", "u1"), ("format", "u1"), ("pad", "<u2")])
 # block-compressed texture sources (zr_texture_source / zr_texture_blocks, include/zetaray_amd.h; the decode is include/zr_bcn.h)
 TEX_SRC_RAW, TEX_SRC_BC7, TEX_SRC_BC5 = 0, 1, 2
+TEX_SRC_RAW_MIP0 = 8      # level 0 alone, uncompressed: the other levels are generated (include/zr_mipgen.h)
 TEXTURE_SOURCE = np.dtype([("offset", "<u8"), ("encoding", "u1"), ("pad", "u1", 7)])
 # keyframe animation (zr_keyframe / zr_anim_node / zr_anim_desc, include/zr_wire.h)
 ANIM_ROOT = 0xFFFFFFFF
