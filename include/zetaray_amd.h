@@ -530,20 +530,35 @@ int zr_pass_render(zr_pass* pass, void* hip_stream, const zr_frame_constants* cb
 #define ZR_HALO_BYTES_PER_PIXEL 62  /* planes A..G back to back: 4 + 8 + 16 + 16 + 2 + 8 + 8, each row-major over the rect */
 int zr_pass_set_owned_rect(zr_pass* pass, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height);   /* global pixels; width 0 = whole tile */
 /* Frame overlap (round 6): K1 + K11 of frame N + 1 beside K15 / K12 / K13 / K16 of frame N.
-   K11's candidates depend on nothing but G-buffer(N + 1), so with enable = 1 the ReSTIR PT pass keeps a THIRD reservoir set, a second target plane and
-   a second FINAL plane, and its stages may be enqueued on two streams:
+   K11's candidates depend on nothing but G-buffer(N + 1), so with enable != 0 the ReSTIR PT pass keeps a THIRD reservoir set, a second target plane and
+   THREE FINAL planes in rotation, and its stages may be enqueued on two streams:
        stream A:  GBUFFER(N + 1), PRELIGHTING(N + 1), INDIRECT stage ZR_STAGE_CANDIDATES(N + 1)
        stream B:  INDIRECT stages ZR_STAGE_TEMPORAL_REUSE | ZR_STAGE_SPATIAL [| ZR_STAGE_SPATIAL2](N + 1), then whatever consumes the frame
-   in exactly that host order, frame after frame.  The library orders them with events: CANDIDATES(N + 1) waits for the temporal reuse of frame N (the last
-   reader of the planes it recycles), TEMPORAL_REUSE(N + 1) waits for CANDIDATES(N + 1); the G-buffer given here is tracked -- a GBUFFER render waits for
-   the passes still reading the plane set it is about to overwrite, a pass on another stream waits for the GBUFFER render.  Results do not depend on
-   the streams (one stream for everything is the plain order) nor on the switch: tests/test_gpu_parity.py::test_frame_overlap_changes_nothing.
-   Outputs: zr_pass_get_output(ZR_OUT_FINAL / ZR_OUT_RPT_*) address the planes of the last frame whose final stage has been enqueued; re-query them every
-   frame (ZR_OUT_FINAL alternates between two planes unless the frame accumulates).  Only the ReSTIR PT integrator; call between frames.
+   in exactly that host order, frame after frame: everything that reads frame N's outputs is enqueued on stream B, behind the frame's last stage, BEFORE
+   the first half of frame N + 1 is enqueued, and stream B is the same stream from frame to frame.  The library orders the stages with events:
+     * TEMPORAL_REUSE(N + 1) waits for CANDIDATES(N + 1);
+     * CANDIDATES(N + 1) waits for what it recycles, which differs between the two modes:
+         ZR_FRAME_OVERLAP        the last stage of frame N - 1 (the free reservoir set and this parity's target plane were last read by that frame's
+                                 spatial stage): two frames of overlap, the first half of frame N + 1 also runs beside the temporal reuse of frame N;
+         ZR_FRAME_OVERLAP_CARRY  the temporal reuse of frame N (the last writer of the set it copies), or the LAST stage of frame N when that frame ran two
+                                 spatial rounds (the set it copies is then the one the first round wrote): one frame of overlap;
+     * accumulating frames (cb.accumulate && cb.camera_static) do not rotate FINAL -- they add to the plane of the frame before -- and K11 itself adds
+       into it whenever the frame has no temporal reuse.  CANDIDATES of such a frame therefore waits for the tail of stream B as it stands when the
+       stage is enqueued: frame N's last stage and its consumers.  Accumulating frames do not overlap; the others are not affected;
+     * the G-buffer given here is tracked -- a GBUFFER render waits for the passes still reading the plane set it is about to overwrite, a pass on
+       another stream waits for the GBUFFER render.  The call keeps the previous frame's planes "previous" (whatever renders between it and the next
+       GBUFFER render reprojects into them as before).
+   Results do not depend on the streams (one stream for everything is the plain order), on how far one stream runs ahead of the other, nor on the
+   switch: tests/test_frame_overlap_gpu.py (every stage boundary held back in turn, against the oracle) and tests/test_gpu_parity.py
+   test_frame_overlap_changes_nothing / test_frame_overlap_back_to_back_frames (at size).
+   Outputs: zr_pass_get_output(ZR_OUT_FINAL / ZR_OUT_RPT_*) address the planes of the last frame whose final stage has been enqueued.  RE-QUERY THEM
+   EVERY FRAME: ZR_OUT_FINAL rotates over three planes (it stays where it is while frames accumulate), the reservoir sets over three, the target plane
+   over two.  Only the ReSTIR PT integrator; call between frames.
    zr_pass_frame_overlap_stream: a non-blocking stream owned by the pass, for callers without streams of their own ("stream A").
    enable = ZR_FRAME_OVERLAP (1): the product mode.  The passes update reservoir records in place and write only the components a record's case uses
    (Reservoir.hlsli:283-456), so the UNUSED bytes of a record -- never read by any pass -- are whatever the set held before: with three sets in
-   rotation that is another frame's leftovers than in the plain order.  Every used byte, FINAL and the ray counters are identical.
+   rotation that is another frame's leftovers than in the plain order.  Every used byte (tests/overlapcheck.py used_mask states which, and
+   tests/test_frame_overlap_cpu.py that no other is read), FINAL and the ray counters are identical.
    enable = ZR_FRAME_OVERLAP_CARRY (2): additionally copies the replaced set and target plane into the set that takes their place before K11 (one
    streaming kernel, 156 B per pixel): every byte of every plane then equals the plain order's -- what the parity tests compare with the oracle. */
 #define ZR_FRAME_OVERLAP       1

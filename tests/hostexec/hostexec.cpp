@@ -714,6 +714,7 @@ int zhx_rpt_write_plane_rect(HxRpt* R, int which, int plane, const void* src, ui
     case 4: base = p.E.data(); bpp = 2; break;
     case 5: base = p.F.data(); bpp = 8; break;
     case 6: base = p.G.data(); bpp = 8; break;
+    case 7: base = R->target.data(); bpp = 16; break;      // (the target plane: one per pass, `which` does not matter)
     default: return 1;
     }
     for (uint32_t y = y0; y < y0 + h; y++)

@@ -207,14 +207,18 @@ def test_restir_pt_bit_exact(api, cornell_emissive, oracle_emissive, w, h):
 
 
 def _overlap_digest(api, scene, w, h, prm, frames, overlap, cam_of_frame=None, denoise=False, toggle_at=(), carry=True):
-    """sha1 per frame over FINAL, every reservoir plane, the target plane (and the denoised image) of a ReSTIR PT sequence; and over FINAL alone"""
+    """sha1 per frame over FINAL, every reservoir plane, the target plane (and the denoised image) of a ReSTIR PT sequence; and over FINAL alone.
+    _overlap_digest.used: the last call's digests, per frame, over the USED bytes of the reservoir planes and the written pixels of the target plane
+    (tests/overlapcheck.py used_mask / target_mask): what the product mode of frame overlap shares with the plain order"""
     import hashlib
+    from tests import overlapcheck
     r = api.Renderer(scene, w, h, params=prm, integrator=api.INTEGRATOR_RESTIR_PT)
     if denoise:
         r.enable_denoise()
     if overlap:
         r.enable_frame_overlap(True, carry)
     out, fin, prev = [], [], None
+    _overlap_digest.used = []
     for f in range(1, frames + 1):
         if f in toggle_at:
             overlap = not overlap
@@ -226,12 +230,15 @@ def _overlap_digest(api, scene, w, h, prm, frames, overlap, cam_of_frame=None, d
         r.render_frame(cb)
         hh = hashlib.sha1(r.final().tobytes())
         fin.append(hh.hexdigest())
+        planes = {nm: r.p_indirect.download_plane(nm) for nm in ("A", "B", "C", "D", "E", "F", "G", "target")}
         for nm in ("B", "C", "D", "E", "F", "G", "target"):
-            hh.update(r.p_indirect.download_plane(nm).tobytes())
-        hh.update((r.p_indirect.download_plane("A") & 0xffffff).tobytes())
+            hh.update(planes[nm].tobytes())
+        hh.update((planes["A"] & 0xffffff).tobytes())
         if denoise:
             hh.update(r.p_denoise.download_plane("denoised").tobytes())
         out.append(hh.hexdigest())
+        skip = (r.gbuffer.download()[0][2].reshape(h, w).astype(np.uint32) & 0x6) != 0      # K11 skips pixels without a surface and emissive ones
+        _overlap_digest.used.append(overlapcheck.used_bytes_digest(planes, len(scene.emissives) > 0, skip, do_temporal=f >= 2))
     return out, fin, r.p_indirect.read_counters()
 
 
@@ -244,7 +251,7 @@ def test_frame_overlap_changes_nothing(api, cornell_emissive, oracle_emissive, c
         of every frame hashes to the digest of the plain order; the same with the denoise pass consuming each frame, and with the switch flipped on and
         off in the middle of the sequence (the plane roles carry over); ray counters identical.
     These run ZR_FRAME_OVERLAP_CARRY (whole planes comparable).  The product mode leaves the UNUSED bytes of the reservoir records to the rotation of the three
-    sets: its FINAL image and ray counters over 12 frames equal the plain order's."""
+    sets: its FINAL image, ray counters and the used bytes of every plane (tests/overlapcheck.py) over 12 frames equal the plain order's."""
     from oracle import zro
     cam = lambda f: dict(cam_pos=(0.05 * max(0, f - 2), 1.2, -4.043))
     _rpt_compare(api, cornell_emissive, oracle_emissive, 200, 120, wire.default_params(), 5, reset_at=4, overlap=True, cam_of_frame=cam)
@@ -271,16 +278,21 @@ def test_frame_overlap_changes_nothing(api, cornell_emissive, oracle_emissive, c
     # the product mode (no carry): the bytes a reservoir record does not use may differ, nothing else -- FINAL of every frame and the ray counters are the plain order's
     # (a used byte that differed would change a later frame's radiance: the reservoirs of frame N are the temporal and spatial inputs of frames N + 1 ...)
     plain12, fin12, c12 = _overlap_digest(api, cornell_emissive, w, h, wire.default_params(), 12, False, cam)
+    used12 = _overlap_digest.used
     _, finp, cp = _overlap_digest(api, cornell_emissive, w, h, wire.default_params(), 12, True, cam, carry=False)
     assert finp == fin12 and cp == c12, ([a == b for a, b in zip(finp, fin12)], cp, c12)
+    # ... and so are the used bytes of every reservoir plane and the target plane where the frame wrote it
+    assert _overlap_digest.used == used12, [a == b for a, b in zip(_overlap_digest.used, used12)]
 
 
 def _back_to_back(api, scene, w, h, prm, frames, mode, cam_of_frame, mover=None, light=None):
     """`frames` ReSTIR PT frames submitted WITHOUT a host wait in between (what bench.py times; the digests of _overlap_digest wait for every frame, so there
     the two halves of consecutive frames never actually share the device), optionally with an instance moved before every frame from the third on;
-    mode: None = plain order, "carry" / "product" = zr_pass_set_frame_overlap.  Returns the digest of the last frame's planes, of its FINAL alone, the ray counters."""
+    mode: None = plain order, "carry" / "product" = zr_pass_set_frame_overlap.  Returns the digest of the last frame's planes, of its FINAL alone, the ray counters,
+    and the digest of the planes' used bytes (tests/overlapcheck.py used_bytes_digest)."""
     import hashlib
     import copy
+    from tests import overlapcheck
     sc = copy.copy(scene)       # the arrays the sequence rewrites are this run's own (the fixture is shared)
     sc.instances, sc.instance_to_world, sc.emissives = scene.instances.copy(), scene.instance_to_world.copy(), scene.emissives.copy()
     r = api.Renderer(sc, w, h, params=prm, integrator=api.INTEGRATOR_RESTIR_PT)
@@ -309,16 +321,19 @@ def _back_to_back(api, scene, w, h, prm, frames, mode, cam_of_frame, mover=None,
         r.render_frame(cb)
     fin = r.final()
     hh = hashlib.sha1(fin.tobytes())
+    planes = {nm: r.p_indirect.download_plane(nm) for nm in ("A", "B", "C", "D", "E", "F", "G", "target")}
     for nm in ("B", "C", "D", "E", "F", "G", "target"):
-        hh.update(r.p_indirect.download_plane(nm).tobytes())
-    hh.update((r.p_indirect.download_plane("A") & 0xffffff).tobytes())
-    return hh.hexdigest(), hashlib.sha1(fin.tobytes()).hexdigest(), r.p_indirect.read_counters()
+        hh.update(planes[nm].tobytes())
+    hh.update((planes["A"] & 0xffffff).tobytes())
+    skip = (r.gbuffer.download()[0][2].reshape(h, w).astype(np.uint32) & 0x6) != 0
+    used = overlapcheck.used_bytes_digest(planes, len(sc.emissives) > 0, skip, do_temporal=frames >= 2)
+    return hh.hexdigest(), hashlib.sha1(fin.tobytes()).hexdigest(), r.p_indirect.read_counters(), used
 
 
 def test_frame_overlap_back_to_back_frames(api, cornell_emissive):
     """Frames in flight for real: 24 frames of the 1920 x 1080 Cornell box with a moving camera, and 16 of a 3000-triangle materials scene whose largest
     instance moves every frame (zr_scene_update_instances between the frames: the refit and the previous-structure swap are ordered against BOTH streams),
-    submitted without a host wait.  Carry mode: every plane of the last frame equals the plain order's; product mode: its FINAL and the ray counters do.
+    submitted without a host wait.  Carry mode: every plane of the last frame equals the plain order's; product mode: its FINAL, the ray counters and the planes' used bytes do.
     The same with the Cornell box's light moving (zr_scene_update_emissives + _instances before every frame, the alias table invalidated every fourth).
     Two or three runs of each overlapped sequence, so that a race has more than one chance to show."""
     w, h = 1920, 1080
@@ -353,7 +368,7 @@ def test_frame_overlap_back_to_back_frames(api, cornell_emissive):
                 cb["prev_view"], cb["prev_view_inv"], cb["prev_camera_jitter"] = prev["curr_view"], prev["curr_view_inv"], prev["curr_camera_jitter"]
             prev = cb.copy()
             t.render_frame(cb)
-        assert (hashlib.sha1(t.r.final().tobytes()).hexdigest(), t.r.p_indirect.read_counters()) == plain[1:], ("tiled, one rank", rep)
+        assert (hashlib.sha1(t.r.final().tobytes()).hexdigest(), t.r.p_indirect.read_counters()) == plain[1:3], ("tiled, one rank", rep)
         del t
     # ... and of four ranks' tile objects on this one device with every halo exchange in between (no host wait anywhere): the stitched FINAL of frame 12
     ref12 = _back_to_back(api, cornell_emissive, w, h, wire.default_params(), 12, None, cam)

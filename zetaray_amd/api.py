@@ -719,7 +719,12 @@ class Renderer:
         Software-pipeline consecutive ReSTIR PT frames on two streams: the G-buffer, PreLighting and K11 of frame N + 1 go to a stream of the pass's
         own and run beside the search / sort / replay / reconnect kernels of frame N (the reference overlaps its direct and async-compute queues the same
         way, RenderGraph.cpp:442-541).  Bit-identical frames; throughput goes up, the latency of one frame does not go down.  Indirect (ReSTIR PT) + denoise
-        only: the DI passes, Compositing and TAA keep single-buffered outputs that the next frame's first half would overwrite under their consumers."""
+        only: the DI passes, Compositing and TAA keep single-buffered outputs that the next frame's first half would overwrite under their consumers.
+        FINAL rotates over three planes and the reservoir sets over three: output_ptr() is re-queried every frame (render_frame does it for the denoise
+        pass).  The first half of frame N + 1 waits for the last stage of frame N - 1 (product mode) or for the temporal reuse of frame N -- its last stage
+        when it ran two spatial rounds -- (carry mode).  Accumulating frames (accumulate and camera_static) keep adding to one FINAL plane, so their first
+        half waits for the previous frame and its consumers on `stream` and they do not overlap.  Whatever consumes a frame goes on `stream`, behind its
+        last stage, before the next render_frame.  tests/test_frame_overlap_gpu.py holds every stage boundary back in turn and compares with the oracle."""
         assert self.p_direct is None and self.p_sky_direct is None and self.p_composit is None and getattr(self, "p_taa", None) is None, \
             "frame overlap covers GBuffer + PreLighting + Indirect (ReSTIR PT) [+ denoise]"
         _check(lib().zr_device_synchronize(self._device))

@@ -946,6 +946,8 @@ struct zr_pass
     Plane<float, 4> finalAlt, finalAlt2;      // FINAL rotates over three planes: K11 of frame N + 2 (which clears the pixels without a surface) may run while frame N's is still being consumed
     // the last stage of the frame before the previous one done (depth-2 pipelining, product mode): evDone[k & 1] is recorded when frame k closes
     hipEvent_t evDone[2] = {nullptr, nullptr}; bool haveDone[2] = {false, false}; hipStream_t doneStream[2] = {nullptr, nullptr}; uint64_t ovFrame = 0;
+    bool doneTwoRounds[2] = {false, false};      // ... and whether that frame ran a second spatial round (carry mode: the round that writes the set the next K11 takes over)
+    hipEvent_t evTail = nullptr;                 // accumulating frames: the tail of the stream that carried the previous frame's last stage (its consumers included)
     hipStream_t overlapStream = nullptr;                     // "stream A" for callers without streams of their own
     hipEvent_t evCand = nullptr, evTemporal = nullptr;       // K11 of the open frame done (on candStream) / K14 of the last frame done (on reuseStream)
     hipStream_t candStream = nullptr, reuseStream = nullptr; bool haveCand = false, haveTemporal = false;
@@ -2457,12 +2459,19 @@ int zr_pass_create(int kind, int device, zr_pass** out)
     return ZR_OK;
 }
 
-// the planes frame overlap adds to a ReSTIR PT pass (zr_pass_set_frame_overlap): a third reservoir set, a second target plane, a second FINAL plane
+// the planes frame overlap adds to a ReSTIR PT pass (zr_pass_set_frame_overlap): a third reservoir set, a second target plane, a second and a third FINAL
+// plane (FINAL rotates over three: zr_pass_get_output(ZR_OUT_FINAL) changes from frame to frame, callers re-query it).  All of them or none: after a
+// failure part-way nothing stays allocated, so res[2].A.p != nullptr means "the overlap planes exist" (the guard of zr_pass_set_frame_overlap).
 static int AllocOverlapPlanes(zr_pass* p)
 {
     const size_t cap = (size_t)p->w * p->h;
     int r;
-    if ((r = PlanesAllocZero(p->res[2], cap)) || (r = p->rptTargetAlt.AllocZero(cap)) || (r = p->finalAlt.AllocZero(cap)) || (r = p->finalAlt2.AllocZero(cap))) return r;
+    if ((r = PlanesAllocZero(p->res[2], cap)) || (r = p->rptTargetAlt.AllocZero(cap)) || (r = p->finalAlt.AllocZero(cap)) || (r = p->finalAlt2.AllocZero(cap)))
+    {
+        zr_pass::ResStorage::Each(p->res[2], [](auto& pl) { pl.Free(); return 0; });
+        p->rptTargetAlt.Free(); p->finalAlt.Free(); p->finalAlt2.Free();
+        return r;
+    }
     return ZR_OK;
 }
 static int AllocPass(zr_pass* p)
@@ -3024,9 +3033,13 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
         p->tgtIdx ^= 1;
         carryFrom = p->overlapCarry ? &p->res[p->rptSet[2]] : nullptr;
         if (!(cb->accumulate && cb->camera_static)) p->finIdx = (p->finIdx + 1) % 3;      // (an accumulating frame adds to the plane the frames before it wrote)
+        const int kPrev = (int)((p->ovFrame + 1) & 1);      // the previous frame's slot of evDone
         if (p->overlapCarry)
-        {   // carry mode copies the replaced set, whose last writer is the previous frame's K14: one frame of overlap (beside that frame's spatial stage)
-            if (p->haveTemporal && p->reuseStream != s) HIP_TRY(hipStreamWaitEvent(s, p->evTemporal, 0));
+        {   // carry mode copies the replaced set, whose last writer is the previous frame's K14: one frame of overlap (beside that frame's spatial stage) --
+            // unless that frame ran two spatial rounds: the set this frame takes over is then the one its FIRST round wrote (K14's set is that frame's
+            // final one), so the copy goes behind the whole frame
+            if (p->haveDone[kPrev] && p->doneTwoRounds[kPrev]) { if (p->doneStream[kPrev] != s) HIP_TRY(hipStreamWaitEvent(s, p->evDone[kPrev], 0)); }
+            else if (p->haveTemporal && p->reuseStream != s) HIP_TRY(hipStreamWaitEvent(s, p->evTemporal, 0));
         }
         else
         {   // product mode: what this stage recycles -- the free reservoir set and this parity's target plane -- was last touched by the frame BEFORE the
@@ -3034,6 +3047,15 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
             // runs beside the temporal reuse of frame N + 1
             const int k = (int)(p->ovFrame & 1);
             if (p->haveDone[k] && p->doneStream[k] != s) HIP_TRY(hipStreamWaitEvent(s, p->evDone[k], 0));
+        }
+        // An accumulating frame keeps the FINAL plane of the frame before it, and its K11 adds into that plane whenever there is no temporal reuse
+        // (PtFinishLane).  That must come after the previous frame's own "+=" AND after whatever consumes that frame, which the caller has enqueued
+        // behind its last stage on the same stream (zetaray_amd.h): this half goes behind that stream's tail as it stands now.  Accumulating frames
+        // therefore do not overlap; the others keep the waits above and nothing else.
+        if (cb->accumulate && cb->camera_static && p->haveDone[kPrev] && p->doneStream[kPrev] != s)
+        {
+            HIP_TRY(hipEventRecord(p->evTail, p->doneStream[kPrev]));
+            HIP_TRY(hipStreamWaitEvent(s, p->evTail, 0));
         }
     }
     RptFrame F;
@@ -3248,7 +3270,11 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
         p->currIdx = 1 - p->currIdx;
         p->frameOpen = false;
         p->finOut = p->finIdx;
-        if (p->overlap) { const int k = (int)(p->ovFrame & 1); HIP_TRY(hipEventRecord(p->evDone[k], s)); p->haveDone[k] = true; p->doneStream[k] = s; p->ovFrame++; }
+        if (p->overlap)
+        {
+            const int k = (int)(p->ovFrame & 1);
+            HIP_TRY(hipEventRecord(p->evDone[k], s)); p->haveDone[k] = true; p->doneStream[k] = s; p->doneTwoRounds[k] = prm.doSpatial && numSpatialPasses == 2u; p->ovFrame++;
+        }
         if (int mr = GBufferMarkRead(gb, gb->cur, s)) return mr;
     }
     return ZR_OK;
@@ -3677,6 +3703,7 @@ int zr_pass_set_frame_overlap(zr_pass* p, zr_gbuffer* gb, int enable)
     {
         HIP_TRY(hipEventCreateWithFlags(&p->evCand, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&p->evTemporal, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&p->evDone[0], hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&p->evDone[1], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&p->evTail, hipEventDisableTiming));
         HIP_TRY(hipStreamCreateWithFlags(&p->overlapStream, hipStreamNonBlocking));
     }
     // switching off keeps the plane roles as they stand (the set last written as FINAL stays the one the next frame reads); FINAL goes on in the plane it is in
@@ -3686,7 +3713,14 @@ int zr_pass_set_frame_overlap(zr_pass* p, zr_gbuffer* gb, int enable)
         for (int i = 0; i < ZR_GB_COUNT; i++)
             if (int r = gb->planeSets[2][i].AllocZero((size_t)gb->w * gb->h * ZR_GB_PLANE_BYTES[i])) return r;
         HIP_TRY(hipDeviceSynchronize());
-        // sets 0 / 1 hold the last two frames; the rotation continues from the current one: cur = 0 -> next 1 (two frames old), cur = 1 -> next 2 (fresh)
+        // sets 0 / 1 hold the last two frames and Prev() must go on naming the older of them for whatever pass renders before the next GBUFFER render.
+        // cur = 1: Prev() stays 0, the next render takes the fresh set 2.  cur = 0: Prev() becomes 2, so the previous frame moves there from set 1 (with what
+        // is known about it) and the next render takes the fresh planes, now in set 1.
+        if (gb->cur == 0)
+        {
+            for (int i = 0; i < ZR_GB_COUNT; i++) gb->planeSets[1][i].Swap(gb->planeSets[2][i]);
+            std::swap(gb->plainAt[1], gb->plainAt[2]); std::swap(gb->sceneAt[1], gb->sceneAt[2]);
+        }
         gb->numSets = 3;
     }
     gb->tracked = enable != 0;
@@ -4131,6 +4165,7 @@ int zr_pass_destroy(zr_pass* p)
     if (p->evCand) (void)hipEventDestroy(p->evCand);
     if (p->evTemporal) (void)hipEventDestroy(p->evTemporal);
     for (auto& e : p->evDone) if (e) (void)hipEventDestroy(e);
+    if (p->evTail) (void)hipEventDestroy(p->evTail);
     delete p;
     return ZR_OK;
 }
