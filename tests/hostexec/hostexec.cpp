@@ -94,6 +94,29 @@ static GBuf ViewOf(const zr_gbuffer_planes* p)
     return g;
 }
 
+// ---- the cross-stream ordering of zr_api.hip (zr_stream_order.h, zr_rpt_overlap.h) with a backend that logs instead of calling HIP: streams and
+// events are small integers, the log is records of four int32 (kind, a, b, c)
+#include "../../zetaray_amd/csrc/zr_rpt_overlap.h"
+enum { HX_LOG_OP = 0,        // an op begins: a = its index, b = stage, c = stream
+       HX_LOG_CREATE = 1,    // a = event
+       HX_LOG_DESTROY = 2,   // a = event
+       HX_LOG_RECORD = 3,    // a = event, b = stream
+       HX_LOG_WAIT = 4,      // a = stream, b = event
+       HX_LOG_ACCESS = 5,    // a = buffer kind (0 reservoir set, 1 target plane, 2 FINAL plane, 3 G-buffer plane set), b = storage index, c = 1 for a write
+       HX_LOG_ROLES = 6,     // a = current set, b = other set, c = target plane
+       HX_LOG_ROLES2 = 7 };  // a = FINAL plane, b = FINAL plane of the last closed frame, c = frameOpen
+static std::vector<int32_t>* g_orderLog = nullptr;
+static int g_orderNextEvent = 0;
+static void OrderLog(int kind, int a, int b, int c) { if (g_orderLog) { g_orderLog->push_back(kind); g_orderLog->push_back(a); g_orderLog->push_back(b); g_orderLog->push_back(c); } }
+struct HxOrderBackend
+{
+    using Stream = int; using Event = int;
+    static int Create(Event* e) { *e = g_orderNextEvent++; OrderLog(HX_LOG_CREATE, *e, 0, 0); return 0; }
+    static void Destroy(Event e) { OrderLog(HX_LOG_DESTROY, e, 0, 0); }
+    static int Record(Event e, Stream s) { OrderLog(HX_LOG_RECORD, e, s, 0); return 0; }
+    static int Wait(Stream s, Event e) { OrderLog(HX_LOG_WAIT, s, e, 0); return 0; }
+};
+
 extern "C" {
 
 HxScene* zhx_scene_create(const zr_scene_desc* d)
@@ -910,5 +933,86 @@ void zhx_kat_sampling(const float* in, float* out, uint32_t n) { hxkat::Sampling
 void zhx_kat_math(const float* in, float* out, uint32_t n) { hxkat::Math_(in, out, n); }
 void zhx_kat_rt(const float* in, float* out, uint32_t n) { hxkat::RT_(in, out, n); }
 void zhx_kat_bsdf(const uint16_t* rho, const uint32_t* rho_dim, const float* in, float* out, uint32_t n) { hxkat::BSDF_(rho, rho_dim, in, out, n); }
+
+// The frame-overlap model: the role state and access declarations RenderReSTIR_PT runs (RptOverlap), the G-buffer's three trackers used the way
+// RenderGBuffer, RenderReSTIR_PT and zr_pass_render_stage use them (those few lines are repeated here: zr_gbuffer itself lives in zr_api.hip), in the
+// host order the caller gives.  ops = n x (stage, stream, flags), stage:
+//   0 GBUFFER render        1 CANDIDATES (flags & 1: an accumulating frame)     2 TEMPORAL_REUSE      3 one spatial round
+//   4 the frame's last stage has been enqueued (after its last round, or after TEMPORAL_REUSE when it has none)
+//   5 a consumer: a pass other than ReSTIR PT on the G-buffer, which also reads the last closed frame's FINAL
+//   6 zr_pass_set_frame_overlap (flags: 0 off, 1 on, 2 carry)                   7 zr_pass_init / zr_pass_resize
+//   8 .. 12: AcquireRead, AcquireWrite, MarkRead, MarkWritten, Reset of one StreamOrder of its own (the type alone)
+// Each stage logs the storage it reads and writes and, for the ReSTIR PT stages, the roles it ran with; the trackers' destructors are part of the log.
+// Returns the number of int32 the log takes; its first min(that, cap) are written to `log`.
+int zhx_stream_order_run(const int32_t* ops, uint32_t n, int32_t* log, uint32_t cap)
+{
+    std::vector<int32_t> out; g_orderLog = &out; g_orderNextEvent = 0;
+    {
+        RptOverlap<HxOrderBackend> ov;
+        OrderPoints<HxOrderBackend> lonePoints; StreamOrder<HxOrderBackend> lone;
+        struct { OrderPoints<HxOrderBackend> points; StreamOrder<HxOrderBackend> order[3]; int cur = 0, numSets = 2; bool tracked = false;
+                 int Next() const { return (cur + 1) % numSets; } int Prev() const { return (cur + numSets - 1) % numSets; } } gb;
+        auto logAcc = [&] { for (int i = 0; i < ov.numAcc; i++) OrderLog(HX_LOG_ACCESS, ov.acc[i].buf, ov.acc[i].idx, ov.acc[i].write); };
+        auto logRoles = [&] { OrderLog(HX_LOG_ROLES, ov.roles.Cur(), ov.roles.Oth(), ov.roles.Target()); OrderLog(HX_LOG_ROLES2, ov.roles.Final(), ov.roles.finOut, ov.roles.frameOpen); };
+        for (uint32_t i = 0; i < n; i++)
+        {
+            const int stage = ops[3 * i], s = ops[3 * i + 1], flags = ops[3 * i + 2];
+            OrderLog(HX_LOG_OP, (int)i, stage, s);
+            switch (stage)
+            {
+            case 0:
+                if (gb.tracked) gb.order[gb.Next()].AcquireWrite(gb.points, s);
+                gb.cur = gb.Next(); OrderLog(HX_LOG_ACCESS, 3, gb.cur, 1);
+                if (gb.tracked) gb.order[gb.cur].MarkWritten(gb.points, s);
+                break;
+            case 1:
+                ov.BeginCandidates(s, (flags & 1) != 0); logRoles(); logAcc();
+                if (gb.tracked) gb.order[gb.cur].AcquireRead(gb.points, s);
+                OrderLog(HX_LOG_ACCESS, 3, gb.cur, 0);
+                ov.EndCandidates(s);
+                break;
+            case 2:
+            {
+                int k11; const bool behindK11 = ov.CandidatesStream(&k11) && k11 != s;
+                ov.BeginTemporalReuse(s); logRoles(); logAcc();
+                if (gb.tracked && !behindK11) gb.order[gb.cur].AcquireRead(gb.points, s);
+                OrderLog(HX_LOG_ACCESS, 3, gb.cur, 0); OrderLog(HX_LOG_ACCESS, 3, gb.Prev(), 0);
+                ov.EndTemporalReuse(s);
+                if (gb.tracked) gb.order[gb.Prev()].MarkRead(gb.points, s);
+                break;
+            }
+            case 3:
+                ov.BeginSpatialRound(s); logRoles(); logAcc();
+                OrderLog(HX_LOG_ACCESS, 3, gb.cur, 0);
+                ov.EndSpatialRound(s);
+                break;
+            case 4:
+                ov.CloseFrame(); logRoles();
+                if (gb.tracked) gb.order[gb.cur].MarkRead(gb.points, s);
+                break;
+            case 5:
+                if (gb.tracked) gb.order[gb.cur].AcquireRead(gb.points, s);
+                OrderLog(HX_LOG_ACCESS, 3, gb.cur, 0); OrderLog(HX_LOG_ACCESS, 3, gb.Prev(), 0); OrderLog(HX_LOG_ACCESS, RPT_BUF_FINAL, ov.roles.finOut, 0);
+                if (gb.tracked) { gb.order[gb.cur].MarkRead(gb.points, s); gb.order[gb.Prev()].MarkRead(gb.points, s); }
+                break;
+            case 6:
+                ov.SetMode(flags != 0, flags == 2);
+                if (flags) gb.numSets = 3;
+                gb.tracked = flags != 0;
+                if (!flags) { for (auto& o : gb.order) o.Reset(); gb.points.Reset(); }
+                break;
+            case 7: ov.Reset(); break;
+            case 8: lone.AcquireRead(lonePoints, s); break;
+            case 9: lone.AcquireWrite(lonePoints, s); break;
+            case 10: lone.MarkRead(lonePoints, s); break;
+            case 11: lone.MarkWritten(lonePoints, s); break;
+            default: lone.Reset(); lonePoints.Reset(); break;
+            }
+        }
+    }
+    g_orderLog = nullptr;
+    if (log && cap) std::memcpy(log, out.data(), std::min<size_t>(out.size(), cap) * sizeof(int32_t));
+    return (int)out.size();
+}
 
 } // extern "C"

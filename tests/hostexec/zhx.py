@@ -423,6 +423,24 @@ def set_k11_park(on):
     lib().zhx_set_k11_park(int(bool(on)))
 
 
+ORDER_STAGES = ("gbuffer", "candidates", "temporal_reuse", "spatial_round", "close", "consumer", "set_overlap", "init",
+                "acquire_read", "acquire_write", "mark_read", "mark_written", "reset")
+ORDER_LOG = ("op", "create", "destroy", "record", "wait", "access", "roles", "roles2")
+
+
+def stream_order_run(ops):
+    """the library's cross-stream ordering (zr_stream_order.h, zr_rpt_overlap.h) with a logging backend.  ops: [(stage name of ORDER_STAGES, stream id, flags)]
+    in host order; returns the log, [(kind of ORDER_LOG, a, b, c)] (hostexec.cpp zhx_stream_order_run says what a, b, c are)"""
+    arr = np.array([(ORDER_STAGES.index(st), s, fl) for st, s, fl in ops], np.int32).reshape(-1, 3)
+    f = lib().zhx_stream_order_run
+    f.argtypes, f.restype = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32], C.c_int
+    need = f(arr.ctypes.data, len(arr), None, 0)
+    out = np.zeros(max(need, 1), np.int32)
+    got = f(arr.ctypes.data, len(arr), out.ctypes.data, need)
+    assert got == need and need % 4 == 0
+    return [(ORDER_LOG[k], int(a), int(b), int(c)) for k, a, b, c in out[:need].reshape(-1, 4)]
+
+
 def svgf(signal_rgba, depth, normal, motion, prev_depth, prev_normal, hist_color, hist_moments, temporal_valid=True, alpha=0.2, alpha_moments=0.2,
          sigma_l=4.0, sigma_z=1.0, normal_power_log2=7, iterations=5):
     """the denoise pass's HIP stage functions (zr_svgf.h) run serially on the host; same interface as oracle.zro.svgf"""

@@ -23,6 +23,7 @@
 #include "zr_taa.h"
 #include "zr_svgf.h"
 #include "zr_post.h"
+#include "zr_rpt_overlap.h"
 #include "../../include/zr_srgb_table.h"
 
 // 512 x half2 spatial-search points (generated from zetaray_amd/assets/rpt_sample_set_f16.bin by the Makefile)
@@ -41,6 +42,17 @@ static int Fail(int code, const char* fmt, ...)
     return code;
 }
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return Fail(ZR_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+
+// cross-stream ordering of the scene's buffers, the G-buffer's plane sets and the ReSTIR PT planes (zr_stream_order.h, zr_rpt_overlap.h) on HIP events
+struct HipOrderBackend
+{
+    using Stream = hipStream_t; using Event = hipEvent_t;
+    static int Create(Event* e) { HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming)); return ZR_OK; }
+    static void Destroy(Event e) { (void)hipEventDestroy(e); }
+    static int Record(Event e, Stream s) { HIP_TRY(hipEventRecord(e, s)); return ZR_OK; }
+    static int Wait(Stream s, Event e) { HIP_TRY(hipStreamWaitEvent(s, e, 0)); return ZR_OK; }
+};
+using HipStreamOrder = zr::StreamOrder<HipOrderBackend>; using HipOrderPoints = zr::OrderPoints<HipOrderBackend>;
 
 static int RequireDevice(int device)
 {
@@ -594,13 +606,13 @@ struct zr_scene
     int64_t maxTex[4] = {-1, -1, -1, -1};     // largest tex16 used per table (base colour, normal, metallic-roughness, emissive)
     uint32_t maxDepth = 0;
     // ---- stream-ordered updates (zr_scene_update_*_async; RtAccelerationStructure.cpp:708-789 records them on the frame's command list).
-    // Host records travel through a ring of pinned staging buffers (a slot is reused only after its copy has run); `updated` is recorded
-    // behind every update and waited for by renders on OTHER streams; `users` holds, per stream that rendered with this scene, an event
-    // recorded behind its last render, which an update on another stream waits for before it overwrites what those renders read.
+    // Host records travel through a ring of pinned staging buffers (a slot is reused only after its copy has run); `order` takes an update as a
+    // write of the scene's buffers and a render as a read: renders on OTHER streams wait for the last update, and an update waits for the last
+    // render of every other stream before it overwrites what those renders read (guarded by mtx).
     struct StageSlot { void* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool pending = false; };
     StageSlot stage[4]; int stageNext = 0;
-    hipEvent_t updated = nullptr; hipStream_t updatedOn = nullptr; bool hasUpdate = false;
-    std::vector<std::pair<hipStream_t, hipEvent_t>> users;
+    mutable HipOrderPoints points; mutable HipStreamOrder order;
+    bool HasUpdate() const { return order.LastWriter(nullptr); }
     // ---- background SAH rebuild (zr_scene_set_background_rebuild; VERDICT r3 item 9, RtAccelerationStructure.cpp:708-789 rebuilds its TLAS every frame).
     // The device refit keeps the topology of the last build, and a tree built for where the instances WERE gets worse the further they move.  With this
     // on, an update that finds no build in flight snapshots the new transforms and starts the host's binned-SAH builder on a thread; the first update
@@ -650,8 +662,6 @@ struct zr_scene
         if (bg.pkg) (void)hipHostFree(bg.pkg);
         if (bg.pkgCopied) (void)hipEventDestroy(bg.pkgCopied);
         for (StageSlot& t : stage) { if (t.ev) (void)hipEventDestroy(t.ev); if (t.host) (void)hipHostFree(t.host); }
-        if (updated) (void)hipEventDestroy(updated);
-        for (auto& u : users) (void)hipEventDestroy(u.second);
     }
 };
 
@@ -674,28 +684,19 @@ static int StageAcquire(zr_scene* s, size_t bytes, zr_scene::StageSlot** out)
     return ZR_OK;
 }
 static int StageCommit(zr_scene::StageSlot* t, hipStream_t st) { HIP_TRY(hipEventRecord(t->ev, st)); t->pending = true; return ZR_OK; }
-// an update on `st` must not overwrite what renders enqueued on other streams still read
+// an update on `st` must not overwrite what renders enqueued on other streams still read, and updates on different streams are ordered against
+// each other (a render then only has to wait for the latest update: SceneAcquireForRender)
 static int SceneWaitUsers(zr_scene* s, hipStream_t st)
 {
     std::lock_guard<std::mutex> lock(s->mtx);
-    // the FIRST update of a scene: renders have not recorded user events yet (SceneReleaseAfterRender starts doing so once hasUpdate is set, so
+    // the FIRST update of a scene: renders have not been marked yet (SceneReleaseAfterRender starts doing so once there has been an update, so
     // that static scenes pay nothing), and kernels of earlier frames on non-blocking streams may still read the buffers this update overwrites
     // in place -- wait for the device once.  (Not legal inside a stream capture: capture a scene's update path only after its first update.)
-    if (!s->hasUpdate) HIP_TRY(hipDeviceSynchronize());
-    for (auto& u : s->users) if (u.first != st) HIP_TRY(hipStreamWaitEvent(st, u.second, 0));
-    // ... and updates on different streams are ordered against each other: this one runs behind the previous one (a render on `st` then only has
-    // to wait for the latest update, which is what SceneAcquireForRender does)
-    if (s->hasUpdate && s->updated && s->updatedOn != st) HIP_TRY(hipStreamWaitEvent(st, s->updated, 0));
-    return ZR_OK;
+    if (!s->HasUpdate()) HIP_TRY(hipDeviceSynchronize());
+    return s->order.AcquireWrite(s->points, st);
 }
-static int SceneMarkUpdatedLocked(zr_scene* s, hipStream_t st)      // (the caller holds mtx)
-{
-    if (!s->updated) HIP_TRY(hipEventCreateWithFlags(&s->updated, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(s->updated, st));
-    s->updatedOn = st; s->hasUpdate = true;
-    return ZR_OK;
-}
-static int SceneMarkUpdated(zr_scene* s, hipStream_t st) { std::lock_guard<std::mutex> lock(s->mtx); return SceneMarkUpdatedLocked(s, st); }
+static int SceneMarkUpdatedLocked(zr_scene* s, hipStream_t st) { return s->order.MarkWritten(s->points, st); }      // (the caller holds mtx)
+static int SceneMarkUpdated(zr_scene* s, hipStream_t st) { std::lock_guard<std::mutex> lock(s->mtx); return s->order.MarkWritten(s->points, st); }
 // cur <-> prev: the only place the two sets change roles (the caller holds mtx, and has ordered `st` behind the readers of both: SceneWaitUsers)
 static void SceneFlip(zr_scene* s)
 {
@@ -710,23 +711,12 @@ static void SceneBind(SceneView& v, const AccelSet& a)
     v.numNodes = a.numNodes; v.numTris = a.numTris;
 }
 // a render on `st`: behind the last update if that ran on another stream ...
-static int SceneAcquireForRender(const zr_scene* sc, hipStream_t st)
+static int SceneAcquireForRender(const zr_scene* sc, hipStream_t st) { std::lock_guard<std::mutex> lock(sc->mtx); return sc->order.AcquireRead(sc->points, st); }
+// ... and remembered as a reader of the scene's buffers (only once the scene has ever been updated: static scenes pay nothing)
+static int SceneReleaseAfterRender(const zr_scene* sc, hipStream_t st)
 {
     std::lock_guard<std::mutex> lock(sc->mtx);
-    if (sc->hasUpdate && sc->updatedOn != st) HIP_TRY(hipStreamWaitEvent(st, sc->updated, 0));
-    return ZR_OK;
-}
-// ... and remembered as a user of the scene's buffers (only once the scene has ever been updated: static scenes pay nothing)
-static int SceneReleaseAfterRender(const zr_scene* scc, hipStream_t st)
-{
-    zr_scene* sc = const_cast<zr_scene*>(scc);
-    std::lock_guard<std::mutex> lock(sc->mtx);
-    if (!sc->hasUpdate) return ZR_OK;
-    for (auto& u : sc->users) if (u.first == st) { HIP_TRY(hipEventRecord(u.second, st)); return ZR_OK; }
-    hipEvent_t ev; HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    sc->users.emplace_back(st, ev);
-    HIP_TRY(hipEventRecord(ev, st));
-    return ZR_OK;
+    return sc->HasUpdate() ? sc->order.MarkRead(sc->points, st) : ZR_OK;
 }
 
 // The scene as one launch sees it: a private copy of the scene's view with the texture descriptor-table offsets of THIS frame's
@@ -790,12 +780,13 @@ struct zr_gbuffer
     // rendered from another scene than the lighting pass is given, carry flags the lighting pass cannot vouch for -- they run the general kernels
     uint64_t sceneAt[3] = {0, 0, 0};
     // stream tracking (zr_pass_set_frame_overlap): with the passes of a frame spread over two streams, a GBUFFER render must not overwrite a plane set
-    // that a pass on another stream still reads, and a pass on another stream must not read a set before its GBUFFER render has finished
+    // that a pass on another stream still reads, and a pass on another stream must not read a set before its GBUFFER render has finished: one tracker per plane set, acting only while `tracked`
     bool tracked = false;
-    hipEvent_t evWritten = nullptr; hipStream_t writer = nullptr; bool hasWrite = false;
-    struct Reader { hipStream_t st; hipEvent_t ev; };
-    std::vector<Reader> readers[3];      // per plane set: the last read of every stream that has read it
-    ~zr_gbuffer() { if (evWritten) (void)hipEventDestroy(evWritten); for (auto& v : readers) for (auto& r : v) (void)hipEventDestroy(r.ev); }
+    HipOrderPoints points; HipStreamOrder order[3];
+    int AcquireRead(hipStream_t s) { return tracked ? order[cur].AcquireRead(points, s) : ZR_OK; }      // a pass on `s` is about to read the current planes
+    int MarkRead(int set, hipStream_t s) { return tracked ? order[set].MarkRead(points, s) : ZR_OK; }    // `s` has finished reading plane set `set` at this point of its queue
+    int AcquireWrite(int set, hipStream_t s) { return tracked ? order[set].AcquireWrite(points, s) : ZR_OK; }      // the GBUFFER pass on `s` is about to overwrite plane set `set`
+    int MarkWritten(hipStream_t s) { return tracked ? order[cur].MarkWritten(points, s) : ZR_OK; }       // ... and has rendered the current one
     DevBuf<uint8_t>* Planes() { return planeSets[cur]; }
     const DevBuf<uint8_t>* Planes() const { return planeSets[cur]; }
     GBuf View() const { return ViewOf(cur); }
@@ -812,39 +803,6 @@ struct zr_gbuffer
         return g;
     }
 };
-
-// tracked G-buffers: `s` has finished reading plane set `set` at this point of its queue
-static int GBufferMarkRead(zr_gbuffer* gb, int set, hipStream_t s)
-{
-    if (!gb || !gb->tracked) return ZR_OK;
-    for (auto& r : gb->readers[set]) if (r.st == s) { HIP_TRY(hipEventRecord(r.ev, s)); return ZR_OK; }
-    hipEvent_t ev; HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    gb->readers[set].push_back({s, ev});
-    HIP_TRY(hipEventRecord(ev, s));
-    return ZR_OK;
-}
-// ... a pass on `s` is about to read the current planes: behind their GBUFFER render if that ran on another stream
-static int GBufferAcquireRead(zr_gbuffer* gb, hipStream_t s)
-{
-    if (!gb || !gb->tracked || !gb->hasWrite || gb->writer == s) return ZR_OK;
-    HIP_TRY(hipStreamWaitEvent(s, gb->evWritten, 0));
-    return ZR_OK;
-}
-// ... the GBUFFER pass on `s` is about to overwrite plane set `set`: behind every other stream's last read of it
-static int GBufferAcquireWrite(zr_gbuffer* gb, int set, hipStream_t s)
-{
-    if (!gb->tracked) return ZR_OK;
-    for (auto& r : gb->readers[set]) if (r.st != s) HIP_TRY(hipStreamWaitEvent(s, r.ev, 0));
-    return ZR_OK;
-}
-static int GBufferMarkWritten(zr_gbuffer* gb, hipStream_t s)
-{
-    if (!gb->tracked) return ZR_OK;
-    if (!gb->evWritten) HIP_TRY(hipEventCreateWithFlags(&gb->evWritten, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(gb->evWritten, s));
-    gb->writer = s; gb->hasWrite = true;
-    return ZR_OK;
-}
 
 struct QueueStorage
 {
@@ -939,29 +897,16 @@ struct zr_pass
         rpt::RBuf View() const { rpt::RBuf v; v.A = A.p; v.B = B.p; v.C = C.p; v.D = D.p; return v; }
     } rb[2];
     Plane<F4> rptTarget, rptTargetAlt; Plane<uint8_t, 2> rptNeighbor; DevBuf<uint16_t> rptSampleSet;
-    // Frame overlap (zr_pass_set_frame_overlap).  rptSet: which storage plays the two roles currIdx flips between ([0], [1]) and which one is free ([2]);
-    // the CANDIDATES stage of an overlapped frame writes the free set and hands the set it replaces back.  tgtIdx / finIdx: the target / FINAL plane of
-    // the frame whose CANDIDATES stage ran last; finOut: the FINAL plane of the last frame whose final stage has been enqueued (zr_pass_get_output)
-    bool overlap = false, overlapCarry = false; int rptSet[3] = {0, 1, 2}; int tgtIdx = 0, finIdx = 0, finOut = 0;
+    // Frame overlap (zr_pass_set_frame_overlap): the roles of the three reservoir sets, the two target planes and the three FINAL planes, the mode, and
+    // the cross-stream order of every stage's accesses to them (zr_rpt_overlap.h).  Without overlap the roles still hold currIdx and frameOpen.
+    zr::RptOverlap<HipOrderBackend> ov;
     Plane<float, 4> finalAlt, finalAlt2;      // FINAL rotates over three planes: K11 of frame N + 2 (which clears the pixels without a surface) may run while frame N's is still being consumed
-    // the last stage of the frame before the previous one done (depth-2 pipelining, product mode): evDone[k & 1] is recorded when frame k closes
-    hipEvent_t evDone[2] = {nullptr, nullptr}; bool haveDone[2] = {false, false}; hipStream_t doneStream[2] = {nullptr, nullptr}; uint64_t ovFrame = 0;
-    bool doneTwoRounds[2] = {false, false};      // ... and whether that frame ran a second spatial round (carry mode: the round that writes the set the next K11 takes over)
-    hipEvent_t evTail = nullptr;                 // accumulating frames: the tail of the stream that carried the previous frame's last stage (its consumers included)
-    hipStream_t overlapStream = nullptr;                     // "stream A" for callers without streams of their own
-    hipEvent_t evCand = nullptr, evTemporal = nullptr;       // K11 of the open frame done (on candStream) / K14 of the last frame done (on reuseStream)
-    hipStream_t candStream = nullptr, reuseStream = nullptr; bool haveCand = false, haveTemporal = false;
-    zr_pass::ResStorage& RptCur() { return res[rptSet[currIdx]]; }
-    zr_pass::ResStorage& RptOth() { return res[rptSet[1 - currIdx]]; }
-    const zr_pass::ResStorage& RptOth() const { return res[rptSet[1 - currIdx]]; }
-    const Plane<F4>& TargetPlane() const { return tgtIdx ? rptTargetAlt : rptTarget; }
+    hipStream_t overlapStream = nullptr;      // "stream A" for callers without streams of their own
+    const Plane<F4>& TargetPlane(int i) const { return i ? rptTargetAlt : rptTarget; }
     const Plane<float, 4>& FinalPlane(int i) const { return i == 0 ? finalRGBA : (i == 1 ? finalAlt : finalAlt2); }
-    F4* Target() const { return TargetPlane().p; }
-    float* Final(int i) const { return FinalPlane(i).p; }
     Plane<uint16_t> rptMap[2];      // K12 thread maps: [0] CtN, [1] NtC
     DevBuf<uint32_t> trip; DevBuf<unsigned long long> tripStats;      // ZR_K11=trip diagnostic
     DevBuf<uint32_t> carry[2], carryCount;                             // K11 with per-bounce compaction: path-state planes (ping-pong), alive counts
-    bool frameOpen = false;      // ReSTIR PT staged rendering: a frame's TEMPORAL stage has run, its last stage has not
     DevBuf<uint32_t> costMap; bool costOn = false, costRays = false;      // rays per 32 x 32-px cell (zr_pass_enable_cost_map)
     DevBuf<uint32_t> rptLists, rptListCounts;      // 4 replay work lists (pixel ids) + their device-side counts
     // DI_EMISSIVE: two reservoir sets (A RGBA32_UINT, B RG32F), target, sample set
@@ -2547,13 +2492,13 @@ static int AllocPass(zr_pass* p)
             if ((r = p->costMap.AllocZero((size_t)((p->w + 31u) / 32u + 1u) * ((p->h + 31u) / 32u + 1u)))) return r;
             if ((r = p->rptSampleSet.Upload(kRptSampleSet, 1024))) return r;
             if ((r = p->rptLists.Alloc(4 * cap))) return r;
-            p->rptSet[0] = 0; p->rptSet[1] = 1; p->rptSet[2] = 2; p->tgtIdx = 0; p->finIdx = 0; p->finOut = 0; p->frameOpen = false; p->haveCand = false; p->haveTemporal = false; p->haveDone[0] = p->haveDone[1] = false;
-            if (p->overlap) { if ((r = AllocOverlapPlanes(p))) return r; }
+            p->ov.Reset();
+            if (p->ov.overlap) { if ((r = AllocOverlapPlanes(p))) return r; }
             // word layout (kRptListWords): [0, 1] temporal counts, [2, 3] first spatial round, [4, 5] the temporal replays' cursors (counts + 4 / + 5 of
             // base 0: the only DYNAMIC replay), [6, 7] second spatial round, [8 .. 11] = base 6's cursor slots -- unused (the spatial replays split
             // their lists statically) but allocated and zeroed, so that no base ever reaches past the buffer
             if ((r = p->rptListCounts.Alloc(kRptListWords))) return r;
-            p->temporalValid = false; p->currIdx = 0;
+            p->temporalValid = false;
         }
     }
     return ZR_OK;
@@ -2623,7 +2568,7 @@ static int RenderGBuffer(zr_pass* p, hipStream_t s, const zr_frame_constants* cb
     if (!gb) return Fail(ZR_ERR_INVALID_ARG, "GBUFFER pass needs a gbuffer");
     if (gb->x0 + gb->w > cb->render_width || gb->y0 + gb->h > cb->render_height) return Fail(ZR_ERR_INVALID_ARG, "gbuffer tile lies outside the render target of the frame constants");
     const uint32_t tilesX = (gb->w + 15) / 16, tilesY = (gb->h + 15) / 16;
-    if (int wr = GBufferAcquireWrite(gb, gb->Next(), s)) return wr;      // (tracked G-buffers: the set about to be overwritten may still be read on another stream)
+    if (int wr = gb->AcquireWrite(gb->Next(), s)) return wr;     // (tracked G-buffers: the set about to be overwritten may still be read on another stream)
     gb->cur = gb->Next(); gb->numRendered++;
     gb->plainAt[gb->cur] = sc->plainMaterials.load(std::memory_order_relaxed); gb->sceneAt[gb->cur] = sc->uid;
     TimerBegin(p, s, "gbuffer");
@@ -2639,7 +2584,7 @@ static int RenderGBuffer(zr_pass* p, hipStream_t s, const zr_frame_constants* cb
     TimerEnd(p, s);
     HIP_TRY(hipGetLastError());
     p->hostCounters.n_closest += (uint64_t)gb->w * gb->h;
-    return GBufferMarkWritten(gb, s);
+    return gb->MarkWritten(s);
 }
 
 // GBufferRT::PickPixel / ClearPick / GetPickReadbackBuffer (GBufferRT.h:36-46): every GBUFFER render while a pick is pending writes the mesh index under
@@ -3017,54 +2962,27 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
 {
     using namespace rpt;
     // the TEMPORAL stage in its two halves (zetaray_amd.h): K11 alone / K12 - K14
-    const zr_pass::ResStorage* carryFrom = nullptr;
     const bool stageCand = (stages & (ZR_STAGE_TEMPORAL | ZR_STAGE_CANDIDATES)) != 0, stageReuseT = (stages & (ZR_STAGE_TEMPORAL | ZR_STAGE_TEMPORAL_REUSE)) != 0;
-    if (stageCand && p->overlap)
+    const zr::RptRoles& roles = p->ov.roles;      // which storage plays which role; every stage below asks, p->ov's Begin / End calls move them
+    if (stageCand)
     {
-        // two frames in flight need the G-buffer's third plane set and its stream tracking: both belong to the G-buffer handed to zr_pass_set_frame_overlap (a renderer
-        // that replaces its G-buffer -- a resize -- hands the new one over again)
-        if (!gb->tracked || gb->numSets < 3) return Fail(ZR_ERR_INVALID_ARG, "ReSTIR PT with frame overlap: this G-buffer is not the one given to zr_pass_set_frame_overlap (call it again with the new G-buffer)");
-        if (p->frameOpen) return Fail(ZR_ERR_INVALID_ARG, "ReSTIR PT with frame overlap: the previous frame's last stage has not been enqueued (stage order: CANDIDATES, TEMPORAL_REUSE, SPATIAL[, SPATIAL2])");
-        // Frame overlap: this frame's K11 runs beside the previous frame's reuse passes, which still read the two sets in play and that frame's target
-        // plane -- so it writes the free set (which takes the "current" role; the set it replaces is free from here on) and the other target / FINAL
-        // plane, behind the previous frame's temporal reuse: the last kernel that read what is recycled here (K16 of the frame before it precedes that
-        // K14 on its stream) and the last reader of the G-buffer set this frame's GBUFFER render overwrote.
-        std::swap(p->rptSet[p->currIdx], p->rptSet[2]);
-        p->tgtIdx ^= 1;
-        carryFrom = p->overlapCarry ? &p->res[p->rptSet[2]] : nullptr;
-        if (!(cb->accumulate && cb->camera_static)) p->finIdx = (p->finIdx + 1) % 3;      // (an accumulating frame adds to the plane the frames before it wrote)
-        const int kPrev = (int)((p->ovFrame + 1) & 1);      // the previous frame's slot of evDone
-        if (p->overlapCarry)
-        {   // carry mode copies the replaced set, whose last writer is the previous frame's K14: one frame of overlap (beside that frame's spatial stage) --
-            // unless that frame ran two spatial rounds: the set this frame takes over is then the one its FIRST round wrote (K14's set is that frame's
-            // final one), so the copy goes behind the whole frame
-            if (p->haveDone[kPrev] && p->doneTwoRounds[kPrev]) { if (p->doneStream[kPrev] != s) HIP_TRY(hipStreamWaitEvent(s, p->evDone[kPrev], 0)); }
-            else if (p->haveTemporal && p->reuseStream != s) HIP_TRY(hipStreamWaitEvent(s, p->evTemporal, 0));
-        }
-        else
-        {   // product mode: what this stage recycles -- the free reservoir set and this parity's target plane -- was last touched by the frame BEFORE the
-            // previous one (its spatial stage read them), and the G-buffer has a third plane set: two frames of overlap, the first half of frame N + 2 also
-            // runs beside the temporal reuse of frame N + 1
-            const int k = (int)(p->ovFrame & 1);
-            if (p->haveDone[k] && p->doneStream[k] != s) HIP_TRY(hipStreamWaitEvent(s, p->evDone[k], 0));
-        }
-        // An accumulating frame keeps the FINAL plane of the frame before it, and its K11 adds into that plane whenever there is no temporal reuse
-        // (PtFinishLane).  That must come after the previous frame's own "+=" AND after whatever consumes that frame, which the caller has enqueued
-        // behind its last stage on the same stream (zetaray_amd.h): this half goes behind that stream's tail as it stands now.  Accumulating frames
-        // therefore do not overlap; the others keep the waits above and nothing else.
-        if (cb->accumulate && cb->camera_static && p->haveDone[kPrev] && p->doneStream[kPrev] != s)
+        if (p->ov.overlap)
         {
-            HIP_TRY(hipEventRecord(p->evTail, p->doneStream[kPrev]));
-            HIP_TRY(hipStreamWaitEvent(s, p->evTail, 0));
+            // two frames in flight need the G-buffer's third plane set and its stream tracking: both belong to the G-buffer handed to zr_pass_set_frame_overlap (a renderer
+            // that replaces its G-buffer -- a resize -- hands the new one over again)
+            if (!gb->tracked || gb->numSets < 3) return Fail(ZR_ERR_INVALID_ARG, "ReSTIR PT with frame overlap: this G-buffer is not the one given to zr_pass_set_frame_overlap (call it again with the new G-buffer)");
+            if (roles.frameOpen) return Fail(ZR_ERR_INVALID_ARG, "ReSTIR PT with frame overlap: the previous frame's last stage has not been enqueued (stage order: CANDIDATES, TEMPORAL_REUSE, SPATIAL[, SPATIAL2])");
         }
+        // K11's accesses (with overlap: after the roles have moved on to this frame's).  Only host work lies between here and its launches.
+        if (int br = p->ov.BeginCandidates(s, cb->accumulate && cb->camera_static)) return br;
     }
     RptFrame F;
     F.sc = FrameView(sc, cb); F.gb = gb->View(); F.gbPrev = gb->PrevView();
     F.scPrev = FrameViewPrev(sc, cb);
     F.sc.texFilter = F.scPrev.texFilter = p->params.tex_filter;
     if (int orc = ResolveOwnedRect(p, gb, cb, &F.ox0, &F.oy0, &F.ow, &F.oh)) return orc;
-    F.rbCtN = p->rb[0].View(); F.rbNtC = p->rb[1].View(); F.tex.target = p->Target(); F.tex.neighbor = p->rptNeighbor.p;
-    F.finalRGBA = p->Final(p->finIdx); F.sampleSet = p->rptSampleSet.p;
+    F.rbCtN = p->rb[0].View(); F.rbNtC = p->rb[1].View(); F.tex.target = p->TargetPlane(roles.Target()).p; F.tex.neighbor = p->rptNeighbor.p;
+    F.finalRGBA = p->FinalPlane(roles.Final()).p; F.sampleSet = p->rptSampleSet.p;
     F.mapCtN = p->rptMap[0].p; F.mapNtC = p->rptMap[1].p;
     F.costMap = p->costOn ? p->costMap.p : nullptr; F.costW = (p->w + 31u) / 32u + 1u; F.costMode = p->costRays ? 1u : 0u;
     F.trip = nullptr; F.tripStats = nullptr; F.tripStride = 0;
@@ -3102,7 +3020,7 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
     prm.doTemporal = p->doTemporal ? 1u : 0u;
     prm.doSpatial = p->doSpatial ? 1u : 0u;
     prm.writeReservoirs = (prm.doTemporal || !p->temporalValid) ? 1u : 0u;
-    F.cur = p->RptCur().View(); F.prev = p->RptOth().View();
+    F.cur = p->res[roles.Cur()].View(); F.prev = p->res[roles.Oth()].View();
     const uint32_t tilesX = (F.ow + 15) / 16, tilesY = (F.oh + 15) / 16;
     const dim3 grid(tilesX * tilesY), block(kBlock);
     const dim3 gridRpt(tilesX * tilesY * (256 / kRptBlock)), blockRpt(kRptBlock);      // K11 (zr_kernels.h kRptBlock)
@@ -3141,15 +3059,15 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
         else { if (texVariant) hipLaunchKernelGGL((kern<false, true>), __VA_ARGS__, view); else hipLaunchKernelGGL((kern<false, false>), __VA_ARGS__, view); } } while (0)
     if (stageCand)
     {
-        if (int ar = GBufferAcquireRead(gb, s)) return ar;
-        if (carryFrom)
+        if (int ar = gb->AcquireRead(s)) return ar;
+        if (roles.carryFrom >= 0)
         {
             // ZR_FRAME_OVERLAP_CARRY: K11 and the passes behind it update reservoir records in place (Reservoir.hlsli:283-456 writes the components a record's case
             // uses), so the bytes a record does NOT use are whatever the set held before -- in the plain order the set K11 wrote last frame, here the free set.
             // Copying the replaced set (and target plane) into the one that takes its place makes every byte of every plane equal to the plain order's.
             const size_t n = (size_t)p->w * p->h;
-            RPT_TIMED("rpt_overlap_carry", hipLaunchKernelGGL(k_rpt_carry, dim3((uint32_t)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, s, F.cur, carryFrom->View(), p->Target(),
-                (const F4*)(p->tgtIdx ? p->rptTarget.p : p->rptTargetAlt.p), n));
+            RPT_TIMED("rpt_overlap_carry", hipLaunchKernelGGL(k_rpt_carry, dim3((uint32_t)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, s, F.cur, p->res[roles.carryFrom].View(), F.tex.target,
+                (const F4*)p->TargetPlane(roles.OtherTarget()).p, n));
         }
         TimerBegin(p, s, "rpt_pathtrace");
         if (view != ZR_RPT_VIEW_NONE) RPT_LAUNCH_VIEW(k_rpt_pathtrace_view, gridRpt, blockRpt, 0, s, F, *cb, tilesX, ctr + 2 * 1);
@@ -3209,12 +3127,15 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
         }
         }
         TimerEnd(p, s);
-        if (p->overlap) { HIP_TRY(hipEventRecord(p->evCand, s)); p->candStream = s; p->haveCand = true; }
+        if (int er = p->ov.EndCandidates(s)) return er;
     }
     if (stageReuseT)
     {
-        if (p->overlap && p->haveCand && p->candStream != s) HIP_TRY(hipStreamWaitEvent(s, p->evCand, 0));      // (K11, and with it the GBUFFER render before it on that stream)
-        else if (int ar = GBufferAcquireRead(gb, s)) return ar;
+        // behind K11 when that ran on another stream (it wrote the current set, the target and FINAL), and with it behind the GBUFFER render before it there
+        hipStream_t k11;
+        const bool behindK11 = p->ov.CandidatesStream(&k11) && k11 != s;      // (K11 read the same planes, behind their render)
+        if (int br = p->ov.BeginTemporalReuse(s)) return br;
+        if (!behindK11) if (int ar = gb->AcquireRead(s)) return ar;
         HIP_TRY(hipMemsetAsync(listCnt, 0, kRptListWords * sizeof(uint32_t), s));      // (the work lists are the reuse passes' alone: K11 of the next frame may already run)
         if (prm.doTemporal)
         {
@@ -3227,14 +3148,15 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
             else RPT_TIMED("rpt_reconnect_temporal", RPT_LAUNCH_E(k_rpt_temporal, gridRecon, blockRecon, 0, s, F, *cb, tilesX, ctr + 2 * 4));
         }
         // nothing after this point reads the PREVIOUS frame's G-buffer, its final reservoirs or scene (the spatial passes read this frame's only)
-        if (p->overlap) { HIP_TRY(hipEventRecord(p->evTemporal, s)); p->reuseStream = s; p->haveTemporal = true; }
-        if (int mr = GBufferMarkRead(gb, gb->Prev(), s)) return mr;
+        if (int er = p->ov.EndTemporalReuse(s)) return er;
+        if (int mr = gb->MarkRead(gb->Prev(), s)) return mr;
     }
     for (uint32_t spass = 0; spass < numSpatialPasses && prm.doSpatial; spass++)
     {
         if (!(stages & (spass == 0 ? ZR_STAGE_SPATIAL : ZR_STAGE_SPATIAL2))) continue;
-        // a round reads res[currIdx] and writes the other set, which then becomes "current" (IndirectLighting.cpp:609-612, 682-688: one flip per round)
-        F.cur = p->RptCur().View(); F.prev = p->RptOth().View();
+        // a round reads the current set and writes the other one, which then becomes "current" (IndirectLighting.cpp:609-612, 682-688: one flip per round)
+        if (int br = p->ov.BeginSpatialRound(s)) return br;
+        F.cur = p->res[roles.Cur()].View(); F.prev = p->res[roles.Oth()].View();
         // replay work lists + their device-side counts of this round: {2, 3} for the first, {6, 7} for the second (zeroed at the start of the frame)
         uint32_t* const sCnt = listCnt + (spass == 0 ? 2 : 6);
 #ifdef ZR_EXPERIMENTS
@@ -3253,29 +3175,21 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
         RPT_TIMED("rpt_replay_spatial", RPT_LAUNCH_PE(k_rpt_replay, RPT_REPLAY_CTS, dim3(gridList.x * 2), block, 0, s, F, *cb, lists[2], lists[3], sCnt, ctr + 2 * 5));
         if (view != ZR_RPT_VIEW_NONE) RPT_TIMED("rpt_reconnect_spatial", RPT_LAUNCH_VIEW(k_rpt_stc_view, gridStc, blockStc, 0, s, F, *cb, tilesX, ctr + 2 * 7));
         else RPT_TIMED("rpt_reconnect_spatial", RPT_LAUNCH_E(k_rpt_stc, gridStc, blockStc, 0, s, F, *cb, tilesX, ctr + 2 * 7));
-        // "Prepare for next iteration" (IndirectLighting.cpp:860-870: std::swap(inputs, outputs)) is the flip itself here: the next round starts from res[currIdx]
-        p->currIdx = 1 - p->currIdx;
+        // "Prepare for next iteration" (IndirectLighting.cpp:860-870: std::swap(inputs, outputs)) is the flip itself here: the next round starts from the set this one wrote
+        if (int er = p->ov.EndSpatialRound(s)) return er;
     }
 #undef RPT_TIMED
 #undef RPT_LAUNCH_E
 #undef RPT_LAUNCH_PE
 #undef RPT_LAUNCH_VIEW
     HIP_TRY(hipGetLastError());
-    if (stageCand) p->frameOpen = true;
     // the frame ends with its last stage: the second round when there is one this frame, else ZR_STAGE_SPATIAL; Render() flips once more (:1018-1024)
     const bool lastStage = (prm.doSpatial && numSpatialPasses == 2u) ? (stages & ZR_STAGE_SPATIAL2) != 0 : (stages & ZR_STAGE_SPATIAL) != 0;
-    if (lastStage && p->frameOpen)
+    if (lastStage && roles.frameOpen)
     {
         p->temporalValid = true;
-        p->currIdx = 1 - p->currIdx;
-        p->frameOpen = false;
-        p->finOut = p->finIdx;
-        if (p->overlap)
-        {
-            const int k = (int)(p->ovFrame & 1);
-            HIP_TRY(hipEventRecord(p->evDone[k], s)); p->haveDone[k] = true; p->doneStream[k] = s; p->doneTwoRounds[k] = prm.doSpatial && numSpatialPasses == 2u; p->ovFrame++;
-        }
-        if (int mr = GBufferMarkRead(gb, gb->cur, s)) return mr;
+        p->ov.CloseFrame();
+        if (int mr = gb->MarkRead(gb->cur, s)) return mr;
     }
     return ZR_OK;
 }
@@ -3694,20 +3608,14 @@ int zr_pass_set_frame_overlap(zr_pass* p, zr_gbuffer* gb, int enable)
     if (!p || !gb) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_frame_overlap: null argument");
     if (!p->initialized) return Fail(ZR_ERR_NOT_INITIALIZED, "pass not initialised");
     if (p->kind != ZR_PASS_INDIRECT || p->integrator != ZR_INTEGRATOR_RESTIR_PT) return Fail(ZR_ERR_UNSUPPORTED, "frame overlap is a mode of the ReSTIR PT pass");
-    if (p->frameOpen) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_frame_overlap: call between frames (a frame's last stage has not been enqueued)");
+    if (p->ov.roles.frameOpen) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_frame_overlap: call between frames (a frame's last stage has not been enqueued)");
     if (gb->device != p->device) return Fail(ZR_ERR_INVALID_ARG, "gbuffer / pass live on different devices");
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipDeviceSynchronize());      // (a host call between frames; the planes allocated below are cleared on the null stream)
     if (enable && !p->res[2].A.p) { if (int r = AllocOverlapPlanes(p)) return r; HIP_TRY(hipDeviceSynchronize()); }
-    if (enable && !p->evCand)
-    {
-        HIP_TRY(hipEventCreateWithFlags(&p->evCand, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&p->evTemporal, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&p->evDone[0], hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&p->evDone[1], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&p->evTail, hipEventDisableTiming));
-        HIP_TRY(hipStreamCreateWithFlags(&p->overlapStream, hipStreamNonBlocking));
-    }
+    if (enable && !p->overlapStream) HIP_TRY(hipStreamCreateWithFlags(&p->overlapStream, hipStreamNonBlocking));
     // switching off keeps the plane roles as they stand (the set last written as FINAL stays the one the next frame reads); FINAL goes on in the plane it is in
-    p->overlap = enable != 0; p->overlapCarry = enable == ZR_FRAME_OVERLAP_CARRY; p->haveCand = false; p->haveTemporal = false; p->haveDone[0] = p->haveDone[1] = false;
+    p->ov.SetMode(enable != 0, enable == ZR_FRAME_OVERLAP_CARRY);      // (behind the device synchronize above: no stage has a predecessor yet)
     if (enable && gb->numSets == 2)
     {   // the third plane set (never given back: the sets' roles rotate)
         for (int i = 0; i < ZR_GB_COUNT; i++)
@@ -3724,7 +3632,7 @@ int zr_pass_set_frame_overlap(zr_pass* p, zr_gbuffer* gb, int enable)
         gb->numSets = 3;
     }
     gb->tracked = enable != 0;
-    if (!enable) { gb->hasWrite = false; for (auto& v : gb->readers) { for (auto& r : v) (void)hipEventDestroy(r.ev); v.clear(); } }
+    if (!enable) { for (auto& o : gb->order) o.Reset(); gb->points.Reset(); }
     return ZR_OK;
 }
 int zr_pass_frame_overlap_stream(zr_pass* p, void** stream)
@@ -3749,7 +3657,7 @@ static zr_pass::ResStorage* HaloSet(zr_pass* p, int which)
 {
     // between the stages of a frame the post-temporal reservoirs are res[currIdx]; after the frame the set the next
     // frame reads as "previous" is res[1 - currIdx]
-    return &p->res[p->rptSet[which == ZR_HALO_POST_TEMPORAL ? p->currIdx : 1 - p->currIdx]];
+    return &p->res[which == ZR_HALO_POST_TEMPORAL ? p->ov.roles.Cur() : p->ov.roles.Oth()];
 }
 // ZR_HALO_DENOISE_INPUT: what the temporal step of a tile reads in its apron -- this frame's signal (the bound input plane: its owner shaded it, in the
 // layout of the history; null while unbound) and the history the previous frame left (colour + length, moments)
@@ -3766,7 +3674,7 @@ static int HaloPlanes(zr_pass* p, int which, HaloPlane* planes, size_t* bytesPer
     // "previous" is [1 - currIdx]
     const int set = which == ZR_HALO_POST_TEMPORAL ? p->currIdx : 1 - p->currIdx;
     int n = 0;
-    if (p->kind == ZR_PASS_INDIRECT && p->integrator == ZR_INTEGRATOR_RESTIR_PT) n = PlanesHalo(p->res[p->rptSet[set]], planes);
+    if (p->kind == ZR_PASS_INDIRECT && p->integrator == ZR_INTEGRATOR_RESTIR_PT) n = PlanesHalo(*HaloSet(p, which), planes);
     else if (p->kind == ZR_PASS_INDIRECT && p->integrator == ZR_INTEGRATOR_RESTIR_GI)
     { planes[n++] = p->giA[set].Halo(); planes[n++] = p->giB[set].Halo(); planes[n++] = p->giC[set].Halo(); }
     else if (p->kind == ZR_PASS_DI_EMISSIVE) { planes[n++] = p->diA[set].Halo(); planes[n++] = p->diB[set].Halo(); }
@@ -3866,10 +3774,10 @@ int zr_pass_render_stage(zr_pass* p, void* stream, const zr_frame_constants* cb,
     // the planes' GBUFFER render when that ran on another stream and leaves an event behind its reads of both plane sets
     const bool rptPass = p->kind == ZR_PASS_INDIRECT && p->integrator == ZR_INTEGRATOR_RESTIR_PT;
     const bool trackedReader = gb && gb->tracked && p->kind != ZR_PASS_GBUFFER && !rptPass;
-    if (trackedReader) { if ((r = GBufferAcquireRead(gb, (hipStream_t)stream))) return r; }
+    if (trackedReader) { if ((r = gb->AcquireRead((hipStream_t)stream))) return r; }
     r = RenderStageInner(p, stream, cb, sc, gb, stages);
     if (r) return r;
-    if (trackedReader) { if ((r = GBufferMarkRead(gb, gb->cur, (hipStream_t)stream)) || (r = GBufferMarkRead(gb, gb->Prev(), (hipStream_t)stream))) return r; }
+    if (trackedReader) { if ((r = gb->MarkRead(gb->cur, (hipStream_t)stream)) || (r = gb->MarkRead(gb->Prev(), (hipStream_t)stream))) return r; }
     return SceneReleaseAfterRender(sc, (hipStream_t)stream);
 }
 static int RenderStageInner(zr_pass* p, void* stream, const zr_frame_constants* cb, const zr_scene* sc, zr_gbuffer* gb, int stages)
@@ -3999,7 +3907,7 @@ int zr_pass_get_output(const zr_pass* p, int which, void** dev, uint32_t* w, uin
         return ZR_OK;
     }
     if (p->kind != ZR_PASS_INDIRECT) return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
-    if (which == ZR_OUT_FINAL) p->FinalPlane(p->finOut).Output(dev, bpp);
+    if (which == ZR_OUT_FINAL) p->FinalPlane(p->ov.roles.finOut).Output(dev, bpp);
     else if (which >= ZR_OUT_RGI_RESERVOIR_A && which <= ZR_OUT_RGI_RESERVOIR_C && p->integrator == ZR_INTEGRATOR_RESTIR_GI)
     {
         const int last = 1 - p->currIdx;
@@ -4013,8 +3921,8 @@ int zr_pass_get_output(const zr_pass* p, int which, void** dev, uint32_t* w, uin
         p->rptMap[which - ZR_OUT_RPT_THREAD_MAP_CTN].Output(dev, bpp);
     else if (which >= ZR_OUT_RPT_RESERVOIR_A && which <= ZR_OUT_RPT_NEIGHBOR && p->integrator == ZR_INTEGRATOR_RESTIR_PT)
     {
-        if (which <= ZR_OUT_RPT_RESERVOIR_G) PlanesOutput(p->RptOth(), which - ZR_OUT_RPT_RESERVOIR_A, dev, bpp);      // the set the next frame reads as "previous"
-        else if (which == ZR_OUT_RPT_TARGET) p->TargetPlane().Output(dev, bpp);
+        if (which <= ZR_OUT_RPT_RESERVOIR_G) PlanesOutput(p->res[p->ov.roles.Oth()], which - ZR_OUT_RPT_RESERVOIR_A, dev, bpp);      // the set the next frame reads as "previous"
+        else if (which == ZR_OUT_RPT_TARGET) p->TargetPlane(p->ov.roles.Target()).Output(dev, bpp);
         else p->rptNeighbor.Output(dev, bpp);
     }
     else return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
@@ -4087,6 +3995,13 @@ int zr_pass_get_emissive_powers(zr_pass* p, void* stream, float* out, uint32_t n
     return ZR_OK;
 }
 
+// frame overlap: K11 may have run on another stream than the one the caller reads its counters on
+static int SyncCandidates(zr_pass* p)
+{
+    hipStream_t k11;
+    if (p->ov.CandidatesStream(&k11)) HIP_TRY(hipStreamSynchronize(k11));
+    return ZR_OK;
+}
 int zr_pass_read_counters(zr_pass* p, void* stream, zr_counters* out, int reset)
 {
     if (!p || !out) return Fail(ZR_ERR_INVALID_ARG, "null argument");
@@ -4096,7 +4011,7 @@ int zr_pass_read_counters(zr_pass* p, void* stream, zr_counters* out, int reset)
     {
         unsigned long long c[2 * kCounterSlots];
         HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-        if (p->haveCand) HIP_TRY(hipStreamSynchronize(p->candStream));      // (frame overlap: K11 may have run on another stream)
+        if (int r = SyncCandidates(p)) return r;
         HIP_TRY(hipMemcpy(c, p->counters.p, sizeof(c), hipMemcpyDeviceToHost));
         for (int i = 0; i < kCounterSlots; i++) { out->n_closest += c[2 * i]; out->n_shadow += c[2 * i + 1]; }
         if (reset) { HIP_TRY(hipMemsetAsync(p->counters.p, 0, sizeof(c), (hipStream_t)stream)); HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); }
@@ -4112,7 +4027,7 @@ int zr_pass_read_kernel_counters(zr_pass* p, void* stream, uint32_t max_entries,
     HIP_TRY(hipSetDevice(p->device));
     unsigned long long c[2 * kCounterSlots];
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    if (p->haveCand) HIP_TRY(hipStreamSynchronize(p->candStream));
+    if (int r = SyncCandidates(p)) return r;
     HIP_TRY(hipMemcpy(c, p->counters.p, sizeof(c), hipMemcpyDeviceToHost));
     uint32_t n = 0;
     for (int i = 0; i < kCounterSlots && n < max_entries; i++)
@@ -4162,10 +4077,6 @@ int zr_pass_destroy(zr_pass* p)
     if (p->powerEv) (void)hipEventDestroy(p->powerEv);
     if (p->powerHost) (void)hipHostFree(p->powerHost);
     if (p->overlapStream) { (void)hipStreamSynchronize(p->overlapStream); (void)hipStreamDestroy(p->overlapStream); }
-    if (p->evCand) (void)hipEventDestroy(p->evCand);
-    if (p->evTemporal) (void)hipEventDestroy(p->evTemporal);
-    for (auto& e : p->evDone) if (e) (void)hipEventDestroy(e);
-    if (p->evTail) (void)hipEventDestroy(p->evTail);
     delete p;
     return ZR_OK;
 }
