@@ -94,9 +94,11 @@ static GBuf ViewOf(const zr_gbuffer_planes* p)
     return g;
 }
 
-// ---- the cross-stream ordering of zr_api.hip (zr_stream_order.h, zr_rpt_overlap.h) with a backend that logs instead of calling HIP: streams and
-// events are small integers, the log is records of four int32 (kind, a, b, c)
+// ---- the frame state of the ReSTIR passes as zr_api.hip derives it (zr_pass_frame.h: reuse flags, kernel parameters, which reservoir set is which),
+// and its cross-stream ordering (zr_stream_order.h, zr_rpt_overlap.h) with a backend that logs instead of calling HIP: streams and events are small
+// integers, the log is records of four int32 (kind, a, b, c)
 #include "../../zetaray_amd/csrc/zr_rpt_overlap.h"
+#include "../../zetaray_amd/csrc/zr_pass_frame.h"
 enum { HX_LOG_OP = 0,        // an op begins: a = its index, b = stage, c = stream
        HX_LOG_CREATE = 1,    // a = event
        HX_LOG_DESTROY = 2,   // a = event
@@ -500,7 +502,7 @@ void zhx_trace_any(const HxScene* s, const float* rays, uint32_t n, uint32_t mas
 // ---------------------------------------------------------------- ReSTIR PT (zr_rpt.h) in program order
 struct HxRpt
 {
-    uint32_t w = 0, h = 0; bool temporalValid = false, doTemporal = false, doSpatial = false, frameOpen = false; int currIdx = 0;
+    uint32_t w = 0, h = 0; PassHistory hist; bool doTemporal = false, doSpatial = false; RptRoles roles;      // (the roles without overlap: sets 0 and 1)
     std::vector<uint16_t> map[2];      // K12 thread maps (CtN, NtC)
     struct Planes { std::vector<uint32_t> A, G; std::vector<float> B, F; std::vector<U4> C, D; std::vector<uint16_t> E;
         void Resize(size_t n) { A.assign(n, 0); B.assign(2 * n, 0); C.assign(n, U4{0, 0, 0, 0}); D.assign(n, U4{0, 0, 0, 0}); E.assign(n, 0); F.assign(2 * n, 0); G.assign(2 * n, 0); }
@@ -520,7 +522,7 @@ HxRpt* zhx_rpt_create(uint32_t w, uint32_t h)
     return r;
 }
 void zhx_rpt_destroy(HxRpt* r) { delete r; }
-void zhx_rpt_reset_temporal(HxRpt* r) { r->temporalValid = false; }
+void zhx_rpt_reset_temporal(HxRpt* r) { r->hist.Invalidate(); }
 
 // owned rect (global pixel coordinates) for the screen-tile split; w == 0 -> the whole plane rect
 static uint32_t g_own[4] = {0, 0, 0, 0};
@@ -544,16 +546,16 @@ void zhx_rpt_render_stage(const HxScene* s, HxRpt* R, const zr_frame_constants* 
     F.rbCtN = R->rb[0].View(); F.rbNtC = R->rb[1].View(); F.tex.target = R->target.data(); F.tex.neighbor = R->neighbor.data();
     F.finalRGBA = finalRGBA; F.sampleSet = kRptSampleSet;
     SetMaterialClass(F, g_plain);
-    RptParams& prm = F.prm;
-    prm.maxNonTrBounces = params->max_non_tr_bounces; prm.maxGlossyTrBounces = params->max_glossy_tr_bounces;
-    prm.russianRoulette = (params->flags & ZR_IND_RUSSIAN_ROULETTE) ? 1u : 0u;
-    prm.numSampleSets = params->presampling ? params->num_sample_sets : 0u;
-    prm.accumulate = (g.accumulate && g.camera_static) ? 1u : 0u;
-    prm.boiling = (params->flags & ZR_IND_BOILING_SUPPRESSION) ? 1u : 0u;
-    prm.M_max_temporal = params->m_max_temporal & 0xf; prm.M_max_spatial = params->m_max_spatial & 0xf; prm.alpha_min = params->alpha_min;
-    prm.emissive = g.num_emissive_triangles ? 1u : 0u;
-    prm.textured = s->view.tex.count ? 1u : 0u;
-    prm.temporalMap = 0; prm.sortTemporal = (params->flags & ZR_IND_SORT_TEMPORAL) ? 1u : 0u; prm.sortSpatial = (params->flags & ZR_IND_SORT_SPATIAL) ? 1u : 0u;
+    RptRoles& roles = R->roles;
+    if (stages & 1)
+    {   // the CANDIDATES stage: what the frame reuses is decided here and held for its later stages ("previous exists" is a non-null `prev` here)
+        roles.BeginCandidates(false, false, g.accumulate && g.camera_static);
+        const ReuseFlags now = ReuseFlagsOf(params->flags, R->hist.valid, prev != nullptr, g);
+        R->doTemporal = now.doTemporal != 0;
+        R->doSpatial = now.doSpatial && params->num_spatial_passes > 0;
+    }
+    const uint32_t numSpatialPasses = params->num_spatial_passes > 2u ? 2u : params->num_spatial_passes;      // (clamped here, refused by the library)
+    const RptParams& prm = F.prm = RptParamsOf(*params, g, ReuseFlagsLatched(R->doTemporal, R->doSpatial, R->hist.valid, g), s->view.tex.count != 0);      // (temporalMap 0: no thread map schedules a serial run)
     R->map[0].resize((size_t)F.gb.w * F.gb.h); R->map[1].resize((size_t)F.gb.w * F.gb.h);
     F.mapCtN = R->map[0].data(); F.mapNtC = R->map[1].data();
     // K12 on the host: the kernel's bucket order (wave, lane, quad slot) is plain thread order when the group runs serially
@@ -583,16 +585,7 @@ void zhx_rpt_render_stage(const HxScene* s, HxRpt* R, const zr_frame_constants* 
             for (auto& b : bucket) for (const Px& q : b) { write(q, idx & 31u, idx >> 5); idx++; }
         }
     };
-    if (stages & 1)
-    {
-        R->doTemporal = (params->flags & ZR_IND_TEMPORAL_RESAMPLE) && R->temporalValid && prev;
-        R->doSpatial = (params->flags & ZR_IND_SPATIAL_RESAMPLE) && R->doTemporal && params->num_spatial_passes > 0;
-    }
-    const uint32_t numSpatialPasses = params->num_spatial_passes > 2u ? 2u : params->num_spatial_passes;
-    prm.doTemporal = R->doTemporal ? 1u : 0u;
-    prm.doSpatial = R->doSpatial ? 1u : 0u;
-    prm.writeReservoirs = (prm.doTemporal || !R->temporalValid) ? 1u : 0u;
-    F.cur = R->res[R->currIdx].View(); F.prev = R->res[1 - R->currIdx].View();
+    F.cur = R->res[roles.Cur()].View(); F.prev = R->res[roles.Oth()].View();
     zr::StackEntry stackMem[zr::kTravStack]; zr::TravStack stack; stack.lds = nullptr; stack.stride = 0; stack.mem = stackMem;
 
     if (stages & 1)
@@ -641,6 +634,7 @@ void zhx_rpt_render_stage(const HxScene* s, HxRpt* R, const zr_frame_constants* 
             for (uint32_t l = 0; l < 64; l++) PtFinishLane(F.gb, prm, F.cur, F.tex, finalRGBA, lanes[l]);
             flush();
         }
+        roles.EndCandidates();
         if (prm.doTemporal)
         {
             sortPass(RPT_SORT_TTC, F.mapNtC); sortPass(RPT_SORT_CTT, F.mapCtN);      // unconditional, like the reference
@@ -651,7 +645,7 @@ void zhx_rpt_render_stage(const HxScene* s, HxRpt* R, const zr_frame_constants* 
     for (uint32_t spass = 0; spass < numSpatialPasses && prm.doSpatial; spass++)
     {
         if (!(stages & (spass == 0 ? 2 : 4))) continue;      // ZR_STAGE_SPATIAL / ZR_STAGE_SPATIAL2
-        F.cur = R->res[R->currIdx].View(); F.prev = R->res[1 - R->currIdx].View();      // a round reads the current set and writes the other, which becomes current
+        F.cur = R->res[roles.Cur()].View(); F.prev = R->res[roles.Oth()].View();      // a round reads the current set and writes the other, which becomes current
         for (uint32_t y = Y0; y < Y1; y++) for (uint32_t x = X0; x < X1; x++) SpatialSearchPixel(F, g, x, y);
         if (prm.sortSpatial) { sortPass(RPT_SORT_CTS, F.mapCtN); sortPass(RPT_SORT_STC, F.mapNtC); }
         for (int v = 0; v < 2; v++) for (uint32_t y = Y0; y < Y1; y++) for (uint32_t x = X0; x < X1; x++) { ReplaySpatialPixel(F, g, v, x, y, stack, cnt); flush(); }
@@ -673,19 +667,13 @@ void zhx_rpt_render_stage(const HxScene* s, HxRpt* R, const zr_frame_constants* 
             const float sum4 = ButterflySum64(v4);
             for (uint32_t l = 0; l < 64; l++) StcPhase3(F, g, L[l], sum2 + sum3 + sum4);
         }
-        R->currIdx = 1 - R->currIdx;      // one flip per round: the round's outputs are the next round's inputs
+        roles.SpatialRound();      // one flip per round: the round's outputs are the next round's inputs
     }
     flush();
     if (counters) { counters->n_closest = total[0]; counters->n_shadow = total[1]; }
-    if (stages & 1) R->frameOpen = true;
     // the frame ends with its last stage (the second round when there is one this frame, else stage 2); Render() flips again
     const bool lastStage = (prm.doSpatial && numSpatialPasses == 2u) ? (stages & 4) != 0 : (stages & 2) != 0;
-    if (lastStage && R->frameOpen)
-    {
-        R->temporalValid = true;
-        R->currIdx = 1 - R->currIdx;
-        R->frameOpen = false;
-    }
+    if (lastStage && roles.frameOpen) { R->hist.valid = true; roles.CloseFrame(); }
 }
 void zhx_rpt_render(const HxScene* s, HxRpt* R, const zr_frame_constants* cb, const zr_gbuffer_planes* curr, const zr_gbuffer_planes* prev,
     const zr_params* params, float* finalRGBA, zr_counters* counters)
@@ -694,7 +682,7 @@ void zhx_rpt_render(const HxScene* s, HxRpt* R, const zr_frame_constants* cb, co
 // which: 0 = the set the next frame reads as "previous", 1 = the other.  plane: 0..6 = A..G, 7 = target, 8 = neighbor
 int zhx_rpt_read_plane(const HxRpt* R, int which, int plane, void* out)
 {
-    const HxRpt::Planes& p = R->res[which == 0 ? 1 - R->currIdx : R->currIdx];
+    const HxRpt::Planes& p = R->res[which == 0 ? R->roles.Oth() : R->roles.Cur()];
     auto cp = [&](const void* src, size_t bytes) { std::memcpy(out, src, bytes); return 0; };
     switch (plane)
     {
@@ -726,7 +714,7 @@ int zhx_rpt_read_plane(const HxRpt* R, int which, int plane, void* out)
 // overwrite the rows [y0, y0 + h) x columns [x0, x0 + w) (plane-local coordinates) of a reservoir plane from a full-size host array
 int zhx_rpt_write_plane_rect(HxRpt* R, int which, int plane, const void* src, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h)
 {
-    HxRpt::Planes& p = R->res[which == 0 ? 1 - R->currIdx : R->currIdx];
+    HxRpt::Planes& p = R->res[which == 0 ? R->roles.Oth() : R->roles.Cur()];
     void* base; size_t bpp;
     switch (plane)
     {
@@ -748,7 +736,7 @@ int zhx_rpt_write_plane_rect(HxRpt* R, int which, int plane, const void* src, ui
 // ---------------------------------------------------------------- ReSTIR DI (zr_rdi.h) in program order
 struct HxRdi
 {
-    uint32_t w = 0, h = 0; bool temporalValid = false; int currIdx = 0;
+    uint32_t w = 0, h = 0; PassHistory hist;
     std::vector<U4> A[2]; std::vector<float> B[2]; std::vector<F4> target;
 };
 HxRdi* zhx_rdi_create(uint32_t w, uint32_t h)
@@ -759,7 +747,7 @@ HxRdi* zhx_rdi_create(uint32_t w, uint32_t h)
     return r;
 }
 void zhx_rdi_destroy(HxRdi* r) { delete r; }
-void zhx_rdi_reset_temporal(HxRdi* r) { r->temporalValid = false; r->currIdx = 0; }
+void zhx_rdi_reset_temporal(HxRdi* r) { r->hist.Rewind(); }
 void zhx_rdi_render(const HxScene* s, HxRdi* R, const zr_frame_constants* cb, const zr_gbuffer_planes* curr, const zr_gbuffer_planes* prev,
     const zr_params* params, float* finalRGBA, zr_counters* counters)
 { Latch(s, cb);
@@ -771,16 +759,10 @@ void zhx_rdi_render(const HxScene* s, HxRdi* R, const zr_frame_constants* cb, co
     F.sc = s->view; F.gb = ViewOf(curr); F.gbPrev = prev ? ViewOf(prev) : F.gb;
     F.scPrev = s->PrevView();
     F.ox0 = 0; F.oy0 = 0; F.ow = W; F.oh = H;
-    F.cur.A = R->A[R->currIdx].data(); F.cur.B = R->B[R->currIdx].data();
-    F.prev.A = R->A[1 - R->currIdx].data(); F.prev.B = R->B[1 - R->currIdx].data();
+    const int cur = R->hist.Cur(), oth = R->hist.Oth();
+    F.cur.A = R->A[cur].data(); F.cur.B = R->B[cur].data(); F.prev.A = R->A[oth].data(); F.prev.B = R->B[oth].data();
     F.target = R->target.data(); F.finalRGBA = finalRGBA; F.sampleSet = kRdiSampleSet;
-    DiParams& prm = F.prm;
-    prm.flags = params->flags; prm.M_max = params->m_max_temporal; prm.numSampleSets = params->presampling ? params->num_sample_sets : 0u;
-    prm.accumulate = (g.accumulate && g.camera_static) ? 1u : 0u;
-    prm.doTemporal = (R->temporalValid && (params->flags & ZR_IND_TEMPORAL_RESAMPLE) && prev) ? 1u : 0u;
-    prm.doSpatial = (prm.doTemporal && (params->flags & ZR_IND_SPATIAL_RESAMPLE)) ? 1u : 0u;
-    prm.writeReservoirs = (prm.doTemporal || !R->temporalValid) ? 1u : 0u;
-    prm.halfVec = (params->flags & ZR_DI_HALF_VECTOR_COPY_SHIFT) ? 1u : 0u; prm.alpha_min = params->alpha_min;
+    const DiParams& prm = F.prm = DiParamsOf(*params, g, R->hist.valid, prev != nullptr);
     zr::StackEntry stackMem[zr::kTravStack]; zr::TravStack stack; stack.lds = nullptr; stack.stride = 0; stack.mem = stackMem;
     for (uint32_t y = 0; y < H; y++) for (uint32_t x = 0; x < W; x++) TemporalPixel(F, g, x, y, stack, cnt);
     if (prm.doSpatial)
@@ -794,13 +776,12 @@ void zhx_rdi_render(const HxScene* s, HxRdi* R, const zr_frame_constants* cb, co
         }
     }
     if (counters) { counters->n_closest = cnt[0]; counters->n_shadow = cnt[1]; }
-    R->temporalValid = true;
-    R->currIdx = 1 - R->currIdx;
+    R->hist.Flip();
 }
 // plane 0 = reservoir A, 1 = B of the set written by the last frame, 2 = target
 int zhx_rdi_read_plane(const HxRdi* R, int plane, void* out)
 {
-    const int last = 1 - R->currIdx;
+    const int last = R->hist.Oth();
     if (plane == 0) std::memcpy(out, R->A[last].data(), R->A[last].size() * 16);
     else if (plane == 1) std::memcpy(out, R->B[last].data(), R->B[last].size() * 4);
     else std::memcpy(out, R->target.data(), R->target.size() * 16);
@@ -810,7 +791,7 @@ int zhx_rdi_read_plane(const HxRdi* R, int plane, void* out)
 // ---------------------------------------------------------------- ReSTIR GI (zr_rgi.h) in program order
 struct HxRgi
 {
-    uint32_t w = 0, h = 0; bool temporalValid = false; int currIdx = 0;
+    uint32_t w = 0, h = 0; PassHistory hist;
     std::vector<F4> A[2], C[2]; std::vector<uint16_t> B[2];
 };
 HxRgi* zhx_rgi_create(uint32_t w, uint32_t h)
@@ -820,7 +801,7 @@ HxRgi* zhx_rgi_create(uint32_t w, uint32_t h)
     return r;
 }
 void zhx_rgi_destroy(HxRgi* r) { delete r; }
-void zhx_rgi_reset_temporal(HxRgi* r) { r->temporalValid = false; }
+void zhx_rgi_reset_temporal(HxRgi* r) { r->hist.Invalidate(); }
 void zhx_rgi_render(const HxScene* s, HxRgi* R, const zr_frame_constants* cb, const zr_gbuffer_planes* curr, const zr_gbuffer_planes* prev,
     const zr_params* params, float* finalRGBA, zr_counters* counters)
 { Latch(s, cb, params);
@@ -831,18 +812,11 @@ void zhx_rgi_render(const HxScene* s, HxRgi* R, const zr_frame_constants* cb, co
     GiFrame F;
     F.sc = s->view; F.gb = ViewOf(curr); F.gbPrev = prev ? ViewOf(prev) : F.gb;
     F.ox0 = 0; F.oy0 = 0; F.ow = W; F.oh = H;
-    F.cur.A = R->A[R->currIdx].data(); F.cur.B = R->B[R->currIdx].data(); F.cur.C = R->C[R->currIdx].data();
-    F.prev.A = R->A[1 - R->currIdx].data(); F.prev.B = R->B[1 - R->currIdx].data(); F.prev.C = R->C[1 - R->currIdx].data();
+    const int cur = R->hist.Cur(), oth = R->hist.Oth();
+    F.cur.A = R->A[cur].data(); F.cur.B = R->B[cur].data(); F.cur.C = R->C[cur].data();
+    F.prev.A = R->A[oth].data(); F.prev.B = R->B[oth].data(); F.prev.C = R->C[oth].data();
     F.finalRGBA = finalRGBA;
-    GiParams& prm = F.prm;
-    prm.flags = params->flags; prm.maxNonTrBounces = params->max_non_tr_bounces; prm.maxGlossyTrBounces = params->max_glossy_tr_bounces;
-    prm.numSampleSets = params->presampling ? params->num_sample_sets : 0u;
-    prm.accumulate = (g.accumulate && g.camera_static) ? 1u : 0u;
-    prm.doTemporal = ((params->flags & ZR_IND_TEMPORAL_RESAMPLE) && R->temporalValid && prev) ? 1u : 0u;
-    prm.writeReservoirs = (prm.doTemporal || !R->temporalValid) ? 1u : 0u;
-    prm.M_max = (float)params->m_max_temporal;
-    prm.useLVG = (params->use_lvg && params->presampling) ? 1u : 0u;
-    prm.textured = s->view.tex.count ? 1u : 0u;
+    F.prm = GiParamsOf(*params, g, R->hist.valid, prev != nullptr, s->view.tex.count != 0);
     zr::StackEntry stackMem[zr::kTravStack]; zr::TravStack stack; stack.lds = nullptr; stack.stride = 0; stack.mem = stackMem;
     std::vector<Lane> L(64);
     float wsum[64];
@@ -863,12 +837,11 @@ void zhx_rgi_render(const HxScene* s, HxRgi* R, const zr_frame_constants* cb, co
         for (uint32_t l = 0; l < 64; l++) SuppressAndWrite(F, L[l], waveSum);
     }
     if (counters) { counters->n_closest = cnt[0]; counters->n_shadow = cnt[1]; }
-    R->temporalValid = true;
-    R->currIdx = 1 - R->currIdx;
+    R->hist.Flip();
 }
 int zhx_rgi_read_plane(const HxRgi* R, int plane, void* out)
 {
-    const int last = 1 - R->currIdx;
+    const int last = R->hist.Oth();
     if (plane == 0) std::memcpy(out, R->A[last].data(), R->A[last].size() * 16);
     else if (plane == 1) std::memcpy(out, R->B[last].data(), R->B[last].size() * 2);
     else std::memcpy(out, R->C[last].data(), R->C[last].size() * 16);
@@ -879,7 +852,7 @@ int zhx_rgi_read_plane(const HxRgi* R, int plane, void* out)
 // ---- ReSTIR DI for sun + sky (zr_sdi.h) ----
 struct HxSdi
 {
-    uint32_t w = 0, h = 0; bool temporalValid = false; int currIdx = 0;
+    uint32_t w = 0, h = 0; PassHistory hist;
     std::vector<uint8_t> A[2]; std::vector<uint16_t> B[2]; std::vector<float> C[2]; std::vector<F4> target;
 };
 HxSdi* zhx_sdi_create(uint32_t w, uint32_t h)
@@ -890,7 +863,7 @@ HxSdi* zhx_sdi_create(uint32_t w, uint32_t h)
     return r;
 }
 void zhx_sdi_destroy(HxSdi* r) { delete r; }
-void zhx_sdi_reset_temporal(HxSdi* r) { r->temporalValid = false; r->currIdx = 0; }
+void zhx_sdi_reset_temporal(HxSdi* r) { r->hist.Rewind(); }
 void zhx_sdi_render(const HxScene* s, HxSdi* R, const zr_frame_constants* cb, const zr_gbuffer_planes* curr, const zr_gbuffer_planes* prev,
     const zr_params* params, float* finalRGBA, zr_counters* counters)
 { Latch(s, cb);
@@ -901,27 +874,22 @@ void zhx_sdi_render(const HxScene* s, HxSdi* R, const zr_frame_constants* cb, co
     SkyFrame F;
     F.sc = s->view; F.gb = ViewOf(curr); F.gbPrev = prev ? ViewOf(prev) : F.gb;
     F.scPrev = s->PrevView();
-    F.cur.A = R->A[R->currIdx].data(); F.cur.B = R->B[R->currIdx].data(); F.cur.C = R->C[R->currIdx].data();
-    F.prev.A = R->A[1 - R->currIdx].data(); F.prev.B = R->B[1 - R->currIdx].data(); F.prev.C = R->C[1 - R->currIdx].data();
+    const int cur = R->hist.Cur(), oth = R->hist.Oth();
+    F.cur.A = R->A[cur].data(); F.cur.B = R->B[cur].data(); F.cur.C = R->C[cur].data();
+    F.prev.A = R->A[oth].data(); F.prev.B = R->B[oth].data(); F.prev.C = R->C[oth].data();
     F.target = R->target.data(); F.finalRGBA = finalRGBA;
     F.ox0 = 0; F.oy0 = 0; F.ow = W; F.oh = H;
-    SkyParams& prm = F.prm;
-    prm.M_max_sky = params->m_max_temporal; prm.M_max_sun = params->m_max_spatial; prm.alpha_min = params->alpha_min;
-    prm.accumulate = (g.accumulate && g.camera_static) ? 1u : 0u;
-    prm.doTemporal = (R->temporalValid && (params->flags & ZR_IND_TEMPORAL_RESAMPLE) && prev) ? 1u : 0u;
-    prm.doSpatial = (prm.doTemporal && (params->flags & ZR_IND_SPATIAL_RESAMPLE)) ? 1u : 0u;
-    prm.writeReservoirs = (prm.doTemporal || !R->temporalValid) ? 1u : 0u;
+    const SkyParams& prm = F.prm = SkyParamsOf(*params, g, R->hist.valid, prev != nullptr);
     zr::StackEntry stackMem[zr::kTravStack]; zr::TravStack stack; stack.lds = nullptr; stack.stride = 0; stack.mem = stackMem;
     for (uint32_t y = 0; y < H; y++) for (uint32_t x = 0; x < W; x++) TemporalPixel(F, g, x, y, stack, cnt);
     if (prm.doSpatial) for (uint32_t y = 0; y < H; y++) for (uint32_t x = 0; x < W; x++) SpatialPixel(F, g, x, y, stack, cnt);
     if (counters) { counters->n_closest = cnt[0]; counters->n_shadow = cnt[1]; }
-    R->temporalValid = true;
-    R->currIdx = 1 - R->currIdx;
+    R->hist.Flip();
 }
 // plane 0 = A, 1 = B, 2 = C of the set written by the last frame, 3 = target
 int zhx_sdi_read_plane(const HxSdi* R, int plane, void* out)
 {
-    const int last = 1 - R->currIdx;
+    const int last = R->hist.Oth();
     if (plane == 0) std::memcpy(out, R->A[last].data(), R->A[last].size());
     else if (plane == 1) std::memcpy(out, R->B[last].data(), R->B[last].size() * 2);
     else if (plane == 2) std::memcpy(out, R->C[last].data(), R->C[last].size() * 4);

@@ -24,6 +24,7 @@
 #include "zr_svgf.h"
 #include "zr_post.h"
 #include "zr_rpt_overlap.h"
+#include "zr_pass_frame.h"
 #include "../../include/zr_srgb_table.h"
 
 // 512 x half2 spatial-search points (generated from zetaray_amd/assets/rpt_sample_set_f16.bin by the Makefile)
@@ -898,7 +899,7 @@ struct zr_pass
     } rb[2];
     Plane<F4> rptTarget, rptTargetAlt; Plane<uint8_t, 2> rptNeighbor; DevBuf<uint16_t> rptSampleSet;
     // Frame overlap (zr_pass_set_frame_overlap): the roles of the three reservoir sets, the two target planes and the three FINAL planes, the mode, and
-    // the cross-stream order of every stage's accesses to them (zr_rpt_overlap.h).  Without overlap the roles still hold currIdx and frameOpen.
+    // the cross-stream order of every stage's accesses to them (zr_rpt_overlap.h).  Without overlap the roles still hold currIdx and frameOpen; whether the pass has a history is hist.valid.
     zr::RptOverlap<HipOrderBackend> ov;
     Plane<float, 4> finalAlt, finalAlt2;      // FINAL rotates over three planes: K11 of frame N + 2 (which clears the pixels without a surface) may run while frame N's is still being consumed
     hipStream_t overlapStream = nullptr;      // "stream A" for callers without streams of their own
@@ -909,12 +910,31 @@ struct zr_pass
     DevBuf<uint32_t> carry[2], carryCount;                             // K11 with per-bounce compaction: path-state planes (ping-pong), alive counts
     DevBuf<uint32_t> costMap; bool costOn = false, costRays = false;      // rays per 32 x 32-px cell (zr_pass_enable_cost_map)
     DevBuf<uint32_t> rptLists, rptListCounts;      // 4 replay work lists (pixel ids) + their device-side counts
-    // DI_EMISSIVE: two reservoir sets (A RGBA32_UINT, B RG32F), target, sample set
-    Plane<U4> diA[2]; Plane<float, 2> diB[2]; Plane<F4> diTarget; DevBuf<uint16_t> diSampleSet;
-    Plane<uint8_t> skyA[2]; Plane<uint16_t, 2> skyB[2]; Plane<float, 2> skyC[2];      // sun + sky DI reservoirs (R8_UINT, RG16_UINT, RG32F)
+    // DI_EMISSIVE: two reservoir sets (A RGBA32_UINT, B RG32F), target (shared with DI_SKY), sample set
+    struct DiStorage
+    {
+        Plane<U4> A; Plane<float, 2> B;
+        template<typename S, typename Fn> static int Each(S& s, Fn f) { int r; if ((r = f(s.A)) || (r = f(s.B))) return r; return ZR_OK; }
+        rdi::DiPlanes View() const { rdi::DiPlanes v; v.A = A.p; v.B = B.p; return v; }
+    } di[2];
+    Plane<F4> diTarget; DevBuf<uint16_t> diSampleSet;
+    // DI_SKY: two sets of sun + sky DI reservoirs (A R8_UINT, B RG16_UINT, C RG32F)
+    struct SkyStorage
+    {
+        Plane<uint8_t> A; Plane<uint16_t, 2> B; Plane<float, 2> C;
+        template<typename S, typename Fn> static int Each(S& s, Fn f) { int r; if ((r = f(s.A)) || (r = f(s.B)) || (r = f(s.C))) return r; return ZR_OK; }
+        sdi::SkyPlanes View() const { sdi::SkyPlanes v; v.A = A.p; v.B = B.p; v.C = C.p; return v; }
+    } sky[2];
     // INDIRECT / ReSTIR GI: two reservoir sets (A RGBA32F, B RGBA16F, C RGBA32F)
-    Plane<F4> giA[2], giC[2]; Plane<uint16_t, 4> giB[2];
-    bool temporalValid = false, doTemporal = false, doSpatial = false; int currIdx = 0;
+    struct GiStorage
+    {
+        Plane<F4> A; Plane<uint16_t, 4> B; Plane<F4> C;
+        template<typename S, typename Fn> static int Each(S& s, Fn f) { int r; if ((r = f(s.A)) || (r = f(s.B)) || (r = f(s.C))) return r; return ZR_OK; }
+        rgi::GiPlanes View() const { rgi::GiPlanes v; v.A = A.p; v.B = B.p; v.C = C.p; return v; }
+    } gi[2];
+    // which of a pass's two sets is which, and whether the pass has a history at all (zr_pass_frame.h: who flips when, who rewinds on a reset)
+    zr::PassHistory hist;
+    bool doTemporal = false, doSpatial = false;      // ReSTIR PT: decided by the frame's CANDIDATES stage, held for its later stages
     const F4* compIn[4] = {nullptr, nullptr, nullptr, nullptr};     // COMPOSITING inputs (emissive DI, indirect, sky DI); [3] = TAA signal
     Plane<F4> svgfHist, svgfAccum, svgfPing, svgfPong; Plane<float, 2> svgfMoments[2]; Plane<float> svgfGuideFw; Plane<svgf::GuideN> svgfGuide; int svgfMomIdx = 0; const F4* svgfOut = nullptr; F4* svgfCur = nullptr; uint32_t svgfStepsDone = 0;      // DENOISE
     Plane<uint16_t, 4> taaOut[2]; int taaIdx = 0;            // TAA: ping-pong RGBA16F outputs; taaIdx = the one written last
@@ -2423,17 +2443,18 @@ static int AllocPass(zr_pass* p)
 {
     int r;
     const size_t cap = (size_t)p->w * p->h;
+    p->hist.Rewind();      // every kind that keeps a history starts over (zr_pass_init / zr_pass_resize)
     if (p->kind == ZR_PASS_SKY) { if ((r = p->skyLut.Alloc(cap))) return r; }
     if (p->kind == ZR_PASS_TAA)
     {
         for (auto& t : p->taaOut) if ((r = t.AllocZero(cap))) return r;
-        p->taaIdx = 0; p->temporalValid = false;
+        p->taaIdx = 0;
     }
     if (p->kind == ZR_PASS_DENOISE)
     {
         if ((r = p->svgfHist.AllocZero(cap)) || (r = p->svgfAccum.Alloc(cap)) || (r = p->svgfPing.AllocZero(cap)) || (r = p->svgfPong.AllocZero(cap)) || (r = p->svgfGuide.Alloc(cap)) || (r = p->svgfGuideFw.Alloc(cap))) return r;
         for (auto& m : p->svgfMoments) if ((r = m.AllocZero(cap))) return r;
-        p->svgfMomIdx = 0; p->svgfOut = p->svgfPing.p; p->svgfCur = p->svgfPing.p; p->temporalValid = false;
+        p->svgfMomIdx = 0; p->svgfOut = p->svgfPing.p; p->svgfCur = p->svgfPing.p;
     }
     if (p->kind == ZR_PASS_AUTO_EXPOSURE)
     {
@@ -2452,20 +2473,16 @@ static int AllocPass(zr_pass* p)
     {
         if ((r = p->finalRGBA.AllocZero(cap))) return r;
         if ((r = p->counters.AllocZero(2 * kCounterSlots))) return r;
-        for (int k = 0; k < 2; k++)
-            if ((r = p->skyA[k].AllocZero(cap)) || (r = p->skyB[k].AllocZero(cap)) || (r = p->skyC[k].AllocZero(cap))) return r;
+        for (auto& set : p->sky) if ((r = PlanesAllocZero(set, cap))) return r;
         if ((r = p->diTarget.AllocZero(cap))) return r;
-        p->temporalValid = false; p->currIdx = 0;
     }
     if (p->kind == ZR_PASS_DI_EMISSIVE)
     {
         if ((r = p->finalRGBA.AllocZero(cap))) return r;
         if ((r = p->counters.AllocZero(2 * kCounterSlots))) return r;
-        for (int k = 0; k < 2; k++)
-            if ((r = p->diA[k].AllocZero(cap)) || (r = p->diB[k].AllocZero(cap))) return r;
+        for (auto& set : p->di) if ((r = PlanesAllocZero(set, cap))) return r;
         if ((r = p->diTarget.AllocZero(cap))) return r;
         if ((r = p->diSampleSet.Upload(kRdiSampleSet, 64))) return r;
-        p->temporalValid = false; p->currIdx = 0;
     }
     if (p->kind == ZR_PASS_INDIRECT)
     {
@@ -2476,12 +2493,7 @@ static int AllocPass(zr_pass* p)
         if ((r = p->counts.Alloc(5 * (kMaxRounds + 2) * kCounterStride))) return r;   // per round: live paths, k_trace cursor, 3 ray counts
         if ((r = p->counters.AllocZero(2 * kCounterSlots))) return r;
         if ((r = p->groupMax.Alloc((size_t)kMaxRounds * ((p->w + 7) / 8) * ((p->h + 7) / 8)))) return r;
-        if (p->integrator == ZR_INTEGRATOR_RESTIR_GI)
-        {
-            for (int k = 0; k < 2; k++)
-                if ((r = p->giA[k].AllocZero(cap)) || (r = p->giB[k].AllocZero(cap)) || (r = p->giC[k].AllocZero(cap))) return r;
-            p->temporalValid = false; p->currIdx = 0;
-        }
+        if (p->integrator == ZR_INTEGRATOR_RESTIR_GI) for (auto& set : p->gi) if ((r = PlanesAllocZero(set, cap))) return r;
         if (p->integrator == ZR_INTEGRATOR_RESTIR_PT)
         {
             for (int k = 0; k < 2; k++)
@@ -2498,7 +2510,6 @@ static int AllocPass(zr_pass* p)
             // base 0: the only DYNAMIC replay), [6, 7] second spatial round, [8 .. 11] = base 6's cursor slots -- unused (the spatial replays split
             // their lists statically) but allocated and zeroed, so that no base ever reaches past the buffer
             if ((r = p->rptListCounts.Alloc(kRptListWords))) return r;
-            p->temporalValid = false;
         }
     }
     return ZR_OK;
@@ -2530,8 +2541,8 @@ int zr_pass_reset_temporal(zr_pass* p)
     if (!p->initialized) return Fail(ZR_ERR_NOT_INITIALIZED, "pass not initialised");
     HIP_TRY(hipSetDevice(p->device));
     if (p->kind == ZR_PASS_INDIRECT) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipMemset(p->finalRGBA.p, 0, p->finalRGBA.n * sizeof(float))); if (p->finalAlt.p) { HIP_TRY(hipMemset(p->finalAlt.p, 0, p->finalAlt.n * sizeof(float))); HIP_TRY(hipMemset(p->finalAlt2.p, 0, p->finalAlt2.n * sizeof(float))); } }
-    p->temporalValid = false;       // IndirectLighting::ResetTemporal -> RESET_TEMPORAL_TEXTURES next frame
-    if (p->kind == ZR_PASS_DI_EMISSIVE || p->kind == ZR_PASS_DI_SKY) { HIP_TRY(hipMemset(p->finalRGBA.p, 0, p->finalRGBA.n * sizeof(float))); p->currIdx = 0; }   // DirectLighting.cpp:159-164, SkyDI.cpp:128-133
+    p->hist.Invalidate();       // IndirectLighting::ResetTemporal -> RESET_TEMPORAL_TEXTURES next frame
+    if (p->kind == ZR_PASS_DI_EMISSIVE || p->kind == ZR_PASS_DI_SKY) { HIP_TRY(hipMemset(p->finalRGBA.p, 0, p->finalRGBA.n * sizeof(float))); p->hist.Rewind(); }   // DirectLighting.cpp:159-164, SkyDI.cpp:128-133
     HIP_TRY(hipDeviceSynchronize());      // a host call between frames: renders on non-blocking streams must see the cleared plane
     return ZR_OK;
 }
@@ -2801,16 +2812,10 @@ static int RenderDirectEmissive(zr_pass* p, hipStream_t s, const zr_frame_consta
     F.sc = FrameView(sc, cb); F.gb = gb->View(); F.gbPrev = gb->PrevView();
     F.scPrev = FrameViewPrev(sc, cb);
     if (int orc = ResolveOwnedRect(p, gb, cb, &F.ox0, &F.oy0, &F.ow, &F.oh)) return orc;
-    F.cur.A = p->diA[p->currIdx].p; F.cur.B = p->diB[p->currIdx].p; F.prev.A = p->diA[1 - p->currIdx].p; F.prev.B = p->diB[1 - p->currIdx].p;
+    F.cur = p->di[p->hist.Cur()].View(); F.prev = p->di[p->hist.Oth()].View();
     F.target = p->diTarget.p; F.finalRGBA = p->finalRGBA.p; F.sampleSet = p->diSampleSet.p;
-    DiParams& prm = F.prm;
-    prm.flags = ip.flags; prm.M_max = ip.m_max_temporal; prm.numSampleSets = ip.presampling ? ip.num_sample_sets : 0u;
-    prm.accumulate = (cb->accumulate && cb->camera_static) ? 1u : 0u;
-    prm.doTemporal = (p->temporalValid && (ip.flags & ZR_IND_TEMPORAL_RESAMPLE) && gb->numRendered >= 2) ? 1u : 0u;
-    prm.doSpatial = (prm.doTemporal && (ip.flags & ZR_IND_SPATIAL_RESAMPLE)) ? 1u : 0u;
-    prm.writeReservoirs = (prm.doTemporal || !p->temporalValid) ? 1u : 0u;
-    const bool hvs = (ip.flags & ZR_DI_HALF_VECTOR_COPY_SHIFT) != 0;      // USE_HALF_VECTOR_COPY_SHIFT (ReSTIR_DI/Params.hlsli:12): its own kernel instantiations
-    prm.halfVec = hvs ? 1u : 0u; prm.alpha_min = ip.alpha_min;
+    const DiParams& prm = F.prm = zr::DiParamsOf(ip, *cb, p->hist.valid, gb->numRendered >= 2);
+    const bool hvs = prm.halfVec != 0;      // the half-vector copy shift has kernel instantiations of its own
     const uint32_t tilesX = (F.ow + 15) / 16, tilesY = (F.oh + 15) / 16;
     const dim3 grid(tilesX * tilesY), block(kBlock);
     const bool plainDi = PlainClass(sc, gb);
@@ -2828,8 +2833,7 @@ static int RenderDirectEmissive(zr_pass* p, hipStream_t s, const zr_frame_consta
         TimerEnd(p, s);
     }
     HIP_TRY(hipGetLastError());
-    p->temporalValid = true;
-    p->currIdx = 1 - p->currIdx;
+    p->hist.Flip();
     return ZR_OK;
 }
 
@@ -2846,15 +2850,9 @@ static int RenderDirectSky(zr_pass* p, hipStream_t s, const zr_frame_constants* 
     F.sc = FrameView(sc, cb); F.gb = gb->View(); F.gbPrev = gb->PrevView();
     F.scPrev = FrameViewPrev(sc, cb);
     if (int orc = ResolveOwnedRect(p, gb, cb, &F.ox0, &F.oy0, &F.ow, &F.oh)) return orc;
-    F.cur.A = p->skyA[p->currIdx].p; F.cur.B = p->skyB[p->currIdx].p; F.cur.C = p->skyC[p->currIdx].p;
-    F.prev.A = p->skyA[1 - p->currIdx].p; F.prev.B = p->skyB[1 - p->currIdx].p; F.prev.C = p->skyC[1 - p->currIdx].p;
+    F.cur = p->sky[p->hist.Cur()].View(); F.prev = p->sky[p->hist.Oth()].View();
     F.target = p->diTarget.p; F.finalRGBA = p->finalRGBA.p;
-    SkyParams& prm = F.prm;
-    prm.M_max_sky = ip.m_max_temporal; prm.M_max_sun = ip.m_max_spatial; prm.alpha_min = ip.alpha_min;
-    prm.accumulate = (cb->accumulate && cb->camera_static) ? 1u : 0u;
-    prm.doTemporal = (p->temporalValid && (ip.flags & ZR_IND_TEMPORAL_RESAMPLE) && gb->numRendered >= 2) ? 1u : 0u;
-    prm.doSpatial = (prm.doTemporal && (ip.flags & ZR_IND_SPATIAL_RESAMPLE)) ? 1u : 0u;
-    prm.writeReservoirs = (prm.doTemporal || !p->temporalValid) ? 1u : 0u;
+    const SkyParams& prm = F.prm = zr::SkyParamsOf(ip, *cb, p->hist.valid, gb->numRendered >= 2);
     const uint32_t tilesX = (F.ow + 15) / 16, tilesY = (F.oh + 15) / 16;
     const dim3 grid(tilesX * tilesY), block(kBlock);
     const bool plainDi = PlainClass(sc, gb);
@@ -2872,14 +2870,13 @@ static int RenderDirectSky(zr_pass* p, hipStream_t s, const zr_frame_constants* 
         TimerEnd(p, s);
     }
     HIP_TRY(hipGetLastError());
-    p->temporalValid = true;
-    p->currIdx = 1 - p->currIdx;
+    p->hist.Flip();
     return ZR_OK;
 }
 
 // IndirectLighting::RenderReSTIR_GI (IndirectLighting.cpp:277-368) + the Render() tail (:1006-1025).  ZR_STAGE_TEMPORAL: k_rgi (the reference's whole pass);
 // ZR_STAGE_SPATIAL: k_rgi_spatial when zr_pass_set_rgi_spatial has switched it on (zr_rgi_spatial.h; no reference counterpart), else nothing.  The reservoir
-// sets flip at the end of the TEMPORAL stage, so between the stages -- as after the frame -- the set k_rgi wrote is [1 - currIdx]: the set ZR_HALO_FINAL moves.
+// sets flip at the end of the TEMPORAL stage, so between the stages -- as after the frame -- the set k_rgi wrote is gi[hist.Oth()]: the set ZR_HALO_FINAL moves.
 static int RenderReSTIR_GI(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, const zr_scene* sc, zr_gbuffer* gb, int stages)
 {
     using namespace rgi;
@@ -2888,23 +2885,14 @@ static int RenderReSTIR_GI(zr_pass* p, hipStream_t s, const zr_frame_constants* 
     F.sc = FrameView(sc, cb); F.gb = gb->View(); F.gbPrev = gb->PrevView();
     F.sc.texFilter = ip.tex_filter;
     if (int orc = ResolveOwnedRect(p, gb, cb, &F.ox0, &F.oy0, &F.ow, &F.oh)) return orc;
-    GiParams& prm = F.prm;
-    prm.flags = ip.flags; prm.maxNonTrBounces = ip.max_non_tr_bounces; prm.maxGlossyTrBounces = ip.max_glossy_tr_bounces;
-    prm.numSampleSets = ip.presampling ? ip.num_sample_sets : 0u;
-    prm.accumulate = (cb->accumulate && cb->camera_static) ? 1u : 0u;
-    prm.M_max = (float)ip.m_max_temporal;
-    prm.useLVG = (ip.use_lvg && ip.presampling) ? 1u : 0u;
-    prm.textured = sc->view.tex.count ? 1u : 0u;
+    GiParams& prm = F.prm = zr::GiParamsOf(ip, *cb, p->hist.valid, gb->numRendered >= 2, sc->view.tex.count != 0);
     const uint32_t tilesX = (F.ow + 15) / 16, tilesY = (F.oh + 15) / 16;
     if (stages & ZR_STAGE_TEMPORAL)
     {
         p->rgiSpatialFrame = p->rgiSpatial;
         const bool spatial = p->rgiSpatialFrame.numSamples != 0;
-        F.cur.A = p->giA[p->currIdx].p; F.cur.B = p->giB[p->currIdx].p; F.cur.C = p->giC[p->currIdx].p;
-        F.prev.A = p->giA[1 - p->currIdx].p; F.prev.B = p->giB[1 - p->currIdx].p; F.prev.C = p->giC[1 - p->currIdx].p;
+        F.cur = p->gi[p->hist.Cur()].View(); F.prev = p->gi[p->hist.Oth()].View();
         F.finalRGBA = p->finalRGBA.p;
-        prm.doTemporal = ((ip.flags & ZR_IND_TEMPORAL_RESAMPLE) && p->temporalValid && gb->numRendered >= 2) ? 1u : 0u;
-        prm.writeReservoirs = (prm.doTemporal || !p->temporalValid) ? 1u : 0u;
         if (spatial)
         {   // FINAL gets one contribution per pixel and frame, from the spatial stage: k_rgi's own radiance is stored (never accumulated) in a scratch plane,
             // and it writes the set the spatial kernel reads every frame
@@ -2917,14 +2905,12 @@ static int RenderReSTIR_GI(zr_pass* p, hipStream_t s, const zr_frame_constants* 
         hipLaunchKernelGGL(sc->view.tex.count ? k_rgi_tex : PlainClass(sc, gb) ? k_rgi<true> : k_rgi<false>, dim3(tilesX * tilesY * (256 / kRgiBlock)), dim3(kRgiBlock), 0, s, F, *cb, tilesX, p->counters.p + 2 * 10);
         TimerEnd(p, s);
         HIP_TRY(hipGetLastError());
-        p->temporalValid = true;
-        p->currIdx = 1 - p->currIdx;
+        p->hist.Flip();
     }
     if ((stages & ZR_STAGE_SPATIAL) && p->rgiSpatialFrame.numSamples != 0)
     {
-        if (!p->temporalValid) return Fail(ZR_ERR_NOT_INITIALIZED, "ReSTIR GI: ZR_STAGE_SPATIAL before the frame's ZR_STAGE_TEMPORAL");
-        const int set = 1 - p->currIdx;      // the set this frame's k_rgi wrote
-        F.cur.A = p->giA[set].p; F.cur.B = p->giB[set].p; F.cur.C = p->giC[set].p; F.prev = F.cur;
+        if (!p->hist.valid) return Fail(ZR_ERR_NOT_INITIALIZED, "ReSTIR GI: ZR_STAGE_SPATIAL before the frame's ZR_STAGE_TEMPORAL");
+        F.cur = F.prev = p->gi[p->hist.Oth()].View();      // the set this frame's k_rgi wrote
         F.finalRGBA = p->finalRGBA.p;
         prm.accumulate = (cb->accumulate && cb->camera_static) ? 1u : 0u;      // (the TEMPORAL stage above cleared it for k_rgi's scratch plane)
         prm.doTemporal = 0u; prm.writeReservoirs = 0u; prm.textured = 0u;
@@ -2990,36 +2976,24 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
     // K12 sorts whole 32 x 32 tiles: an owned rect may end inside one only where the render target ends
     if (((F.ox0 + F.ow) & 31u) && F.ox0 + F.ow != cb->render_width) return Fail(ZR_ERR_INVALID_ARG, "ReSTIR PT: the owned rect must end on a 32-pixel boundary or at the right edge of the render target");
     if (((F.oy0 + F.oh) & 31u) && F.oy0 + F.oh != cb->render_height) return Fail(ZR_ERR_INVALID_ARG, "ReSTIR PT: the owned rect must end on a 32-pixel boundary or at the bottom edge of the render target");
-    RptParams& prm = F.prm;
     const zr_params& ip = p->params;
-    const bool havePrevGBuffer = gb->numRendered >= 2;
-    prm.maxNonTrBounces = ip.max_non_tr_bounces; prm.maxGlossyTrBounces = ip.max_glossy_tr_bounces;
-    prm.russianRoulette = (ip.flags & ZR_IND_RUSSIAN_ROULETTE) ? 1u : 0u;
-    prm.numSampleSets = ip.presampling ? ip.num_sample_sets : 0u;
-    prm.accumulate = (cb->accumulate && cb->camera_static) ? 1u : 0u;
-    prm.boiling = (ip.flags & ZR_IND_BOILING_SUPPRESSION) ? 1u : 0u;
-    prm.M_max_temporal = ip.m_max_temporal & 0xf; prm.M_max_spatial = ip.m_max_spatial & 0xf; prm.alpha_min = ip.alpha_min;
-    prm.emissive = cb->num_emissive_triangles ? 1u : 0u;
-    prm.textured = sc->view.tex.count ? 1u : 0u;
-    prm.sortTemporal = (ip.flags & ZR_IND_SORT_TEMPORAL) ? 1u : 0u; prm.sortSpatial = (ip.flags & ZR_IND_SORT_SPATIAL) ? 1u : 0u;
-    // the CtN map (current reservoirs bucketed by k) schedules the fused CtT + TtC kernel: 0.540 -> 0.495 ms Cornell, 3.27 -> 3.16 ms atrium at
-    // 1080p; the NtC map does not pay (0.546 / 3.34).  ZR_TEMPORAL_MAP = 0 / 1 / 2 overrides (scripts/gpu_sortmap.sh [rounds 1-4: git history up to 31e92fa; today scripts/gpu.sh ab])
-    static const uint32_t temporalMapEnv = [] { const char* e = ZR_EXP_ENV("ZR_TEMPORAL_MAP"); return e ? (uint32_t)atoi(e) : 1u; }();
-    prm.temporalMap = prm.sortTemporal ? temporalMapEnv : 0u;
     if (stageCand)
-    {
+    {   // what the frame reuses is decided here and held (p->doTemporal, p->doSpatial) for its later stages
         p->rptViewFrame = p->rptView;
-        p->doTemporal = (ip.flags & ZR_IND_TEMPORAL_RESAMPLE) && p->temporalValid && havePrevGBuffer;
-        p->doSpatial = (ip.flags & ZR_IND_SPATIAL_RESAMPLE) && p->doTemporal && ip.num_spatial_passes > 0;      // IndirectLighting.cpp:906
+        const zr::ReuseFlags now = zr::ReuseFlagsOf(ip.flags, p->hist.valid, gb->numRendered >= 2, *cb);
+        p->doTemporal = now.doTemporal != 0;
+        p->doSpatial = now.doSpatial && ip.num_spatial_passes > 0;      // IndirectLighting.cpp:906
     }
     // m_numSpatialPasses (IndirectLighting.cpp:616-621, 1240): 0..2
     if (ip.num_spatial_passes > 2u) return Fail(ZR_ERR_INVALID_ARG, "ReSTIR PT: num_spatial_passes must be 0, 1 or 2");
     const uint32_t numSpatialPasses = ip.num_spatial_passes;
+    RptParams& prm = F.prm = zr::RptParamsOf(ip, *cb, zr::ReuseFlagsLatched(p->doTemporal, p->doSpatial, p->hist.valid, *cb), sc->view.tex.count != 0);
+    // the CtN map (current reservoirs bucketed by k) schedules the fused CtT + TtC kernel: 0.540 -> 0.495 ms Cornell, 3.27 -> 3.16 ms atrium at
+    // 1080p; the NtC map does not pay (0.546 / 3.34).  ZR_TEMPORAL_MAP = 0 / 1 / 2 overrides (scripts/gpu_sortmap.sh [rounds 1-4: git history up to 31e92fa; today scripts/gpu.sh ab])
+    static const uint32_t temporalMapEnv = [] { const char* e = ZR_EXP_ENV("ZR_TEMPORAL_MAP"); return e ? (uint32_t)atoi(e) : 1u; }();
+    prm.temporalMap = prm.sortTemporal ? temporalMapEnv : 0u;
     // staged (tile-split) rendering with two rounds: ZR_STAGE_SPATIAL runs the first, ZR_STAGE_SPATIAL2 the second -- it reads the first round's outputs at
-    // neighbouring pixels, so the host exchanges ZR_HALO_POST_TEMPORAL (= the set the next stage reads: res[currIdx]) once more in between
-    prm.doTemporal = p->doTemporal ? 1u : 0u;
-    prm.doSpatial = p->doSpatial ? 1u : 0u;
-    prm.writeReservoirs = (prm.doTemporal || !p->temporalValid) ? 1u : 0u;
+    // neighbouring pixels, so the host exchanges ZR_HALO_POST_TEMPORAL (= the set the next stage reads: res[roles.Cur()]) once more in between
     F.cur = p->res[roles.Cur()].View(); F.prev = p->res[roles.Oth()].View();
     const uint32_t tilesX = (F.ow + 15) / 16, tilesY = (F.oh + 15) / 16;
     const dim3 grid(tilesX * tilesY), block(kBlock);
@@ -3187,7 +3161,7 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
     const bool lastStage = (prm.doSpatial && numSpatialPasses == 2u) ? (stages & ZR_STAGE_SPATIAL2) != 0 : (stages & ZR_STAGE_SPATIAL) != 0;
     if (lastStage && roles.frameOpen)
     {
-        p->temporalValid = true;
+        p->hist.valid = true;
         p->ov.CloseFrame();
         if (int mr = gb->MarkRead(gb->cur, s)) return mr;
     }
@@ -3476,13 +3450,13 @@ static int RenderTAA(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, zr
     taa::TaaFrame F;
     F.signal = p->compIn[3]; F.depth = (const float*)gb->Planes()[ZR_GB_DEPTH].p; F.motion = (const uint32_t*)gb->Planes()[ZR_GB_MOTION_VECTOR].p;
     F.prevOut = p->taaOut[p->taaIdx].p; F.currOut = p->taaOut[curr].p; F.w = p->w; F.h = p->h;
-    F.blendWeight = p->params.taa_blend_weight; F.temporalIsValid = p->temporalValid ? 1u : 0u;
+    F.blendWeight = p->params.taa_blend_weight; F.temporalIsValid = p->hist.valid ? 1u : 0u;
     const uint32_t n = p->w * p->h;
     TimerBegin(p, s, "taa");
     hipLaunchKernelGGL(k_taa, dim3((n + 255) / 256), dim3(256), 0, s, F);
     TimerEnd(p, s);
     HIP_TRY(hipGetLastError());
-    p->taaIdx = curr; p->temporalValid = true;
+    p->taaIdx = curr; p->hist.valid = true;
     return ZR_OK;
 }
 
@@ -3509,7 +3483,7 @@ static int RenderDenoise(zr_pass* p, hipStream_t s, const zr_frame_constants* cb
         svgf::SvgfFrame T;
         T.signal = p->compIn[3]; T.depth = cur.depth; T.normal = cur.normal; T.motion = cur.motion; T.prevDepth = prev.depth; T.prevNormal = prev.normal;
         T.histColor = p->svgfHist.p; T.histMoments = p->svgfMoments[mi].p; T.accum = p->svgfAccum.p; T.moments = p->svgfMoments[mi ^ 1].p; T.guide = p->svgfGuide.p; T.guideFw = p->svgfGuideFw.p;
-        T.win = win; T.temporalValid = (p->temporalValid && gb->numRendered >= 2) ? 1u : 0u; T.prm = sp;
+        T.win = win; T.temporalValid = (p->hist.valid && gb->numRendered >= 2) ? 1u : 0u; T.prm = sp;
         TimerBegin(p, s, "denoise_temporal");
         hipLaunchKernelGGL(k_svgf_temporal, grid, block, 0, s, T);
         TimerEnd(p, s);
@@ -3554,7 +3528,7 @@ static int RenderDenoise(zr_pass* p, hipStream_t s, const zr_frame_constants* cb
     HIP_TRY(hipGetLastError());
     // the frame is complete when its last step has run: the last a-trous iteration, or the variance stage when there are none
     const uint32_t last = sp.iterations ? ZR_STAGE_DENOISE_ATROUS(sp.iterations - 1u) : (uint32_t)ZR_STAGE_DENOISE_VARIANCE;
-    if (steps & last) { p->svgfOut = p->svgfCur; p->svgfMomIdx = mi ^ 1; p->temporalValid = true; }
+    if (steps & last) { p->svgfOut = p->svgfCur; p->svgfMomIdx = mi ^ 1; p->hist.valid = true; }
     return ZR_OK;
 }
 
@@ -3652,13 +3626,6 @@ int zr_pass_set_owned_rect(zr_pass* p, uint32_t x0, uint32_t y0, uint32_t w, uin
     return ZR_OK;
 }
 
-// which reservoir set a halo transfer addresses (zr_halo_set)
-static zr_pass::ResStorage* HaloSet(zr_pass* p, int which)
-{
-    // between the stages of a frame the post-temporal reservoirs are res[currIdx]; after the frame the set the next
-    // frame reads as "previous" is res[1 - currIdx]
-    return &p->res[which == ZR_HALO_POST_TEMPORAL ? p->ov.roles.Cur() : p->ov.roles.Oth()];
-}
 // ZR_HALO_DENOISE_INPUT: what the temporal step of a tile reads in its apron -- this frame's signal (the bound input plane: its owner shaded it, in the
 // layout of the history; null while unbound) and the history the previous frame left (colour + length, moments)
 static int DenoiseInputPlanes(const zr_pass* p, HaloPlane* planes)
@@ -3670,15 +3637,15 @@ static size_t HaloBytes(const HaloPlane* planes, int n) { size_t b = 0; for (int
 // the planes a halo transfer of this pass moves, and their bytes per pixel
 static int HaloPlanes(zr_pass* p, int which, HaloPlane* planes, size_t* bytesPerPixel)
 {
-    // between the stages of a frame the post-temporal set is [currIdx]; after the frame the set the next frame reads as
-    // "previous" is [1 - currIdx]
-    const int set = which == ZR_HALO_POST_TEMPORAL ? p->currIdx : 1 - p->currIdx;
+    // which reservoir set a transfer addresses (zr_halo_set): between the stages of a frame the post-temporal set is Cur(); after the frame the set the
+    // next frame reads as "previous" is Oth() -- of the overlap roles for ReSTIR PT, of the pass's history for the others
+    const bool post = which == ZR_HALO_POST_TEMPORAL;
+    const int set = post ? p->hist.Cur() : p->hist.Oth();
     int n = 0;
-    if (p->kind == ZR_PASS_INDIRECT && p->integrator == ZR_INTEGRATOR_RESTIR_PT) n = PlanesHalo(*HaloSet(p, which), planes);
-    else if (p->kind == ZR_PASS_INDIRECT && p->integrator == ZR_INTEGRATOR_RESTIR_GI)
-    { planes[n++] = p->giA[set].Halo(); planes[n++] = p->giB[set].Halo(); planes[n++] = p->giC[set].Halo(); }
-    else if (p->kind == ZR_PASS_DI_EMISSIVE) { planes[n++] = p->diA[set].Halo(); planes[n++] = p->diB[set].Halo(); }
-    else if (p->kind == ZR_PASS_DI_SKY) { planes[n++] = p->skyA[set].Halo(); planes[n++] = p->skyB[set].Halo(); planes[n++] = p->skyC[set].Halo(); }
+    if (p->kind == ZR_PASS_INDIRECT && p->integrator == ZR_INTEGRATOR_RESTIR_PT) n = PlanesHalo(p->res[post ? p->ov.roles.Cur() : p->ov.roles.Oth()], planes);
+    else if (p->kind == ZR_PASS_INDIRECT && p->integrator == ZR_INTEGRATOR_RESTIR_GI) n = PlanesHalo(p->gi[set], planes);
+    else if (p->kind == ZR_PASS_DI_EMISSIVE) n = PlanesHalo(p->di[set], planes);
+    else if (p->kind == ZR_PASS_DI_SKY) n = PlanesHalo(p->sky[set], planes);
     else if (p->kind == ZR_PASS_DENOISE)
     {
         // ITER: the plane the next a-trous iteration reads (svgfPing or svgfPong)
@@ -3845,76 +3812,54 @@ int zr_pass_get_output(const zr_pass* p, int which, void** dev, uint32_t* w, uin
         if (which == ZR_OUT_AE_HISTOGRAM) { *dev = p->aeHist.p; if (w) *w = post::kHistBins; if (h) *h = 1; if (bpp) *bpp = 4; return ZR_OK; }
         return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
     }
+    if (p->kind == ZR_PASS_DISPLAY && which == ZR_OUT_PICK_MASK)
+    {
+        if (!p->pickMaskW) return Fail(ZR_ERR_INVALID_ARG, "DISPLAY: no picked instance has been rendered (zr_pass_set_picked_instances)");
+        *dev = p->pickMask.p; if (w) *w = p->pickMaskW; if (h) *h = p->pickMaskH; if (bpp) *bpp = 1; return ZR_OK;
+    }
+    // every other output is a per-pixel plane of the pass's size.  Reservoir outputs name the set the last frame wrote: hist.Oth()
+    const int last = p->hist.Oth();
     if (p->kind == ZR_PASS_DISPLAY)
     {
-        if (which == ZR_OUT_DISPLAY) { p->displayOut.Output(dev, bpp); if (w) *w = p->w; if (h) *h = p->h; return ZR_OK; }
-        if (which == ZR_OUT_DISPLAY_SRGB8) { p->displaySrgb.Output(dev, bpp); if (w) *w = p->w; if (h) *h = p->h; return ZR_OK; }
-        if (which == ZR_OUT_PICK_MASK)
-        {
-            if (!p->pickMaskW) return Fail(ZR_ERR_INVALID_ARG, "DISPLAY: no picked instance has been rendered (zr_pass_set_picked_instances)");
-            *dev = p->pickMask.p; if (w) *w = p->pickMaskW; if (h) *h = p->pickMaskH; if (bpp) *bpp = 1; return ZR_OK;
-        }
-        return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
+        if (which == ZR_OUT_DISPLAY) p->displayOut.Output(dev, bpp);
+        else if (which == ZR_OUT_DISPLAY_SRGB8) p->displaySrgb.Output(dev, bpp);
+        else return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
     }
-    if (p->kind == ZR_PASS_DENOISE)
+    else if (p->kind == ZR_PASS_DENOISE)
     {
-        if (w) *w = p->w;
-        if (h) *h = p->h;
-        if (which == ZR_OUT_DENOISED) { *dev = (void*)p->svgfOut; if (bpp) *bpp = (uint32_t)p->svgfPing.bpp; return ZR_OK; }      // svgfPing or svgfPong
-        if (which == ZR_OUT_DENOISE_HISTORY) { p->svgfHist.Output(dev, bpp); return ZR_OK; }
-        if (which == ZR_OUT_DENOISE_MOMENTS) { p->svgfMoments[p->svgfMomIdx].Output(dev, bpp); return ZR_OK; }
-        return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
+        if (which == ZR_OUT_DENOISED) { *dev = (void*)p->svgfOut; if (bpp) *bpp = (uint32_t)p->svgfPing.bpp; }      // svgfPing or svgfPong
+        else if (which == ZR_OUT_DENOISE_HISTORY) p->svgfHist.Output(dev, bpp);
+        else if (which == ZR_OUT_DENOISE_MOMENTS) p->svgfMoments[p->svgfMomIdx].Output(dev, bpp);
+        else return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
     }
-    if (p->kind == ZR_PASS_TAA)
+    else if (p->kind == ZR_PASS_TAA)
     {
         if (which != ZR_OUT_TAA) return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
         p->taaOut[p->taaIdx].Output(dev, bpp);
-        if (w) *w = p->w;
-        if (h) *h = p->h;
-        return ZR_OK;
     }
-    if (p->kind == ZR_PASS_COMPOSITING)
+    else if (p->kind == ZR_PASS_COMPOSITING)
     {
         if (which != ZR_OUT_FINAL) return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
         p->finalRGBA.Output(dev, bpp);
-        if (w) *w = p->w;
-        if (h) *h = p->h;
-        return ZR_OK;
     }
-    if (p->kind == ZR_PASS_DI_SKY)
+    else if (p->kind == ZR_PASS_DI_SKY)
     {
-        const int last = 1 - p->currIdx;
         if (which == ZR_OUT_FINAL) p->finalRGBA.Output(dev, bpp);
-        else if (which == ZR_OUT_SDI_RESERVOIR_A) p->skyA[last].Output(dev, bpp);
-        else if (which == ZR_OUT_SDI_RESERVOIR_B) p->skyB[last].Output(dev, bpp);
-        else if (which == ZR_OUT_SDI_RESERVOIR_C) p->skyC[last].Output(dev, bpp);
+        else if (which >= ZR_OUT_SDI_RESERVOIR_A && which <= ZR_OUT_SDI_RESERVOIR_C) PlanesOutput(p->sky[last], which - ZR_OUT_SDI_RESERVOIR_A, dev, bpp);
         else if (which == ZR_OUT_SDI_TARGET) p->diTarget.Output(dev, bpp);
         else return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
-        if (w) *w = p->w;
-        if (h) *h = p->h;
-        return ZR_OK;
     }
-    if (p->kind == ZR_PASS_DI_EMISSIVE)
+    else if (p->kind == ZR_PASS_DI_EMISSIVE)
     {
-        const int last = 1 - p->currIdx;        // the reservoir set written by the last frame
         if (which == ZR_OUT_FINAL) p->finalRGBA.Output(dev, bpp);
-        else if (which == ZR_OUT_RDI_RESERVOIR_A) p->diA[last].Output(dev, bpp);
-        else if (which == ZR_OUT_RDI_RESERVOIR_B) p->diB[last].Output(dev, bpp);
+        else if (which >= ZR_OUT_RDI_RESERVOIR_A && which <= ZR_OUT_RDI_RESERVOIR_B) PlanesOutput(p->di[last], which - ZR_OUT_RDI_RESERVOIR_A, dev, bpp);
         else if (which == ZR_OUT_RDI_TARGET) p->diTarget.Output(dev, bpp);
         else return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
-        if (w) *w = p->w;
-        if (h) *h = p->h;
-        return ZR_OK;
     }
-    if (p->kind != ZR_PASS_INDIRECT) return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
-    if (which == ZR_OUT_FINAL) p->FinalPlane(p->ov.roles.finOut).Output(dev, bpp);
+    else if (p->kind != ZR_PASS_INDIRECT) return Fail(ZR_ERR_INVALID_ARG, "pass has no such output");
+    else if (which == ZR_OUT_FINAL) p->FinalPlane(p->ov.roles.finOut).Output(dev, bpp);
     else if (which >= ZR_OUT_RGI_RESERVOIR_A && which <= ZR_OUT_RGI_RESERVOIR_C && p->integrator == ZR_INTEGRATOR_RESTIR_GI)
-    {
-        const int last = 1 - p->currIdx;
-        if (which == ZR_OUT_RGI_RESERVOIR_A) p->giA[last].Output(dev, bpp);
-        else if (which == ZR_OUT_RGI_RESERVOIR_B) p->giB[last].Output(dev, bpp);
-        else p->giC[last].Output(dev, bpp);
-    }
+        PlanesOutput(p->gi[last], which - ZR_OUT_RGI_RESERVOIR_A, dev, bpp);
     else if (which >= ZR_OUT_RPT_RBUF_CTN_A && which <= ZR_OUT_RPT_RBUF_NTC_D && p->integrator == ZR_INTEGRATOR_RESTIR_PT)
         PlanesOutput(p->rb[(which - ZR_OUT_RPT_RBUF_CTN_A) / 4], (which - ZR_OUT_RPT_RBUF_CTN_A) % 4, dev, bpp);
     else if ((which == ZR_OUT_RPT_THREAD_MAP_CTN || which == ZR_OUT_RPT_THREAD_MAP_NTC) && p->integrator == ZR_INTEGRATOR_RESTIR_PT)
