@@ -310,7 +310,15 @@ enum { ZR_TEX_SRC_RAW = 0, ZR_TEX_SRC_BC7 = 1, ZR_TEX_SRC_BC5 = 2,
         * 1 .. num_mips - 1 are generated on the device, each from the stored bytes of the level above it, by the box filter include/zr_mipgen.h states
         * (zr_tu_mipgen.hip: one launch per level for all such textures of the scene, behind the block decode).  num_mips == 1 generates nothing.
         * More than 2^32 - 1 texels in one generated level of all such textures together are refused like the other malformed inputs. */
-       ZR_TEX_SRC_RAW_MIP0 = 8 };
+       ZR_TEX_SRC_RAW_MIP0 = 8,
+       /* level 0 ALONE, as the entropy-decoded coefficients of a baseline JPEG image: `offset` (a multiple of 16) names one record of include/zr_jpeg.h,
+        * written by the host's entropy decoder (zrh_jpeg_pack) -- a 496-byte header (size, components, sampling, quantisation tables, channel map), the
+        * table coef_begin[B + 1] and each block's leading quantised coefficients, de-interleaved.  Dequantisation, the inverse DCT, chroma upsampling,
+        * YCbCr -> RGB and the channel map run on the device (zr_tu_jpeg.hip: two launches for all such textures of the scene, behind the block decode);
+        * the other levels are then generated as for RAW_MIP0.  The channel map RGBA needs format RGBA8 or RGBA8_SRGB, the two RG maps need RG8.  The
+        * whole record is validated on the host before anything is enqueued (zrjp::CheckRecord); more than 2^32 - 1 blocks or level-0 texels in all such
+        * textures together are refused. */
+       ZR_TEX_SRC_JPEG_COEF = 16 };
 typedef struct zr_texture_source { uint64_t offset; uint8_t encoding; uint8_t pad[7]; } zr_texture_source;
 typedef struct zr_texture_blocks { const zr_texture_source* sources; const uint8_t* payload; uint64_t payload_bytes; } zr_texture_blocks;
 /* zr_scene_create with the texel heap produced on the device: desc->texels must be NULL, desc->texel_bytes is the size of the decoded heap and
@@ -318,7 +326,7 @@ typedef struct zr_texture_blocks { const zr_texture_source* sources; const uint8
  * one device copy per texture) into a zero-filled heap, and released.  The heap then equals, in every byte, the one zr_scene_create holds when handed
  * the host-decoded texels (zrh_bc7_decode / zrh_bc5_decode) with zeros between the chains.  ZR_ERR_INVALID_ARG, with nothing created and *out
  * untouched, for: a null blocks / sources / payload; texels != NULL; an unknown encoding; BC7 on a format that is not RGBA8 / RGBA8_SRGB; BC5 on a
- * format that is not RG8; a misaligned source offset; a chain (RAW_MIP0: a level 0) that ends beyond payload_bytes; more than 2^32 - 1 blocks in all; and every
+ * format that is not RG8; a JPEG_COEF record that zrjp::CheckRecord refuses, whose size differs from the desc's or whose channel map does not fit the format; a misaligned source offset; a chain (RAW_MIP0: a level 0) that ends beyond payload_bytes; more than 2^32 - 1 blocks in all; and every
  * zr_texture_desc zr_scene_create refuses.  A scene without textures takes no blocks argument checks beyond the null checks.
  * Textures cannot be replaced after creation. */
 int zr_scene_create_compressed(int device, const zr_scene_desc* desc, const zr_texture_blocks* blocks, zr_scene** out);
@@ -333,6 +341,14 @@ int zr_bcn_decode_device(int device, void* hip_stream, const zr_texture_desc* de
  * zr_texture_desc zr_scene_create refuses (an unknown format, a zero dimension, no mips, an offset that is no multiple of 4, a chain that ends
  * beyond texel_bytes).  zr_bcn_decode_device does not take ZR_TEX_SRC_RAW_MIP0 sources: their level 0 is the caller's copy, the rest is this call. */
 int zr_mipgen_device(int device, void* hip_stream, const zr_texture_desc* descs, uint32_t n, void* d_texels, uint64_t texel_bytes);
+/* The level-0 decode of the ZR_TEX_SRC_JPEG_COEF sources alone, on caller buffers (tests and tools): d_payload (16-byte aligned) and d_texels (4-byte
+ * aligned) on `device`, descs / sources host pointers.  The records are validated on the host first, so their headers and coef_begin tables are read
+ * back from d_payload (a wait on `hip_stream`); the two launches, their job tables and the sample planes (stream-ordered allocations, freed behind the
+ * second launch) are then ENQUEUED on `hip_stream`.  Writes level 0 of the JPEG sources and nothing else; sources of other encodings are left alone, as
+ * zr_bcn_decode_device leaves JPEG_COEF and RAW_MIP0 ones (which it takes only here: with them in `sources` it refuses as before).  Refuses what
+ * zr_scene_create_compressed refuses. */
+int zr_jpeg_decode_device(int device, void* hip_stream, const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n,
+                          const void* d_payload, uint64_t payload_bytes, void* d_texels, uint64_t texel_bytes);
 /* read-back of bytes [first_byte, first_byte + count) of the scene's texel heap, for tests and tools; waits for `hip_stream` */
 int zr_scene_get_texels(const zr_scene* scene, void* hip_stream, uint8_t* out, uint64_t first_byte, uint64_t count);
 /* Per-frame update of dynamic instances (TLAS::FillMeshInstanceData + the TLAS rebuild, RtAccelerationStructure.cpp:318-506, 708-787;

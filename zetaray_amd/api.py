@@ -65,7 +65,7 @@ EXPORTS = [
     "zr_scene_set_object_emissives", "zr_scene_has_object_emissives", "zr_scene_move_instances", "zr_scene_move_instances_async", "zr_scene_get_instances", "zr_scene_get_emissives",
     "zr_scene_set_animation", "zr_scene_animate", "zr_scene_animate_async",
     "zr_scene_set_alias_build", "zr_alias_table_build_device", "zr_pass_get_emissive_powers",
-    "zr_scene_create_compressed", "zr_bcn_decode_device", "zr_scene_get_texels", "zr_mipgen_device",
+    "zr_scene_create_compressed", "zr_bcn_decode_device", "zr_scene_get_texels", "zr_mipgen_device", "zr_jpeg_decode_device",
 ]
 ALIAS_BUILD_HOST, ALIAS_BUILD_DEVICE = 0, 1
 ALIAS_BUILD_MODES = {"host": ALIAS_BUILD_HOST, "device": ALIAS_BUILD_DEVICE}
@@ -114,6 +114,7 @@ def lib():
         L.zr_bcn_decode_device.argtypes = [i32, vp, vp, vp, u32, vp, C.c_uint64, vp, C.c_uint64]
         L.zr_scene_get_texels.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64]
         L.zr_mipgen_device.argtypes = [i32, vp, vp, u32, vp, C.c_uint64]
+        L.zr_jpeg_decode_device.argtypes = [i32, vp, vp, vp, u32, vp, C.c_uint64, vp, C.c_uint64]
         L.zr_scene_set_alias_table.argtypes = [vp, vp, u32]
         L.zr_alias_table_build.argtypes = [vp, u32, u32, vp]
         L.zr_scene_get_alias_table.argtypes = [vp, vp, u32]
@@ -206,6 +207,23 @@ def bcn_decode_device(descs, sources, payload, texel_bytes, fill=0, device=0, st
     d_out = torch.full((int(texel_bytes),), int(fill), dtype=torch.uint8, device=f"cuda:{device}")
     torch.cuda.synchronize(device)
     _check(lib().zr_bcn_decode_device(device, stream, descs.ctypes.data, sources.ctypes.data, len(descs), d_payload.data_ptr(), len(payload), d_out.data_ptr(), int(texel_bytes)))
+    torch.cuda.synchronize(device)
+    return d_out.cpu().numpy().copy()
+
+
+def jpeg_decode_device(descs, sources, payload, texel_bytes, fill=0, device=0, stream=None):
+    """zr_jpeg_decode_device: level 0 of the wire.TEX_SRC_JPEG_COEF sources in `payload` (records of scene_io.pack_jpeg) decoded on the device into a heap of
+    `texel_bytes` bytes pre-filled with `fill`, at the places `descs` name; returns the heap.  stream: a torch.cuda.Stream (None: the null stream)"""
+    import torch
+    descs, sources = np.ascontiguousarray(descs, wire.TEXTURE_DESC), np.ascontiguousarray(sources, wire.TEXTURE_SOURCE)
+    payload = np.ascontiguousarray(payload, np.uint8).reshape(-1)
+    d_payload = torch.from_numpy(payload.copy()).to(f"cuda:{device}")
+    d_out = torch.full((int(texel_bytes),), int(fill), dtype=torch.uint8, device=f"cuda:{device}")
+    torch.cuda.synchronize(device)
+    _check(lib().zr_jpeg_decode_device(device, stream.cuda_stream if stream is not None else None, descs.ctypes.data, sources.ctypes.data, len(descs), d_payload.data_ptr(),
+                                       len(payload), d_out.data_ptr(), int(texel_bytes)))
+    if stream is not None:
+        stream.synchronize()
     torch.cuda.synchronize(device)
     return d_out.cpu().numpy().copy()
 

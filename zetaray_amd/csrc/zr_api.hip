@@ -93,6 +93,9 @@ namespace zr { size_t AliasScratchWords(uint32_t n);      // zr_tu_alias.hip
 #include "../../include/zr_bcn.h"
 namespace zr { hipError_t LaunchBcnDecode(hipStream_t st, const zrbc::Job* jobs, uint32_t numJobs, uint32_t numBlocks, const uint8_t* payload, uint8_t* texels); }   // zr_tu_texdecode.hip
 #include "../../include/zr_mipgen.h"
+#include "../../include/zr_jpeg.h"
+namespace zr { hipError_t LaunchJpegDecode(hipStream_t st, const zrjp::BlockJob* blockJobs, uint32_t numBlockJobs, uint32_t numBlocks, const zrjp::TexJob* texJobs, uint32_t numTexJobs,
+                   uint32_t numItems, const uint8_t* payload, uint8_t* planes, uint8_t* texels); }   // zr_tu_jpeg.hip
 namespace zr { hipError_t LaunchMipLevel(hipStream_t st, const zrmg::Job* jobs, uint32_t numJobs, uint32_t numItems, uint8_t* texels); }   // zr_tu_mipgen.hip
 // the ReSTIR PT kernels are compiled in zr_tu_rpt_[a-i].hip (see zr_kernels.h)
 ZR_RPT_GROUPS_PRODUCT(extern template)
@@ -1375,14 +1378,43 @@ static bool TextureDescOk(const zr_texture_desc& t, uint64_t texelBytes)
 struct BcnPlan { std::vector<zrbc::Job> jobs; struct Copy { uint64_t src, dst, bytes; }; std::vector<Copy> copies; uint32_t numBlocks = 0;
                  std::vector<uint32_t> mip0;      // the textures whose source is level 0 alone (ZR_TEX_SRC_RAW_MIP0): their other levels are generated (MipPlan)
                  std::vector<std::pair<uint64_t, uint64_t>> chains; };
+// What the ZR_TEX_SRC_JPEG_COEF sources of a call take (PlanJpegDecode, below): one zrjp::BlockJob per component and one zrjp::TexJob per texture, in texture
+// order, for the two launches of zr_tu_jpeg.hip, and the bytes of the sample planes between them
+struct JpegPlan { std::vector<zrjp::BlockJob> blockJobs; std::vector<zrjp::TexJob> texJobs; uint64_t numBlocks = 0, numItems = 0, planeBytes = 0; };
+// One JPEG_COEF source: the whole record is validated here, on the host, before anything is enqueued -- the kernels trust what this accepted.
+// payload: the payload ON THE HOST
+static int PlanJpegDecode(const char* fn, uint32_t i, const zr_texture_desc& t, const zr_texture_source& src, const uint8_t* payload, uint64_t payloadBytes, JpegPlan& jp)
+{
+    if (src.offset & 15u) return Fail(ZR_ERR_INVALID_ARG, "%s: the source offset of texture %u is not a multiple of 16", fn, i);
+    if (src.offset > payloadBytes) return Fail(ZR_ERR_INVALID_ARG, "%s: the record of texture %u starts beyond the payload", fn, i);
+    zrjp::Header h;
+    if (const char* why = zrjp::CheckRecord(payload + src.offset, payloadBytes - src.offset, &h)) return Fail(ZR_ERR_INVALID_ARG, "%s: the JPEG record of texture %u: %s", fn, i, why);
+    if (h.w != t.width || h.h != t.height) return Fail(ZR_ERR_INVALID_ARG, "%s: the JPEG record of texture %u is %u x %u, its desc %u x %u", fn, i, h.w, h.h, (unsigned)t.width, (unsigned)t.height);
+    if ((h.map == (uint32_t)zrjp::kMapRgba) != (t.format != ZR_TEX_RG8)) return Fail(ZR_ERR_INVALID_ARG, "%s: the channel map of the JPEG record of texture %u does not fit its format", fn, i);
+    if (jp.numBlocks + h.num_blocks > 0xffffffffull || jp.numItems + (uint64_t)h.w * h.h > 0xffffffffull) return Fail(ZR_ERR_INVALID_ARG, "%s: more than 2^32 - 1 JPEG blocks or texels", fn);
+    zrjp::BlockJob bj[3]; zrjp::TexJob tj;
+    zrjp::MakeJobs(h, src.offset, jp.planeBytes, t.offset, (uint32_t)jp.numBlocks, (uint32_t)jp.numItems, bj, &tj);
+    jp.blockJobs.insert(jp.blockJobs.end(), bj, bj + h.ncomp); jp.texJobs.push_back(tj);
+    jp.numBlocks += h.num_blocks; jp.numItems += (uint64_t)h.w * h.h; jp.planeBytes += zrjp::PlaneBytes(h);
+    return ZR_OK;
+}
+// jpeg / hostPayload: where JPEG_COEF sources are planned and the payload on the host they are validated in (null: such a source is an unknown encoding)
 static int PlanBcnDecode(const char* fn, const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n, uint64_t payloadBytes, uint64_t texelBytes, BcnPlan& plan,
-    bool allowMip0)
+    bool allowMip0, JpegPlan* jpeg = nullptr, const uint8_t* hostPayload = nullptr)
 {
     uint64_t blocks = 0;
     for (uint32_t i = 0; i < n; i++)
     {
         const zr_texture_desc& t = descs[i]; const zr_texture_source& src = sources[i];
         if (!TextureDescOk(t, texelBytes)) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is malformed or lies outside the texel blob", fn, i);
+        if (jpeg && src.encoding == ZR_TEX_SRC_JPEG_COEF)
+        {   // level 0 from the record; the other levels generated like a RAW_MIP0 chain's
+            if (int r = PlanJpegDecode(fn, i, t, src, hostPayload, payloadBytes, *jpeg)) return r;
+            if (t.num_mips > 1u) plan.mip0.push_back(i);
+            const zr_tex_mip last = zr_tex_mip_of(&t, t.num_mips - 1u);
+            plan.chains.push_back({t.offset, last.offset + (uint64_t)last.w * last.h * (t.format == ZR_TEX_RG8 ? 2u : 4u)});
+            continue;
+        }
         const bool mip0 = allowMip0 && src.encoding == ZR_TEX_SRC_RAW_MIP0, raw = src.encoding == ZR_TEX_SRC_RAW || mip0;
         if (src.encoding > ZR_TEX_SRC_BC5 && !mip0) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u has the unknown source encoding %u", fn, i, (unsigned)src.encoding);
         if (src.encoding == ZR_TEX_SRC_BC7 && t.format != ZR_TEX_RGBA8 && t.format != ZR_TEX_RGBA8_SRGB) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is BC7 but its format is not RGBA8 / RGBA8_SRGB", fn, i);
@@ -1416,6 +1448,24 @@ static int RunBcnPlan(hipStream_t st, const BcnPlan& plan, const zrbc::Job* dJob
 {
     if (!plan.jobs.empty()) HIP_TRY(zr::LaunchBcnDecode(st, dJobs, (uint32_t)plan.jobs.size(), plan.numBlocks, dPayload, dTexels));
     for (const BcnPlan::Copy& c : plan.copies) if (c.bytes) HIP_TRY(hipMemcpyAsync(dTexels + c.dst, dPayload + c.src, c.bytes, hipMemcpyDeviceToDevice, st));
+    return ZR_OK;
+}
+// enqueues the plan on `st`: the job tables and the sample planes in stream-ordered allocations, the two launches, the frees behind them.  The tables are
+// copied from the plan's pageable vectors (synchronous towards the host buffer: see zr_bcn_decode_device)
+static int RunJpegPlan(const char* fn, hipStream_t st, const JpegPlan& jp, const uint8_t* dPayload, uint8_t* dTexels)
+{
+    if (jp.texJobs.empty()) return ZR_OK;
+    const size_t bBytes = jp.blockJobs.size() * sizeof(zrjp::BlockJob), tBytes = jp.texJobs.size() * sizeof(zrjp::TexJob);
+    void* mem[3] = {nullptr, nullptr, nullptr};
+    const size_t sizes[3] = {bBytes, tBytes, (size_t)jp.planeBytes};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipMallocAsync(&mem[k], sizes[k], st);
+    if (e == hipSuccess) e = hipMemcpyAsync(mem[0], jp.blockJobs.data(), bBytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(mem[1], jp.texJobs.data(), tBytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = zr::LaunchJpegDecode(st, (const zrjp::BlockJob*)mem[0], (uint32_t)jp.blockJobs.size(), (uint32_t)jp.numBlocks, (const zrjp::TexJob*)mem[1],
+                                                  (uint32_t)jp.texJobs.size(), (uint32_t)jp.numItems, dPayload, (uint8_t*)mem[2], dTexels);
+    for (int k = 0; k < 3; k++) if (mem[k]) { const hipError_t f = hipFreeAsync(mem[k], st); if (e == hipSuccess) e = f; }      // freed behind whatever was enqueued
+    if (e != hipSuccess) return Fail(ZR_ERR_HIP, "%s: the JPEG decode could not be enqueued: %s", fn, hipGetErrorString(e));
     return ZR_OK;
 }
 // What the mip generation of n textures takes (zr_scene_create_compressed for its RAW_MIP0 sources, zr_mipgen_device): one zrmg::Job per generated level of
@@ -1472,13 +1522,13 @@ static int SceneCreate(const char* fn, int device, const zr_scene_desc* d, const
     if (!d || !out) return Fail(ZR_ERR_INVALID_ARG, "%s: null argument", fn);
     if (!d->vertices || !d->indices || !d->instances || !d->materials || !d->rho_lut || !d->instance_to_world || !d->instance_mask || !d->instance_num_tris)
         return Fail(ZR_ERR_INVALID_ARG, "%s: incomplete scene description", fn);
-    BcnPlan plan; MipPlan mipPlan;
+    BcnPlan plan; MipPlan mipPlan; JpegPlan jpegPlan;
     if (blocks)
     {   // refused before the acceleration structure is built
         if (!blocks->sources || !blocks->payload) return Fail(ZR_ERR_INVALID_ARG, "%s: null sources / payload", fn);
         if (d->texels) return Fail(ZR_ERR_INVALID_ARG, "%s: desc->texels must be null: the heap is decoded from the blocks", fn);
         if (d->num_textures && !d->textures) return Fail(ZR_ERR_INVALID_ARG, "%s: num_textures > 0 without textures", fn);
-        if (int pr = PlanBcnDecode(fn, d->textures, blocks->sources, d->num_textures, blocks->payload_bytes, d->texel_bytes, plan, true)) return pr;
+        if (int pr = PlanBcnDecode(fn, d->textures, blocks->sources, d->num_textures, blocks->payload_bytes, d->texel_bytes, plan, true, &jpegPlan, blocks->payload)) return pr;
         if (int pr = PlanMipGen(fn, d->textures, plan.mip0.data(), (uint32_t)plan.mip0.size(), mipPlan)) return pr;
     }
     DevBuf<uint8_t> payload; DevBuf<zrbc::Job> jobs; DevBuf<zrmg::Job> mipJobs;      // (live until the synchronize at the end)
@@ -1513,7 +1563,9 @@ static int SceneCreate(const char* fn, int device, const zr_scene_desc* d, const
         if ((r = s->texDescs.Upload(d->textures, d->num_textures)) || (r = payload.Upload(blocks->payload, blocks->payload_bytes)) ||
             (r = s->texels.Alloc(d->texel_bytes)) || (r = ClearHeapGaps(plan, s->texels.p, d->texel_bytes)) || (r = jobs.Upload(plan.jobs.data(), plan.jobs.size())) ||
             (r = RunBcnPlan(nullptr, plan, jobs.p, payload.p, s->texels.p))) return r;
-        // ... and behind the decode and the copies of level 0, the other levels of the RAW_MIP0 chains: one launch per level
+        // ... level 0 of the JPEG_COEF sources: the inverse DCT into sample planes, then the texels
+        if ((r = RunJpegPlan(fn, nullptr, jpegPlan, payload.p, s->texels.p))) return r;
+        // ... and behind the decode and the copies of level 0, the other levels of the RAW_MIP0 and JPEG_COEF chains: one launch per level
         if (!mipPlan.jobs.empty() && ((r = mipJobs.Upload(mipPlan.jobs.data(), mipPlan.jobs.size())) || (r = RunMipPlan(nullptr, mipPlan, mipJobs.p, s->texels.p)))) return r;
     }
     else if (d->num_textures)
@@ -1607,6 +1659,29 @@ int zr_bcn_decode_device(int device, void* stream, const zr_texture_desc* descs,
         if (e != hipSuccess && !r) return Fail(ZR_ERR_HIP, "%s: hipFreeAsync failed: %s", fn, hipGetErrorString(e));
     }
     return r;
+}
+// level 0 of the JPEG_COEF sources of zr_scene_create_compressed on caller buffers.  The records are validated on the host like the scene path's, so the
+// payload is read back first (a wait on the stream); the decode itself is enqueued only
+int zr_jpeg_decode_device(int device, void* stream, const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n, const void* d_payload, uint64_t payload_bytes,
+    void* d_texels, uint64_t texel_bytes)
+{
+    const char* fn = "zr_jpeg_decode_device";
+    if (!descs || !sources || !d_payload || !d_texels || n == 0) return Fail(ZR_ERR_INVALID_ARG, "%s: null/empty input", fn);
+    if (((uintptr_t)d_payload & 15u) || ((uintptr_t)d_texels & 3u)) return Fail(ZR_ERR_INVALID_ARG, "%s: d_payload must be 16-byte and d_texels 4-byte aligned", fn);
+    bool any = false;
+    for (uint32_t i = 0; i < n; i++) any = any || sources[i].encoding == ZR_TEX_SRC_JPEG_COEF;
+    if (hipSetDevice(device) != hipSuccess) return Fail(ZR_ERR_NO_DEVICE, "%s: no usable HIP device %d", fn, device);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<uint8_t> host;
+    if (any && payload_bytes)
+    {
+        host.resize(payload_bytes);
+        HIP_TRY(hipMemcpyAsync(host.data(), d_payload, payload_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    BcnPlan plan; JpegPlan jp;
+    if (int r = PlanBcnDecode(fn, descs, sources, n, payload_bytes, texel_bytes, plan, true, &jp, host.data())) return r;
+    return RunJpegPlan(fn, st, jp, (const uint8_t*)d_payload, (uint8_t*)d_texels);
 }
 // the level launches of zr_scene_create_compressed on caller buffers; enqueues only, like zr_bcn_decode_device
 int zr_mipgen_device(int device, void* stream, const zr_texture_desc* descs, uint32_t n, void* d_texels, uint64_t texel_bytes)

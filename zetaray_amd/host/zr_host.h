@@ -52,7 +52,8 @@ int zrh_halo_exchange_run(zrh_halo_exchange* x, void* hip_stream, int which);
 struct zrh_scene_data;
 // Model::glTF::Load + SceneCore + TLAS build in one call; tex_offsets4 = the four descriptor-table offsets for cbFrameConstants
 int zrh_scene_create_from_gltf(int device, const char* path, const uint16_t* rho_lut, const uint32_t* rho_dim3, zr_scene** out, uint32_t* tex_offsets4);
-// ... with the loader's flags (zr_scene_io.h): ZRH_LOAD_KEEP_COMPRESSED hands the .dds blocks to zr_scene_create_compressed, which decodes them on the device
+// ... with the loader's flags (zr_scene_io.h): ZRH_LOAD_KEEP_COMPRESSED hands the .dds blocks to zr_scene_create_compressed, which decodes them on the device;
+// ZRH_LOAD_JPEG reads .jpg / .jpeg images, and with both flags their coefficient records travel as ZR_TEX_SRC_JPEG_COEF sources
 int zrh_scene_create_from_gltf_ex(int device, const char* path, const uint16_t* rho_lut, const uint32_t* rho_dim3, uint32_t load_flags, zr_scene** out, uint32_t* tex_offsets4);
 // the device scene of a loaded zrh_scene_data: zr_scene_create_compressed when the data carries texture blocks (zrh_scene_data_texture_blocks), else zr_scene_create
 int zrh_scene_create_from_data(int device, const zrh_scene_data* data, zr_scene** out);

@@ -8,6 +8,7 @@
 #include "../../include/zr_bcn.h"
 #include "../../include/zr_texture.h"
 #include "../../include/zr_mipgen.h"
+#include "../../include/zr_jpeg.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -473,6 +474,262 @@ Image LoadPNG(const std::string& path, bool colour, uint32_t r0, uint32_t r1)
     return img;
 }
 
+// ------------------------------------------------------------------------------------------------ JPEG -> the record of include/zr_jpeg.h
+// The sequential part of a baseline JPEG: markers, tables and the Huffman-coded scan, into the record the header (here) or the kernels of zr_tu_jpeg.hip
+// turn into texels.  SOF0 / SOF1, 8 bits, 1 or 3 components (4:4:4, 4:2:2, 4:2:0), one scan, DRI / RSTn.  Every read is bounds-checked.
+struct JpegReader
+{
+    const std::string& name; const uint8_t* d; size_t n;
+    size_t pos = 0; uint32_t buf = 0; int cnt = 0, fake = 0;      // buf: the next cnt bits, left-aligned; the last `fake` of them are zeros fed behind the data's end
+    struct Huff { bool set = false; uint8_t count[17] = {}; uint8_t symbol[256] = {}; int32_t maxcode[18] = {}; int32_t valptr[17] = {}; uint16_t fast[512] = {}; };
+    Huff dc[4], ac[4];
+    [[noreturn]] void Bad(const char* why) { Throw(name + ": " + why); }
+    void Build(Huff& h, const uint8_t* counts, const uint8_t* symbols, uint32_t total)
+    {
+        h = Huff();
+        int32_t code = 0; uint32_t p = 0;
+        for (int len = 1; len <= 16; len++)
+        {
+            h.count[len] = counts[len - 1]; h.valptr[len] = (int32_t)p - code;
+            if (code + (int32_t)counts[len - 1] > (1 << len)) Bad("invalid DHT: over-subscribed Huffman code");
+            for (uint32_t i = 0; i < counts[len - 1]; i++, p++, code++)
+            {
+                h.symbol[p] = symbols[p];
+                if (len <= 9) for (int32_t f = code << (9 - len); f < ((code + 1) << (9 - len)); f++) h.fast[f] = (uint16_t)((len << 8) | symbols[p]);
+            }
+            h.maxcode[len] = counts[len - 1] ? code - 1 : -1;
+            code <<= 1;
+        }
+        h.maxcode[17] = 0x7fffffff; h.set = true; (void)total;
+    }
+    void Fill()
+    {
+        while (cnt <= 24)
+        {
+            uint32_t b = 0;
+            if (pos < n && !(d[pos] == 0xffu && (pos + 1 >= n || d[pos + 1] != 0u))) { b = d[pos]; pos += b == 0xffu ? 2u : 1u; }
+            else fake += 8;      // a marker or the end of the file: zeros, counted
+            buf |= b << (24 - cnt); cnt += 8;
+        }
+    }
+    void Drop(int bits) { buf <<= bits; cnt -= bits; if (cnt < fake) Bad("truncated: the entropy-coded data ends early"); }
+    uint32_t Bits(int need)      // need <= 16
+    {
+        if (!need) return 0u;
+        Fill();
+        const uint32_t v = buf >> (32 - need);
+        Drop(need);
+        return v;
+    }
+    uint32_t Decode(const Huff& h)
+    {
+        Fill();
+        const uint32_t f = h.fast[buf >> 23];
+        if (f) { Drop((int)(f >> 8)); return f & 0xffu; }
+        for (int len = 10; len <= 16; len++)
+        {
+            const int32_t code = (int32_t)(buf >> (32 - len));
+            if (code <= h.maxcode[len]) { Drop(len); return h.symbol[(code + h.valptr[len]) & 0xff]; }
+        }
+        Bad("invalid entropy-coded data: a Huffman code that is not in the table");
+    }
+    static int32_t Extend(uint32_t v, int s) { return s && v < (1u << (s - 1)) ? (int32_t)v - (int32_t)((1u << s) - 1u) : (int32_t)v; }
+    // one block into blk[0 .. 63] (zigzag order, zeroed here); returns n = the index of the last non-zero coefficient + 1, at least 1
+    uint32_t Block(const Huff& hd, const Huff& ha, uint32_t& pred, int16_t* blk)
+    {
+        std::memset(blk, 0, 64 * sizeof(int16_t));
+        const uint32_t s = Decode(hd);
+        if (s > 11u) Bad("invalid entropy-coded data: a DC difference of more than 11 bits");
+        pred += (uint32_t)Extend(Bits((int)s), (int)s);
+        blk[0] = (int16_t)pred;
+        uint32_t last = 0u;
+        for (uint32_t k = 1; k < 64u;)
+        {
+            const uint32_t rs = Decode(ha), r = rs >> 4, sz = rs & 15u;
+            if (!sz)
+            {
+                if (r != 15u) break;      // end of block
+                k += 16u;
+                if (k > 64u) Bad("invalid entropy-coded data: a coefficient index past 63");
+                continue;
+            }
+            k += r;
+            if (k > 63u) Bad("invalid entropy-coded data: a coefficient index past 63");
+            blk[k] = (int16_t)Extend(Bits((int)sz), (int)sz);
+            last = k++;
+        }
+        return last + 1u;
+    }
+};
+struct JpegPacked { zrjp::Header hdr; std::vector<uint32_t> begin; std::vector<int16_t> coef; };
+JpegPacked PackJpeg(const std::string& name, const uint8_t* d, size_t n, uint32_t map)
+{
+    JpegReader rd{name, d, n};
+    if (n < 4 || d[0] != 0xffu || d[1] != 0xd8u) Throw(name + ": not a JPEG file");
+    JpegPacked out; std::memset(&out.hdr, 0, sizeof(out.hdr));
+    zrjp::Header& hdr = out.hdr;
+    hdr.magic = zrjp::kMagic; hdr.map = map;
+    uint16_t qt[4][64]; bool haveQt[4] = {false, false, false, false};
+    uint8_t compId[3] = {0, 0, 0}, compTq[3] = {0, 0, 0};
+    bool haveFrame = false; int adobe = -1; uint32_t restart = 0;
+    size_t at = 2;
+    auto be16 = [&](size_t off) { return ((uint32_t)d[off] << 8) | d[off + 1]; };
+    for (;;)
+    {
+        if (at >= n || d[at] != 0xffu) Throw(name + ": truncated or corrupt: no marker where one must stand");
+        while (at < n && d[at] == 0xffu) at++;      // (fill bytes)
+        if (at >= n) Throw(name + ": truncated: the file ends before the scan");
+        const uint32_t m = d[at++];
+        if (m == 0xd9u) Throw(name + ": truncated: no scan before the end of the image");
+        if (m == 0x01u || (m >= 0xd0u && m <= 0xd7u)) continue;      // (stand-alone markers)
+        if (n - at < 2) Throw(name + ": truncated: a marker segment is cut off");
+        const uint32_t len = be16(at);
+        if (len < 2u || len > n - at) Throw(name + ": truncated: a marker segment is longer than the file");
+        const uint8_t* seg = d + at + 2; const uint32_t segLen = len - 2u;
+        if (m == 0xc2u) Throw(name + ": progressive JPEG files are not supported");
+        if (m == 0xc9u || m == 0xcau || m == 0xcbu || m == 0xccu || m == 0xcdu || m == 0xceu || m == 0xcfu) Throw(name + ": arithmetic-coded JPEG files are not supported");
+        if (m == 0xc3u || m == 0xc5u || m == 0xc6u || m == 0xc7u || m == 0xdeu) Throw(name + ": lossless / hierarchical JPEG files are not supported");
+        if (m == 0xc0u || m == 0xc1u)
+        {
+            if (haveFrame) Throw(name + ": more than one frame header");
+            if (segLen < 6u) Throw(name + ": invalid frame header");
+            if (seg[0] == 12u) Throw(name + ": 12-bit JPEG files are not supported");
+            if (seg[0] != 8u) Throw(name + ": invalid sample precision");
+            hdr.h = be16(at + 3); hdr.w = be16(at + 5); hdr.ncomp = seg[5];
+            if (hdr.w == 0u || hdr.h == 0u) Throw(name + ": texture dimensions must be in [1, 65535]");
+            if (hdr.ncomp == 4u) Throw(name + ": 4-component (CMYK / YCCK) JPEG files are not supported");
+            if (hdr.ncomp != 1u && hdr.ncomp != 3u) Throw(name + ": invalid component count");
+            if (segLen != 6u + 3u * hdr.ncomp) Throw(name + ": invalid frame header");
+            for (uint32_t c = 0; c < hdr.ncomp; c++)
+            {
+                compId[c] = seg[6u + 3u * c]; compTq[c] = seg[8u + 3u * c];
+                hdr.comp[c].hs = seg[7u + 3u * c] >> 4; hdr.comp[c].vs = seg[7u + 3u * c] & 15u;
+                if (compTq[c] > 3u) Throw(name + ": invalid quantisation table selector");
+            }
+            if (hdr.ncomp == 1u) hdr.comp[0].hs = hdr.comp[0].vs = 1u;      // (a single component is not interleaved: its sampling factors mean nothing)
+            if (!zrjp::LayoutComponents(hdr)) Throw(name + ": unsupported chroma sampling (4:4:4, 4:2:2 and 4:2:0 are read)");
+            haveFrame = true;
+        }
+        else if (m == 0xc4u)
+        {
+            for (uint32_t p = 0; p < segLen;)
+            {
+                if (segLen - p < 17u) Throw(name + ": invalid DHT");
+                const uint32_t tc = seg[p] >> 4, th = seg[p] & 15u;
+                uint32_t total = 0; for (uint32_t i = 0; i < 16u; i++) total += seg[p + 1u + i];
+                if (tc > 1u || th > 3u || total > 256u || segLen - p - 17u < total) Throw(name + ": invalid DHT");
+                rd.Build(tc ? rd.ac[th] : rd.dc[th], seg + p + 1u, seg + p + 17u, total);
+                p += 17u + total;
+            }
+        }
+        else if (m == 0xdbu)
+        {
+            for (uint32_t p = 0; p < segLen;)
+            {
+                const uint32_t pq = seg[p] >> 4, tq = seg[p] & 15u;
+                if (pq > 1u || tq > 3u || segLen - p - 1u < 64u * (pq + 1u)) Throw(name + ": invalid DQT");
+                for (uint32_t k = 0; k < 64u; k++) qt[tq][k] = pq ? (uint16_t)((seg[p + 1u + 2u * k] << 8) | seg[p + 2u + 2u * k]) : seg[p + 1u + k];
+                haveQt[tq] = true; p += 1u + 64u * (pq + 1u);
+            }
+        }
+        else if (m == 0xddu) { if (segLen != 2u) Throw(name + ": invalid DRI"); restart = be16(at + 2); }
+        else if (m == 0xeeu && segLen >= 12u && !std::memcmp(seg, "Adobe", 5)) adobe = seg[11];
+        else if (m == 0xdau)
+        {
+            if (!haveFrame) Throw(name + ": a scan before the frame header");
+            if (segLen < 1u || segLen != 4u + 2u * seg[0]) Throw(name + ": invalid scan header");
+            if (seg[0] != hdr.ncomp) Throw(name + ": JPEG files with several scans are not supported");
+            if (hdr.ncomp == 3u && adobe == 0) Throw(name + ": RGB (Adobe transform 0) JPEG files are not supported");
+            const JpegReader::Huff* hd[3]; const JpegReader::Huff* ha[3];
+            for (uint32_t c = 0; c < hdr.ncomp; c++)
+            {
+                if (seg[1u + 2u * c] != compId[c]) Throw(name + ": the scan names its components in another order than the frame");
+                const uint32_t td = seg[2u + 2u * c] >> 4, ta = seg[2u + 2u * c] & 15u;
+                if (td > 3u || ta > 3u || !rd.dc[td].set || !rd.ac[ta].set) Throw(name + ": the scan names a Huffman table the file does not define");
+                hd[c] = &rd.dc[td]; ha[c] = &rd.ac[ta];
+                if (!haveQt[compTq[c]]) Throw(name + ": the frame names a quantisation table the file does not define");
+                std::memcpy(hdr.comp[c].q, qt[compTq[c]], sizeof(qt[0]));
+            }
+            if (seg[segLen - 3u] != 0u || seg[segLen - 2u] != 63u || seg[segLen - 1u] != 0u) Throw(name + ": invalid spectral selection for a sequential scan");
+            at += len;
+            // (a block is at least a 1-bit DC code and a 1-bit end of block: a header that promises more than the data can hold is refused before
+            // anything is allocated)
+            if ((uint64_t)hdr.num_blocks > 4ull * (n - at)) Throw(name + ": truncated: the header promises more blocks than the data can hold");
+            // the scan: MCU by MCU, each block appended in scan order; `slot` says where it stands in the record
+            const uint32_t B = hdr.num_blocks, hs = hdr.comp[0].hs, vs = hdr.comp[0].vs;
+            const uint32_t mcusX = hdr.comp[0].bw / hs, mcusY = hdr.comp[0].bh / vs;
+            std::vector<uint32_t> scanBegin; scanBegin.reserve((size_t)B + 1u); std::vector<uint32_t> slot; slot.reserve(B);
+            std::vector<int16_t> scanCoef; scanCoef.reserve((size_t)B * 4u);
+            rd.pos = at;
+            uint32_t pred[3] = {0, 0, 0}, sinceRestart = 0, nextRst = 0;
+            int16_t blk[64];
+            for (uint32_t my = 0; my < mcusY; my++) for (uint32_t mx = 0; mx < mcusX; mx++)
+            {
+                if (restart && sinceRestart == restart)
+                {   // byte-align; what is left of the last byte is padding, and RSTn stands next
+                    if (rd.cnt - rd.fake >= 8) Throw(name + ": bad or missing restart marker");
+                    size_t p = rd.pos;
+                    while (p + 1 < n && d[p] == 0xffu && d[p + 1] == 0xffu) p++;
+                    if (p + 1 >= n || d[p] != 0xffu || d[p + 1] != 0xd0u + nextRst) Throw(name + ": bad or missing restart marker");
+                    rd.pos = p + 2; rd.buf = 0; rd.cnt = 0; rd.fake = 0;
+                    nextRst = (nextRst + 1u) & 7u; sinceRestart = 0; pred[0] = pred[1] = pred[2] = 0;
+                }
+                sinceRestart++;
+                for (uint32_t c = 0; c < hdr.ncomp; c++) for (uint32_t v = 0; v < hdr.comp[c].vs; v++) for (uint32_t h = 0; h < hdr.comp[c].hs; h++)
+                {
+                    const uint32_t nz = rd.Block(*hd[c], *ha[c], pred[c], blk);
+                    if (scanCoef.size() + nz > 0xffffffffull) Throw(name + ": more than 2^32 - 1 coefficients");
+                    scanBegin.push_back((uint32_t)scanCoef.size());
+                    scanCoef.insert(scanCoef.end(), blk, blk + nz);
+                    slot.push_back(hdr.comp[c].first_block + (my * hdr.comp[c].vs + v) * hdr.comp[c].bw + mx * hdr.comp[c].hs + h);
+                }
+            }
+            scanBegin.push_back((uint32_t)scanCoef.size());
+            // de-interleave: per component, row-major
+            std::vector<uint32_t> len(B);
+            for (uint32_t i = 0; i < B; i++) len[slot[i]] = scanBegin[i + 1u] - scanBegin[i];
+            out.begin.resize((size_t)B + 1u); out.begin[0] = 0u;
+            for (uint32_t b = 0; b < B; b++) out.begin[b + 1u] = out.begin[b] + len[b];
+            out.coef.resize(scanCoef.size());
+            for (uint32_t i = 0; i < B; i++) std::memcpy(out.coef.data() + out.begin[slot[i]], scanCoef.data() + scanBegin[i], sizeof(int16_t) * (scanBegin[i + 1u] - scanBegin[i]));
+            hdr.bytes = sizeof(zrjp::Header) + 4ull * ((uint64_t)B + 1u) + 2ull * out.coef.size();
+            return out;
+        }
+        // (APPn, COM and every other segment with a length: skipped)
+        at += len;
+    }
+}
+// the record's bytes, padded with zeros to a multiple of 16 (hdr.bytes says where the record ends)
+std::vector<uint8_t> JpegRecord(const JpegPacked& p)
+{
+    std::vector<uint8_t> r(((size_t)p.hdr.bytes + 15u) & ~(size_t)15u, 0);
+    std::memcpy(r.data(), &p.hdr, sizeof(p.hdr));
+    std::memcpy(r.data() + sizeof(p.hdr), p.begin.data(), 4u * p.begin.size());
+    if (!p.coef.empty()) std::memcpy(r.data() + sizeof(p.hdr) + 4u * p.begin.size(), p.coef.data(), 2u * p.coef.size());
+    return r;
+}
+// a checked record -> the texels of its channel map
+std::vector<uint8_t> ExpandJpegRecord(const std::string& name, const uint8_t* rec, size_t bytes, zrjp::Header& h)
+{
+    if (const char* why = zrjp::CheckRecord(rec, bytes, &h)) Throw(name + ": invalid JPEG coefficient record: " + why);
+    std::vector<uint8_t> planes(zrjp::PlaneBytes(h)), out((size_t)h.w * h.h * (h.map == (uint32_t)zrjp::kMapRgba ? 4u : 2u));
+    zrjp::DecodeRecord(rec, h, planes.data(), out.data());
+    return out;
+}
+// a .jpg image as the one-level Image of its slot: the texels of its channel map (default mode), or the record as `chain` (ZRH_LOAD_KEEP_COMPRESSED)
+Image LoadJPEG(const std::string& path, bool colour, uint32_t map, bool keep)
+{
+    const std::vector<uint8_t> d = ReadFile(path);
+    const std::vector<uint8_t> rec = JpegRecord(PackJpeg(path, d.data(), d.size(), map));
+    zrjp::Header h;
+    Image img; img.channels = colour ? 4 : 2; img.srgbFormat = colour;
+    if (keep) { if (const char* why = zrjp::CheckRecord(rec.data(), rec.size(), &h)) Throw(path + ": invalid JPEG coefficient record: " + why); img.chain = rec; }
+    else img.mip.push_back(ExpandJpegRecord(path, rec.data(), rec.size(), h));
+    img.w = h.w; img.h = h.h;
+    img.mips = 1; for (uint32_t m = h.w > h.h ? h.w : h.h; m > 1u; m >>= 1) img.mips++;
+    return img;
+}
+
 } // namespace
 
 struct zrh_scene_data
@@ -482,6 +739,7 @@ struct zrh_scene_data
     std::vector<uint16_t> rho; uint32_t rhoDim[3] = {0, 0, 0};
     std::vector<zr_texture_desc> textures; std::vector<uint8_t> texels; uint32_t texOffsets[4] = {0, 0, 0, 0};
     // ZRH_LOAD_KEEP_COMPRESSED: `texels` stays empty; texSources[i] names the chain of textures[i] in texPayload, heapBytes is the size of the heap they decode to
+    bool loadJpeg = false;      // ZRH_LOAD_JPEG
     bool keepCompressed = false; std::vector<zr_texture_source> texSources; std::vector<uint8_t> texPayload; uint64_t heapBytes = 0; zr_texture_blocks blocks{};
     std::vector<float> prevWorld; uint32_t dirtyFirst = 0xffffffffu, dirtyEnd = 0;      // per-frame maintenance (zrh_scene_data_begin_frame / _set_instance_world)
     // the instances set_instance_world named this frame, each once, with their matrices; movedSlot[i] = where instance i stands in that list
@@ -609,15 +867,19 @@ void Load(const std::string& path, zrh_scene_data& sc)
         {
             const std::string uri = g.root.At("images").arr.at(image).StrOr("uri", "");
             const bool png = EndsWith(uri, ".png");
-            if (EndsWith(uri, ".jpg") || EndsWith(uri, ".jpeg")) Throw("glTF: image '" + uri + "': JPEG images are not supported (.dds and .png are)");
-            if (!png && !EndsWith(uri, ".dds")) Throw("glTF: image '" + uri + "': only .dds and .png images are supported");
+            const bool jpeg = sc.loadJpeg && (EndsWith(uri, ".jpg") || EndsWith(uri, ".jpeg"));      // (ZRH_LOAD_JPEG; refused by name without it)
+            if (!jpeg && (EndsWith(uri, ".jpg") || EndsWith(uri, ".jpeg"))) Throw("glTF: image '" + uri + "': JPEG images are not supported (.dds and .png are)");
+            if (!png && !jpeg && !EndsWith(uri, ".dds")) Throw("glTF: image '" + uri + "': only .dds and .png images are supported");
             const bool colour = (kind == 0 || kind == 3);
             // a colour map keeps its BC7 blocks and an RG map its BC5 blocks: those decode straight to the heap's format.  Anything else (an RGBA8 file, a
             // 4-channel file in an RG slot) is decoded here as in the default mode and travels as a RAW chain.
             // A .png is level 0 alone: RGBA8 for a colour map, the file's (R, G) for a normal map and its (B, G) for a metallic-roughness map (glTF keeps
             // roughness in G and metalness in B; the reference's converter moves them to (metalness, roughness) with -swizzle bg).  Its full chain,
             // 1 + floor(log2(max(w, h))) levels, is generated by include/zr_mipgen.h: here (default mode), or on the device from a RAW_MIP0 source
-            const Image img = png ? LoadPNG(g.dir + "/" + uri, colour, kind == 2 ? 2u : 0u, 1u)
+            // A .jpg is level 0 alone too, with the same slots and chain: decoded here through include/zr_jpeg.h (default mode), or handed over as the
+            // record of its entropy-decoded coefficients (a JPEG_COEF source), which the same header turns into level 0 on the device
+            const Image img = jpeg ? LoadJPEG(g.dir + "/" + uri, colour, colour ? (uint32_t)zrjp::kMapRgba : (kind == 2 ? (uint32_t)zrjp::kMapBg : (uint32_t)zrjp::kMapRg), sc.keepCompressed)
+                            : png ? LoadPNG(g.dir + "/" + uri, colour, kind == 2 ? 2u : 0u, 1u)
                                   : LoadDDS(g.dir + "/" + uri, !sc.keepCompressed ? ZR_TEX_SRC_RAW : (colour ? ZR_TEX_SRC_BC7 : ZR_TEX_SRC_BC5));
             if (colour && img.channels != 4) Throw(uri + ": base colour / emissive maps must be 4-channel");
             zr_texture_desc td; std::memset(&td, 0, sizeof(td));
@@ -632,7 +894,7 @@ void Load(const std::string& path, zrh_scene_data& sc)
                 if (!colour && img.channels == 4) { for (size_t i = 0; i < mp.size(); i += 4) { texels.push_back(mp[i]); texels.push_back(mp[i + 1]); } }      // RGBA8 normal / MR map: keep RG
                 else texels.insert(texels.end(), mp.begin(), mp.end());
             }
-            if (png && !sc.keepCompressed)
+            if ((png || jpeg) && !sc.keepCompressed)
             {   // the other levels, from level 0 in place
                 const zr_tex_mip last = zr_tex_mip_of(&td, td.num_mips - 1u);
                 sc.texels.resize(last.offset + (size_t)last.w * last.h * (colour ? 4u : 2u));
@@ -642,7 +904,7 @@ void Load(const std::string& path, zrh_scene_data& sc)
             {
                 zr_texture_source src; std::memset(&src, 0, sizeof(src));
                 while (sc.texPayload.size() & 15) sc.texPayload.push_back(0);
-                src.offset = sc.texPayload.size(); src.encoding = png ? (uint8_t)ZR_TEX_SRC_RAW_MIP0 : img.chain.empty() ? (uint8_t)ZR_TEX_SRC_RAW : (uint8_t)(colour ? ZR_TEX_SRC_BC7 : ZR_TEX_SRC_BC5);
+                src.offset = sc.texPayload.size(); src.encoding = jpeg ? (uint8_t)ZR_TEX_SRC_JPEG_COEF : png ? (uint8_t)ZR_TEX_SRC_RAW_MIP0 : img.chain.empty() ? (uint8_t)ZR_TEX_SRC_RAW : (uint8_t)(colour ? ZR_TEX_SRC_BC7 : ZR_TEX_SRC_BC5);
                 const std::vector<uint8_t>& chain = img.chain.empty() ? raw : img.chain;
                 sc.texPayload.insert(sc.texPayload.end(), chain.begin(), chain.end());
                 const zr_tex_mip last = zr_tex_mip_of(&td, td.num_mips - 1u);
@@ -904,9 +1166,9 @@ const zr_texture_blocks* zrh_scene_data_texture_blocks(const zrh_scene_data* s) 
 int zrh_gltf_load_ex(const char* path, const uint16_t* rho, const uint32_t* rhoDim, uint32_t flags, zrh_scene_data** out)
 {
     if (!path || !out) { g_err = "null argument"; return -1; }
-    if (flags & ~(uint32_t)ZRH_LOAD_KEEP_COMPRESSED) { g_err = "zrh_gltf_load_ex: unknown flag"; return -1; }
+    if (flags & ~(uint32_t)(ZRH_LOAD_KEEP_COMPRESSED | ZRH_LOAD_JPEG)) { g_err = "zrh_gltf_load_ex: unknown flag"; return -1; }
     std::unique_ptr<zrh_scene_data> sc(new zrh_scene_data());
-    sc->keepCompressed = (flags & ZRH_LOAD_KEEP_COMPRESSED) != 0;
+    sc->keepCompressed = (flags & ZRH_LOAD_KEEP_COMPRESSED) != 0; sc->loadJpeg = (flags & ZRH_LOAD_JPEG) != 0;
     try { Load(path, *sc); }
     catch (const Error& e) { g_err = e.what; return -1; }
     catch (const std::exception& e) { g_err = std::string("glTF: malformed file (") + e.what() + ")"; return -1; }
@@ -1034,6 +1296,69 @@ int zrh_png_decode(const char* name, const uint8_t* data, size_t bytes, uint32_t
             if (capacity < png.rgba.size()) Throw(std::string(name ? name : "<memory>") + ": the output buffer is smaller than the image");
             std::memcpy(rgba8, png.rgba.data(), png.rgba.size());
         }
+    }
+    catch (const Error& e) { g_err = e.what; return -1; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+    return 0;
+}
+int zrh_jpeg_decode(const char* name, const uint8_t* data, size_t bytes, uint32_t* w, uint32_t* h, uint8_t* rgba8, size_t capacity)
+{
+    if (!data || !w || !h) { g_err = "zrh_jpeg_decode: null argument"; return -1; }
+    try
+    {
+        const std::string nm = name ? name : "<memory>";
+        const std::vector<uint8_t> rec = JpegRecord(PackJpeg(nm, data, bytes, zrjp::kMapRgba));
+        zrjp::Header hd;
+        if (!rgba8)
+        {
+            if (const char* why = zrjp::CheckRecord(rec.data(), rec.size(), &hd)) Throw(nm + ": invalid JPEG coefficient record: " + why);
+            *w = hd.w; *h = hd.h;
+            return 0;
+        }
+        const std::vector<uint8_t> px = ExpandJpegRecord(nm, rec.data(), rec.size(), hd);
+        *w = hd.w; *h = hd.h;
+        if (capacity < px.size()) Throw(nm + ": the output buffer is smaller than the image");
+        std::memcpy(rgba8, px.data(), px.size());
+    }
+    catch (const Error& e) { g_err = e.what; return -1; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+    return 0;
+}
+int zrh_jpeg_pack(const char* name, const uint8_t* data, size_t bytes, uint32_t channel_map, uint8_t* record, size_t capacity, size_t* record_bytes)
+{
+    if (!data || !record_bytes) { g_err = "zrh_jpeg_pack: null argument"; return -1; }
+    if (channel_map > (uint32_t)zrjp::kMapBg) { g_err = "zrh_jpeg_pack: unknown channel map"; return -1; }
+    try
+    {
+        const std::string nm = name ? name : "<memory>";
+        const std::vector<uint8_t> rec = JpegRecord(PackJpeg(nm, data, bytes, channel_map));
+        *record_bytes = rec.size();
+        if (record)
+        {
+            if (capacity < rec.size()) Throw(nm + ": the output buffer is smaller than the record");
+            std::memcpy(record, rec.data(), rec.size());
+        }
+    }
+    catch (const Error& e) { g_err = e.what; return -1; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+    return 0;
+}
+int zrh_jpeg_expand(const uint8_t* record, size_t bytes, uint32_t* w, uint32_t* h, uint8_t* texels, size_t capacity)
+{
+    if (!record || !w || !h) { g_err = "zrh_jpeg_expand: null argument"; return -1; }
+    try
+    {
+        zrjp::Header hd;
+        if (!texels)
+        {
+            if (const char* why = zrjp::CheckRecord(record, bytes, &hd)) Throw(std::string("zrh_jpeg_expand: invalid JPEG coefficient record: ") + why);
+            *w = hd.w; *h = hd.h;
+            return 0;
+        }
+        const std::vector<uint8_t> px = ExpandJpegRecord("zrh_jpeg_expand", record, bytes, hd);
+        *w = hd.w; *h = hd.h;
+        if (capacity < px.size()) Throw("zrh_jpeg_expand: the output buffer is smaller than the image");
+        std::memcpy(texels, px.data(), px.size());
     }
     catch (const Error& e) { g_err = e.what; return -1; }
     catch (const std::exception& e) { g_err = e.what(); return -1; }

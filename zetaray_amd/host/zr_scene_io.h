@@ -32,8 +32,12 @@ int zrh_gltf_load(const char* path, const uint16_t* rho_lut, const uint32_t* rho
 // A .png image (what stock glTF files carry; a file may mix .dds and .png) is level 0 alone: RGBA8 in a base colour / emissive slot (RGBA8_SRGB), the
 // file's (R, G) in a normal slot and its (B, G) in a metallic-roughness slot (RG8; the reference converter's -swizzle bg), with
 // num_mips = 1 + floor(log2(max(w, h))).  The default mode generates the chain here, by include/zr_mipgen.h; ZRH_LOAD_KEEP_COMPRESSED hands level 0 over
-// as a ZR_TEX_SRC_RAW_MIP0 source and the same header runs on the device.  .jpg / .jpeg images are refused: JPEG is not supported.
-enum { ZRH_LOAD_KEEP_COMPRESSED = 1u };
+// as a ZR_TEX_SRC_RAW_MIP0 source and the same header runs on the device.  .jpg / .jpeg images are refused without ZRH_LOAD_JPEG (below).
+// ZRH_LOAD_JPEG: a .jpg / .jpeg image is read wherever a .png is (without the flag it is refused by name, as before): baseline / extended sequential
+// Huffman files of 8 bits, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0 (zrh_jpeg_decode below), same slots, same chain.  The default mode decodes it here through
+// include/zr_jpeg.h; with ZRH_LOAD_KEEP_COMPRESSED only the entropy decode runs here and the record of quantised coefficients travels as a
+// ZR_TEX_SRC_JPEG_COEF source, which the same header turns into level 0 on the device.  A file may mix .dds, .png and .jpg.
+enum { ZRH_LOAD_KEEP_COMPRESSED = 1u, ZRH_LOAD_JPEG = 2u };
 int zrh_gltf_load_ex(const char* path, const uint16_t* rho_lut, const uint32_t* rho_dim3, uint32_t flags, zrh_scene_data** out);
 const zr_texture_blocks* zrh_scene_data_texture_blocks(const zrh_scene_data* s);
 const char* zrh_scene_io_last_error(void);
@@ -98,6 +102,20 @@ int zrh_bc5_decode(const uint8_t* blocks, uint32_t w, uint32_t h, uint8_t* rg8);
 // CRC-32 are the loader's own: no link dependency.  -1 with a message that starts with `name` (zrh_scene_io_last_error()) for an interlaced file, a bit
 // depth below 8, a bad CRC or Adler-32, truncated data, and dimensions outside [1, 65535].
 int zrh_png_decode(const char* name, const uint8_t* data, size_t bytes, uint32_t* w, uint32_t* h, uint8_t* rgba8, size_t capacity);
+// A JPEG file in memory -> *w x *h RGBA8 texels, rows top-down, alpha 255 (rgba8 null: the size alone; else capacity >= 4 w h bytes): the entropy decode
+// of zrh_jpeg_pack, then include/zr_jpeg.h (13-bit integer IDCT, triangle-filter chroma upsampling, 16-bit fixed-point YCbCr -> RGB) -- on files libjpeg
+// wrote, libjpeg's bytes.  Reads SOF0 / SOF1 with Huffman coding, 8 bits, 1 or 3 components (4:4:4, 4:2:2, 4:2:0; grey gives r = g = b), one scan, 8- and
+// 16-bit DQT, DRI / RSTn; APPn / COM are skipped.  -1 with a message that starts with `name` for progressive, arithmetic-coded, lossless / hierarchical,
+// 12-bit, 4-component, Adobe-RGB and multi-scan files, any other sampling, a Huffman code that is not in the table, a coefficient index past 63, a bad or
+// missing restart marker, data that ends early, and a header that promises more blocks than the bytes can hold.
+int zrh_jpeg_decode(const char* name, const uint8_t* data, size_t bytes, uint32_t* w, uint32_t* h, uint8_t* rgba8, size_t capacity);
+// The entropy decode alone: the record of include/zr_jpeg.h (what a ZR_TEX_SRC_JPEG_COEF source names) with channel_map 0 = RGBA8, 1 = RG8 from the
+// file's (R, G), 2 = RG8 from its (B, G).  record null: *record_bytes alone (a multiple of 16); else capacity >= *record_bytes.  Refuses what
+// zrh_jpeg_decode refuses.
+int zrh_jpeg_pack(const char* name, const uint8_t* data, size_t bytes, uint32_t channel_map, uint8_t* record, size_t capacity, size_t* record_bytes);
+// A record -> the w x h texels of its channel map (4 or 2 bytes each) on the host, by the header the kernels compile; the record is checked like a
+// ZR_TEX_SRC_JPEG_COEF source (zrjp::CheckRecord).  texels null: the size alone
+int zrh_jpeg_expand(const uint8_t* record, size_t bytes, uint32_t* w, uint32_t* h, uint8_t* texels, size_t capacity);
 // levels 1 .. num_mips - 1 of the n chains `descs` names in `texels`, in place, from their level 0: include/zr_mipgen.h on the host, the bytes
 // zr_mipgen_device and zr_scene_create_compressed (ZR_TEX_SRC_RAW_MIP0) produce on the device
 int zrh_mip_generate(const zr_texture_desc* descs, uint32_t n, uint8_t* texels);

@@ -149,13 +149,16 @@ class Scene:
         self._desc = None
 
     @staticmethod
-    def _chain_layout(width, height, num_mips, fmt, encoding):
-        """(w, h, source bytes, texel bytes) of each mip of a chain; a TEX_SRC_RAW_MIP0 source holds level 0 alone"""
+    def _chain_layout(width, height, num_mips, fmt, encoding, record_bytes=0):
+        """(w, h, source bytes, texel bytes) of each mip of a chain; a TEX_SRC_RAW_MIP0 source holds level 0 alone, and so does a TEX_SRC_JPEG_COEF source,
+        as a record of record_bytes bytes"""
         bpp = 2 if fmt == wire.TEX_RG8 else 4
         out = []
         for m in range(num_mips):
             w, h = max(1, width >> m), max(1, height >> m)
-            if encoding == wire.TEX_SRC_RAW_MIP0:
+            if encoding == wire.TEX_SRC_JPEG_COEF:
+                nsrc = record_bytes if m == 0 else 0
+            elif encoding == wire.TEX_SRC_RAW_MIP0:
                 nsrc = w * h * bpp if m == 0 else 0
             else:
                 nsrc = w * h * bpp if encoding == wire.TEX_SRC_RAW else ((w + 3) // 4) * ((h + 3) // 4) * 16
@@ -165,14 +168,16 @@ class Scene:
     def add_texture_blocks(self, blocks, width, height, num_mips, fmt, encoding):
         """Appends one texture from its stored chain -- BC7 / BC5 blocks (wire.TEX_SRC_BC7 needs an RGBA8 format, TEX_SRC_BC5 RG8), or uncompressed texels
         (TEX_SRC_RAW) -- mips back to back in DDS order, mip m of max(1, w >> m) x max(1, h >> m) texels -- or from its uncompressed level 0 alone
-        (TEX_SRC_RAW_MIP0: levels 1 .. num_mips - 1 are generated, include/zr_mipgen.h).  Nothing is decoded.  Returns its heap index."""
+        (TEX_SRC_RAW_MIP0: levels 1 .. num_mips - 1 are generated, include/zr_mipgen.h), or from the coefficient record of a JPEG image (TEX_SRC_JPEG_COEF,
+        pack_jpeg: level 0 is decoded by include/zr_jpeg.h, the other levels generated; an RGBA record needs an RGBA8 format, an RG record RG8).  Nothing is
+        decoded.  Returns its heap index."""
         blocks = np.ascontiguousarray(blocks, np.uint8).reshape(-1)
         if len(self.textures) != len(self.texture_sources):
             raise ValueError("the scene already holds decoded textures: a heap is either all sources or all texels")
-        if encoding not in (wire.TEX_SRC_RAW, wire.TEX_SRC_BC7, wire.TEX_SRC_BC5, wire.TEX_SRC_RAW_MIP0) or (encoding == wire.TEX_SRC_BC7 and fmt == wire.TEX_RG8) or \
+        if encoding not in (wire.TEX_SRC_RAW, wire.TEX_SRC_BC7, wire.TEX_SRC_BC5, wire.TEX_SRC_RAW_MIP0, wire.TEX_SRC_JPEG_COEF) or (encoding == wire.TEX_SRC_BC7 and fmt == wire.TEX_RG8) or \
                 (encoding == wire.TEX_SRC_BC5 and fmt != wire.TEX_RG8):
             raise ValueError("encoding %r does not decode to format %r" % (encoding, fmt))
-        layout = self._chain_layout(width, height, num_mips, fmt, encoding)
+        layout = self._chain_layout(width, height, num_mips, fmt, encoding, len(blocks))
         if num_mips < 1 or len(blocks) != sum(l[2] for l in layout):
             raise ValueError("a %d x %d chain of %d mips is %d bytes, not %d" % (width, height, num_mips, sum(l[2] for l in layout), len(blocks)))
         src = np.zeros(1, wire.TEXTURE_SOURCE)
@@ -188,7 +193,8 @@ class Scene:
 
     def decode_textures(self):
         """Fills `texels` from the sources on the host, with the loader's decoder (zrh_bc7_decode / zrh_bc5_decode) and, for TEX_SRC_RAW_MIP0 sources, its
-        mip generation (zrh_mip_generate): the heap zr_scene_create_compressed produces on the device.  The sources stay."""
+        mip generation (zrh_mip_generate); TEX_SRC_JPEG_COEF records are expanded by include/zr_jpeg.h (zrh_jpeg_expand) and their chains generated
+        likewise: the heap zr_scene_create_compressed produces on the device.  The sources stay."""
         import ctypes as C
         L = _sceneio_lib()
         for f in (L.zrh_bc7_decode, L.zrh_bc5_decode):
@@ -197,13 +203,19 @@ class Scene:
         heap = np.zeros(self.texel_heap_bytes, np.uint8)
         for t, s in zip(self.textures, self.texture_sources):
             enc, at, to = int(s["encoding"]), int(s["offset"]), int(t["offset"])
+            if enc == wire.TEX_SRC_JPEG_COEF:
+                px = jpeg_expand(self.texture_payload[at:])
+                if px.shape[:2] != (int(t["height"]), int(t["width"])) or px.shape[2] != (2 if int(t["format"]) == wire.TEX_RG8 else 4):
+                    raise ValueError("a JPEG record of shape %r does not fit its texture desc" % (px.shape,))
+                heap[to:to + px.size] = px.reshape(-1)
+                continue
             for w, h, nsrc, ndst in self._chain_layout(int(t["width"]), int(t["height"]), int(t["num_mips"]), int(t["format"]), enc):
                 if enc in (wire.TEX_SRC_RAW, wire.TEX_SRC_RAW_MIP0):
                     heap[to:to + nsrc] = self.texture_payload[at:at + nsrc]
                 else:
                     (L.zrh_bc7_decode if enc == wire.TEX_SRC_BC7 else L.zrh_bc5_decode)(self.texture_payload.ctypes.data + at, w, h, heap.ctypes.data + to)
                 at, to = at + nsrc, to + ndst
-        gen = np.ascontiguousarray(self.textures[self.texture_sources["encoding"] == wire.TEX_SRC_RAW_MIP0])
+        gen = np.ascontiguousarray(self.textures[np.isin(self.texture_sources["encoding"], (wire.TEX_SRC_RAW_MIP0, wire.TEX_SRC_JPEG_COEF))])
         if len(gen):
             mip_generate(gen, heap)
         self.texels = heap
@@ -526,6 +538,7 @@ def _sceneio_lib():
 
 
 LOAD_KEEP_COMPRESSED = 1      # ZRH_LOAD_KEEP_COMPRESSED
+LOAD_JPEG = 2      # ZRH_LOAD_JPEG
 
 
 def mip_generate(descs, texels):
@@ -559,14 +572,62 @@ def png_decode(data, name="<memory>"):
     return out
 
 
-def load_gltf_native(path, rho=None, textures="decoded"):
+def decode_jpeg(data, name="<memory>"):
+    """zrh_jpeg_decode: the bytes of a baseline JPEG file -> (h, w, 4) uint8 RGBA (alpha 255), through include/zr_jpeg.h"""
+    import ctypes as C
+    L = _sceneio_lib()
+    L.zrh_jpeg_decode.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    data = bytes(data)
+    w, h = C.c_uint32(), C.c_uint32()
+    if L.zrh_jpeg_decode(os.fsencode(name), data, len(data), C.byref(w), C.byref(h), None, 0) != 0:
+        raise RuntimeError(L.zrh_scene_io_last_error().decode())
+    out = np.zeros((h.value, w.value, 4), np.uint8)
+    if L.zrh_jpeg_decode(os.fsencode(name), data, len(data), C.byref(w), C.byref(h), out.ctypes.data, out.nbytes) != 0:
+        raise RuntimeError(L.zrh_scene_io_last_error().decode())
+    return out
+
+
+def pack_jpeg(data, name="<memory>", channel_map=wire.JPEG_MAP_RGBA):
+    """zrh_jpeg_pack: the entropy decode of a baseline JPEG file alone -> the record of include/zr_jpeg.h (uint8; what a wire.TEX_SRC_JPEG_COEF source names)"""
+    import ctypes as C
+    L = _sceneio_lib()
+    L.zrh_jpeg_pack.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+    data = bytes(data)
+    n = C.c_size_t()
+    if L.zrh_jpeg_pack(os.fsencode(name), data, len(data), channel_map, None, 0, C.byref(n)) != 0:
+        raise RuntimeError(L.zrh_scene_io_last_error().decode())
+    out = np.zeros(n.value, np.uint8)
+    if L.zrh_jpeg_pack(os.fsencode(name), data, len(data), channel_map, out.ctypes.data, out.nbytes, C.byref(n)) != 0:
+        raise RuntimeError(L.zrh_scene_io_last_error().decode())
+    return out
+
+
+def jpeg_expand(record):
+    """zrh_jpeg_expand: a record of pack_jpeg (uint8; bytes behind its end are ignored) -> (h, w, 4) or (h, w, 2) uint8, by its channel map, on the host"""
+    import ctypes as C
+    L = _sceneio_lib()
+    L.zrh_jpeg_expand.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    record = np.ascontiguousarray(record, np.uint8)
+    w, h = C.c_uint32(), C.c_uint32()
+    if L.zrh_jpeg_expand(record.ctypes.data, len(record), C.byref(w), C.byref(h), None, 0) != 0:
+        raise RuntimeError(L.zrh_scene_io_last_error().decode())
+    ch = 4 if len(record) >= 32 and int(record[28:32].view("<u4")[0]) == wire.JPEG_MAP_RGBA else 2
+    out = np.zeros((h.value, w.value, ch), np.uint8)
+    if L.zrh_jpeg_expand(record.ctypes.data, len(record), C.byref(w), C.byref(h), out.ctypes.data, out.nbytes) != 0:
+        raise RuntimeError(L.zrh_scene_io_last_error().decode())
+    return out
+
+
+def load_gltf_native(path, rho=None, textures="decoded", jpeg=False):
     """glTF -> wire formats through the C++ loader (MeshInstance quantisation by decomposeSRT of the world matrix, node hierarchies, matrix
     nodes, DDS material textures decoded to the texel heap, PNG ones with their mip chain generated by include/zr_mipgen.h).  Returns (Scene, texture-table offsets dict for set_texture_heap_offsets).
     A file with "animations" (LINEAR translation / rotation / scale channels) also gives sc.animation, a wire.AnimDesc over the dynamic closure of
     its node hierarchy (Scene.set_animation / Scene.animate in api.py), and sc.emissives_initial, the object-space light records; None without.
     textures="compressed": the .dds payloads are not decoded (ZRH_LOAD_KEEP_COMPRESSED): sc.texels stays empty, sc.texture_sources / sc.texture_payload
     carry the blocks and api.Scene decodes them on the device (zr_scene_create_compressed); sc.decode_textures() makes the texels on the host.
-    A .png image travels as its level 0 (wire.TEX_SRC_RAW_MIP0) and its other levels are generated on the device."""
+    A .png image travels as its level 0 (wire.TEX_SRC_RAW_MIP0) and its other levels are generated on the device.
+    jpeg=True (ZRH_LOAD_JPEG): .jpg / .jpeg images are read wherever a .png is (refused by name without it): decoded on the host through include/zr_jpeg.h, or
+    with textures="compressed" entropy-decoded only and handed over as wire.TEX_SRC_JPEG_COEF records, which the same header turns into level 0 on the device."""
     import ctypes as C
     if textures not in ("decoded", "compressed"):
         raise ValueError("textures must be 'decoded' or 'compressed', not %r" % (textures,))
@@ -575,7 +636,7 @@ def load_gltf_native(path, rho=None, textures="decoded"):
     rho_data = np.ascontiguousarray(rho_data, np.uint16)
     dims = (C.c_uint32 * 3)(*rho_dim)
     h = C.c_void_p()
-    if L.zrh_gltf_load_ex(os.fsencode(path), rho_data.ctypes.data, dims, LOAD_KEEP_COMPRESSED if textures == "compressed" else 0, C.byref(h)) != 0:
+    if L.zrh_gltf_load_ex(os.fsencode(path), rho_data.ctypes.data, dims, (LOAD_KEEP_COMPRESSED if textures == "compressed" else 0) | (LOAD_JPEG if jpeg else 0), C.byref(h)) != 0:
         raise RuntimeError(L.zrh_scene_io_last_error().decode())
     try:
         d = L.zrh_scene_data_desc(h).contents

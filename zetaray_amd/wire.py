@@ -69,6 +69,8 @@ TEXTURE_DESC = np.dtype([("offset", "<u8"), ("width", "<u2"), ("height", "<u2"),
 # block-compressed texture sources (zr_texture_source / zr_texture_blocks, include/zetaray_amd.h; the decode is include/zr_bcn.h)
 TEX_SRC_RAW, TEX_SRC_BC7, TEX_SRC_BC5 = 0, 1, 2
 TEX_SRC_RAW_MIP0 = 8      # level 0 alone, uncompressed: the other levels are generated (include/zr_mipgen.h)
+TEX_SRC_JPEG_COEF = 16      # level 0 alone, as the record of a JPEG image's entropy-decoded coefficients (include/zr_jpeg.h; scene_io.pack_jpeg)
+JPEG_MAP_RGBA, JPEG_MAP_RG, JPEG_MAP_BG = 0, 1, 2      # the record's channel map: RGBA8, or RG8 from the file's (R, G) / (B, G)
 TEXTURE_SOURCE = np.dtype([("offset", "<u8"), ("encoding", "u1"), ("pad", "u1", 7)])
 # keyframe animation (zr_keyframe / zr_anim_node / zr_anim_desc, include/zr_wire.h)
 ANIM_ROOT = 0xFFFFFFFF
