@@ -437,6 +437,40 @@ int zr_scene_move_instances(zr_scene* scene, const uint32_t* instance_idx, const
 int zr_scene_set_animation(zr_scene* scene, const zr_anim_desc* desc);
 int zr_scene_animate_async(zr_scene* scene, void* hip_stream, float t);
 int zr_scene_animate(zr_scene* scene, float t);
+/* Deformed geometry.  zr_scene_update_vertices_async (the host form, and the entry point of a caller that deforms geometry itself) replaces vertices
+ * [first, first + count) through the staging ring, refreshes their entries of the hit tables (zr_hit_tables.h) with the kernel that filled them, and
+ * is ordered as a write of the scene like the other updates.  The ACCELERATION STRUCTURE FOLLOWS WITH THE FRAME'S INSTANCE UPDATE, of any form
+ * (zr_scene_update_instances, zr_scene_move_instances with n_moved == 0 included, zr_scene_animate): every such update refits from the vertex buffer.
+ * A render between the two traces the old triangles and shades them with the new attributes.  Emissive records are not touched: a deformed light keeps
+ * shining from its rest pose.  The host's copy of the vertices follows (once a background build in flight, which reads it, is done: no call waits).
+ * A range that a skin set covers is rewritten by the next zr_scene_animate from the set's rest records: what this call put there does not last.
+ * Refused, with nothing changed: a range past the scene's vertices, a null pointer with count > 0 (ZR_ERR_INVALID_ARG); ZR_SCENE_UPDATE=rebuild /
+ * rebuild_host (ZR_ERR_UNSUPPORTED).  zr_scene_update_vertices = _async on the null stream, then wait.  zr_scene_get_vertices reads the device's
+ * vertices back after waiting for `hip_stream`, for tests and tools.
+ *
+ * Skinned meshes.  zr_scene_set_skinning (a host call, after zr_scene_set_animation) takes a zr_skin_desc (zr_wire.h): joints that name nodes of the
+ * animation's table with their inverse bind matrices, vertex ranges, four (joint, weight) influences per vertex.  It uploads the tables once and keeps
+ * the rest-pose records of the listed ranges -- the vertices as they are at the call, or as the set it replaces found them -- in a device buffer of its
+ * own.  It replaces an earlier set; a null or empty desc clears the set and puts the rest pose back (vertex buffer and hit tables; the acceleration
+ * structure follows with the next instance update, as above).  zr_scene_set_animation on a scene with a skin set clears the skin the same way.
+ * There is no new per-frame call: with a set, zr_scene_animate_async(scene, stream, t) also runs the joint and the vertex kernel (zr_tu_skin.hip, the
+ * arithmetic of include/zr_skin.h) between the node matrices and the move / refit tail.  In every device byte -- vertex buffer, both hit tables, both
+ * instance buffers, object-to-world matrices, emissive records, BVH triangles and nodes, the role swap, the ordering against renders on other streams --
+ * it equals the host sequence
+ *   1. zrh_scene_data_animate(t),
+ *   2. zr_scene_update_vertices_async with the vertices include/zr_skin.h computes on the host from the node matrices of time t,
+ *   3. the host-form emissive and instance updates.
+ * The host's copy of the vertices keeps the rest pose: only the background SAH builder reads it, and topology is all it delivers -- the refit of the
+ * installing update makes the boxes from the device's vertices.  Caller guarantees: det > 0 for the upper 3 x 3 of every blended matrix (else the
+ * normal's code words are unspecified; nothing is written out of bounds).  The byte equivalence holds for the contract build, not for -DZR_ARITH_FAST.
+ * zr_scene_set_skinning refuses, with nothing changed: no animation set (ZR_ERR_NOT_INITIALIZED); a joint node >= the animation's num_nodes, a joint
+ * index >= the joint count, more than 65 535 joints, ranges that overlap or reach past the scene's vertices or past the influence table, a weight or a
+ * matrix entry that is not finite (ZR_ERR_INVALID_ARG). */
+int zr_scene_update_vertices_async(zr_scene* scene, void* hip_stream, uint32_t first, uint32_t count, const zr_vertex* vertices);
+int zr_scene_update_vertices(zr_scene* scene, uint32_t first, uint32_t count, const zr_vertex* vertices);
+int zr_scene_get_vertices(const zr_scene* scene, void* hip_stream, zr_vertex* out, uint32_t first, uint32_t count);
+int zr_scene_set_skinning(zr_scene* scene, const zr_skin_desc* desc);
+int zr_scene_has_skinning(const zr_scene* scene);      /* 1 while a skin set is in place (zr_scene_set_skinning succeeded and nothing has cleared it), else 0 */
 /* Read-backs for tests and tools, after waiting for `hip_stream` (pass the stream of the last update).  which: 0 = the current instance buffer,
  * 1 = the previous one (the current one while the scene has never been updated); to_world_or_null: n x 12 floats. */
 int zr_scene_get_instances(const zr_scene* scene, void* hip_stream, int which, zr_mesh_instance* out, float* to_world_or_null, uint32_t n);

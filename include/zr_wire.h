@@ -280,6 +280,37 @@ static_assert(sizeof(zr_keyframe) == 44, "zr_keyframe");
 static_assert(sizeof(zr_anim_node) == 108, "zr_anim_node");
 #endif
 
+/*
+ * Skinned meshes (zr_scene_set_skinning, zetaray_amd.h; the arithmetic is include/zr_skin.h).  zr_skin_joint: `node` indexes the node table of the
+ * zr_anim_desc the scene holds, inverse_bind is 3 x 4 row-major like instance_to_world.  zr_skin_influence: the four joints of a vertex (indices into
+ * the desc's joint table; a slot with weight 0 may name any valid joint) and their weights.  zr_skin_range: vertices [first_vertex, first_vertex +
+ * num_vertices) of the scene are posed, vertex first_vertex + k by influences[first_influence + k].  Ranges do not overlap; influence ranges may.
+ */
+typedef struct zr_skin_joint {
+    uint32_t node;
+    float    inverse_bind[12];
+} zr_skin_joint;
+typedef struct zr_skin_influence {
+    uint16_t joint[4];
+    float    weight[4];
+} zr_skin_influence;
+typedef struct zr_skin_range {
+    uint32_t first_vertex;
+    uint32_t num_vertices;
+    uint32_t first_influence;
+} zr_skin_range;
+typedef struct zr_skin_desc {
+    const zr_skin_joint*     joints;      uint32_t num_joints;
+    const zr_skin_range*     ranges;      uint32_t num_ranges;
+    const zr_skin_influence* influences;  uint32_t num_influences;
+} zr_skin_desc;
+#ifdef __cplusplus
+static_assert(sizeof(zr_skin_joint) == 52, "zr_skin_joint");
+static_assert(sizeof(zr_skin_influence) == 24, "zr_skin_influence");
+static_assert(sizeof(zr_skin_range) == 12, "zr_skin_range");
+static_assert(sizeof(zr_skin_desc) == 48, "zr_skin_desc");
+#endif
+
 #ifdef __cplusplus
 }
 #endif

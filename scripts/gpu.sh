@@ -14,6 +14,7 @@
 #   texdecode [ARGS]   tools/texture_decode_bench.py: scene creation with host-decoded texels against zr_scene_create_compressed -> ${TAG}_texture_decode.json
 #   mipgen [ARGS]      tools/mipgen_bench.py: zr_scene_create_compressed with full RAW chains against RAW_MIP0 sources (mips generated on the device) -> ${TAG}_mipgen.json
 #   jpeg [ARGS]        tools/jpeg_decode_bench.py: JPEG files decoded on the host and uploaded as RAW_MIP0 against their coefficient records decoded on the device (JPEG_COEF) -> ${TAG}_jpeg_decode.json
+#   skin [ARGS]        tools/refit_bench.py --skin: a skinned tube posed by the host form against zr_scene_animate with the skin set -> ${TAG}_scene_skin.json
 #   prof LIB           section profiler (-DZR_PROF build LIB) on Cornell + atrium -> ${TAG}_section_profile_*.json
 R=${GRAFT_REPO_ROOT:-$PWD}; TAG=${TAG:-r06}; OUT=$R/gpurun_out; mkdir -p $OUT
 task=$1; shift
@@ -117,6 +118,10 @@ mipgen)
 jpeg)
   cd $R; set -o pipefail
   timeout 1100 python tools/jpeg_decode_bench.py "$@" 2> $OUT/${TAG}_jpeg_err.log | tail -1 | tee $OUT/${TAG}_jpeg_decode.json || { echo "jpeg_decode_bench: requirement missed or failed"; tail -5 $OUT/${TAG}_jpeg_err.log; exit 1; }
+  ;;
+skin)
+  cd $R; set -o pipefail
+  timeout 1100 python tools/refit_bench.py --skin "$@" 2> $OUT/${TAG}_skin_err.log | tail -1 | tee $OUT/${TAG}_scene_skin.json || { echo "refit_bench --skin: requirement missed or failed"; tail -5 $OUT/${TAG}_skin_err.log; exit 1; }
   ;;
 *) echo "unknown task $task"; exit 2;;
 esac

@@ -13,7 +13,13 @@ carries one static clutter instance that brings it to the larger one's triangle 
 launch per level costs either size the same host time).  (A) the C++ mirror samples on the host (zrh_scene_data_begin_frame + zrh_scene_data_animate)
 and hands the moved list to zr_scene_move_instances_async; (B) zr_scene_animate_async.  Host wall time of the update and stream time between two events,
 median and p10 / p90 of --frames frames after --warmup; one JSON line with the device probes.  Exit status 1 when (B)'s host time at 16 N exceeds that
-at N by more than the smaller run's p10 - p90 spread, or (B)'s stream time is longer than (A)'s at either size."""
+at N by more than the smaller run's p10 - p90 spread, or (B)'s stream time is longer than (A)'s at either size.
+
+--skin: one skinned tube of N vertices over 64 joints, all animated (--vertices N and 16 N; the smaller scene carries one static clutter instance that
+brings it to the larger one's triangle count, as under --animate).  (A) the host form: zrh_skin_pose on the host, zr_scene_update_vertices_async, then
+the host-form instance update; (B) zr_scene_animate_async with the skin set; (C) the same animation without a skin, whose stream time taken from (B)'s
+leaves the two skin kernels' own, reported next to the bytes they must move (28 + 24 in, 28 + 16 out per vertex).  Same statistics, same JSON line,
+exit status 1 under the same two conditions on (B), or when the twin scenes' vertex buffers differ."""
 import json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -264,17 +270,147 @@ def animate(n_small, frames, warmup):
     return 0 if ok else 1
 
 
+def _tube_scene(n_verts, clutter_tris, segs=64):
+    """one instance: a tube of n_verts vertices (segs per ring) up the y axis, identity world matrix (+ one static instance of clutter_tris small triangles)"""
+    rng = np.random.default_rng(5)
+    rings = n_verts // segs
+    assert rings * segs == n_verts and rings >= 2
+    ring, seg = np.divmod(np.arange(n_verts), segs)
+    a = 2 * np.pi * seg / segs
+    v = np.zeros(n_verts + 3 * clutter_tris, wire.VERTEX)
+    v["pos"][:n_verts] = np.stack([0.2 * np.cos(a), 4.0 * ring / (rings - 1) - 2.0, 0.2 * np.sin(a)], 1).astype(np.float32)
+    nrm = np.tile(np.float32([0, 1, 0]), (len(v), 1))
+    nrm[:n_verts] = np.stack([np.cos(a), np.zeros(n_verts), np.sin(a)], 1)
+    v["normal"] = scene_io.encode_octahedral(nrm, sse_order=False)
+    v["tangent"] = scene_io.encode_octahedral(np.tile(np.float32([0, 1, 0]), (len(v), 1)), sse_order=False)
+    p = (ring[:-segs] * segs + seg[:-segs]).astype(np.uint32)
+    q = (ring[:-segs] * segs + (seg[:-segs] + 1) % segs).astype(np.uint32)
+    idx = [np.stack([p, q, p + segs, q, q + segs, p + segs], 1).reshape(-1).astype(np.uint32)]
+    if clutter_tris:
+        c = rng.uniform(-3, 3, (clutter_tris, 1, 3)).astype(np.float32) + np.float32([6, 0, 0])
+        v["pos"][n_verts:] = (c + rng.uniform(-0.01, 0.01, (clutter_tris, 3, 3)).astype(np.float32)).reshape(-1, 3)
+        idx.append(np.arange(3 * clutter_tris, dtype=np.uint32))
+    sc = scene_io.Scene()
+    sc.materials = np.array([scene_io.pack_material(base_color=(0.7, 0.6, 0.5, 1), roughness=0.6, double_sided=True)], wire.MATERIAL)
+    sc.vertices, sc.indices = v, np.concatenate(idx)
+    n = 2 if clutter_tris else 1
+    inst = np.zeros(n, wire.MESH_INSTANCE)
+    inst["rotation"] = inst["prev_rotation"] = np.rint((np.array([0, 0, 0, 1], np.float32) * np.float32(0.5) + np.float32(0.5)) * np.float32(65535.0)).astype(np.uint16)
+    inst["scale"] = inst["prev_scale"] = scene_io.f32_to_f16_bits([1, 1, 1])
+    inst["base_emissive_tri_offset"], inst["base_color_tex"], inst["alpha_factor_cutoff"] = 0xFFFFFFFF, 0xFFFF, 255 | (128 << 8)
+    ntris = np.uint32([len(idx[0]) // 3] + ([clutter_tris] if clutter_tris else []))
+    if clutter_tris:
+        inst["base_vtx_offset"][1], inst["base_idx_offset"][1] = n_verts, len(idx[0])
+    sc.instances, sc.instance_to_world, sc.instance_num_tris = inst, np.tile(np.float32([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]), (n, 1)), ntris
+    sc.instance_mask = np.full(n, wire.SUBGROUP_NON_EMISSIVE, np.uint8)
+    sc.emissives = np.zeros(0, wire.EMISSIVE_TRI)
+    sc.rho, sc.rho_dim = scene_io.load_rho_default()
+    return sc
+
+
+def _tube_skin(sc, n_verts, nj=64):
+    """nj joints up the tube, each a root node of its own with three keys (a small turn about z, a translation); a vertex hangs on the four joints around
+    its height.  Inverse bind matrices: the joints' translations at rest, negated"""
+    rng = np.random.default_rng(6)
+    nodes, keys = np.zeros(nj, wire.ANIM_NODE), np.zeros(3 * nj, wire.KEYFRAME)
+    jy = (4.0 * (np.arange(nj) + 0.5) / nj - 2.0).astype(np.float32)
+    nodes["parent"], nodes["first_key"], nodes["num_keys"], nodes["loop"] = wire.ANIM_ROOT, 3 * np.arange(nj), 3, 1
+    nodes["rest_scale"], nodes["rest_rotation"], nodes["parent_world"] = 1, (0, 0, 0, 1), np.float32([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0])
+    nodes["rest_translation"][:, 1] = jy
+    ang = rng.uniform(-0.2, 0.2, 3 * nj)
+    keys["rotation"] = np.stack([np.zeros(3 * nj), np.zeros(3 * nj), np.sin(ang / 2), np.cos(ang / 2)], 1)
+    keys["scale"], keys["time"] = 1, np.tile(np.float32([0.0, 0.5, 1.0]), nj)
+    keys["translation"][:, 1] = np.repeat(jy, 3)
+    keys["translation"][:, 0] = rng.uniform(-0.05, 0.05, 3 * nj)
+    anim = wire.AnimDesc(nodes, keys, [], [])
+    joints = np.zeros(nj, wire.SKIN_JOINT)
+    joints["node"], joints["inverse_bind"] = np.arange(nj), np.float32([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0])
+    joints["inverse_bind"][:, 7] = -jy
+    h = (sc.vertices["pos"][:n_verts, 1].astype(np.float64) + 2.0) / 4.0 * nj - 0.5
+    j0 = np.clip(np.floor(h), 0, nj - 1).astype(np.int64)
+    fr = np.clip(h - j0, 0, 1)
+    f = np.zeros(n_verts, wire.SKIN_INFLUENCE)
+    f["joint"] = np.stack([j0, np.minimum(j0 + 1, nj - 1), np.maximum(j0 - 1, 0), np.minimum(j0 + 2, nj - 1)], 1)
+    w = np.stack([1 - fr, fr, np.full(n_verts, 0.05), np.full(n_verts, 0.05)], 1).astype(np.float32)
+    f["weight"] = w / w.sum(1, dtype=np.float32, keepdims=True)
+    return anim, wire.SkinDesc(joints, np.array([(0, n_verts, 0)], wire.SKIN_RANGE), f)
+
+
+def skin(n_small, frames, warmup):
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import bench
+    out = {"mode": "skin", "frames": frames, "warmup": warmup, "library": os.path.basename(api.LIB_PATH), "device_state": bench.device_state(api, 0), "joints": 64, "sizes": []}
+    n_large, raw = 16 * n_small, {}
+    for nv in (n_small, n_large):
+        sc = _tube_scene(nv, 2 * (n_large - nv))
+        anim, sk = _tube_skin(sc, nv)
+        rest = sc.vertices[:nv].copy()
+        A, B, Cn = api.Scene(sc), api.Scene(sc), api.Scene(sc)
+        B.set_animation(anim); B.set_skinning(sk)
+        Cn.set_animation(anim)
+        st = torch.cuda.Stream()
+
+        def host_form(t):
+            A.update_vertices(0, scene_io.skin_pose(anim, sk, rest, t), stream=st.cuda_stream)
+            A.update_instances(sc.instances, sc.instance_to_world, stream=st.cuda_stream)
+
+        def device_form(t):
+            B.animate(t, stream=st.cuda_stream)
+
+        def without_skin(t):
+            Cn.animate(t, stream=st.cuda_stream)
+
+        res = {"skinned_vertices": nv, "num_tris": int(sc.num_tris), "bvh": list(A.bvh_info())}
+        for name, fn in (("A_host_form", host_form), ("B_scene_animate", device_form), ("C_animate_without_skin", without_skin)):
+            wall, stream_ms = [], []
+            for k in range(1, warmup + frames + 1):
+                t = 0.013 * k
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record(st)
+                a = time.perf_counter()
+                fn(t)
+                b = time.perf_counter()
+                e1.record(st)
+                torch.cuda.synchronize()
+                if k > warmup:
+                    wall.append((b - a) * 1e3); stream_ms.append(e0.elapsed_time(e1))
+            res[name] = {"host_wall_ms": _stats(wall), "stream_ms": _stats(stream_ms)}
+            raw[(nv, name)] = (np.asarray(wall, np.float64), np.asarray(stream_ms, np.float64))
+        res["same_device_bytes"] = bool(A.download_vertices().tobytes() == B.download_vertices().tobytes())
+        kern_ms = res["B_scene_animate"]["stream_ms"]["median"] - res["C_animate_without_skin"]["stream_ms"]["median"]
+        moved = nv * (28 + 24 + 28 + 16) + 64 * (4 + 48 + 48 + 48)
+        res["skin_kernels_stream_ms"] = round(kern_ms, 4)
+        res["skin_kernels_bytes"] = int(moved)
+        res["skin_kernels_gb_per_s"] = round(moved / (kern_ms * 1e-3) / 1e9, 1) if kern_ms > 0 else None
+        res["host_wall_ratio_A_over_B"] = round(res["A_host_form"]["host_wall_ms"]["median"] / res["B_scene_animate"]["host_wall_ms"]["median"], 2)
+        out["sizes"].append(res)
+        A.close(); B.close(); Cn.close()
+    small, large = raw[(n_small, "B_scene_animate")][0], raw[(n_large, "B_scene_animate")][0]
+    growth, spread = float(np.median(large) - np.median(small)), float(np.percentile(small, 90) - np.percentile(small, 10))
+    out["B_host_wall_growth_ms"], out["small_p10_p90_spread_ms"], out["B_host_wall_flat"] = growth, spread, bool(growth <= spread)
+    out["B_stream_not_longer_than_A"] = [bool(np.median(raw[(nv, "B_scene_animate")][1]) <= np.median(raw[(nv, "A_host_form")][1])) for nv in (n_small, n_large)]
+    ok = out["B_host_wall_flat"] and all(out["B_stream_not_longer_than_A"]) and all(r["same_device_bytes"] for r in out["sizes"])
+    print(json.dumps(out))
+    return 0 if ok else 1
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--device-records", action="store_true")
     ap.add_argument("--animate", action="store_true")
+    ap.add_argument("--skin", action="store_true")
+    ap.add_argument("--vertices", type=int, default=65536)
     ap.add_argument("--instances", type=int, default=4096)
     ap.add_argument("--emissive", type=int, default=100000)
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=16)
     a = ap.parse_args()
-    if a.animate:
+    if a.skin:
+        sys.exit(skin(a.vertices, max(a.frames, 64), max(a.warmup, 16)))
+    elif a.animate:
         sys.exit(animate(a.instances, max(a.frames, 64), max(a.warmup, 16)))
     elif a.device_records:
         sys.exit(device_records(a.emissive, max(a.frames, 64), max(a.warmup, 16)))

@@ -64,6 +64,7 @@ EXPORTS = [
     "zr_pass_set_rgi_spatial",
     "zr_scene_set_object_emissives", "zr_scene_has_object_emissives", "zr_scene_move_instances", "zr_scene_move_instances_async", "zr_scene_get_instances", "zr_scene_get_emissives",
     "zr_scene_set_animation", "zr_scene_animate", "zr_scene_animate_async",
+    "zr_scene_update_vertices", "zr_scene_update_vertices_async", "zr_scene_get_vertices", "zr_scene_set_skinning", "zr_scene_has_skinning",
     "zr_scene_set_alias_build", "zr_alias_table_build_device", "zr_pass_get_emissive_powers",
     "zr_scene_create_compressed", "zr_bcn_decode_device", "zr_scene_get_texels", "zr_mipgen_device", "zr_jpeg_decode_device",
 ]
@@ -124,6 +125,7 @@ def lib():
         L.zr_scene_get_light_voxel_grid.argtypes = [vp, vp, vp, u32]
         L.zr_scene_get_presampled_sets.argtypes = [vp, vp, vp, u32]
         L.zr_scene_bvh_info.argtypes = [vp, vp, vp, vp]
+        L.zr_scene_has_skinning.argtypes = [vp]
         L.zr_gbuffer_create.argtypes = [i32, u32, u32, vp]
         L.zr_gbuffer_destroy.argtypes = [vp]
         L.zr_gbuffer_set_tile_origin.argtypes = [vp, u32, u32]
@@ -327,11 +329,11 @@ class Scene:
         L.zr_scene_set_animation.argtypes = [C.c_void_p, C.c_void_p]
         if desc is None:
             _check(L.zr_scene_set_animation(self.h, None))
-            self._anim = None
+            self._anim = self._skin = None      # (a skin goes with the animation it was set on)
             return
         d = desc.c_desc()
         _check(L.zr_scene_set_animation(self.h, C.addressof(d)))
-        self._anim = desc
+        self._anim, self._skin = desc, None
 
     def animate(self, t, stream=False):
         """the frame's scene update from the time alone (zr_scene_animate): the animation is sampled, composed down the hierarchy and applied on the
@@ -346,6 +348,47 @@ class Scene:
         self.version += 1
         anim = getattr(self, "_anim", None)
         self.instances_in_motion = anim is not None and len(anim.instance_idx) > 0
+
+    def update_vertices(self, first, vertices, stream=False):
+        """vertices [first, first + len(vertices)) replaced (zr_scene_update_vertices; wire.VERTEX records): the hit tables follow at once, the acceleration
+        structure with the frame's instance update of any form.  A range a skin set covers is rewritten by the next animate().  stream as update_instances"""
+        L = lib()
+        v = np.ascontiguousarray(vertices, wire.VERTEX).reshape(-1)
+        vp = v.ctypes.data if len(v) else None
+        if stream is False:
+            L.zr_scene_update_vertices.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            _check(L.zr_scene_update_vertices(self.h, int(first), len(v), vp))
+        else:
+            L.zr_scene_update_vertices_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            _check(L.zr_scene_update_vertices_async(self.h, stream, int(first), len(v), vp))
+        self.version += 1
+
+    def download_vertices(self, first=0, count=None, stream=None):
+        """the vertices [first, first + count) as the device holds them (count None: to the end)"""
+        L = lib()
+        if count is None:
+            count = len(self.host.vertices) - first
+        out = np.zeros(count, wire.VERTEX)
+        L.zr_scene_get_vertices.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        _check(L.zr_scene_get_vertices(self.h, stream, out.ctypes.data, int(first), count))
+        return out
+
+    def set_skinning(self, desc):
+        """skinned meshes (zr_scene_set_skinning): a wire.SkinDesc -- joints on nodes of the animation set before, vertex ranges, four influences per vertex --
+        uploaded once; every animate() then poses the ranges on the device.  None (or an empty one) clears and puts the rest pose back"""
+        L = lib()
+        L.zr_scene_set_skinning.argtypes = [C.c_void_p, C.c_void_p]
+        if desc is None:
+            _check(L.zr_scene_set_skinning(self.h, None))
+        else:
+            d = desc.c_desc()
+            _check(L.zr_scene_set_skinning(self.h, C.addressof(d)))
+        self._skin = desc
+        self.version += 1
+
+    def has_skinning(self):
+        """is a skin set in place (zr_scene_has_skinning)?"""
+        return bool(lib().zr_scene_has_skinning(self.h))
 
     def download_instances(self, which=0, stream=None):
         """(MeshInstance records, (n, 12) object-to-world matrices) as the device holds them; which: 0 current, 1 previous"""
@@ -840,6 +883,10 @@ class Renderer:
     def set_animation(self, desc):
         """keyframe animation of instances (Scene.set_animation)"""
         self.scene.set_animation(desc)
+
+    def set_skinning(self, desc):
+        """skinned meshes (Scene.set_skinning), after set_animation"""
+        self.scene.set_skinning(desc)
 
     def animate(self, t, stream=False):
         """the frame's scene update from the time alone (Scene.animate)"""

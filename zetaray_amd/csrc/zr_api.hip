@@ -86,6 +86,10 @@ namespace zr { hipError_t LaunchMoveInstances(hipStream_t st, zr_mesh_instance* 
     const uint32_t* moved, uint32_t nMoved, zr_emissive_triangle* emissives, const zr_emissive_triangle* object, const uint32_t* owner, uint32_t emFirst, uint32_t emEnd); }   // zr_tu_scene_update.hip
 namespace zr { hipError_t LaunchAnimate(hipStream_t st, float t, const zr_anim_node* nodes, const zr_keyframe* keys, const uint32_t* animated, uint32_t nAnimated,
     const uint32_t* levelNodes, const uint32_t* levelOffsets, uint32_t numLevels, float* nodeLocal, float* nodeWorld, const uint32_t* instNode, uint32_t nInst, uint32_t* moved); }   // zr_tu_anim.hip
+#include "../../include/zr_skin.h"
+namespace zr { using SkinRange = zrsk::DeviceRange;      // zr_tu_skin.hip
+    hipError_t LaunchSkin(hipStream_t st, float* J, const float* nodeWorld, const uint32_t* jointNode, const float* inverseBind, uint32_t numJoints, const SkinRange* ranges,
+        uint32_t numRanges, const zr_vertex* rest, const zr_skin_influence* influences, zr_vertex* vertices, VtxDir* vtxNormals, VtxDir* vtxTangents); }
 namespace zr { hipError_t LaunchFillInstRecs(hipStream_t st, InstRec* recs, const zr_mesh_instance* instances, uint32_t n);      // zr_tu_scene_update.hip
                hipError_t LaunchFillVtxNormals(hipStream_t st, VtxDir* out, const zr_vertex* vertices, uint32_t n, bool tangent); }
 namespace zr { size_t AliasScratchWords(uint32_t n);      // zr_tu_alias.hip
@@ -660,6 +664,19 @@ struct zr_scene
         float lastT = 0; bool hasT = false, hostStale = false;
     };
     std::unique_ptr<Anim> anim; std::mutex animMtx;
+    // ---- skinned meshes (zr_scene_set_skinning; kernels in zr_tu_skin.hip, arithmetic in include/zr_skin.h): with a set, every zr_scene_animate also poses
+    // the listed vertex ranges from their rest records.  What set_skinning lays out once: the joints' nodes and inverse bind matrices as two arrays (48-byte
+    // matrices: 16-byte rows), the influences, the rest records of the ranges, range after range, in a buffer of the set's own, and the joint matrices
+    // the frame's first kernel writes.  ranges / hRest: the host's copies (hRest in the device layout); a clear puts hRest back.  hVertices keeps the rest pose (only the background builder reads it: topology)
+    struct Skin
+    {
+        std::vector<zr::SkinRange> ranges; std::vector<zr_vertex> hRest; uint32_t numJoints = 0;
+        DevBuf<uint32_t> dJointNode; DevBuf<float> dInverseBind, dJ; DevBuf<zr_skin_influence> dInfluences; DevBuf<zr_vertex> dRest;
+    };
+    std::unique_ptr<Skin> skin;
+    // zr_scene_update_vertices while a background build reads hVertices: the ranges wait here and reach hVertices once the builder's thread is done
+    // (SceneFlushVertexCopies) -- the builder delivers topology, so the pose it saw does not matter, and the call does not wait for it
+    std::vector<std::pair<uint32_t, std::vector<zr_vertex>>> hVertexPending;
     ~zr_scene()
     {
         if (bg.th.joinable()) bg.th.join();
@@ -1837,6 +1854,12 @@ static RefitFrame RefitFrameOf(const zr_scene* s, const FrameUpdate& u)
     F.takesSlot = F.stageBytes || u.form != UpdateForm::Animated;
     return F;
 }
+// the vertex ranges zr_scene_update_vertices held back while a build was reading hVertices, in call order (the caller knows no build is running)
+static void SceneFlushVertexCopies(zr_scene* s)
+{
+    for (const auto& p : s->hVertexPending) std::copy(p.second.begin(), p.second.end(), s->hVertices.begin() + p.first);
+    s->hVertexPending.clear();
+}
 // background SAH rebuild: is a finished tree waiting to be installed by this update?  Its thread is joined either way; a tree that cannot be used
 // (the scene changed shape under it, or it is too deep for the traversal stack) is dropped
 static bool BgJoinFinished(zr_scene* s)
@@ -1919,6 +1942,16 @@ static int RefitWriteRecords(zr_scene* s, hipStream_t st, const FrameUpdate& u, 
             HIP_TRY(zr::LaunchAnimate(st, u.t, A.dNodes.p, A.dKeys.p, A.dAnimated.p, A.nAnimated, A.dLevelNodes.p, A.levelOffsets.data(),
                 (uint32_t)A.levelOffsets.size() - 1, A.dLocal.p, A.dWorld.p, A.dInstNode.p, u.nMoved, A.dMoved.p));
             movedList = A.dMoved.p;
+            if (s->skin)
+            {   // the node matrices are on the device: joint matrices, then the listed vertices and their hit-table entries, ahead of the refit that reads them
+                zr_scene::Skin& K = *s->skin;
+                VtxDir* tangents = nullptr;
+#if ZR_HIT_TANGENTS
+                tangents = s->vtxTangents.p;
+#endif
+                HIP_TRY(zr::LaunchSkin(st, K.dJ.p, A.dWorld.p, K.dJointNode.p, K.dInverseBind.p, K.numJoints, K.ranges.data(), (uint32_t)K.ranges.size(), K.dRest.p,
+                    K.dInfluences.p, s->vertices.p, s->vtxNormals.p, tangents));
+            }
         }
         else if (u.nMoved) HIP_TRY(hipMemcpyAsync(s->movedDev.p, h + F.seedBytes, F.listBytes, hipMemcpyHostToDevice, st));
         HIP_TRY(zr::LaunchMoveInstances(st, s->cur.instances.p, s->prev.instances.p, s->toWorld.p, F.n, s->movedSlot.p, movedList, u.nMoved,
@@ -2012,6 +2045,7 @@ static void BgStartBuild(zr_scene* s)
     if (!B.enabled || B.state.load(std::memory_order_acquire) != 0 || B.refitsSince < 1 || !B.movedSinceBuild || s->cur.meta.n <= BvhBuilder::kTinyScene) return;
     B.movedSinceBuild = false;
     if (B.th.joinable()) B.th.join();
+    SceneFlushVertexCopies(s);
     SceneAnimSyncHost(s);
     B.inst = s->hInstances; B.xf = s->hToWorld;
     { const char* e = ZR_EXP_ENV("ZR_BVH_GROUP"); if (e && !std::strcmp(e, "0")) B.own.clear(); else B.own = s->movedEver; }
@@ -2197,12 +2231,14 @@ int zr_scene_move_instances_async(zr_scene* s, void* stream, const uint32_t* ins
     return SceneRefitUpdate(s, (hipStream_t)stream, u);
 }
 // ---- keyframe animation: the tables once (zr_scene_set_animation), then one float per frame (zr_scene_animate_async)
+static int SceneClearSkin(zr_scene* s);
 int zr_scene_set_animation(zr_scene* s, const zr_anim_desc* d)
 {
     if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_animation: null scene");
     HIP_TRY(hipSetDevice(s->device));
     if (!d || (!d->num_nodes && !d->num_instances))
     {
+        if (int r = SceneClearSkin(s)) return r;      // (its joints are nodes of the table that goes)
         SceneAnimSyncHost(s);
         HIP_TRY(hipDeviceSynchronize());      // an animate in flight still reads the tables
         std::lock_guard<std::mutex> lock(s->animMtx);
@@ -2244,6 +2280,7 @@ int zr_scene_set_animation(zr_scene* s, const zr_anim_desc* d)
     // nothing of the scene has changed up to here.  The animation it replaces: its last frame reaches the host's matrices, its kernels finish
     SceneAnimSyncHost(s);
     HIP_TRY(hipDeviceSynchronize());
+    if ((r = SceneClearSkin(s))) return r;      // a skin belongs to the animation it was set on: its joints index the table this call replaces
     for (uint32_t i : A->instIdx) s->movedEver[i] = 1;      // the background builder gives each animated instance a subtree of its own
     std::lock_guard<std::mutex> lock(s->animMtx);
     s->anim = std::move(A);
@@ -2285,6 +2322,111 @@ int zr_scene_get_emissives(const zr_scene* s, void* stream, zr_emissive_triangle
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     HIP_TRY(hipMemcpy(out, s->emissives.p + first, (size_t)count * sizeof(zr_emissive_triangle), hipMemcpyDeviceToHost));
+    return ZR_OK;
+}
+
+int zr_scene_has_skinning(const zr_scene* s) { return s && s->skin ? 1 : 0; }
+// ---- deformed geometry: a vertex range replaced by the caller (the host form), or posed on the device by every zr_scene_animate (zr_scene_set_skinning)
+static int SceneFillVtxTables(zr_scene* s, hipStream_t st, uint32_t first, uint32_t count)
+{
+    hipError_t e = zr::LaunchFillVtxNormals(st, s->vtxNormals.p + first, s->vertices.p + first, count, false);
+#if ZR_HIT_TANGENTS
+    if (e == hipSuccess) e = zr::LaunchFillVtxNormals(st, s->vtxTangents.p + first, s->vertices.p + first, count, true);
+#endif
+    if (e != hipSuccess) return Fail(ZR_ERR_HIP, "k_fill_vtx_normals failed: %s", hipGetErrorString(e));
+    return ZR_OK;
+}
+int zr_scene_update_vertices_async(zr_scene* s, void* stream, uint32_t first, uint32_t count, const zr_vertex* vertices)
+{
+    if (!s || (!vertices && count)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_update_vertices: null argument");
+    if ((uint64_t)first + count > s->vertices.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_update_vertices: [%u, %llu) exceeds the scene's %zu vertices", first, (unsigned long long)first + count, s->vertices.n);
+    if (int r = RefuseRebuildMode("zr_scene_update_vertices")) return r;
+    if (!count) return ZR_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    int r; zr_scene::StageSlot* t;
+    if ((r = StageAcquire(s, (size_t)count * sizeof(zr_vertex), &t))) return r;
+    memcpy(t->host, vertices, (size_t)count * sizeof(zr_vertex));
+    if ((r = SceneWaitUsers(s, st))) return r;          // kernels of earlier frames on other streams may still read the old vertices
+    HIP_TRY(hipMemcpyAsync(s->vertices.p + first, t->host, (size_t)count * sizeof(zr_vertex), hipMemcpyHostToDevice, st));
+    if ((r = SceneFillVtxTables(s, st, first, count))) return r;
+    if ((r = StageCommit(t, st))) return r;
+    // the host's copy: a background build in flight reads it, so the range waits until its thread is done (no host wait here)
+    if (s->bg.state.load(std::memory_order_acquire) == 1) s->hVertexPending.emplace_back(first, std::vector<zr_vertex>(vertices, vertices + count));
+    else { SceneFlushVertexCopies(s); std::copy(vertices, vertices + count, s->hVertices.begin() + first); }
+    s->bg.movedSinceBuild = true;
+    return SceneMarkUpdated(s, st);
+}
+int zr_scene_update_vertices(zr_scene* s, uint32_t first, uint32_t count, const zr_vertex* v) { const int r = zr_scene_update_vertices_async(s, nullptr, first, count, v); return count ? ThenWait(r) : r; }
+int zr_scene_get_vertices(const zr_scene* s, void* stream, zr_vertex* out, uint32_t first, uint32_t count)
+{
+    if (!s || (!out && count)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_vertices: null argument");
+    if ((uint64_t)first + count > s->vertices.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_vertices: [%u, %llu) exceeds the scene's %zu vertices", first, (unsigned long long)first + count, s->vertices.n);
+    if (!count) return ZR_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(hipMemcpy(out, s->vertices.p + first, (size_t)count * sizeof(zr_vertex), hipMemcpyDeviceToHost));
+    return ZR_OK;
+}
+// the rest pose back into the listed ranges and their hit-table entries, host-synchronous; the set is dropped
+static int SceneClearSkin(zr_scene* s)
+{
+    if (!s->skin) return ZR_OK;
+    HIP_TRY(hipDeviceSynchronize());      // an animate in flight still reads the tables; renders in flight read the vertices
+    zr_scene::Skin& K = *s->skin;
+    for (const zr::SkinRange& g : K.ranges)
+    {
+        if (!g.numVertices) continue;
+        HIP_TRY(hipMemcpy(s->vertices.p + g.firstVertex, K.hRest.data() + g.restFirst, (size_t)g.numVertices * sizeof(zr_vertex), hipMemcpyHostToDevice));
+        if (int r = SceneFillVtxTables(s, nullptr, g.firstVertex, g.numVertices)) return r;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    s->skin.reset();
+    return ZR_OK;
+}
+int zr_scene_set_skinning(zr_scene* s, const zr_skin_desc* d)
+{
+    if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_skinning: null scene");
+    HIP_TRY(hipSetDevice(s->device));
+    if (!d || (!d->num_joints && !d->num_ranges && !d->num_influences)) return SceneClearSkin(s);
+    uint32_t animNodes = 0;
+    {
+        std::lock_guard<std::mutex> lock(s->animMtx);
+        if (!s->anim) return Fail(ZR_ERR_NOT_INITIALIZED, "zr_scene_set_skinning: no animation set (zr_scene_set_animation): the joints are nodes of its table");
+        animNodes = s->anim->desc.num_nodes;
+    }
+    char msg[256];
+    if (zrsk::ValidateSkin(*d, animNodes, (uint32_t)s->vertices.n, msg, sizeof(msg))) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_skinning: %s", msg);
+    std::unique_ptr<zr_scene::Skin> K(new zr_scene::Skin());
+    K->numJoints = d->num_joints;
+    std::vector<uint32_t> jointNode(d->num_joints); std::vector<float> inverseBind(12 * (size_t)d->num_joints);
+    for (uint32_t j = 0; j < d->num_joints; j++) { jointNode[j] = d->joints[j].node; std::memcpy(inverseBind.data() + 12 * (size_t)j, d->joints[j].inverse_bind, 12 * sizeof(float)); }
+    size_t restRecords = 0;
+    for (uint32_t i = 0; i < d->num_ranges; i++)
+    {
+        K->ranges.push_back(zr::SkinRange{d->ranges[i].first_vertex, d->ranges[i].num_vertices, d->ranges[i].first_influence, (uint32_t)restRecords});
+        restRecords += d->ranges[i].num_vertices;
+    }
+    // the rest records: what the ranges hold once the set this one replaces has put its own rest pose back (ranges of the old set may lie outside the new one's)
+    // -- the new ranges alone are read back, and the old set's rest records laid over them where the two meet
+    HIP_TRY(hipDeviceSynchronize());
+    K->hRest.assign(restRecords, zr_vertex{});
+    for (const zr::SkinRange& g : K->ranges)
+    {
+        if (!g.numVertices) continue;
+        HIP_TRY(hipMemcpy(K->hRest.data() + g.restFirst, s->vertices.p + g.firstVertex, (size_t)g.numVertices * sizeof(zr_vertex), hipMemcpyDeviceToHost));
+        if (s->skin) for (const zr::SkinRange& o : s->skin->ranges)
+        {
+            const uint64_t lo = std::max(g.firstVertex, o.firstVertex), hi = std::min((uint64_t)g.firstVertex + g.numVertices, (uint64_t)o.firstVertex + o.numVertices);
+            if (hi > lo) std::copy(s->skin->hRest.begin() + o.restFirst + (lo - o.firstVertex), s->skin->hRest.begin() + o.restFirst + (hi - o.firstVertex), K->hRest.begin() + g.restFirst + (lo - g.firstVertex));
+        }
+    }
+    int r;
+    if ((r = K->dJointNode.Upload(jointNode.data(), jointNode.size())) || (r = K->dInverseBind.Upload(inverseBind.data(), inverseBind.size())) ||
+        (r = K->dJ.Alloc(inverseBind.size())) || (r = K->dInfluences.Upload(d->influences, d->num_influences)) || (r = K->dRest.Upload(K->hRest.data(), K->hRest.size()))) return r;
+    // nothing of the scene has changed up to here
+    if ((r = SceneClearSkin(s))) return r;
+    s->skin = std::move(K);
     return ZR_OK;
 }
 

@@ -819,20 +819,50 @@ extern "C" int zrh_scene_apply_updates(zr_scene* scene, const zrh_scene_data* da
 // A frame of a scene with keyframe animation (zrh_scene_data_set_animation or an animated glTF), enqueued on `stream`.  Host path: begin_frame,
 // zrh_scene_data_animate (include/zr_anim.h on the host), then the hand-over above.  After zrh_scene_data_set_device_animation(data, 1): the time alone
 // (zr_scene_animate_async); the tables -- and the object-space light records -- go to a device scene the first time it is asked to animate without any.
+// A skinned scene (zrh_scene_data_skinning: a glTF with skins, or zrh_scene_data_set_skinning).  Host form: zrh_scene_data_skin_pose for time t, handed over
+// range by range with zr_scene_update_vertices_async AHEAD of the frame's instance update, which refits from the new vertices.  After
+// zrh_scene_data_set_device_skinning(data, 1), on the device path: zr_scene_set_skinning once per device scene, behind its animation tables.
+static int HandSkinnedVertices(zrh_scene_data* data, zr_scene* scene, void* stream, float t)
+{
+    const zr_skin_desc* k = zrh_scene_data_skinning(data);
+    const zr_vertex* posed = zrh_scene_data_skin_pose(data, t);
+    if (!posed) return -1;
+    for (uint32_t i = 0; i < k->num_ranges; i++)
+    {
+        if (const int r = zr_scene_update_vertices_async(scene, stream, k->ranges[i].first_vertex, k->ranges[i].num_vertices, posed)) return r;
+        posed += k->ranges[i].num_vertices;
+    }
+    return 0;
+}
 extern "C" int zrh_scene_animate(zrh_scene_data* data, zr_scene* scene, void* stream, float t)
 {
     if (!scene || !data || !zrh_scene_data_animation(data)) return -1;
+    const zr_skin_desc* skin = zrh_scene_data_skinning(data);
     if (!zrh_scene_data_device_animation(data))
     {
         zrh_scene_data_begin_frame(data);
         if (zrh_scene_data_animate(data, t)) return -1;
+        if (skin) { if (const int r = HandSkinnedVertices(data, scene, stream, t)) return r; }
         return zrh_scene_apply_updates_on(scene, data, stream);
     }
-    int r = zr_scene_animate_async(scene, stream, t);
+    int r;
+    auto handTables = [&]() -> int {
+        if (!zr_scene_has_object_emissives(scene) && zrh_scene_data_initial_emissives(data))
+            if (const int e = zr_scene_set_object_emissives(scene, zrh_scene_data_initial_emissives(data), zrh_scene_data_desc(data)->num_emissives)) return e;
+        return zr_scene_set_animation(scene, zrh_scene_data_animation(data)); };
+    if (skin && zrh_scene_data_device_skinning(data))
+    {
+        if (!zr_scene_has_skinning(scene))
+        {
+            r = zr_scene_set_skinning(scene, skin);
+            if (r == ZR_ERR_NOT_INITIALIZED) { if ((r = handTables())) return r; r = zr_scene_set_skinning(scene, skin); }
+            if (r) return r;
+        }
+    }
+    else if (skin) { if ((r = HandSkinnedVertices(data, scene, stream, t))) return r; }      // (the vertices first: zr_scene_animate refits from them)
+    r = zr_scene_animate_async(scene, stream, t);
     if (r != ZR_ERR_NOT_INITIALIZED) return r;
-    if (!zr_scene_has_object_emissives(scene) && zrh_scene_data_initial_emissives(data) &&
-        (r = zr_scene_set_object_emissives(scene, zrh_scene_data_initial_emissives(data), zrh_scene_data_desc(data)->num_emissives))) return r;
-    if ((r = zr_scene_set_animation(scene, zrh_scene_data_animation(data)))) return r;
+    if ((r = handTables())) return r;
     return zr_scene_animate_async(scene, stream, t);
 }
 

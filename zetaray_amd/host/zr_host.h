@@ -68,6 +68,9 @@ int zrh_scene_apply_updates_on(zr_scene* scene, const struct zrh_scene_data* dat
 // zrh_scene_data_set_device_animation(data, 1): zr_scene_animate_async -- only t crosses the bus; the tables (and the object-space light records) are
 // handed to a device scene that has none the first time.  The device path leaves data's own records and matrices where they were.  A table replaced
 // on `data` later reaches a device scene through zr_scene_set_animation.
+// A skinned scene (zrh_scene_data_skinning) is posed by the same call.  Host form (the default): zrh_scene_data_skin_pose for time t, handed over with
+// zr_scene_update_vertices_async ahead of the frame's instance update.  After zrh_scene_data_set_device_skinning(data, 1), together with the device path
+// above: the skin tables go to the device scene once (zr_scene_set_skinning), and zr_scene_animate_async poses the vertices -- the same device bytes.
 int zrh_scene_animate(struct zrh_scene_data* data, zr_scene* scene, void* hip_stream, float t);
 }
 

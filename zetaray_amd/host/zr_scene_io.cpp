@@ -5,6 +5,7 @@
 #include "../../include/zr_detmath.h"
 #include "../../include/zr_scene_math.h"
 #include "../../include/zr_anim.h"
+#include "../../include/zr_skin.h"
 #include "../../include/zr_bcn.h"
 #include "../../include/zr_texture.h"
 #include "../../include/zr_mipgen.h"
@@ -748,6 +749,10 @@ struct zrh_scene_data
     // keyframe animation (zrh_scene_data_set_animation: a deep copy; anim points into the vectors) and the node matrices of the last zrh_scene_data_animate
     std::vector<zr_anim_node> animNodes; std::vector<zr_keyframe> animKeys; std::vector<uint32_t> animInstIdx, animInstNode; std::vector<float> animWorld;
     zr_anim_desc anim{}; bool hasAnim = false, deviceAnimation = false;      // deviceAnimation: zrh_scene_data_set_device_animation (zr_host.h: zrh_scene_animate)
+    // skinned meshes of the file (zrh_scene_data_skinning; skin points into the vectors): joints on entries of animNodes, one range per skinned primitive
+    std::vector<zr_skin_joint> skinJoints; std::vector<zr_skin_range> skinRanges; std::vector<zr_skin_influence> skinInfluences;
+    zr_skin_desc skin{}; bool hasSkin = false, deviceSkinning = false;      // deviceSkinning: zrh_scene_data_set_device_skinning (zr_host.h: zrh_scene_animate)
+    std::vector<zr_vertex> skinRest, skinPosed;      // zrh_scene_data_skin_pose: the ranges' rest records (this scene's vertices, which keep the rest pose) and the posed ones
     zr_scene_desc desc;
     void Finish()
     {
@@ -771,9 +776,14 @@ struct Gltf
     Json root; std::string dir; std::vector<std::vector<uint8_t>> buffers;
     Accessor Acc(int idx) const
     {
-        const Json& a = root.At("accessors").arr.at(idx);
-        const Json& bv = root.At("bufferViews").arr.at(a.At("bufferView").num);
-        const std::vector<uint8_t>& buf = buffers.at((size_t)bv.At("buffer").num);
+        // (indices as non-negative numbers below 2^32 before they become size_t: the conversion of a negative double is undefined)
+        auto index = [](double v) -> size_t { if (!(v >= 0.0) || v >= 4294967296.0) Throw("glTF: accessor, bufferView or buffer index out of range"); return (size_t)v; };
+        const Json& a = root.At("accessors").arr.at(index((double)idx));
+        const Json& bv = root.At("bufferViews").arr.at(index(a.At("bufferView").num));
+        const std::vector<uint8_t>& buf = buffers.at(index(bv.At("buffer").num));
+        // (offsets, count and stride as non-negative numbers below 2^32: the size_t arithmetic below cannot wrap)
+        for (double v : {a.At("count").num, a.NumOr("byteOffset", 0), bv.NumOr("byteOffset", 0), bv.NumOr("byteStride", 0)})
+            if (!(v >= 0.0) || v >= 4294967296.0) Throw("glTF: accessor with a negative or oversized count, offset or stride");
         Accessor r; r.comp = (int)a.At("componentType").num; r.count = (size_t)a.At("count").num; r.normalized = a.BoolOr("normalized", false);
         const std::string t = a.At("type").str;
         r.ncomp = t == "SCALAR" ? 1 : t == "VEC2" ? 2 : t == "VEC3" ? 3 : t == "VEC4" ? 4 : t == "MAT4" ? 16 : 0;
@@ -809,7 +819,7 @@ struct Gltf
     }
 };
 
-struct MeshPrim { uint32_t vtx, idx, nidx; int mat; };
+struct MeshPrim { uint32_t vtx, idx, nidx; int mat; uint32_t nvtx; };
 
 void Load(const std::string& path, zrh_scene_data& sc)
 {
@@ -958,7 +968,7 @@ void Load(const std::string& path, zrh_scene_data& sc)
                 if (i0 >= pos.count || i1 >= pos.count || i2 >= pos.count) Throw("glTF: vertex index out of range");
                 sc.indices.push_back(i0); sc.indices.push_back(i1); sc.indices.push_back(i2);
             }
-            mp.nidx = (uint32_t)ia.count;
+            mp.nidx = (uint32_t)ia.count; mp.nvtx = (uint32_t)pos.count;
             prims[{(int)mi, (int)pi}] = mp;
         }
     }
@@ -1008,6 +1018,52 @@ void Load(const std::string& path, zrh_scene_data& sc)
                 if (out.count < in.count || out.ncomp != (which == 1 ? 4 : 3) || in.ncomp != 1) Throw(where + "sampler accessors do not match the " + path + " path");
             }
         }
+    // ---- "skins": the joints (nodes of the file) and inverse bind matrices of every skin a node with a mesh uses.  The matrices take the loader's
+    // handedness rule for node matrices (z row and z column negated: S M S with S = diag(1, 1, -1), what negating a translation's z and a rotation's x
+    // and y is), so that J = world x inverse bind acts on the z-negated vertices as the file's J acts on the file's
+    struct SkinUse { std::vector<int> joints; std::vector<float> ibm; std::string name; bool used = false; uint32_t base = 0; };
+    std::vector<SkinUse> skins;
+    if (const Json* sk = g.root.Find("skins"))
+        for (size_t si = 0; si < sk->Size(); si++)
+        {
+            SkinUse u; u.name = "glTF: skin " + std::to_string(si) + " ('" + sk->arr[si].StrOr("name", "") + "'): ";
+            for (const Json& j : sk->arr[si].At("joints").arr)
+            {
+                if (!(j.num >= 0) || j.num >= (double)nodes.arr.size()) Throw(u.name + "joint " + std::to_string(u.joints.size()) + " is not a node of the file");
+                u.joints.push_back((int)j.num);
+            }
+            if (u.joints.empty()) Throw(u.name + "no joints");
+            if (u.joints.size() > 65535) Throw(u.name + "more than 65 535 joints");
+            u.ibm.assign(12 * u.joints.size(), 0.0f);
+            for (size_t j = 0; j < u.joints.size(); j++) u.ibm[12 * j] = u.ibm[12 * j + 5] = u.ibm[12 * j + 10] = 1.0f;
+            const int ibmAcc = sk->arr[si].IntOr("inverseBindMatrices", -1);
+            if (ibmAcc >= 0)
+            {
+                const Accessor a = g.Acc(ibmAcc);
+                if (a.ncomp != 16 || a.comp != 5126 || a.count < u.joints.size()) Throw(u.name + "inverseBindMatrices must be a float MAT4 accessor with one matrix per joint");
+                for (size_t j = 0; j < u.joints.size(); j++)
+                {
+                    Mat43 r; for (int i = 0; i < 4; i++) for (int c = 0; c < 3; c++) r.m[i][c] = Gltf::Comp(a, j, 4 * i + c);
+                    r.m[0][2] *= -1.0f; r.m[1][2] *= -1.0f; r.m[2][0] *= -1.0f; r.m[2][1] *= -1.0f; r.m[3][2] *= -1.0f;
+                    ToToWorld(r, u.ibm.data() + 12 * j);
+                }
+            }
+            skins.push_back(std::move(u));
+        }
+    for (const Json& n : nodes.arr)
+    {
+        const int s = n.IntOr("skin", -1);
+        if (s < 0 || n.IntOr("mesh", -1) < 0) continue;
+        if ((size_t)s >= skins.size()) Throw("glTF: a node names skin " + std::to_string(s) + " but the file has " + std::to_string(skins.size()));
+        skins[(size_t)s].used = true;
+    }
+    // is the node a joint of a used skin, or an ancestor of one?  (the dynamic closure keeps those: their world matrices feed the joint matrices)
+    std::vector<int8_t> leadsToJoint(nodes.arr.size(), -1);
+    std::vector<uint8_t> isJoint(nodes.arr.size(), 0);
+    for (const SkinUse& u : skins) if (u.used) for (int j : u.joints) isJoint[(size_t)j] = 1;
+    std::vector<uint32_t> nodeEntry(nodes.arr.size(), ZR_ANIM_ROOT);      // a visited node's entry of the closure table
+    struct SkinnedPrim { int skin; uint32_t range; };
+    std::vector<SkinnedPrim> skinnedPrims;
     // does the subtree of a node hold a mesh?  (a descendant of an animated node joins the closure only if it carries, or leads to, an instance)
     std::vector<int8_t> leadsToMesh(nodes.arr.size(), -1);
     struct Walker
@@ -1015,6 +1071,56 @@ void Load(const std::string& path, zrh_scene_data& sc)
         Gltf& g; zrh_scene_data& sc; std::map<std::pair<int, int>, MeshPrim>& prims; std::vector<Em>& emissive; const Json& nodes; decltype(isEmissive)& isEm;
         std::vector<uint8_t> onPath;
         std::map<int, NodeAnim>& nodeAnims; std::vector<int8_t>& leadsToMesh;
+        std::vector<SkinUse>& skins; std::vector<int8_t>& leadsToJoint; std::vector<uint8_t>& isJoint; std::vector<uint32_t>& nodeEntry; std::vector<SkinnedPrim>& skinnedPrims;
+        bool LeadsToJoint(int nidx, int depth = 0)
+        {
+            if (nidx < 0 || (size_t)nidx >= nodes.arr.size() || depth > 4096) return false;
+            if (leadsToJoint[nidx] >= 0) return leadsToJoint[nidx] != 0;
+            leadsToJoint[nidx] = 0;      // (a cycle ends here; Visit names it)
+            const Json& node = nodes.arr.at(nidx);
+            bool any = isJoint[nidx] != 0;
+            if (const Json* ch = node.Find("children")) for (const Json& c : ch->arr) any = LeadsToJoint((int)c.num, depth + 1) || any;
+            leadsToJoint[nidx] = any ? 1 : 0;
+            return any;
+        }
+        // one primitive of a skinned node: a vertex range of its own (a copy of the mesh's: no sharing with another node that uses the mesh), its influences
+        // (JOINTS_0: unsigned bytes or shorts; WEIGHTS_0: floats, or normalised bytes / shorts; renormalised to sum 1 in float32).  Returns the copy's first vertex
+        uint32_t SkinPrimitive(int nidx, int skin, const Json& prim, const MeshPrim& mp)
+        {
+            const std::string where = "glTF: node " + std::to_string(nidx) + " (skin " + std::to_string(skin) + "): ";
+            const Json& at = prim.At("attributes");
+            if (at.Find("JOINTS_1") || at.Find("WEIGHTS_1")) Throw(where + "JOINTS_1 / WEIGHTS_1: more than four influences per vertex are not supported");
+            const bool hj = at.Find("JOINTS_0") != nullptr, hw = at.Find("WEIGHTS_0") != nullptr;
+            if (hj && !hw) Throw(where + "JOINTS_0 without WEIGHTS_0");
+            if (hw && !hj) Throw(where + "WEIGHTS_0 without JOINTS_0");
+            if (!hj) Throw(where + "a primitive of a skinned node has neither JOINTS_0 nor WEIGHTS_0");
+            if (isEm(mp.mat)) Throw(where + "a skinned primitive with an emissive material is not supported (a deformed light would keep shining from its rest pose)");
+            const Accessor ja = g.Acc((int)at.At("JOINTS_0").num), wa = g.Acc((int)at.At("WEIGHTS_0").num);
+            if (ja.ncomp != 4 || (ja.comp != 5121 && ja.comp != 5123) || ja.normalized) Throw(where + "JOINTS_0 must be VEC4 of unsigned bytes or unsigned shorts");
+            if (wa.ncomp != 4 || !(wa.comp == 5126 || ((wa.comp == 5121 || wa.comp == 5123) && wa.normalized))) Throw(where + "WEIGHTS_0 must be VEC4 of floats, or of normalised unsigned bytes / shorts");
+            if (ja.count < mp.nvtx || wa.count < mp.nvtx) Throw(where + "JOINTS_0 / WEIGHTS_0 accessor shorter than POSITION");
+            const size_t numJoints = skins[(size_t)skin].joints.size();
+            const uint32_t first = (uint32_t)sc.vertices.size();
+            zr_skin_range range; range.first_vertex = first; range.num_vertices = mp.nvtx; range.first_influence = (uint32_t)sc.skinInfluences.size();
+            for (uint32_t v = 0; v < mp.nvtx; v++)
+            {
+                sc.vertices.push_back(sc.vertices[mp.vtx + v]);
+                zr_skin_influence f; float w[4];
+                for (int k = 0; k < 4; k++)
+                {
+                    const uint32_t j = (uint32_t)Gltf::Comp(ja, v, k);
+                    if (j >= numJoints) Throw(where + "vertex " + std::to_string(v) + ": joint " + std::to_string(j) + ", the skin has " + std::to_string(numJoints));
+                    f.joint[k] = (uint16_t)j; w[k] = Gltf::Comp(wa, v, k);
+                }
+                const float sum = ((w[0] + w[1]) + w[2]) + w[3];
+                if (!(sum > 0.0f) || !Finite(sum)) Throw(where + "vertex " + std::to_string(v) + ": the weights do not sum to a positive finite number");
+                for (int k = 0; k < 4; k++) f.weight[k] = w[k] / sum;
+                sc.skinInfluences.push_back(f);
+            }
+            skinnedPrims.push_back(SkinnedPrim{skin, (uint32_t)sc.skinRanges.size()});
+            sc.skinRanges.push_back(range);
+            return first;
+        }
         bool LeadsToMesh(int nidx, int depth = 0)
         {
             if (nidx < 0 || (size_t)nidx >= nodes.arr.size() || depth > 4096) return false;
@@ -1053,7 +1159,7 @@ void Load(const std::string& path, zrh_scene_data& sc)
             // ---- the dynamic closure, depth first (a parent precedes its children): the animated nodes and what hangs on them
             uint32_t entry = ZR_ANIM_ROOT;
             const auto anim = nodeAnims.find(nidx);
-            if (anim != nodeAnims.end() || (closureParent != ZR_ANIM_ROOT && LeadsToMesh(nidx)))
+            if (anim != nodeAnims.end() || (closureParent != ZR_ANIM_ROOT && LeadsToMesh(nidx)) || LeadsToJoint(nidx))
             {
                 zr_anim_node an; std::memset(&an, 0, sizeof(an));
                 an.parent = closureParent;
@@ -1081,8 +1187,10 @@ void Load(const std::string& path, zrh_scene_data& sc)
                 }
                 entry = (uint32_t)sc.animNodes.size();
                 sc.animNodes.push_back(an);
+                nodeEntry[nidx] = entry;
             }
             const int mesh = node.IntOr("mesh", -1);
+            const int skin = mesh >= 0 ? node.IntOr("skin", -1) : -1;      // a skinned node: glTF ignores its own transform, the joints place the mesh
             if (mesh >= 0)
             {
                 const size_t np = g.root.At("meshes").arr.at(mesh).At("primitives").Size();
@@ -1092,6 +1200,12 @@ void Load(const std::string& path, zrh_scene_data& sc)
                     zr_mesh_instance I; std::memset(&I, 0, sizeof(I));
                     float M[12]; ToToWorld(world, M);
                     I.base_vtx_offset = mp.vtx; I.base_idx_offset = mp.idx; I.mat_idx = (uint16_t)(mp.mat + 1);
+                    if (skin >= 0)
+                    {
+                        I.base_vtx_offset = SkinPrimitive(nidx, skin, g.root.At("meshes").arr.at(mesh).At("primitives").arr.at(pi), mp);
+                        Mat43 id; std::memset(&id, 0, sizeof(id)); for (int i = 0; i < 3; i++) id.m[i][i] = 1.0f;
+                        ToToWorld(id, M);
+                    }
                     FillMeshInstance(M, I);
                     const zr_material& mat = sc.materials.at((size_t)mp.mat + 1);
                     const uint32_t bct = mat.base_color_tex_subsurf_coat_weight & 0xffffu;
@@ -1102,7 +1216,7 @@ void Load(const std::string& path, zrh_scene_data& sc)
                     const bool em = isEm(mp.mat);
                     const int alphaMode = (int)((mat.coat_color_flags >> 27) & 3u);
                     sc.instances.push_back(I);
-                    if (entry != ZR_ANIM_ROOT) { sc.animInstIdx.push_back((uint32_t)sc.instances.size() - 1); sc.animInstNode.push_back(entry); }
+                    if (entry != ZR_ANIM_ROOT && skin < 0) { sc.animInstIdx.push_back((uint32_t)sc.instances.size() - 1); sc.animInstNode.push_back(entry); }
                     sc.toWorld.insert(sc.toWorld.end(), M, M + 12);
                     sc.mask.push_back((uint8_t)((em ? ZR_SUBGROUP_EMISSIVE : ZR_SUBGROUP_NON_EMISSIVE) | (alphaMode != 0 ? ZR_INSTANCE_NON_OPAQUE : 0u)));
                     sc.numTris.push_back(mp.nidx / 3);
@@ -1111,7 +1225,7 @@ void Load(const std::string& path, zrh_scene_data& sc)
             }
             if (const Json* ch = node.Find("children")) for (const Json& c : ch->arr) Visit((int)c.num, world, entry);
         }
-    } walker{g, sc, prims, emissive, nodes, isEmissive, {}, nodeAnims, leadsToMesh};
+    } walker{g, sc, prims, emissive, nodes, isEmissive, {}, nodeAnims, leadsToMesh, skins, leadsToJoint, isJoint, nodeEntry, skinnedPrims};
     const Json& scenes = g.root.At("scenes");
     const Json& scene = scenes.arr.at((size_t)g.root.IntOr("scene", 0));
     for (const Json& n : scene.At("nodes").arr) walker.Visit((int)n.num, identity);
@@ -1123,6 +1237,36 @@ void Load(const std::string& path, zrh_scene_data& sc)
         char msg[256];
         if (ValidateAnimation(d, (uint32_t)sc.instances.size(), nullptr, msg, sizeof(msg))) Throw(std::string("glTF: animations: ") + msg);
         sc.anim = d; sc.hasAnim = true;
+    }
+    if (!skinnedPrims.empty())
+    {   // the joint tables of the skins in use, one after the other; an influence's joint index counts from its skin's first joint
+        if (nodeAnims.empty()) Throw("glTF: the file has a skin but no animation: nothing would pose it (skins are driven by zr_scene_animate)");
+        for (size_t si = 0; si < skins.size(); si++)
+        {
+            SkinUse& u = skins[si];
+            bool inUse = false; for (const SkinnedPrim& p : skinnedPrims) inUse = inUse || p.skin == (int)si;
+            if (!inUse) continue;
+            u.base = (uint32_t)sc.skinJoints.size();
+            for (size_t j = 0; j < u.joints.size(); j++)
+            {
+                zr_skin_joint sj; sj.node = nodeEntry[(size_t)u.joints[j]];
+                if (sj.node == ZR_ANIM_ROOT) Throw(u.name + "joint " + std::to_string(j) + " (node " + std::to_string(u.joints[j]) + ") is not part of the scene's node hierarchy");
+                std::memcpy(sj.inverse_bind, u.ibm.data() + 12 * j, sizeof(sj.inverse_bind));
+                sc.skinJoints.push_back(sj);
+            }
+        }
+        if (sc.skinJoints.size() > 65535) Throw("glTF: skins: more than 65 535 joints in use");
+        for (const SkinnedPrim& p : skinnedPrims)
+        {
+            const zr_skin_range& r = sc.skinRanges[p.range];
+            for (uint32_t v = 0; v < r.num_vertices; v++) for (int k = 0; k < 4; k++) sc.skinInfluences[r.first_influence + v].joint[k] = (uint16_t)(sc.skinInfluences[r.first_influence + v].joint[k] + skins[(size_t)p.skin].base);
+        }
+        zr_skin_desc d; std::memset(&d, 0, sizeof(d));
+        d.joints = sc.skinJoints.data(); d.num_joints = (uint32_t)sc.skinJoints.size(); d.ranges = sc.skinRanges.data(); d.num_ranges = (uint32_t)sc.skinRanges.size();
+        d.influences = sc.skinInfluences.data(); d.num_influences = (uint32_t)sc.skinInfluences.size();
+        char msg[256];
+        if (zrsk::ValidateSkin(d, (uint32_t)sc.animNodes.size(), (uint32_t)sc.vertices.size(), msg, sizeof(msg))) Throw(std::string("glTF: skins: ") + msg);
+        sc.skin = d; sc.hasSkin = true;
     }
     // ---- emissive triangles in world space (glTF.cpp:692-767, SceneCore.cpp:196-236): ID = PCG3d(instance, 0, triangle).x
     for (const Em& em : emissive)
@@ -1182,6 +1326,19 @@ void zrh_scene_data_tex_offsets(const zrh_scene_data* s, uint32_t* out4) { for (
 void zrh_scene_data_destroy(zrh_scene_data* s) { delete s; }
 
 void zrh_decompose_srt(const float* M, float* s, float* q, float* t) { DecomposeSRT(FromToWorld(M), s, q, t); }
+int zrh_skin_pose(const zr_anim_desc* anim, const zr_skin_desc* skin, float t, const zr_vertex* rest, zr_vertex* out)
+{
+    if (!anim || !skin || ((!rest || !out) && skin->num_ranges)) { g_err = "zrh_skin_pose: null argument"; return -1; }
+    uint64_t verts = 0;
+    for (uint32_t r = 0; r < skin->num_ranges; r++) verts = std::max<uint64_t>(verts, (uint64_t)skin->ranges[r].first_vertex + skin->ranges[r].num_vertices);
+    char msg[256];
+    if (verts > 0xffffffffull || zrsk::ValidateSkin(*skin, anim->num_nodes, (uint32_t)verts, msg, sizeof(msg))) { g_err = std::string("zrh_skin_pose: ") + (verts > 0xffffffffull ? "a range wraps" : msg); return -1; }
+    std::vector<float> world(12 * (size_t)anim->num_nodes), J(12 * (size_t)skin->num_joints);
+    EvalNodeWorlds(*anim, t, world.data());
+    zrsk::EvalJointMatrices(*skin, world.data(), J.data());
+    zrsk::SkinRanges(*skin, J.data(), rest, out);
+    return 0;
+}
 void zrh_compose_world(const float* s, const float* q, const float* t, const float* parent, float* out)
 {
     Mat43 P; std::memset(&P, 0, sizeof(P)); for (int i = 0; i < 3; i++) P.m[i][i] = 1.0f;
@@ -1239,6 +1396,7 @@ int zrh_scene_data_set_animation(zrh_scene_data* s, const zr_anim_desc* d)
     { s->hasAnim = false; s->animNodes.clear(); s->animKeys.clear(); s->animInstIdx.clear(); s->animInstNode.clear(); std::memset(&s->anim, 0, sizeof(s->anim)); return 0; }
     char msg[256];
     if (ValidateAnimation(*d, (uint32_t)s->instances.size(), nullptr, msg, sizeof(msg))) { g_err = std::string("zrh_scene_data_set_animation: ") + msg; return -1; }
+    zrh_scene_data_set_skinning(s, nullptr);      // a skin belongs to the animation it was set on (zr_scene_set_animation does the same)
     s->animNodes.assign(d->nodes, d->nodes + d->num_nodes); s->animKeys.assign(d->keys, d->keys + d->num_keys);
     s->animInstIdx.assign(d->instance_idx, d->instance_idx + d->num_instances); s->animInstNode.assign(d->instance_node, d->instance_node + d->num_instances);
     s->anim.nodes = s->animNodes.data(); s->anim.num_nodes = d->num_nodes; s->anim.keys = s->animKeys.data(); s->anim.num_keys = d->num_keys;
@@ -1247,6 +1405,33 @@ int zrh_scene_data_set_animation(zrh_scene_data* s, const zr_anim_desc* d)
     return 0;
 }
 const zr_anim_desc* zrh_scene_data_animation(const zrh_scene_data* s) { return s && s->hasAnim ? &s->anim : nullptr; }
+const zr_skin_desc* zrh_scene_data_skinning(const zrh_scene_data* s) { return s && s->hasSkin ? &s->skin : nullptr; }
+int zrh_scene_data_set_skinning(zrh_scene_data* s, const zr_skin_desc* d)
+{
+    if (!s) { g_err = "zrh_scene_data_set_skinning: null scene"; return -1; }
+    if (!d || (!d->num_joints && !d->num_ranges && !d->num_influences))
+    { s->hasSkin = false; s->skinJoints.clear(); s->skinRanges.clear(); s->skinInfluences.clear(); std::memset(&s->skin, 0, sizeof(s->skin)); return 0; }
+    if (!s->hasAnim) { g_err = "zrh_scene_data_set_skinning: no animation set (zrh_scene_data_set_animation): the joints are nodes of its table"; return -1; }
+    char msg[256];
+    if (zrsk::ValidateSkin(*d, s->anim.num_nodes, (uint32_t)s->vertices.size(), msg, sizeof(msg))) { g_err = std::string("zrh_scene_data_set_skinning: ") + msg; return -1; }
+    s->skinJoints.assign(d->joints, d->joints + d->num_joints); s->skinRanges.assign(d->ranges, d->ranges + d->num_ranges);
+    s->skinInfluences.assign(d->influences, d->influences + d->num_influences);
+    s->skin.joints = s->skinJoints.data(); s->skin.num_joints = d->num_joints; s->skin.ranges = s->skinRanges.data(); s->skin.num_ranges = d->num_ranges;
+    s->skin.influences = s->skinInfluences.data(); s->skin.num_influences = d->num_influences;
+    s->hasSkin = true;
+    return 0;
+}
+const zr_vertex* zrh_scene_data_skin_pose(zrh_scene_data* s, float t)
+{
+    if (!s || !s->hasSkin || !s->hasAnim) { g_err = "zrh_scene_data_skin_pose: no skin set"; return nullptr; }
+    s->skinRest.clear();
+    for (const zr_skin_range& r : s->skinRanges) s->skinRest.insert(s->skinRest.end(), s->vertices.begin() + r.first_vertex, s->vertices.begin() + r.first_vertex + r.num_vertices);
+    s->skinPosed.resize(s->skinRest.size() + 1);      // (+ 1: a pointer that is not null for a set without vertices)
+    if (zrh_skin_pose(&s->anim, &s->skin, t, s->skinRest.data(), s->skinPosed.data())) return nullptr;
+    return s->skinPosed.data();
+}
+void zrh_scene_data_set_device_skinning(zrh_scene_data* s, int on) { if (s) s->deviceSkinning = on != 0; }
+int zrh_scene_data_device_skinning(const zrh_scene_data* s) { return s && s->deviceSkinning ? 1 : 0; }
 int zrh_scene_data_animate(zrh_scene_data* s, float t)
 {
     if (!s || !s->hasAnim) { g_err = "zrh_scene_data_animate: no animation set"; return -1; }

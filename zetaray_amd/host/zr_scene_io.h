@@ -71,6 +71,25 @@ int zrh_scene_data_device_records(const zrh_scene_data* s);
 int zrh_scene_data_set_animation(zrh_scene_data* s, const zr_anim_desc* desc);
 const zr_anim_desc* zrh_scene_data_animation(const zrh_scene_data* s);
 int zrh_scene_data_animate(zrh_scene_data* s, float t);
+// ---- skinned meshes.  zrh_gltf_load reads "skins", JOINTS_0 (unsigned bytes / shorts) and WEIGHTS_0 (floats, normalised unsigned bytes / shorts;
+// renormalised to sum 1 in float32).  A node with a mesh and a skin: every primitive gets a vertex range of its own (a copy: nothing is shared with
+// another node that uses the mesh), the instance's world matrix is the identity (glTF ignores a skinned node's own transform) and the instance is not
+// listed in the animation.  The joints of a used skin and their ancestors join the dynamic closure; the inverse bind matrices take the node matrices'
+// handedness rule.  zrh_scene_data_skinning returns the tables (zr_scene_set_skinning takes them after zr_scene_set_animation), null for a file
+// without a skinned node.  Refused by name and reason: a skin whose joints are not nodes of the file (or not in the scene's hierarchy), JOINTS_0
+// without WEIGHTS_0 or the other way round, JOINTS_1 / WEIGHTS_1, a joint index >= the skin's joint count, weights without a positive finite sum, a
+// skinned primitive with an emissive material, a skin in a file with no animation
+const zr_skin_desc* zrh_scene_data_skinning(const zrh_scene_data* s);
+// ... and for a scene that did not come from a file: a deep copy of `desc` (null or empty clears), after zrh_scene_data_set_animation, refused (-1) for what
+// zr_scene_set_skinning refuses as invalid; zrh_scene_data_set_animation clears a skin, as zr_scene_set_animation does.
+// zrh_scene_data_skin_pose(s, t) is the HOST FORM of a frame's skinning: zrh_skin_pose (below) on this scene's tables and on its vertices, which keep the
+// rest pose; returns the posed records of the ranges, range after range (valid until the next call), null without a skin.
+// zrh_scene_data_set_device_skinning: which of the two zrh_scene_animate (zr_host.h) takes for the skin: 0 (default) the host form, handed over with
+// zr_scene_update_vertices_async; 1 zr_scene_set_skinning once, then the time alone (it takes effect together with zrh_scene_data_set_device_animation)
+int zrh_scene_data_set_skinning(zrh_scene_data* s, const zr_skin_desc* desc);
+const zr_vertex* zrh_scene_data_skin_pose(zrh_scene_data* s, float t);
+void zrh_scene_data_set_device_skinning(zrh_scene_data* s, int on);
+int zrh_scene_data_device_skinning(const zrh_scene_data* s);
 // which of the two zrh_scene_animate (zr_host.h) takes: 0 (default) the host path above, 1 zr_scene_animate_async
 void zrh_scene_data_set_device_animation(zrh_scene_data* s, int on);
 int zrh_scene_data_device_animation(const zrh_scene_data* s);
@@ -83,6 +102,11 @@ int zrh_scene_data_from_desc(const zr_scene_desc* desc, const zr_emissive_triang
 void zrh_decompose_srt(const float* to_world_3x4, float* scale3, float* quat4, float* translation3);
 // affineTransformation(s, q, t) x parent (both 3 x 4 row-major, column-vector convention; parent may be null = identity)
 void zrh_compose_world(const float* scale3, const float* quat4, const float* translation3, const float* parent_3x4, float* out_3x4);
+// the HOST FORM of skinning (include/zr_skin.h; zr_skin_desc: include/zr_wire.h), the definition zr_scene_animate on a scene with a skin set is held to byte
+// for byte: the node matrices of `anim` at time t (include/zr_anim.h), the joint matrices, then every listed vertex.  rest / out: the records of the
+// ranges, range after range; the caller hands `out` to zr_scene_update_vertices range by range.  -1 (zrh_scene_io_last_error()) for tables
+// zr_scene_set_skinning would refuse
+int zrh_skin_pose(const zr_anim_desc* anim, const zr_skin_desc* skin, float t, const zr_vertex* rest, zr_vertex* out);
 // TLAS::FillMeshInstanceData for a static instance: rotation / scale / translation (+ prev_* = current, d_translation = 0)
 void zrh_fill_mesh_instance(const float* to_world_3x4, zr_mesh_instance* inst);
 // RT::EmissiveTriangle(v0, v1, v2, uv0..2, factor RGB8, texture, half strength bits, id, double sided)

@@ -541,6 +541,22 @@ LOAD_KEEP_COMPRESSED = 1      # ZRH_LOAD_KEEP_COMPRESSED
 LOAD_JPEG = 2      # ZRH_LOAD_JPEG
 
 
+def skin_pose(anim, skin, rest, t):
+    """zrh_skin_pose: the host form of skinning -- the rest records of skin's ranges (range after range; wire.VERTEX) posed for time t by include/zr_anim.h
+    and include/zr_skin.h on the host; anim / skin: wire.AnimDesc / wire.SkinDesc"""
+    import ctypes as C
+    L = _sceneio_lib()
+    L.zrh_skin_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+    rest = np.ascontiguousarray(rest, wire.VERTEX).reshape(-1)
+    if len(rest) != int(skin.ranges["num_vertices"].sum()):
+        raise ValueError(f"skin_pose: {len(rest)} rest records, the ranges list {int(skin.ranges['num_vertices'].sum())} vertices")
+    out = np.zeros(len(rest), wire.VERTEX)
+    a, k = anim.c_desc(), skin.c_desc()
+    if L.zrh_skin_pose(C.addressof(a), C.addressof(k), float(t), rest.ctypes.data if len(rest) else None, out.ctypes.data if len(rest) else None) != 0:
+        raise ValueError(L.zrh_scene_io_last_error().decode())
+    return out
+
+
 def mip_generate(descs, texels):
     """zrh_mip_generate: levels 1 .. of the chains `descs` (wire.TEXTURE_DESC) names in `texels` (uint8, contiguous), in place, from their level 0"""
     import ctypes as C
@@ -623,6 +639,8 @@ def load_gltf_native(path, rho=None, textures="decoded", jpeg=False):
     nodes, DDS material textures decoded to the texel heap, PNG ones with their mip chain generated by include/zr_mipgen.h).  Returns (Scene, texture-table offsets dict for set_texture_heap_offsets).
     A file with "animations" (LINEAR translation / rotation / scale channels) also gives sc.animation, a wire.AnimDesc over the dynamic closure of
     its node hierarchy (Scene.set_animation / Scene.animate in api.py), and sc.emissives_initial, the object-space light records; None without.
+    A file with skinned nodes ("skins", JOINTS_0 / WEIGHTS_0) also gives sc.skinning, a wire.SkinDesc over the animation's node table (Scene.set_skinning,
+    after Scene.set_animation); None without.
     textures="compressed": the .dds payloads are not decoded (ZRH_LOAD_KEEP_COMPRESSED): sc.texels stays empty, sc.texture_sources / sc.texture_payload
     carry the blocks and api.Scene decodes them on the device (zr_scene_create_compressed); sc.decode_textures() makes the texels on the host.
     A .png image travels as its level 0 (wire.TEX_SRC_RAW_MIP0) and its other levels are generated on the device.
@@ -674,6 +692,14 @@ def load_gltf_native(path, rho=None, textures="decoded", jpeg=False):
             L.zrh_scene_data_initial_emissives.restype = C.c_void_p
             L.zrh_scene_data_initial_emissives.argtypes = [C.c_void_p]
             sc.emissives_initial = arr(L.zrh_scene_data_initial_emissives(h), d.num_emissives, wire.EMISSIVE_TRI)
+        sc.skinning = None
+        L.zrh_scene_data_skinning.argtypes = [C.c_void_p]
+        L.zrh_scene_data_skinning.restype = C.POINTER(wire.SkinDescC)
+        k = L.zrh_scene_data_skinning(h)
+        if k:
+            k = k.contents
+            sc.skinning = wire.SkinDesc(arr(k.joints, k.num_joints, wire.SKIN_JOINT), arr(k.ranges, k.num_ranges, wire.SKIN_RANGE),
+                                        arr(k.influences, k.num_influences, wire.SKIN_INFLUENCE))
         offs = (C.c_uint32 * 4)()
         L.zrh_scene_data_tex_offsets(h, offs)
         return sc, dict(base_color=offs[0], normal=offs[1], metallic_roughness=offs[2], emissive=offs[3])

@@ -78,6 +78,11 @@ KEYFRAME = np.dtype([("scale", "<f4", 3), ("rotation", "<f4", 4), ("translation"
 ANIM_NODE = np.dtype([("parent", "<u4"), ("first_key", "<u4"), ("num_keys", "<u4"), ("loop", "<u4"), ("t0", "<f4"), ("rest_scale", "<f4", 3),
                       ("rest_rotation", "<f4", 4), ("rest_translation", "<f4", 3), ("parent_world", "<f4", 12)])
 assert KEYFRAME.itemsize == 44 and ANIM_NODE.itemsize == 108
+# skinned meshes (zr_skin_joint / zr_skin_influence / zr_skin_range / zr_skin_desc, include/zr_wire.h)
+SKIN_JOINT = np.dtype([("node", "<u4"), ("inverse_bind", "<f4", 12)])
+SKIN_INFLUENCE = np.dtype([("joint", "<u2", 4), ("weight", "<f4", 4)])
+SKIN_RANGE = np.dtype([("first_vertex", "<u4"), ("num_vertices", "<u4"), ("first_influence", "<u4")])
+assert SKIN_JOINT.itemsize == 52 and SKIN_INFLUENCE.itemsize == 24 and SKIN_RANGE.itemsize == 12
 
 GB_PLANE_NAMES = ["base_color", "normal", "metallic_roughness", "motion_vector", "emissive_color", "ior", "coat",
                   "depth", "tri_diff_geo_a", "tri_diff_geo_b"]
@@ -129,6 +134,28 @@ class AnimDesc:
         d.nodes, d.num_nodes = self.nodes.ctypes.data, len(self.nodes)
         d.keys, d.num_keys = self.keys.ctypes.data, len(self.keys)
         d.instance_idx, d.instance_node, d.num_instances = self.instance_idx.ctypes.data, self.instance_node.ctypes.data, len(self.instance_idx)
+        return d
+
+
+class SkinDescC(C.Structure):
+    _fields_ = [("joints", C.c_void_p), ("num_joints", C.c_uint32), ("ranges", C.c_void_p), ("num_ranges", C.c_uint32),
+                ("influences", C.c_void_p), ("num_influences", C.c_uint32)]
+
+
+class SkinDesc:
+    """zr_skin_desc over numpy arrays it keeps alive: joints (SKIN_JOINT; node = an entry of the AnimDesc's node table), ranges (SKIN_RANGE) and
+    influences (SKIN_INFLUENCE; vertex first_vertex + k of a range takes influences[first_influence + k])"""
+
+    def __init__(self, joints, ranges, influences):
+        self.joints = np.ascontiguousarray(joints, SKIN_JOINT).reshape(-1)
+        self.ranges = np.ascontiguousarray(ranges, SKIN_RANGE).reshape(-1)
+        self.influences = np.ascontiguousarray(influences, SKIN_INFLUENCE).reshape(-1)
+
+    def c_desc(self):
+        d = SkinDescC()
+        d.joints, d.num_joints = (self.joints.ctypes.data if len(self.joints) else None), len(self.joints)
+        d.ranges, d.num_ranges = (self.ranges.ctypes.data if len(self.ranges) else None), len(self.ranges)
+        d.influences, d.num_influences = (self.influences.ctypes.data if len(self.influences) else None), len(self.influences)
         return d
 
 
