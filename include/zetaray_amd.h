@@ -443,7 +443,7 @@ int zr_scene_animate(zr_scene* scene, float t);
  * (zr_scene_update_instances, zr_scene_move_instances with n_moved == 0 included, zr_scene_animate): every such update refits from the vertex buffer.
  * A render between the two traces the old triangles and shades them with the new attributes.  Emissive records are not touched: a deformed light keeps
  * shining from its rest pose.  The host's copy of the vertices follows (once a background build in flight, which reads it, is done: no call waits).
- * A range that a skin set covers is rewritten by the next zr_scene_animate from the set's rest records: what this call put there does not last.
+ * A range that a skin set or a morph set covers is rewritten by the next zr_scene_animate from the set's rest records: what this call put there does not last.
  * Refused, with nothing changed: a range past the scene's vertices, a null pointer with count > 0 (ZR_ERR_INVALID_ARG); ZR_SCENE_UPDATE=rebuild /
  * rebuild_host (ZR_ERR_UNSUPPORTED).  zr_scene_update_vertices = _async on the null stream, then wait.  zr_scene_get_vertices reads the device's
  * vertices back after waiting for `hip_stream`, for tests and tools.
@@ -471,6 +471,29 @@ int zr_scene_update_vertices(zr_scene* scene, uint32_t first, uint32_t count, co
 int zr_scene_get_vertices(const zr_scene* scene, void* hip_stream, zr_vertex* out, uint32_t first, uint32_t count);
 int zr_scene_set_skinning(zr_scene* scene, const zr_skin_desc* desc);
 int zr_scene_has_skinning(const zr_scene* scene);      /* 1 while a skin set is in place (zr_scene_set_skinning succeeded and nothing has cleared it), else 0 */
+/* Morph targets (glTF blend shapes).  zr_scene_set_morph (a host call, after zr_scene_set_animation and, where a range is also skinned, after
+ * zr_scene_set_skinning) takes a zr_morph_desc (zr_wire.h): weight tracks over time, targets with POSITION / NORMAL / TANGENT deltas, vertex ranges.  It
+ * uploads the tables once and keeps the rest-pose records of the morph-only ranges -- the vertices as they are at the call, or as the set it replaces
+ * found them -- in a device buffer of its own; a range that is also a range of the skin set uses the skin set's rest records.  It replaces an earlier
+ * set; a null or empty desc clears the set and puts the rest pose back (vertex buffer and hit tables; the acceleration structure follows with the next
+ * instance update).  zr_scene_set_animation and zr_scene_set_skinning on a scene with a morph set clear it the same way.
+ * There is no new per-frame call: with a set, zr_scene_animate_async(scene, stream, t) also samples the weights (k_morph_weights) and poses the morph
+ * ranges (k_morph_vertices, zr_tu_morph.hip; the arithmetic of include/zr_morph.h) between the node matrices and the move / refit tail.  A range that is
+ * morphed and skinned is posed once, by the fused kernel: the morphed record, with its encoded words, is the rest record the skin blend takes.  In every
+ * device byte -- vertex buffer, both hit tables, both instance buffers, object-to-world matrices, emissive records, BVH -- it equals the host sequence
+ *   1. zrh_scene_data_animate(t),
+ *   2. zr_scene_update_vertices_async with the vertices include/zr_morph.h computes on the host for time t, followed by include/zr_skin.h where the range
+ *      is skinned,
+ *   3. the host-form emissive and instance updates.
+ * The host's copy of the vertices keeps the rest pose (topology only).  A range handed to zr_scene_update_vertices that a morph set covers is rewritten
+ * by the next zr_scene_animate.  Caller guarantee: a morphed normal or tangent is not the zero vector (else its code words are unspecified; nothing
+ * else is).  The byte equivalence holds for the contract build, not for -DZR_ARITH_FAST.  Motion vectors carry no deformation, as with skinning.
+ * Refused, with nothing changed: no animation set (ZR_ERR_NOT_INITIALIZED); what zrmo::ValidateMorph lists (ZR_ERR_INVALID_ARG): a null table with a
+ * non-zero count; a range past the scene's vertices, past a delta pool or past the target table; a track past its pools or a range naming no track;
+ * morph ranges that overlap; a morph range that meets a skin range without being equal to it; num_targets unequal to the track's; num_keys == 1; key
+ * times not finite or not strictly increasing; a weight, rest weight, t0 or delta that is not finite. */
+int zr_scene_set_morph(zr_scene* scene, const zr_morph_desc* desc);
+int zr_scene_has_morph(const zr_scene* scene);         /* 1 while a morph set is in place, else 0 */
 /* Read-backs for tests and tools, after waiting for `hip_stream` (pass the stream of the last update).  which: 0 = the current instance buffer,
  * 1 = the previous one (the current one while the scene has never been updated); to_world_or_null: n x 12 floats. */
 int zr_scene_get_instances(const zr_scene* scene, void* hip_stream, int which, zr_mesh_instance* out, float* to_world_or_null, uint32_t n);

@@ -311,6 +311,53 @@ static_assert(sizeof(zr_skin_range) == 12, "zr_skin_range");
 static_assert(sizeof(zr_skin_desc) == 48, "zr_skin_desc");
 #endif
 
+/*
+ * Morph targets (zr_scene_set_morph, zetaray_amd.h; the arithmetic is include/zr_morph.h).  zr_morph_track: the weights of num_targets targets over time --
+ * key k (k < num_keys; 0 keys, or >= 2) has the time times[first_key + k] and the weights values[first_value + k * num_targets + j]; with 0 keys the weights
+ * are rest_weights[first_rest + j] at every time; loop and t0 as zr_anim_node's.  zr_morph_target: where the target's POSITION / NORMAL / TANGENT deltas
+ * start in the one pool of float triples (ZR_MORPH_NONE: the target has none of that attribute); vertex v of a range reads triple first_* + v.
+ * zr_morph_range: vertices [first_vertex, first_vertex + num_vertices) of the scene take targets [first_target, first_target + num_targets) under the
+ * weights of `track`, whose num_targets is the range's.  Ranges do not overlap; several may share a track, or targets.  Like the animation and skin records,
+ * these have no counterpart in the reference and are not listed by zr_wire_layout.
+ */
+#define ZR_MORPH_NONE 0xffffffffu
+typedef struct zr_morph_track {
+    uint32_t num_targets;
+    uint32_t first_key;
+    uint32_t num_keys;
+    uint32_t first_value;
+    uint32_t first_rest;
+    uint32_t loop;
+    float    t0;
+} zr_morph_track;
+typedef struct zr_morph_target {
+    uint32_t first_pos;
+    uint32_t first_nrm;
+    uint32_t first_tan;
+} zr_morph_target;
+typedef struct zr_morph_range {
+    uint32_t first_vertex;
+    uint32_t num_vertices;
+    uint32_t first_target;
+    uint32_t num_targets;
+    uint32_t track;
+} zr_morph_range;
+typedef struct zr_morph_desc {
+    const zr_morph_track*  tracks;        uint32_t num_tracks;
+    const zr_morph_target* targets;       uint32_t num_targets;
+    const zr_morph_range*  ranges;        uint32_t num_ranges;
+    const float*           times;         uint32_t num_times;
+    const float*           values;        uint32_t num_values;
+    const float*           rest_weights;  uint32_t num_rest_weights;
+    const float*           deltas;        uint32_t num_deltas;      /* float triples */
+} zr_morph_desc;
+#ifdef __cplusplus
+static_assert(sizeof(zr_morph_track) == 28, "zr_morph_track");
+static_assert(sizeof(zr_morph_target) == 12, "zr_morph_target");
+static_assert(sizeof(zr_morph_range) == 20, "zr_morph_range");
+static_assert(sizeof(zr_morph_desc) == 112, "zr_morph_desc");
+#endif
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 #   mipgen [ARGS]      tools/mipgen_bench.py: zr_scene_create_compressed with full RAW chains against RAW_MIP0 sources (mips generated on the device) -> ${TAG}_mipgen.json
 #   jpeg [ARGS]        tools/jpeg_decode_bench.py: JPEG files decoded on the host and uploaded as RAW_MIP0 against their coefficient records decoded on the device (JPEG_COEF) -> ${TAG}_jpeg_decode.json
 #   skin [ARGS]        tools/refit_bench.py --skin: a skinned tube posed by the host form against zr_scene_animate with the skin set -> ${TAG}_scene_skin.json
+#   morph [ARGS]       tools/refit_bench.py --morph: a tube under 8 morph targets posed by the host form against zr_scene_animate with the morph set -> ${TAG}_scene_morph.json
 #   prof LIB           section profiler (-DZR_PROF build LIB) on Cornell + atrium -> ${TAG}_section_profile_*.json
 R=${GRAFT_REPO_ROOT:-$PWD}; TAG=${TAG:-r06}; OUT=$R/gpurun_out; mkdir -p $OUT
 task=$1; shift
@@ -122,6 +123,10 @@ jpeg)
 skin)
   cd $R; set -o pipefail
   timeout 1100 python tools/refit_bench.py --skin "$@" 2> $OUT/${TAG}_skin_err.log | tail -1 | tee $OUT/${TAG}_scene_skin.json || { echo "refit_bench --skin: requirement missed or failed"; tail -5 $OUT/${TAG}_skin_err.log; exit 1; }
+  ;;
+morph)
+  cd $R; set -o pipefail
+  timeout 1100 python tools/refit_bench.py --morph "$@" 2> $OUT/${TAG}_morph_err.log | tail -1 | tee $OUT/${TAG}_scene_morph.json || { echo "refit_bench --morph: requirement missed or failed"; tail -5 $OUT/${TAG}_morph_err.log; exit 1; }
   ;;
 *) echo "unknown task $task"; exit 2;;
 esac

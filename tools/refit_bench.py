@@ -19,7 +19,14 @@ at N by more than the smaller run's p10 - p90 spread, or (B)'s stream time is lo
 brings it to the larger one's triangle count, as under --animate).  (A) the host form: zrh_skin_pose on the host, zr_scene_update_vertices_async, then
 the host-form instance update; (B) zr_scene_animate_async with the skin set; (C) the same animation without a skin, whose stream time taken from (B)'s
 leaves the two skin kernels' own, reported next to the bytes they must move (28 + 24 in, 28 + 16 out per vertex).  Same statistics, same JSON line,
-exit status 1 under the same two conditions on (B), or when the twin scenes' vertex buffers differ."""
+exit status 1 under the same two conditions on (B), or when the twin scenes' vertex buffers differ.
+
+--morph: the same tube of N vertices (--vertices N and 16 N, the clutter as above) under 8 morph targets, each with POSITION and NORMAL deltas, driven by
+one looping track of 3 keys.  (A) the host form: zrh_morph_pose on the host, zr_scene_update_vertices_async, then the host-form instance update;
+(B) zr_scene_animate_async with the morph set, in two variants: all 8 weights non-zero at every time, and 1 of 8 non-zero (the other 7 targets are
+skipped: no loads); (C) the same animation without the set, whose stream time taken from (B)'s leaves the morph kernels' own, reported next to the
+bytes they must move (28 in, 28 + 16 out and 24 per applied target per vertex).  Same statistics, same JSON line; exit status 1 when (B)'s host time
+at 16 N exceeds that at N by more than the smaller run's p10 - p90 spread, or when the twin scenes' vertex buffers differ."""
 import json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -396,19 +403,98 @@ def skin(n_small, frames, warmup):
     return 0 if ok else 1
 
 
+def _tube_morph(n_verts, applied, num_targets=8):
+    """one node that moves nothing (an animation to set), and a morph set over the tube: num_targets targets with POSITION and NORMAL deltas under one looping
+    track of 3 keys whose first `applied` targets have non-zero weights at every time, the others exact zeros"""
+    rng = np.random.default_rng(7)
+    nodes, keys = np.zeros(1, wire.ANIM_NODE), np.zeros(2, wire.KEYFRAME)
+    nodes["parent"], nodes["num_keys"], nodes["loop"] = wire.ANIM_ROOT, 2, 1
+    nodes["rest_scale"], nodes["rest_rotation"], nodes["parent_world"] = 1, (0, 0, 0, 1), np.float32([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0])
+    keys["rotation"], keys["scale"], keys["time"] = (0, 0, 0, 1), 1, np.float32([0.0, 1.0])
+    anim = wire.AnimDesc(nodes, keys, [], [])
+    values = rng.uniform(0.1, 1.0, (3, num_targets)).astype(np.float32)
+    values[:, applied:] = 0.0
+    track = np.zeros(1, wire.MORPH_TRACK)
+    track["num_targets"], track["num_keys"], track["loop"] = num_targets, 3, 1
+    targets = np.zeros(num_targets, wire.MORPH_TARGET)
+    targets["first_pos"], targets["first_nrm"], targets["first_tan"] = 2 * n_verts * np.arange(num_targets), 2 * n_verts * np.arange(num_targets) + n_verts, wire.MORPH_NONE
+    deltas = rng.uniform(-0.02, 0.02, (2 * num_targets * n_verts, 3)).astype(np.float32)
+    return anim, wire.MorphDesc(track, targets, np.array([(0, n_verts, 0, num_targets, 0)], wire.MORPH_RANGE), np.float32([0.0, 0.5, 1.0]), values, np.zeros(num_targets, np.float32), deltas)
+
+
+def morph(n_small, frames, warmup):
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import bench
+    out = {"mode": "morph", "frames": frames, "warmup": warmup, "library": os.path.basename(api.LIB_PATH), "device_state": bench.device_state(api, 0), "targets": 8, "sizes": []}
+    n_large, raw = 16 * n_small, {}
+    for nv in (n_small, n_large):
+        sc = _tube_scene(nv, 2 * (n_large - nv))
+        anim, m8 = _tube_morph(nv, 8)
+        _, m1 = _tube_morph(nv, 1)
+        rest = sc.vertices[:nv].copy()
+        A, B8, B1, Cn = api.Scene(sc), api.Scene(sc), api.Scene(sc), api.Scene(sc)
+        for S, m in ((B8, m8), (B1, m1)):
+            S.set_animation(anim); S.set_morph(m)
+        Cn.set_animation(anim)
+        st = torch.cuda.Stream()
+
+        def host_form(t):
+            A.update_vertices(0, scene_io.morph_pose(anim, None, m8, rest, t), stream=st.cuda_stream)
+            A.update_instances(sc.instances, sc.instance_to_world, stream=st.cuda_stream)
+
+        res = {"morphed_vertices": nv, "num_tris": int(sc.num_tris), "bvh": list(A.bvh_info())}
+        for name, fn in (("A_host_form", host_form), ("B_scene_animate_8_of_8", lambda t: B8.animate(t, stream=st.cuda_stream)),
+                         ("B_scene_animate_1_of_8", lambda t: B1.animate(t, stream=st.cuda_stream)), ("C_animate_without_morph", lambda t: Cn.animate(t, stream=st.cuda_stream))):
+            wall, stream_ms = [], []
+            for k in range(1, warmup + frames + 1):
+                t = 0.013 * k
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record(st)
+                a = time.perf_counter()
+                fn(t)
+                b = time.perf_counter()
+                e1.record(st)
+                torch.cuda.synchronize()
+                if k > warmup:
+                    wall.append((b - a) * 1e3); stream_ms.append(e0.elapsed_time(e1))
+            res[name] = {"host_wall_ms": _stats(wall), "stream_ms": _stats(stream_ms)}
+            raw[(nv, name)] = (np.asarray(wall, np.float64), np.asarray(stream_ms, np.float64))
+        res["same_device_bytes"] = bool(A.download_vertices().tobytes() == B8.download_vertices().tobytes())
+        for name, applied in (("8_of_8", 8), ("1_of_8", 1)):
+            kern_ms = res["B_scene_animate_" + name]["stream_ms"]["median"] - res["C_animate_without_morph"]["stream_ms"]["median"]
+            moved = nv * (28 + 28 + 16 + 24 * applied)
+            res["morph_kernels_stream_ms_" + name] = round(kern_ms, 4)
+            res["morph_kernels_bytes_" + name] = int(moved)
+            res["morph_kernels_gb_per_s_" + name] = round(moved / (kern_ms * 1e-3) / 1e9, 1) if kern_ms > 0 else None
+        res["host_wall_ratio_A_over_B"] = round(res["A_host_form"]["host_wall_ms"]["median"] / res["B_scene_animate_8_of_8"]["host_wall_ms"]["median"], 2)
+        out["sizes"].append(res)
+        A.close(); B8.close(); B1.close(); Cn.close()
+    small, large = raw[(n_small, "B_scene_animate_8_of_8")][0], raw[(n_large, "B_scene_animate_8_of_8")][0]
+    growth, spread = float(np.median(large) - np.median(small)), float(np.percentile(small, 90) - np.percentile(small, 10))
+    out["B_host_wall_growth_ms"], out["small_p10_p90_spread_ms"], out["B_host_wall_flat"] = growth, spread, bool(growth <= spread)
+    ok = out["B_host_wall_flat"] and all(r["same_device_bytes"] for r in out["sizes"])
+    print(json.dumps(out))
+    return 0 if ok else 1
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--device-records", action="store_true")
     ap.add_argument("--animate", action="store_true")
     ap.add_argument("--skin", action="store_true")
+    ap.add_argument("--morph", action="store_true")
     ap.add_argument("--vertices", type=int, default=65536)
     ap.add_argument("--instances", type=int, default=4096)
     ap.add_argument("--emissive", type=int, default=100000)
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=16)
     a = ap.parse_args()
-    if a.skin:
+    if a.morph:
+        sys.exit(morph(a.vertices, max(a.frames, 64), max(a.warmup, 16)))
+    elif a.skin:
         sys.exit(skin(a.vertices, max(a.frames, 64), max(a.warmup, 16)))
     elif a.animate:
         sys.exit(animate(a.instances, max(a.frames, 64), max(a.warmup, 16)))

@@ -64,7 +64,7 @@ EXPORTS = [
     "zr_pass_set_rgi_spatial",
     "zr_scene_set_object_emissives", "zr_scene_has_object_emissives", "zr_scene_move_instances", "zr_scene_move_instances_async", "zr_scene_get_instances", "zr_scene_get_emissives",
     "zr_scene_set_animation", "zr_scene_animate", "zr_scene_animate_async",
-    "zr_scene_update_vertices", "zr_scene_update_vertices_async", "zr_scene_get_vertices", "zr_scene_set_skinning", "zr_scene_has_skinning",
+    "zr_scene_update_vertices", "zr_scene_update_vertices_async", "zr_scene_get_vertices", "zr_scene_set_skinning", "zr_scene_has_skinning", "zr_scene_set_morph", "zr_scene_has_morph",
     "zr_scene_set_alias_build", "zr_alias_table_build_device", "zr_pass_get_emissive_powers",
     "zr_scene_create_compressed", "zr_bcn_decode_device", "zr_scene_get_texels", "zr_mipgen_device", "zr_jpeg_decode_device",
 ]
@@ -126,6 +126,7 @@ def lib():
         L.zr_scene_get_presampled_sets.argtypes = [vp, vp, vp, u32]
         L.zr_scene_bvh_info.argtypes = [vp, vp, vp, vp]
         L.zr_scene_has_skinning.argtypes = [vp]
+        L.zr_scene_has_morph.argtypes = [vp]
         L.zr_gbuffer_create.argtypes = [i32, u32, u32, vp]
         L.zr_gbuffer_destroy.argtypes = [vp]
         L.zr_gbuffer_set_tile_origin.argtypes = [vp, u32, u32]
@@ -329,11 +330,11 @@ class Scene:
         L.zr_scene_set_animation.argtypes = [C.c_void_p, C.c_void_p]
         if desc is None:
             _check(L.zr_scene_set_animation(self.h, None))
-            self._anim = self._skin = None      # (a skin goes with the animation it was set on)
+            self._anim = self._skin = self._morph = None      # (a skin and a morph set go with the animation they were set on)
             return
         d = desc.c_desc()
         _check(L.zr_scene_set_animation(self.h, C.addressof(d)))
-        self._anim, self._skin = desc, None
+        self._anim, self._skin, self._morph = desc, None, None
 
     def animate(self, t, stream=False):
         """the frame's scene update from the time alone (zr_scene_animate): the animation is sampled, composed down the hierarchy and applied on the
@@ -351,7 +352,7 @@ class Scene:
 
     def update_vertices(self, first, vertices, stream=False):
         """vertices [first, first + len(vertices)) replaced (zr_scene_update_vertices; wire.VERTEX records): the hit tables follow at once, the acceleration
-        structure with the frame's instance update of any form.  A range a skin set covers is rewritten by the next animate().  stream as update_instances"""
+        structure with the frame's instance update of any form.  A range a skin set or a morph set covers is rewritten by the next animate().  stream as update_instances"""
         L = lib()
         v = np.ascontiguousarray(vertices, wire.VERTEX).reshape(-1)
         vp = v.ctypes.data if len(v) else None
@@ -383,12 +384,30 @@ class Scene:
         else:
             d = desc.c_desc()
             _check(L.zr_scene_set_skinning(self.h, C.addressof(d)))
-        self._skin = desc
+        self._skin, self._morph = desc, None      # (a morph set is laid out against the skin set it was set after: it goes)
         self.version += 1
 
     def has_skinning(self):
         """is a skin set in place (zr_scene_has_skinning)?"""
         return bool(lib().zr_scene_has_skinning(self.h))
+
+    def set_morph(self, desc):
+        """morph targets (zr_scene_set_morph): a wire.MorphDesc -- weight tracks, targets with their deltas, vertex ranges -- uploaded once, after set_animation
+        and (where a range is also skinned) set_skinning; every animate() then samples the weights and poses the ranges on the device.  None (or an empty
+        one) clears and puts the rest pose back"""
+        L = lib()
+        L.zr_scene_set_morph.argtypes = [C.c_void_p, C.c_void_p]
+        if desc is None:
+            _check(L.zr_scene_set_morph(self.h, None))
+        else:
+            d = desc.c_desc()
+            _check(L.zr_scene_set_morph(self.h, C.addressof(d)))
+        self._morph = desc
+        self.version += 1
+
+    def has_morph(self):
+        """is a morph set in place (zr_scene_has_morph)?"""
+        return bool(lib().zr_scene_has_morph(self.h))
 
     def download_instances(self, which=0, stream=None):
         """(MeshInstance records, (n, 12) object-to-world matrices) as the device holds them; which: 0 current, 1 previous"""
@@ -887,6 +906,10 @@ class Renderer:
     def set_skinning(self, desc):
         """skinned meshes (Scene.set_skinning), after set_animation"""
         self.scene.set_skinning(desc)
+
+    def set_morph(self, desc):
+        """morph targets (Scene.set_morph), after set_animation and set_skinning"""
+        self.scene.set_morph(desc)
 
     def animate(self, t, stream=False):
         """the frame's scene update from the time alone (Scene.animate)"""

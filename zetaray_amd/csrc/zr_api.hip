@@ -90,6 +90,11 @@ namespace zr { hipError_t LaunchAnimate(hipStream_t st, float t, const zr_anim_n
 namespace zr { using SkinRange = zrsk::DeviceRange;      // zr_tu_skin.hip
     hipError_t LaunchSkin(hipStream_t st, float* J, const float* nodeWorld, const uint32_t* jointNode, const float* inverseBind, uint32_t numJoints, const SkinRange* ranges,
         uint32_t numRanges, const zr_vertex* rest, const zr_skin_influence* influences, zr_vertex* vertices, VtxDir* vtxNormals, VtxDir* vtxTangents); }
+#include "../../include/zr_morph.h"
+namespace zr { using MorphRange = zrmo::DeviceRange;      // zr_tu_morph.hip
+    hipError_t LaunchMorph(hipStream_t st, float t, float* weights, uint32_t numWeights, const zr_morph_track* tracks, const uint32_t* trackOfWeight, const uint32_t* weightFirst,
+        const float* times, const float* values, const float* restWeights, const zr_morph_target* targets, const float* deltas, const MorphRange* ranges, uint32_t numRanges,
+        const zr_vertex* restOwn, const zr_vertex* restSkin, const zr_skin_influence* influences, const float* J, zr_vertex* vertices, VtxDir* vtxNormals, VtxDir* vtxTangents); }
 namespace zr { hipError_t LaunchFillInstRecs(hipStream_t st, InstRec* recs, const zr_mesh_instance* instances, uint32_t n);      // zr_tu_scene_update.hip
                hipError_t LaunchFillVtxNormals(hipStream_t st, VtxDir* out, const zr_vertex* vertices, uint32_t n, bool tangent); }
 namespace zr { size_t AliasScratchWords(uint32_t n);      // zr_tu_alias.hip
@@ -674,6 +679,18 @@ struct zr_scene
         DevBuf<uint32_t> dJointNode; DevBuf<float> dInverseBind, dJ; DevBuf<zr_skin_influence> dInfluences; DevBuf<zr_vertex> dRest;
     };
     std::unique_ptr<Skin> skin;
+    // ---- morph targets (zr_scene_set_morph; kernels in zr_tu_morph.hip, arithmetic in include/zr_morph.h): with a set, every zr_scene_animate also samples
+    // the tracks' weights into dWeights (track after track) and poses the listed ranges.  What set_morph lays out once: the tables, each weight's track
+    // and each track's first weight, the rest records of the morph-only ranges (range after range, hRest the host's copy; a clear puts it back) -- a
+    // range that is also a range of the skin set takes the skin set's rest records and is posed by the fused kernel alone: skinLeft are the skin
+    // ranges LaunchSkin still gets
+    struct Morph
+    {
+        std::vector<zr::MorphRange> ranges; std::vector<zr::SkinRange> skinLeft; std::vector<zr_vertex> hRest; uint32_t numWeights = 0;
+        DevBuf<zr_morph_track> dTracks; DevBuf<zr_morph_target> dTargets; DevBuf<uint32_t> dTrackOfWeight, dWeightFirst;
+        DevBuf<float> dTimes, dValues, dRestWeights, dDeltas, dWeights; DevBuf<zr_vertex> dRest;
+    };
+    std::unique_ptr<Morph> morph;
     // zr_scene_update_vertices while a background build reads hVertices: the ranges wait here and reach hVertices once the builder's thread is done
     // (SceneFlushVertexCopies) -- the builder delivers topology, so the pose it saw does not matter, and the call does not wait for it
     std::vector<std::pair<uint32_t, std::vector<zr_vertex>>> hVertexPending;
@@ -1942,15 +1959,24 @@ static int RefitWriteRecords(zr_scene* s, hipStream_t st, const FrameUpdate& u, 
             HIP_TRY(zr::LaunchAnimate(st, u.t, A.dNodes.p, A.dKeys.p, A.dAnimated.p, A.nAnimated, A.dLevelNodes.p, A.levelOffsets.data(),
                 (uint32_t)A.levelOffsets.size() - 1, A.dLocal.p, A.dWorld.p, A.dInstNode.p, u.nMoved, A.dMoved.p));
             movedList = A.dMoved.p;
+            VtxDir* tangents = nullptr;
+#if ZR_HIT_TANGENTS
+            tangents = s->vtxTangents.p;
+#endif
             if (s->skin)
             {   // the node matrices are on the device: joint matrices, then the listed vertices and their hit-table entries, ahead of the refit that reads them
+                // (with a morph set: only the ranges that are not morphed -- a morphed and skinned range is posed once, by the fused kernel below)
                 zr_scene::Skin& K = *s->skin;
-                VtxDir* tangents = nullptr;
-#if ZR_HIT_TANGENTS
-                tangents = s->vtxTangents.p;
-#endif
-                HIP_TRY(zr::LaunchSkin(st, K.dJ.p, A.dWorld.p, K.dJointNode.p, K.dInverseBind.p, K.numJoints, K.ranges.data(), (uint32_t)K.ranges.size(), K.dRest.p,
+                const std::vector<zr::SkinRange>& ranges = s->morph ? s->morph->skinLeft : K.ranges;
+                HIP_TRY(zr::LaunchSkin(st, K.dJ.p, A.dWorld.p, K.dJointNode.p, K.dInverseBind.p, K.numJoints, ranges.data(), (uint32_t)ranges.size(), K.dRest.p,
                     K.dInfluences.p, s->vertices.p, s->vtxNormals.p, tangents));
+            }
+            if (s->morph)
+            {   // the weights of time t, then the morph ranges from their rest records (the skin set's, its influences and the joint matrices just written, for a range that is also skinned)
+                zr_scene::Morph& M = *s->morph;
+                HIP_TRY(zr::LaunchMorph(st, u.t, M.dWeights.p, M.numWeights, M.dTracks.p, M.dTrackOfWeight.p, M.dWeightFirst.p, M.dTimes.p, M.dValues.p, M.dRestWeights.p,
+                    M.dTargets.p, M.dDeltas.p, M.ranges.data(), (uint32_t)M.ranges.size(), M.dRest.p, s->skin ? s->skin->dRest.p : nullptr,
+                    s->skin ? s->skin->dInfluences.p : nullptr, s->skin ? s->skin->dJ.p : nullptr, s->vertices.p, s->vtxNormals.p, tangents));
             }
         }
         else if (u.nMoved) HIP_TRY(hipMemcpyAsync(s->movedDev.p, h + F.seedBytes, F.listBytes, hipMemcpyHostToDevice, st));
@@ -2232,12 +2258,14 @@ int zr_scene_move_instances_async(zr_scene* s, void* stream, const uint32_t* ins
 }
 // ---- keyframe animation: the tables once (zr_scene_set_animation), then one float per frame (zr_scene_animate_async)
 static int SceneClearSkin(zr_scene* s);
+static int SceneClearMorph(zr_scene* s);
 int zr_scene_set_animation(zr_scene* s, const zr_anim_desc* d)
 {
     if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_animation: null scene");
     HIP_TRY(hipSetDevice(s->device));
     if (!d || (!d->num_nodes && !d->num_instances))
     {
+        if (int r = SceneClearMorph(s)) return r;     // (a morph set goes with the animation it was set on, ahead of the skin whose rest records it uses)
         if (int r = SceneClearSkin(s)) return r;      // (its joints are nodes of the table that goes)
         SceneAnimSyncHost(s);
         HIP_TRY(hipDeviceSynchronize());      // an animate in flight still reads the tables
@@ -2280,6 +2308,7 @@ int zr_scene_set_animation(zr_scene* s, const zr_anim_desc* d)
     // nothing of the scene has changed up to here.  The animation it replaces: its last frame reaches the host's matrices, its kernels finish
     SceneAnimSyncHost(s);
     HIP_TRY(hipDeviceSynchronize());
+    if ((r = SceneClearMorph(s))) return r;
     if ((r = SceneClearSkin(s))) return r;      // a skin belongs to the animation it was set on: its joints index the table this call replaces
     for (uint32_t i : A->instIdx) s->movedEver[i] = 1;      // the background builder gives each animated instance a subtree of its own
     std::lock_guard<std::mutex> lock(s->animMtx);
@@ -2388,7 +2417,7 @@ int zr_scene_set_skinning(zr_scene* s, const zr_skin_desc* d)
 {
     if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_skinning: null scene");
     HIP_TRY(hipSetDevice(s->device));
-    if (!d || (!d->num_joints && !d->num_ranges && !d->num_influences)) return SceneClearSkin(s);
+    if (!d || (!d->num_joints && !d->num_ranges && !d->num_influences)) { if (int r = SceneClearMorph(s)) return r; return SceneClearSkin(s); }
     uint32_t animNodes = 0;
     {
         std::lock_guard<std::mutex> lock(s->animMtx);
@@ -2397,6 +2426,7 @@ int zr_scene_set_skinning(zr_scene* s, const zr_skin_desc* d)
     }
     char msg[256];
     if (zrsk::ValidateSkin(*d, animNodes, (uint32_t)s->vertices.n, msg, sizeof(msg))) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_skinning: %s", msg);
+    if (int r = SceneClearMorph(s)) return r;      // a morph set is laid out against the skin set it was set after: it goes, and its ranges are at rest before the read-back below
     std::unique_ptr<zr_scene::Skin> K(new zr_scene::Skin());
     K->numJoints = d->num_joints;
     std::vector<uint32_t> jointNode(d->num_joints); std::vector<float> inverseBind(12 * (size_t)d->num_joints);
@@ -2427,6 +2457,88 @@ int zr_scene_set_skinning(zr_scene* s, const zr_skin_desc* d)
     // nothing of the scene has changed up to here
     if ((r = SceneClearSkin(s))) return r;
     s->skin = std::move(K);
+    return ZR_OK;
+}
+
+// ---- morph targets: the tables once (zr_scene_set_morph), then every zr_scene_animate samples the weights and poses the ranges
+int zr_scene_has_morph(const zr_scene* s) { return s && s->morph ? 1 : 0; }
+// the rest pose back into the listed ranges and their hit-table entries, host-synchronous; the set is dropped
+static int SceneClearMorph(zr_scene* s)
+{
+    if (!s->morph) return ZR_OK;
+    HIP_TRY(hipDeviceSynchronize());      // an animate in flight still reads the tables; renders in flight read the vertices
+    zr_scene::Morph& M = *s->morph;
+    for (const zr::MorphRange& g : M.ranges)
+    {
+        if (!g.numVertices) continue;
+        const zr_vertex* rest = g.skinned ? s->skin->hRest.data() + g.restFirst : M.hRest.data() + g.restFirst;
+        HIP_TRY(hipMemcpy(s->vertices.p + g.firstVertex, rest, (size_t)g.numVertices * sizeof(zr_vertex), hipMemcpyHostToDevice));
+        if (int r = SceneFillVtxTables(s, nullptr, g.firstVertex, g.numVertices)) return r;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    s->morph.reset();
+    return ZR_OK;
+}
+int zr_scene_set_morph(zr_scene* s, const zr_morph_desc* d)
+{
+    if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_morph: null scene");
+    HIP_TRY(hipSetDevice(s->device));
+    if (!d || (!d->num_tracks && !d->num_targets && !d->num_ranges)) return SceneClearMorph(s);
+    {
+        std::lock_guard<std::mutex> lock(s->animMtx);
+        if (!s->anim) return Fail(ZR_ERR_NOT_INITIALIZED, "zr_scene_set_morph: no animation set (zr_scene_set_animation): zr_scene_animate owns the frame's time");
+    }
+    // the skin set as a desc over its laid-out ranges: what the check and the fused kernel need of it
+    std::vector<zr_skin_range> skinRanges;
+    if (s->skin) for (const zr::SkinRange& g : s->skin->ranges) skinRanges.push_back(zr_skin_range{g.firstVertex, g.numVertices, g.firstInfluence});
+    zr_skin_desc skinDesc{};
+    skinDesc.ranges = skinRanges.data(); skinDesc.num_ranges = (uint32_t)skinRanges.size();
+    char msg[256];
+    if (zrmo::ValidateMorph(*d, s->skin ? &skinDesc : nullptr, (uint32_t)s->vertices.n, msg, sizeof(msg))) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_morph: %s", msg);
+    std::unique_ptr<zr_scene::Morph> M(new zr_scene::Morph());
+    std::vector<uint32_t> weightFirst(d->num_tracks), trackOfWeight;
+    M->numWeights = zrmo::WeightOffsets(*d, weightFirst.data());
+    for (uint32_t i = 0; i < d->num_tracks; i++) trackOfWeight.insert(trackOfWeight.end(), d->tracks[i].num_targets, i);
+    std::vector<uint8_t> skinTaken(skinRanges.size(), 0);
+    size_t restRecords = 0;
+    for (uint32_t i = 0; i < d->num_ranges; i++)
+    {
+        const zr_morph_range& g = d->ranges[i];
+        const int64_t sr = zrmo::SkinRangeOf(g, s->skin ? &skinDesc : nullptr);
+        if (sr >= 0)
+        {
+            skinTaken[sr] = 1;
+            M->ranges.push_back(zr::MorphRange{g.first_vertex, g.num_vertices, g.first_target, g.num_targets, weightFirst[g.track], s->skin->ranges[sr].restFirst, s->skin->ranges[sr].firstInfluence, 1u});
+        }
+        else
+        {
+            M->ranges.push_back(zr::MorphRange{g.first_vertex, g.num_vertices, g.first_target, g.num_targets, weightFirst[g.track], (uint32_t)restRecords, 0u, 0u});
+            restRecords += g.num_vertices;
+        }
+    }
+    if (s->skin) for (size_t q = 0; q < skinRanges.size(); q++) if (!skinTaken[q]) M->skinLeft.push_back(s->skin->ranges[q]);
+    // the rest records of the morph-only ranges: what they hold once the set this one replaces has put its own rest pose back (as zr_scene_set_skinning)
+    HIP_TRY(hipDeviceSynchronize());
+    M->hRest.assign(restRecords, zr_vertex{});
+    for (const zr::MorphRange& g : M->ranges)
+    {
+        if (!g.numVertices || g.skinned) continue;
+        HIP_TRY(hipMemcpy(M->hRest.data() + g.restFirst, s->vertices.p + g.firstVertex, (size_t)g.numVertices * sizeof(zr_vertex), hipMemcpyDeviceToHost));
+        if (s->morph) for (const zr::MorphRange& o : s->morph->ranges)
+        {
+            if (o.skinned) continue;      // (a morph-only range of the new set cannot meet a skin range)
+            const uint64_t lo = std::max(g.firstVertex, o.firstVertex), hi = std::min((uint64_t)g.firstVertex + g.numVertices, (uint64_t)o.firstVertex + o.numVertices);
+            if (hi > lo) std::copy(s->morph->hRest.begin() + o.restFirst + (lo - o.firstVertex), s->morph->hRest.begin() + o.restFirst + (hi - o.firstVertex), M->hRest.begin() + g.restFirst + (lo - g.firstVertex));
+        }
+    }
+    int r;
+    if ((r = M->dTracks.Upload(d->tracks, d->num_tracks)) || (r = M->dTargets.Upload(d->targets, d->num_targets)) ||
+        (r = M->dTrackOfWeight.Upload(trackOfWeight.data(), trackOfWeight.size())) || (r = M->dWeightFirst.Upload(weightFirst.data(), weightFirst.size())) ||
+        (r = M->dTimes.Upload(d->times, d->num_times)) || (r = M->dValues.Upload(d->values, d->num_values)) || (r = M->dRestWeights.Upload(d->rest_weights, d->num_rest_weights)) ||
+        (r = M->dDeltas.Upload(d->deltas, 3 * (size_t)d->num_deltas)) || (r = M->dWeights.Alloc(M->numWeights)) || (r = M->dRest.Upload(M->hRest.data(), M->hRest.size()))) return r;
+    // nothing of the scene has changed up to here
+    if ((r = SceneClearMorph(s))) return r;
+    s->morph = std::move(M);
     return ZR_OK;
 }
 

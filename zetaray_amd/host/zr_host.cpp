@@ -834,23 +834,44 @@ static int HandSkinnedVertices(zrh_scene_data* data, zr_scene* scene, void* stre
     }
     return 0;
 }
+// A morphed scene (zrh_scene_data_morph: a glTF with a weights channel, or zrh_scene_data_set_morph).  Host form: zrh_scene_data_morph_pose for time t --
+// include/zr_morph.h, then include/zr_skin.h where a range is skinned too -- handed over range by range like the skinned vertices, and after them (a range
+// with both is written twice on the stream; the second record stands).  After zrh_scene_data_set_device_morph(data, 1), on the device path:
+// zr_scene_set_morph once per device scene, behind its animation and skin tables.  A file with skinned AND morphed ranges takes the device form of both
+// or of neither: one kernel poses such a range.
+static int HandMorphedVertices(zrh_scene_data* data, zr_scene* scene, void* stream, float t)
+{
+    const zr_morph_desc* m = zrh_scene_data_morph(data);
+    const zr_vertex* posed = zrh_scene_data_morph_pose(data, t);
+    if (!posed) return -1;
+    for (uint32_t i = 0; i < m->num_ranges; i++)
+    {
+        if (const int r = zr_scene_update_vertices_async(scene, stream, m->ranges[i].first_vertex, m->ranges[i].num_vertices, posed)) return r;
+        posed += m->ranges[i].num_vertices;
+    }
+    return 0;
+}
 extern "C" int zrh_scene_animate(zrh_scene_data* data, zr_scene* scene, void* stream, float t)
 {
     if (!scene || !data || !zrh_scene_data_animation(data)) return -1;
     const zr_skin_desc* skin = zrh_scene_data_skinning(data);
+    const zr_morph_desc* morph = zrh_scene_data_morph(data);
     if (!zrh_scene_data_device_animation(data))
     {
         zrh_scene_data_begin_frame(data);
         if (zrh_scene_data_animate(data, t)) return -1;
         if (skin) { if (const int r = HandSkinnedVertices(data, scene, stream, t)) return r; }
+        if (morph) { if (const int r = HandMorphedVertices(data, scene, stream, t)) return r; }
         return zrh_scene_apply_updates_on(scene, data, stream);
     }
+    const bool devMorph = morph && zrh_scene_data_device_morph(data) && (!skin || zrh_scene_data_device_skinning(data));
+    const bool devSkin = skin && zrh_scene_data_device_skinning(data) && (!morph || devMorph);
     int r;
     auto handTables = [&]() -> int {
         if (!zr_scene_has_object_emissives(scene) && zrh_scene_data_initial_emissives(data))
             if (const int e = zr_scene_set_object_emissives(scene, zrh_scene_data_initial_emissives(data), zrh_scene_data_desc(data)->num_emissives)) return e;
         return zr_scene_set_animation(scene, zrh_scene_data_animation(data)); };
-    if (skin && zrh_scene_data_device_skinning(data))
+    if (devSkin)
     {
         if (!zr_scene_has_skinning(scene))
         {
@@ -860,6 +881,16 @@ extern "C" int zrh_scene_animate(zrh_scene_data* data, zr_scene* scene, void* st
         }
     }
     else if (skin) { if ((r = HandSkinnedVertices(data, scene, stream, t))) return r; }      // (the vertices first: zr_scene_animate refits from them)
+    if (devMorph)
+    {
+        if (!zr_scene_has_morph(scene))
+        {
+            r = zr_scene_set_morph(scene, morph);
+            if (r == ZR_ERR_NOT_INITIALIZED) { if ((r = handTables())) return r; r = zr_scene_set_morph(scene, morph); }
+            if (r) return r;
+        }
+    }
+    else if (morph) { if ((r = HandMorphedVertices(data, scene, stream, t))) return r; }
     r = zr_scene_animate_async(scene, stream, t);
     if (r != ZR_ERR_NOT_INITIALIZED) return r;
     if ((r = handTables())) return r;

@@ -71,6 +71,9 @@ int zrh_scene_apply_updates_on(zr_scene* scene, const struct zrh_scene_data* dat
 // A skinned scene (zrh_scene_data_skinning) is posed by the same call.  Host form (the default): zrh_scene_data_skin_pose for time t, handed over with
 // zr_scene_update_vertices_async ahead of the frame's instance update.  After zrh_scene_data_set_device_skinning(data, 1), together with the device path
 // above: the skin tables go to the device scene once (zr_scene_set_skinning), and zr_scene_animate_async poses the vertices -- the same device bytes.
+// A morphed scene (zrh_scene_data_morph) likewise: zrh_scene_data_morph_pose handed over with zr_scene_update_vertices_async by default; after
+// zrh_scene_data_set_device_morph(data, 1) the tables go to the device scene once (zr_scene_set_morph).  A file with ranges that are skinned AND morphed
+// takes the device form of both (set both switches) or of neither.
 int zrh_scene_animate(struct zrh_scene_data* data, zr_scene* scene, void* hip_stream, float t);
 }
 

@@ -6,6 +6,7 @@
 #include "../../include/zr_scene_math.h"
 #include "../../include/zr_anim.h"
 #include "../../include/zr_skin.h"
+#include "../../include/zr_morph.h"
 #include "../../include/zr_bcn.h"
 #include "../../include/zr_texture.h"
 #include "../../include/zr_mipgen.h"
@@ -753,6 +754,19 @@ struct zrh_scene_data
     std::vector<zr_skin_joint> skinJoints; std::vector<zr_skin_range> skinRanges; std::vector<zr_skin_influence> skinInfluences;
     zr_skin_desc skin{}; bool hasSkin = false, deviceSkinning = false;      // deviceSkinning: zrh_scene_data_set_device_skinning (zr_host.h: zrh_scene_animate)
     std::vector<zr_vertex> skinRest, skinPosed;      // zrh_scene_data_skin_pose: the ranges' rest records (this scene's vertices, which keep the rest pose) and the posed ones
+    // morph targets of the file (zrh_scene_data_morph; morph points into the vectors): one track per node with a weights channel, one range per primitive of such a node
+    std::vector<zr_morph_track> morphTracks; std::vector<zr_morph_target> morphTargets; std::vector<zr_morph_range> morphRanges;
+    std::vector<float> morphTimes, morphValues, morphRestWeights, morphDeltas;
+    zr_morph_desc morph{}; bool hasMorph = false, deviceMorph = false;      // deviceMorph: zrh_scene_data_set_device_morph (zr_host.h: zrh_scene_animate)
+    std::vector<zr_vertex> morphRest, morphPosed;      // zrh_scene_data_morph_pose
+    void PointMorph()
+    {
+        std::memset(&morph, 0, sizeof(morph));
+        morph.tracks = morphTracks.data(); morph.num_tracks = (uint32_t)morphTracks.size(); morph.targets = morphTargets.data(); morph.num_targets = (uint32_t)morphTargets.size();
+        morph.ranges = morphRanges.data(); morph.num_ranges = (uint32_t)morphRanges.size(); morph.times = morphTimes.data(); morph.num_times = (uint32_t)morphTimes.size();
+        morph.values = morphValues.data(); morph.num_values = (uint32_t)morphValues.size(); morph.rest_weights = morphRestWeights.data(); morph.num_rest_weights = (uint32_t)morphRestWeights.size();
+        morph.deltas = morphDeltas.data(); morph.num_deltas = (uint32_t)(morphDeltas.size() / 3);
+    }
     zr_scene_desc desc;
     void Finish()
     {
@@ -794,6 +808,60 @@ struct Gltf
         if (off + (r.count ? (r.count - 1) * r.stride + csz * r.ncomp : 0) > buf.size()) Throw("glTF: accessor reads past its buffer");
         r.base = buf.data() + off;
         return r;
+    }
+    // `count` tightly packed elements of a bufferView, `byteOffset` into it: the parts of a sparse accessor (no accessor record of their own)
+    Accessor View(double bufferView, double byteOffset, int comp, int ncomp, double count, bool normalized) const
+    {
+        for (double v : {bufferView, byteOffset, count}) if (!(v >= 0.0) || v >= 4294967296.0) Throw("glTF: sparse accessor with a negative or oversized count, offset or index");
+        const Json& bv = root.At("bufferViews").arr.at((size_t)bufferView);
+        const double bufIdx = bv.At("buffer").num, bvOff = bv.NumOr("byteOffset", 0);
+        if (!(bufIdx >= 0.0) || bufIdx >= 4294967296.0 || !(bvOff >= 0.0) || bvOff >= 4294967296.0) Throw("glTF: accessor, bufferView or buffer index out of range");
+        const std::vector<uint8_t>& buf = buffers.at((size_t)bufIdx);
+        Accessor r; r.comp = comp; r.ncomp = ncomp; r.count = (size_t)count; r.normalized = normalized;
+        const size_t csz = (comp == 5120 || comp == 5121) ? 1 : (comp == 5122 || comp == 5123) ? 2 : 4;
+        const size_t off = (size_t)bvOff + (size_t)byteOffset;
+        r.stride = csz * ncomp;
+        if (off + r.count * r.stride > buf.size()) Throw("glTF: sparse accessor reads past its buffer");
+        r.base = buf.data() + off;
+        return r;
+    }
+    // a morph target's attribute: `nvtx` float triples from a VEC3 accessor of floats or normalised bytes / shorts, dense or SPARSE (sparse.indices /
+    // sparse.values laid over the bufferView's elements, or over zeros without a bufferView -- the form exporters write deltas in); z negated like the vertices' z
+    std::vector<float> Deltas(int idx, size_t nvtx, const std::string& where) const
+    {
+        if (idx < 0 || (size_t)idx >= root.At("accessors").Size()) Throw(where + "accessor index out of range");
+        const Json& a = root.At("accessors").arr[(size_t)idx];
+        const int comp = (int)a.At("componentType").num;
+        const bool normalized = a.BoolOr("normalized", false);
+        if (a.At("type").str != "VEC3" || !(comp == 5126 || ((comp == 5120 || comp == 5122 || comp == 5121 || comp == 5123) && normalized)))
+            Throw(where + "a target attribute must be VEC3 of floats, or of normalised bytes / shorts");
+        const double count = a.At("count").num;
+        if (!(count >= 0.0) || count >= 4294967296.0) Throw("glTF: accessor with a negative or oversized count, offset or stride");
+        if ((size_t)count < nvtx) Throw(where + "target accessor shorter than POSITION");
+        std::vector<float> out(3 * nvtx, 0.0f);
+        const Json* sp = a.Find("sparse");
+        if (a.Find("bufferView"))
+        {
+            const Accessor d = Acc(idx);
+            for (size_t v = 0; v < nvtx; v++) for (int c = 0; c < 3; c++) out[3 * v + c] = Comp(d, v, c);
+        }
+        else if (!sp) Throw(where + "a target accessor has neither a bufferView nor sparse data");
+        if (sp)
+        {
+            const Json& si = sp->At("indices"); const Json& sv = sp->At("values");
+            const int icomp = (int)si.At("componentType").num;
+            if (icomp != 5121 && icomp != 5123 && icomp != 5125) Throw(where + "sparse indices must be unsigned bytes, shorts or ints");
+            const Accessor ia = View(si.At("bufferView").num, si.NumOr("byteOffset", 0), icomp, 1, sp->At("count").num, false);
+            const Accessor va = View(sv.At("bufferView").num, sv.NumOr("byteOffset", 0), comp, 3, sp->At("count").num, normalized);
+            for (size_t k = 0; k < ia.count; k++)
+            {
+                const uint32_t i = Index(ia, k);
+                if ((double)i >= count) Throw(where + "sparse index " + std::to_string(i) + " out of range: the accessor has " + std::to_string((size_t)count) + " elements");
+                if (i < nvtx) for (int c = 0; c < 3; c++) out[3 * (size_t)i + c] = Comp(va, k, c);
+            }
+        }
+        for (size_t v = 0; v < nvtx; v++) out[3 * v + 2] *= -1.0f;
+        return out;
     }
     static float Comp(const Accessor& a, size_t i, int c)
     {
@@ -972,6 +1040,28 @@ void Load(const std::string& path, zrh_scene_data& sc)
             prims[{(int)mi, (int)pi}] = mp;
         }
     }
+    // ---- morph targets: how many every mesh has (all primitives of a mesh alike: the node's weights drive them together) and its default weights
+    std::vector<uint32_t> meshTargets(meshes.Size(), 0);
+    std::vector<std::vector<float>> meshWeights(meshes.Size());
+    for (size_t mi = 0; mi < meshes.Size(); mi++)
+    {
+        const Json& plist = meshes.arr[mi].At("primitives");
+        const std::string where = "glTF: mesh " + std::to_string(mi) + " ('" + meshes.arr[mi].StrOr("name", "") + "'): ";
+        for (size_t pi = 0; pi < plist.Size(); pi++)
+        {
+            const Json* tg = plist.arr[pi].Find("targets");
+            const uint32_t n = tg ? (uint32_t)tg->Size() : 0u;
+            if (pi && n != meshTargets[mi]) Throw(where + "its primitives have different morph target counts (" + std::to_string(meshTargets[mi]) + " and " + std::to_string(n) + ")");
+            meshTargets[mi] = n;
+        }
+        if (!meshTargets[mi]) continue;
+        meshWeights[mi].assign(meshTargets[mi], 0.0f);
+        if (const Json* w = meshes.arr[mi].Find("weights"))
+        {
+            if (w->Size() != meshTargets[mi]) Throw(where + "a weights array of " + std::to_string(w->Size()) + " entries, the mesh has " + std::to_string(meshTargets[mi]) + " morph targets");
+            for (uint32_t k = 0; k < meshTargets[mi]; k++) meshWeights[mi][k] = (float)w->arr[k].num;
+        }
+    }
     // ---- nodes, depth first: world = local x parent (SceneCore.cpp:871-873); one instance per primitive
     struct Em { uint32_t inst; MeshPrim mp; };
     std::vector<Em> emissive;
@@ -989,6 +1079,9 @@ void Load(const std::string& path, zrh_scene_data& sc)
     // key).  LINEAR samplers on translation / rotation / scale only; anything else fails the load with the animation and the node named
     struct NodeAnim { int input = -1, out[3] = {-1, -1, -1}; std::string anim; };      // out: translation, rotation, scale
     std::map<int, NodeAnim> nodeAnims;
+    // ... and per node with a `weights` channel (LINEAR; the output a SCALAR accessor of keys x targets) its sampler's accessors
+    struct WeightAnim { int input = -1, output = -1; std::string anim; };
+    std::map<int, WeightAnim> weightAnims;
     if (const Json* anims = g.root.Find("animations"))
         for (size_t ai = 0; ai < anims->Size(); ai++)
         {
@@ -1003,6 +1096,22 @@ void Load(const std::string& path, zrh_scene_data& sc)
                 const std::string where = "glTF: " + aname + ", node " + std::to_string(node) + ": ";
                 if ((size_t)node >= nodes.arr.size()) Throw(where + "node index out of range");
                 const std::string path = target.StrOr("path", "");
+                if (path == "weights")
+                {
+                    const int mesh = nodes.arr[(size_t)node].IntOr("mesh", -1);
+                    const uint32_t T = mesh >= 0 && (size_t)mesh < meshTargets.size() ? meshTargets[(size_t)mesh] : 0u;
+                    if (!T) Throw(where + "target path 'weights': the node's mesh has no morph targets");
+                    const Json& sm = samplers.arr.at((size_t)ch.At("sampler").num);
+                    const std::string interp = sm.StrOr("interpolation", "LINEAR");
+                    if (interp != "LINEAR") Throw(where + "target path 'weights': " + interp + " samplers are not supported (LINEAR is)");
+                    if (weightAnims.count(node)) Throw(where + "two channels target its weights");
+                    WeightAnim wa; wa.input = (int)sm.At("input").num; wa.output = (int)sm.At("output").num; wa.anim = aname;
+                    const Accessor in = g.Acc(wa.input), out = g.Acc(wa.output);
+                    if (in.count < 2) Throw(where + "target path 'weights': fewer than 2 keys");
+                    if (in.ncomp != 1 || out.ncomp != 1 || out.count < in.count * T) Throw(where + "sampler accessors do not match the weights path (a SCALAR output of keys x " + std::to_string(T) + " targets)");
+                    weightAnims[node] = wa;
+                    continue;
+                }
                 const int which = path == "translation" ? 0 : path == "rotation" ? 1 : path == "scale" ? 2 : -1;
                 if (which < 0) Throw(where + "target path '" + path + "' is not supported (translation, rotation and scale are)");
                 const Json& sm = samplers.arr.at((size_t)ch.At("sampler").num);
@@ -1072,6 +1181,78 @@ void Load(const std::string& path, zrh_scene_data& sc)
         std::vector<uint8_t> onPath;
         std::map<int, NodeAnim>& nodeAnims; std::vector<int8_t>& leadsToMesh;
         std::vector<SkinUse>& skins; std::vector<int8_t>& leadsToJoint; std::vector<uint8_t>& isJoint; std::vector<uint32_t>& nodeEntry; std::vector<SkinnedPrim>& skinnedPrims;
+        std::vector<uint32_t>& meshTargets; std::vector<std::vector<float>>& meshWeights; std::map<int, WeightAnim>& weightAnims;
+        std::map<std::pair<int, int>, uint32_t> primTargets;      // (mesh, primitive) -> its first entry of the target table: nodes that share a mesh share its deltas
+        // a copy of the primitive's vertices as a range of its own (nothing is shared with another node that uses the mesh); returns its first vertex
+        uint32_t CopyPrimitive(const MeshPrim& mp)
+        {
+            const uint32_t first = (uint32_t)sc.vertices.size();
+            for (uint32_t v = 0; v < mp.nvtx; v++) sc.vertices.push_back(sc.vertices[mp.vtx + v]);
+            return first;
+        }
+        // the targets of one primitive in the target table and the delta pool (read once per mesh primitive); returns the first entry
+        uint32_t PrimTargets(int mesh, int pi, const Json& prim, const MeshPrim& mp, const std::string& where)
+        {
+            const auto it = primTargets.find({mesh, pi});
+            if (it != primTargets.end()) return it->second;
+            const uint32_t first = (uint32_t)sc.morphTargets.size();
+            const Json& tg = prim.At("targets");
+            for (size_t k = 0; k < tg.Size(); k++)
+            {
+                zr_morph_target m; m.first_pos = m.first_nrm = m.first_tan = ZR_MORPH_NONE;
+                uint32_t* firsts[3] = {&m.first_pos, &m.first_nrm, &m.first_tan};
+                const char* names[3] = {"POSITION", "NORMAL", "TANGENT"};
+                for (int a = 0; a < 3; a++)
+                    if (const Json* acc = tg.arr[k].Find(names[a]))
+                    {
+                        const std::vector<float> d = g.Deltas((int)acc->num, mp.nvtx, where + "target " + std::to_string(k) + " " + names[a] + ": ");
+                        *firsts[a] = (uint32_t)(sc.morphDeltas.size() / 3);
+                        sc.morphDeltas.insert(sc.morphDeltas.end(), d.begin(), d.end());
+                    }
+                sc.morphTargets.push_back(m);
+            }
+            primTargets[{mesh, pi}] = first;
+            return first;
+        }
+        // one primitive of a node whose mesh has morph targets, its vertices a range of the node's own at `first`.  With a weights channel (track >= 0): a
+        // morph range under the node's track.  Without: the default weights are applied here, once, by zrmo::MorphVertex, and no range is listed
+        void MorphPrimitive(int nidx, int mesh, int pi, const Json& prim, const MeshPrim& mp, uint32_t first, int track, const std::vector<float>& weights)
+        {
+            const std::string where = "glTF: node " + std::to_string(nidx) + " (mesh " + std::to_string(mesh) + ", primitive " + std::to_string(pi) + "): ";
+            if (isEm(mp.mat)) Throw(where + "a morphed primitive with an emissive material is not supported (a deformed light would keep shining from its rest pose)");
+            const uint32_t T = meshTargets[(size_t)mesh];
+            if (track >= 0)
+            {
+                const uint32_t firstTarget = PrimTargets(mesh, pi, prim, mp, where);
+                sc.morphRanges.push_back(zr_morph_range{first, mp.nvtx, firstTarget, T, (uint32_t)track});
+                return;
+            }
+            bool any = false; for (float w : weights) { if (!Finite(w)) Throw(where + "a default weight is not finite"); any = any || w != 0.0f; }
+            if (!any) return;
+            // (the baked mesh's targets go to a table of their own: nothing of them stays in the scene)
+            std::vector<zr_morph_target> table; std::vector<float> pool;
+            const Json& tg = prim.At("targets");
+            for (size_t k = 0; k < tg.Size(); k++)
+            {
+                zr_morph_target m; m.first_pos = m.first_nrm = m.first_tan = ZR_MORPH_NONE;
+                uint32_t* firsts[3] = {&m.first_pos, &m.first_nrm, &m.first_tan};
+                const char* names[3] = {"POSITION", "NORMAL", "TANGENT"};
+                for (int a = 0; a < 3; a++)
+                    if (const Json* acc = tg.arr[k].Find(names[a]))
+                    {
+                        const std::vector<float> d = g.Deltas((int)acc->num, mp.nvtx, where + "target " + std::to_string(k) + " " + names[a] + ": ");
+                        for (float x : d) if (!Finite(x)) Throw(where + "target " + std::to_string(k) + ": a delta is not finite");
+                        *firsts[a] = (uint32_t)(pool.size() / 3);
+                        pool.insert(pool.end(), d.begin(), d.end());
+                    }
+                table.push_back(m);
+            }
+            for (uint32_t v = 0; v < mp.nvtx; v++)
+            {
+                const zr_vertex rest = sc.vertices[first + v];
+                zrmo::MorphVertex(rest, table.data(), T, weights.data(), pool.data(), v, sc.vertices[first + v]);
+            }
+        }
         bool LeadsToJoint(int nidx, int depth = 0)
         {
             if (nidx < 0 || (size_t)nidx >= nodes.arr.size() || depth > 4096) return false;
@@ -1159,7 +1340,11 @@ void Load(const std::string& path, zrh_scene_data& sc)
             // ---- the dynamic closure, depth first (a parent precedes its children): the animated nodes and what hangs on them
             uint32_t entry = ZR_ANIM_ROOT;
             const auto anim = nodeAnims.find(nidx);
-            if (anim != nodeAnims.end() || (closureParent != ZR_ANIM_ROOT && LeadsToMesh(nidx)) || LeadsToJoint(nidx))
+            const int meshOfNode = node.IntOr("mesh", -1);
+            const bool morphed = meshOfNode >= 0 && (size_t)meshOfNode < meshTargets.size() && meshTargets[(size_t)meshOfNode] > 0;
+            const auto wanim = morphed ? weightAnims.find(nidx) : weightAnims.end();
+            // (a node whose weights are animated joins the closure even when no transform of it is: a file whose only animation is a weights channel has an animation to set)
+            if (anim != nodeAnims.end() || (closureParent != ZR_ANIM_ROOT && LeadsToMesh(nidx)) || LeadsToJoint(nidx) || wanim != weightAnims.end())
             {
                 zr_anim_node an; std::memset(&an, 0, sizeof(an));
                 an.parent = closureParent;
@@ -1191,6 +1376,30 @@ void Load(const std::string& path, zrh_scene_data& sc)
             }
             const int mesh = node.IntOr("mesh", -1);
             const int skin = mesh >= 0 ? node.IntOr("skin", -1) : -1;      // a skinned node: glTF ignores its own transform, the joints place the mesh
+            int track = -1;
+            std::vector<float> nodeWeights;
+            if (morphed)
+            {   // the node's weights (its own override the mesh's), and its track when a channel drives them
+                const uint32_t T = meshTargets[(size_t)mesh];
+                nodeWeights = meshWeights[(size_t)mesh];
+                if (const Json* w = node.Find("weights"))
+                {
+                    if (w->Size() != T) Throw("glTF: node " + std::to_string(nidx) + ": a weights array of " + std::to_string(w->Size()) + " entries, its mesh has " + std::to_string(T) + " morph targets");
+                    for (uint32_t k = 0; k < T; k++) nodeWeights[k] = (float)w->arr[k].num;
+                }
+                if (wanim != weightAnims.end())
+                {
+                    const Accessor in = g.Acc(wanim->second.input), out = g.Acc(wanim->second.output);
+                    zr_morph_track tr; std::memset(&tr, 0, sizeof(tr));
+                    tr.num_targets = T; tr.first_key = (uint32_t)sc.morphTimes.size(); tr.num_keys = (uint32_t)in.count; tr.first_value = (uint32_t)sc.morphValues.size();
+                    tr.first_rest = (uint32_t)sc.morphRestWeights.size(); tr.loop = 1; tr.t0 = 0.0f;
+                    for (size_t k = 0; k < in.count; k++) sc.morphTimes.push_back(Gltf::Comp(in, k, 0));
+                    for (size_t k = 0; k < in.count * T; k++) sc.morphValues.push_back(Gltf::Comp(out, k, 0));
+                    sc.morphRestWeights.insert(sc.morphRestWeights.end(), nodeWeights.begin(), nodeWeights.end());
+                    track = (int)sc.morphTracks.size();
+                    sc.morphTracks.push_back(tr);
+                }
+            }
             if (mesh >= 0)
             {
                 const size_t np = g.root.At("meshes").arr.at(mesh).At("primitives").Size();
@@ -1205,6 +1414,11 @@ void Load(const std::string& path, zrh_scene_data& sc)
                         I.base_vtx_offset = SkinPrimitive(nidx, skin, g.root.At("meshes").arr.at(mesh).At("primitives").arr.at(pi), mp);
                         Mat43 id; std::memset(&id, 0, sizeof(id)); for (int i = 0; i < 3; i++) id.m[i][i] = 1.0f;
                         ToToWorld(id, M);
+                    }
+                    if (morphed)
+                    {   // a range of the node's own (the skin's copy, where the node is skinned too: one range listed in both tables)
+                        if (skin < 0) I.base_vtx_offset = CopyPrimitive(mp);
+                        MorphPrimitive(nidx, mesh, (int)pi, g.root.At("meshes").arr.at(mesh).At("primitives").arr.at(pi), mp, I.base_vtx_offset, track, nodeWeights);
                     }
                     FillMeshInstance(M, I);
                     const zr_material& mat = sc.materials.at((size_t)mp.mat + 1);
@@ -1225,7 +1439,7 @@ void Load(const std::string& path, zrh_scene_data& sc)
             }
             if (const Json* ch = node.Find("children")) for (const Json& c : ch->arr) Visit((int)c.num, world, entry);
         }
-    } walker{g, sc, prims, emissive, nodes, isEmissive, {}, nodeAnims, leadsToMesh, skins, leadsToJoint, isJoint, nodeEntry, skinnedPrims};
+    } walker{g, sc, prims, emissive, nodes, isEmissive, {}, nodeAnims, leadsToMesh, skins, leadsToJoint, isJoint, nodeEntry, skinnedPrims, meshTargets, meshWeights, weightAnims, {}};
     const Json& scenes = g.root.At("scenes");
     const Json& scene = scenes.arr.at((size_t)g.root.IntOr("scene", 0));
     for (const Json& n : scene.At("nodes").arr) walker.Visit((int)n.num, identity);
@@ -1240,7 +1454,7 @@ void Load(const std::string& path, zrh_scene_data& sc)
     }
     if (!skinnedPrims.empty())
     {   // the joint tables of the skins in use, one after the other; an influence's joint index counts from its skin's first joint
-        if (nodeAnims.empty()) Throw("glTF: the file has a skin but no animation: nothing would pose it (skins are driven by zr_scene_animate)");
+        if (nodeAnims.empty() && weightAnims.empty()) Throw("glTF: the file has a skin but no animation: nothing would pose it (skins are driven by zr_scene_animate)");
         for (size_t si = 0; si < skins.size(); si++)
         {
             SkinUse& u = skins[si];
@@ -1268,6 +1482,14 @@ void Load(const std::string& path, zrh_scene_data& sc)
         if (zrsk::ValidateSkin(d, (uint32_t)sc.animNodes.size(), (uint32_t)sc.vertices.size(), msg, sizeof(msg))) Throw(std::string("glTF: skins: ") + msg);
         sc.skin = d; sc.hasSkin = true;
     }
+    if (!sc.morphRanges.empty())
+    {   // the tables are held to what zr_scene_set_morph checks
+        sc.PointMorph();
+        char msg[256];
+        if (zrmo::ValidateMorph(sc.morph, sc.hasSkin ? &sc.skin : nullptr, (uint32_t)sc.vertices.size(), msg, sizeof(msg))) Throw(std::string("glTF: morph targets: ") + msg);
+        sc.hasMorph = true;
+    }
+    else { sc.morphTracks.clear(); sc.morphTimes.clear(); sc.morphValues.clear(); sc.morphRestWeights.clear(); }
     // ---- emissive triangles in world space (glTF.cpp:692-767, SceneCore.cpp:196-236): ID = PCG3d(instance, 0, triangle).x
     for (const Em& em : emissive)
     {
@@ -1339,6 +1561,28 @@ int zrh_skin_pose(const zr_anim_desc* anim, const zr_skin_desc* skin, float t, c
     zrsk::SkinRanges(*skin, J.data(), rest, out);
     return 0;
 }
+int zrh_morph_pose(const zr_anim_desc* anim, const zr_skin_desc* skin, const zr_morph_desc* morph, float t, const zr_vertex* rest, zr_vertex* out)
+{
+    if (!morph || (skin && !anim) || ((!rest || !out) && morph->num_ranges)) { g_err = "zrh_morph_pose: null argument"; return -1; }
+    uint64_t verts = 0;
+    for (uint32_t r = 0; r < morph->num_ranges && morph->ranges; r++) verts = std::max<uint64_t>(verts, (uint64_t)morph->ranges[r].first_vertex + morph->ranges[r].num_vertices);
+    for (uint32_t r = 0; skin && r < skin->num_ranges && skin->ranges; r++) verts = std::max<uint64_t>(verts, (uint64_t)skin->ranges[r].first_vertex + skin->ranges[r].num_vertices);
+    char msg[256];
+    if (verts > 0xffffffffull) { g_err = "zrh_morph_pose: a range wraps"; return -1; }
+    if (skin && zrsk::ValidateSkin(*skin, anim->num_nodes, (uint32_t)verts, msg, sizeof(msg))) { g_err = std::string("zrh_morph_pose: the skin: ") + msg; return -1; }
+    if (zrmo::ValidateMorph(*morph, skin, (uint32_t)verts, msg, sizeof(msg))) { g_err = std::string("zrh_morph_pose: ") + msg; return -1; }
+    std::vector<uint32_t> offs(morph->num_tracks);
+    std::vector<float> W(zrmo::WeightOffsets(*morph, offs.data())), world, J;
+    zrmo::EvalWeights(*morph, t, W.data());
+    if (skin)
+    {
+        world.resize(12 * (size_t)anim->num_nodes); J.resize(12 * (size_t)skin->num_joints);
+        EvalNodeWorlds(*anim, t, world.data());
+        zrsk::EvalJointMatrices(*skin, world.data(), J.data());
+    }
+    zrmo::MorphRanges(*morph, W.data(), skin, J.data(), rest, out);
+    return 0;
+}
 void zrh_compose_world(const float* s, const float* q, const float* t, const float* parent, float* out)
 {
     Mat43 P; std::memset(&P, 0, sizeof(P)); for (int i = 0; i < 3; i++) P.m[i][i] = 1.0f;
@@ -1389,14 +1633,15 @@ uint32_t zrh_scene_data_moved(const zrh_scene_data* s, const uint32_t** idx, con
     return (uint32_t)s->movedIdx.size();
 }
 // ---- keyframe animation: the host path (include/zr_anim.h on the host, then set_instance_world in list order)
+static void ClearMorph(zrh_scene_data* s);
 int zrh_scene_data_set_animation(zrh_scene_data* s, const zr_anim_desc* d)
 {
     if (!s) { g_err = "zrh_scene_data_set_animation: null scene"; return -1; }
     if (!d || (!d->num_nodes && !d->num_instances))
-    { s->hasAnim = false; s->animNodes.clear(); s->animKeys.clear(); s->animInstIdx.clear(); s->animInstNode.clear(); std::memset(&s->anim, 0, sizeof(s->anim)); return 0; }
+    { zrh_scene_data_set_skinning(s, nullptr); s->hasAnim = false; s->animNodes.clear(); s->animKeys.clear(); s->animInstIdx.clear(); s->animInstNode.clear(); std::memset(&s->anim, 0, sizeof(s->anim)); return 0; }
     char msg[256];
     if (ValidateAnimation(*d, (uint32_t)s->instances.size(), nullptr, msg, sizeof(msg))) { g_err = std::string("zrh_scene_data_set_animation: ") + msg; return -1; }
-    zrh_scene_data_set_skinning(s, nullptr);      // a skin belongs to the animation it was set on (zr_scene_set_animation does the same)
+    zrh_scene_data_set_skinning(s, nullptr);      // a skin belongs to the animation it was set on (zr_scene_set_animation does the same); the morph set goes with it
     s->animNodes.assign(d->nodes, d->nodes + d->num_nodes); s->animKeys.assign(d->keys, d->keys + d->num_keys);
     s->animInstIdx.assign(d->instance_idx, d->instance_idx + d->num_instances); s->animInstNode.assign(d->instance_node, d->instance_node + d->num_instances);
     s->anim.nodes = s->animNodes.data(); s->anim.num_nodes = d->num_nodes; s->anim.keys = s->animKeys.data(); s->anim.num_keys = d->num_keys;
@@ -1410,10 +1655,11 @@ int zrh_scene_data_set_skinning(zrh_scene_data* s, const zr_skin_desc* d)
 {
     if (!s) { g_err = "zrh_scene_data_set_skinning: null scene"; return -1; }
     if (!d || (!d->num_joints && !d->num_ranges && !d->num_influences))
-    { s->hasSkin = false; s->skinJoints.clear(); s->skinRanges.clear(); s->skinInfluences.clear(); std::memset(&s->skin, 0, sizeof(s->skin)); return 0; }
+    { ClearMorph(s); s->hasSkin = false; s->skinJoints.clear(); s->skinRanges.clear(); s->skinInfluences.clear(); std::memset(&s->skin, 0, sizeof(s->skin)); return 0; }
     if (!s->hasAnim) { g_err = "zrh_scene_data_set_skinning: no animation set (zrh_scene_data_set_animation): the joints are nodes of its table"; return -1; }
     char msg[256];
     if (zrsk::ValidateSkin(*d, s->anim.num_nodes, (uint32_t)s->vertices.size(), msg, sizeof(msg))) { g_err = std::string("zrh_scene_data_set_skinning: ") + msg; return -1; }
+    ClearMorph(s);      // a morph set is laid out against the skin set it was set after (zr_scene_set_skinning does the same)
     s->skinJoints.assign(d->joints, d->joints + d->num_joints); s->skinRanges.assign(d->ranges, d->ranges + d->num_ranges);
     s->skinInfluences.assign(d->influences, d->influences + d->num_influences);
     s->skin.joints = s->skinJoints.data(); s->skin.num_joints = d->num_joints; s->skin.ranges = s->skinRanges.data(); s->skin.num_ranges = d->num_ranges;
@@ -1430,6 +1676,40 @@ const zr_vertex* zrh_scene_data_skin_pose(zrh_scene_data* s, float t)
     if (zrh_skin_pose(&s->anim, &s->skin, t, s->skinRest.data(), s->skinPosed.data())) return nullptr;
     return s->skinPosed.data();
 }
+const zr_morph_desc* zrh_scene_data_morph(const zrh_scene_data* s) { return s && s->hasMorph ? &s->morph : nullptr; }
+static void ClearMorph(zrh_scene_data* s)
+{
+    s->hasMorph = false; s->morphTracks.clear(); s->morphTargets.clear(); s->morphRanges.clear(); s->morphTimes.clear(); s->morphValues.clear();
+    s->morphRestWeights.clear(); s->morphDeltas.clear(); std::memset(&s->morph, 0, sizeof(s->morph));
+}
+int zrh_scene_data_set_morph(zrh_scene_data* s, const zr_morph_desc* d)
+{
+    if (!s) { g_err = "zrh_scene_data_set_morph: null scene"; return -1; }
+    if (!d || (!d->num_tracks && !d->num_targets && !d->num_ranges)) { ClearMorph(s); return 0; }
+    if (!s->hasAnim) { g_err = "zrh_scene_data_set_morph: no animation set (zrh_scene_data_set_animation)"; return -1; }
+    char msg[256];
+    if (zrmo::ValidateMorph(*d, s->hasSkin ? &s->skin : nullptr, (uint32_t)s->vertices.size(), msg, sizeof(msg))) { g_err = std::string("zrh_scene_data_set_morph: ") + msg; return -1; }
+    const zr_morph_desc c = *d;      // (d may point into this scene's own vectors)
+    std::vector<zr_morph_track> tracks(c.tracks, c.tracks + c.num_tracks); std::vector<zr_morph_target> targets(c.targets, c.targets + c.num_targets);
+    std::vector<zr_morph_range> ranges(c.ranges, c.ranges + c.num_ranges); std::vector<float> times(c.times, c.times + c.num_times), values(c.values, c.values + c.num_values),
+        rest(c.rest_weights, c.rest_weights + c.num_rest_weights), deltas(c.deltas, c.deltas + 3 * (size_t)c.num_deltas);
+    s->morphTracks.swap(tracks); s->morphTargets.swap(targets); s->morphRanges.swap(ranges); s->morphTimes.swap(times); s->morphValues.swap(values);
+    s->morphRestWeights.swap(rest); s->morphDeltas.swap(deltas);
+    s->PointMorph();
+    s->hasMorph = true;
+    return 0;
+}
+const zr_vertex* zrh_scene_data_morph_pose(zrh_scene_data* s, float t)
+{
+    if (!s || !s->hasMorph || !s->hasAnim) { g_err = "zrh_scene_data_morph_pose: no morph set"; return nullptr; }
+    s->morphRest.clear();
+    for (const zr_morph_range& r : s->morphRanges) s->morphRest.insert(s->morphRest.end(), s->vertices.begin() + r.first_vertex, s->vertices.begin() + r.first_vertex + r.num_vertices);
+    s->morphPosed.resize(s->morphRest.size() + 1);      // (+ 1: a pointer that is not null for a set without vertices)
+    if (zrh_morph_pose(&s->anim, s->hasSkin ? &s->skin : nullptr, &s->morph, t, s->morphRest.data(), s->morphPosed.data())) return nullptr;
+    return s->morphPosed.data();
+}
+void zrh_scene_data_set_device_morph(zrh_scene_data* s, int on) { if (s) s->deviceMorph = on != 0; }
+int zrh_scene_data_device_morph(const zrh_scene_data* s) { return s && s->deviceMorph ? 1 : 0; }
 void zrh_scene_data_set_device_skinning(zrh_scene_data* s, int on) { if (s) s->deviceSkinning = on != 0; }
 int zrh_scene_data_device_skinning(const zrh_scene_data* s) { return s && s->deviceSkinning ? 1 : 0; }
 int zrh_scene_data_animate(zrh_scene_data* s, float t)

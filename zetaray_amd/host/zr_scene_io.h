@@ -90,6 +90,25 @@ int zrh_scene_data_set_skinning(zrh_scene_data* s, const zr_skin_desc* desc);
 const zr_vertex* zrh_scene_data_skin_pose(zrh_scene_data* s, float t);
 void zrh_scene_data_set_device_skinning(zrh_scene_data* s, int on);
 int zrh_scene_data_device_skinning(const zrh_scene_data* s);
+// ---- morph targets.  zrh_gltf_load reads a primitive's "targets" (POSITION / NORMAL / TANGENT deltas as float VEC3, or as normalised bytes / shorts; dense
+// or SPARSE accessors -- sparse.indices / sparse.values over a bufferView or over zeros; z negated like the vertices' z), "weights" of the mesh and of the
+// node (the node's override the mesh's) and animation channels with the path "weights" (LINEAR; a SCALAR output of keys x targets).  A node whose
+// weights a channel drives: every primitive gets a vertex range of its own (the skin's copy, where the node is skinned too: one range listed in both
+// tables), the node joins the dynamic closure even when no transform of it is animated, and zrh_scene_data_morph returns the tables (zr_scene_set_morph
+// takes them after zr_scene_set_animation and zr_scene_set_skinning); nodes that share a mesh share its deltas.  Targets WITHOUT a weights channel: the
+// default weights are applied once at load by zrmo::MorphVertex (to a copy of the node's own) and no morph set is made for them.
+// Refused by name and reason: primitives of one mesh with different target counts, a weights array whose length is not the target count, a target
+// accessor shorter than POSITION, a CUBICSPLINE or STEP weights sampler, a weights channel on a node whose mesh has no targets, a sparse index out of
+// range, a morphed primitive with an emissive material (a deformed light would keep shining from its rest pose).
+// zrh_scene_data_set_morph replaces the tables (a deep copy; null or empty: clears) after the checks of zr_scene_set_morph; zrh_scene_data_set_animation and
+// _set_skinning clear them, as the device scene's calls do.  zrh_scene_data_morph_pose(s, t) is the HOST FORM of a frame's morphing: zrh_morph_pose (below)
+// on this scene's tables and vertices, which keep the rest pose; returns the posed records of the ranges, range after range (valid until the next call).
+// zrh_scene_data_set_device_morph: which of the two zrh_scene_animate (zr_host.h) takes: 0 (default) the host form, 1 zr_scene_set_morph once
+const zr_morph_desc* zrh_scene_data_morph(const zrh_scene_data* s);
+int zrh_scene_data_set_morph(zrh_scene_data* s, const zr_morph_desc* desc);
+const zr_vertex* zrh_scene_data_morph_pose(zrh_scene_data* s, float t);
+void zrh_scene_data_set_device_morph(zrh_scene_data* s, int on);
+int zrh_scene_data_device_morph(const zrh_scene_data* s);
 // which of the two zrh_scene_animate (zr_host.h) takes: 0 (default) the host path above, 1 zr_scene_animate_async
 void zrh_scene_data_set_device_animation(zrh_scene_data* s, int on);
 int zrh_scene_data_device_animation(const zrh_scene_data* s);
@@ -107,6 +126,11 @@ void zrh_compose_world(const float* scale3, const float* quat4, const float* tra
 // ranges, range after range; the caller hands `out` to zr_scene_update_vertices range by range.  -1 (zrh_scene_io_last_error()) for tables
 // zr_scene_set_skinning would refuse
 int zrh_skin_pose(const zr_anim_desc* anim, const zr_skin_desc* skin, float t, const zr_vertex* rest, zr_vertex* out);
+// the HOST FORM of morph targets (include/zr_morph.h; zr_morph_desc: include/zr_wire.h), the definition zr_scene_animate on a scene with a morph set is held
+// to byte for byte: rest = the rest-pose records of morph's ranges, range after range; out = the posed ones in the same order, for time t.  The weights are
+// sampled, every vertex is morphed, and with `skin` (else null; then anim may be null too) a range that is also a range of the skin goes on through
+// zr_skin.h with the node matrices of time t: MorphVertex, then SkinVertex.  Returns -1 with zrh_scene_io_last_error() for tables zr_scene_set_morph would refuse
+int zrh_morph_pose(const zr_anim_desc* anim, const zr_skin_desc* skin_or_null, const zr_morph_desc* morph, float t, const zr_vertex* rest, zr_vertex* out);
 // TLAS::FillMeshInstanceData for a static instance: rotation / scale / translation (+ prev_* = current, d_translation = 0)
 void zrh_fill_mesh_instance(const float* to_world_3x4, zr_mesh_instance* inst);
 // RT::EmissiveTriangle(v0, v1, v2, uv0..2, factor RGB8, texture, half strength bits, id, double sided)

@@ -557,6 +557,24 @@ def skin_pose(anim, skin, rest, t):
     return out
 
 
+def morph_pose(anim, skin, morph, rest, t):
+    """zrh_morph_pose: the host form of morph targets -- the rest records of morph's ranges (range after range; wire.VERTEX) posed for time t by
+    include/zr_morph.h on the host, and by include/zr_skin.h after it where a range is also a range of `skin`; anim / skin (or None) / morph:
+    wire.AnimDesc / wire.SkinDesc / wire.MorphDesc"""
+    import ctypes as C
+    L = _sceneio_lib()
+    L.zrh_morph_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+    rest = np.ascontiguousarray(rest, wire.VERTEX).reshape(-1)
+    if len(rest) != int(morph.ranges["num_vertices"].sum()):
+        raise ValueError(f"morph_pose: {len(rest)} rest records, the ranges list {int(morph.ranges['num_vertices'].sum())} vertices")
+    out = np.zeros(len(rest), wire.VERTEX)
+    a, k, m = (anim.c_desc() if anim is not None else None), (skin.c_desc() if skin is not None else None), morph.c_desc()
+    if L.zrh_morph_pose(C.addressof(a) if a is not None else None, C.addressof(k) if k is not None else None, C.addressof(m), float(t),
+                        rest.ctypes.data if len(rest) else None, out.ctypes.data if len(rest) else None) != 0:
+        raise ValueError(L.zrh_scene_io_last_error().decode())
+    return out
+
+
 def mip_generate(descs, texels):
     """zrh_mip_generate: levels 1 .. of the chains `descs` (wire.TEXTURE_DESC) names in `texels` (uint8, contiguous), in place, from their level 0"""
     import ctypes as C
@@ -641,6 +659,8 @@ def load_gltf_native(path, rho=None, textures="decoded", jpeg=False):
     its node hierarchy (Scene.set_animation / Scene.animate in api.py), and sc.emissives_initial, the object-space light records; None without.
     A file with skinned nodes ("skins", JOINTS_0 / WEIGHTS_0) also gives sc.skinning, a wire.SkinDesc over the animation's node table (Scene.set_skinning,
     after Scene.set_animation); None without.
+    A file with morph targets driven by a "weights" channel also gives sc.morph, a wire.MorphDesc (Scene.set_morph, after set_animation and set_skinning); None
+    without.  Targets without a channel are applied once at load with their default weights.
     textures="compressed": the .dds payloads are not decoded (ZRH_LOAD_KEEP_COMPRESSED): sc.texels stays empty, sc.texture_sources / sc.texture_payload
     carry the blocks and api.Scene decodes them on the device (zr_scene_create_compressed); sc.decode_textures() makes the texels on the host.
     A .png image travels as its level 0 (wire.TEX_SRC_RAW_MIP0) and its other levels are generated on the device.
@@ -700,6 +720,15 @@ def load_gltf_native(path, rho=None, textures="decoded", jpeg=False):
             k = k.contents
             sc.skinning = wire.SkinDesc(arr(k.joints, k.num_joints, wire.SKIN_JOINT), arr(k.ranges, k.num_ranges, wire.SKIN_RANGE),
                                         arr(k.influences, k.num_influences, wire.SKIN_INFLUENCE))
+        sc.morph = None
+        L.zrh_scene_data_morph.argtypes = [C.c_void_p]
+        L.zrh_scene_data_morph.restype = C.POINTER(wire.MorphDescC)
+        m = L.zrh_scene_data_morph(h)
+        if m:
+            m = m.contents
+            sc.morph = wire.MorphDesc(arr(m.tracks, m.num_tracks, wire.MORPH_TRACK), arr(m.targets, m.num_targets, wire.MORPH_TARGET), arr(m.ranges, m.num_ranges, wire.MORPH_RANGE),
+                                      arr(m.times, m.num_times, np.dtype("<f4")), arr(m.values, m.num_values, np.dtype("<f4")),
+                                      arr(m.rest_weights, m.num_rest_weights, np.dtype("<f4")), arr(m.deltas, 3 * m.num_deltas, np.dtype("<f4")))
         offs = (C.c_uint32 * 4)()
         L.zrh_scene_data_tex_offsets(h, offs)
         return sc, dict(base_color=offs[0], normal=offs[1], metallic_roughness=offs[2], emissive=offs[3])

@@ -83,6 +83,12 @@ SKIN_JOINT = np.dtype([("node", "<u4"), ("inverse_bind", "<f4", 12)])
 SKIN_INFLUENCE = np.dtype([("joint", "<u2", 4), ("weight", "<f4", 4)])
 SKIN_RANGE = np.dtype([("first_vertex", "<u4"), ("num_vertices", "<u4"), ("first_influence", "<u4")])
 assert SKIN_JOINT.itemsize == 52 and SKIN_INFLUENCE.itemsize == 24 and SKIN_RANGE.itemsize == 12
+# morph targets (zr_morph_track / zr_morph_target / zr_morph_range / zr_morph_desc, include/zr_wire.h)
+MORPH_NONE = 0xffffffff
+MORPH_TRACK = np.dtype([("num_targets", "<u4"), ("first_key", "<u4"), ("num_keys", "<u4"), ("first_value", "<u4"), ("first_rest", "<u4"), ("loop", "<u4"), ("t0", "<f4")])
+MORPH_TARGET = np.dtype([("first_pos", "<u4"), ("first_nrm", "<u4"), ("first_tan", "<u4")])
+MORPH_RANGE = np.dtype([("first_vertex", "<u4"), ("num_vertices", "<u4"), ("first_target", "<u4"), ("num_targets", "<u4"), ("track", "<u4")])
+assert MORPH_TRACK.itemsize == 28 and MORPH_TARGET.itemsize == 12 and MORPH_RANGE.itemsize == 20
 
 GB_PLANE_NAMES = ["base_color", "normal", "metallic_roughness", "motion_vector", "emissive_color", "ior", "coat",
                   "depth", "tri_diff_geo_a", "tri_diff_geo_b"]
@@ -156,6 +162,38 @@ class SkinDesc:
         d.joints, d.num_joints = (self.joints.ctypes.data if len(self.joints) else None), len(self.joints)
         d.ranges, d.num_ranges = (self.ranges.ctypes.data if len(self.ranges) else None), len(self.ranges)
         d.influences, d.num_influences = (self.influences.ctypes.data if len(self.influences) else None), len(self.influences)
+        return d
+
+
+class MorphDescC(C.Structure):
+    _fields_ = [("tracks", C.c_void_p), ("num_tracks", C.c_uint32), ("targets", C.c_void_p), ("num_targets", C.c_uint32), ("ranges", C.c_void_p), ("num_ranges", C.c_uint32),
+                ("times", C.c_void_p), ("num_times", C.c_uint32), ("values", C.c_void_p), ("num_values", C.c_uint32),
+                ("rest_weights", C.c_void_p), ("num_rest_weights", C.c_uint32), ("deltas", C.c_void_p), ("num_deltas", C.c_uint32)]
+
+
+assert C.sizeof(MorphDescC) == 112
+
+
+class MorphDesc:
+    """zr_morph_desc over numpy arrays it keeps alive: tracks (MORPH_TRACK), targets (MORPH_TARGET), ranges (MORPH_RANGE), the pools of key times, of key-major
+    weight values and of rest weights (float32), and deltas: the pool of float32 triples, (n, 3).  Vertex first_vertex + v of a range reads triple first_* + v of
+    each of its targets"""
+
+    def __init__(self, tracks, targets, ranges, times, values, rest_weights, deltas):
+        self.tracks = np.ascontiguousarray(tracks, MORPH_TRACK).reshape(-1)
+        self.targets = np.ascontiguousarray(targets, MORPH_TARGET).reshape(-1)
+        self.ranges = np.ascontiguousarray(ranges, MORPH_RANGE).reshape(-1)
+        self.times = np.ascontiguousarray(times, np.float32).reshape(-1)
+        self.values = np.ascontiguousarray(values, np.float32).reshape(-1)
+        self.rest_weights = np.ascontiguousarray(rest_weights, np.float32).reshape(-1)
+        self.deltas = np.ascontiguousarray(deltas, np.float32).reshape(-1, 3)
+
+    def c_desc(self):
+        d = MorphDescC()
+        for name in ("tracks", "targets", "ranges", "times", "values", "rest_weights", "deltas"):
+            a = getattr(self, name)
+            setattr(d, name, a.ctypes.data if len(a) else None)
+            setattr(d, "num_" + name, len(a))
         return d
 
 
