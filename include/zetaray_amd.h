@@ -453,7 +453,7 @@ int zr_scene_animate(zr_scene* scene, float t);
  * the rest-pose records of the listed ranges -- the vertices as they are at the call, or as the set it replaces found them -- in a device buffer of its
  * own.  It replaces an earlier set; a null or empty desc clears the set and puts the rest pose back (vertex buffer and hit tables; the acceleration
  * structure follows with the next instance update, as above).  zr_scene_set_animation on a scene with a skin set clears the skin the same way.
- * There is no new per-frame call: with a set, zr_scene_animate_async(scene, stream, t) also runs the joint and the vertex kernel (zr_tu_skin.hip, the
+ * There is no new per-frame call: with a set, zr_scene_animate_async(scene, stream, t) also runs the joint and the vertex kernel (zr_tu_pose.hip, the
  * arithmetic of include/zr_skin.h) between the node matrices and the move / refit tail.  In every device byte -- vertex buffer, both hit tables, both
  * instance buffers, object-to-world matrices, emissive records, BVH triangles and nodes, the role swap, the ordering against renders on other streams --
  * it equals the host sequence
@@ -478,7 +478,7 @@ int zr_scene_has_skinning(const zr_scene* scene);      /* 1 while a skin set is 
  * set; a null or empty desc clears the set and puts the rest pose back (vertex buffer and hit tables; the acceleration structure follows with the next
  * instance update).  zr_scene_set_animation and zr_scene_set_skinning on a scene with a morph set clear it the same way.
  * There is no new per-frame call: with a set, zr_scene_animate_async(scene, stream, t) also samples the weights (k_morph_weights) and poses the morph
- * ranges (k_morph_vertices, zr_tu_morph.hip; the arithmetic of include/zr_morph.h) between the node matrices and the move / refit tail.  A range that is
+ * ranges (k_pose_vertices, zr_tu_pose.hip; the arithmetic of include/zr_morph.h) between the node matrices and the move / refit tail.  A range that is
  * morphed and skinned is posed once, by the fused kernel: the morphed record, with its encoded words, is the rest record the skin blend takes.  In every
  * device byte -- vertex buffer, both hit tables, both instance buffers, object-to-world matrices, emissive records, BVH -- it equals the host sequence
  *   1. zrh_scene_data_animate(t),

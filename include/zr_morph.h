@@ -3,7 +3,7 @@
  *
  * glTF 2.0 section 3.7.2.2: a morphed vertex is its rest attribute plus the weighted sum of its targets' deltas; the weights are the mesh's or the node's,
  * or sampled from an animation channel with the path `weights`.  zr_scene_io.cpp (zrh_morph_pose, the host form), zr_api.hip (the setter's check),
- * tests/morphmath and zr_tu_morph.hip (zr_scene_animate with a morph set) all compile these functions; under the arithmetic contract of zr_detmath.h
+ * tests/morphmath and zr_tu_pose.hip (zr_scene_animate with a morph set) all compile these functions; under the arithmetic contract of zr_detmath.h
  * (+ - * / sqrt fma, round to nearest even, -ffp-contract=off) they give the same bytes.  Every fma below is written; nothing else is fused.
  *
  *   weights        SampleWeight: zran::SampleAnimation's control flow over a plain array of key times.  u = t - t0; u <= first key: the first key's
@@ -85,7 +85,7 @@ ZR_HD void AddDelta(float w, const float* d, float* acc)
     ZR_UNROLL
     for (int c = 0; c < 3; c++) acc[c] = zr_fma(w, d[c], acc[c]);
 }
-/* one vertex in three steps, so that the device form can schedule its loads (zr_tu_morph.hip issues two targets' loads before the first one's fmas) and
+/* one vertex in three steps, so that the device form can schedule its loads (zr_tu_pose.hip issues two targets' loads before the first one's fmas) and
  * still compile this arithmetic: Begin, Apply for the targets k = 0 .. T - 1 in order, End */
 struct Acc { float p[3], n[3], t[3]; bool anyN, anyT; };
 ZR_HD void Begin(const zr_vertex& rest, Acc& a)
@@ -125,10 +125,6 @@ ZR_HD void MorphVertex(const zr_vertex& rest, const zr_morph_target* targets, ui
     }
     End(rest, a, out);
 }
-
-/* a range as zr_scene_set_morph lays it out for the kernels of zr_tu_morph.hip: weightFirst = where its track's weights start in the weight array;
- * skinned = 0: restFirst = where its rest records start in the set's own buffer; skinned = 1: in the skin set's, and firstInfluence is the skin range's */
-struct DeviceRange { uint32_t firstVertex, numVertices, firstTarget, numTargets, weightFirst, restFirst, firstInfluence, skinned; };
 
 /* ---- host side: the whole set */
 /* offs[i]: where track i's weights start in the set's weight array; returns the array's length */

@@ -3,7 +3,7 @@
  *
  * glTF 2.0 section 3.7.3: a skinned vertex is moved by the weighted sum of its (up to four) joint matrices, a joint matrix being the joint node's world
  * matrix times the joint's inverse bind matrix.  zr_scene_io.cpp (zrh_skin_pose, the host form, and the loader's check of its tables), zr_api.hip
- * (the setter's check), tests/skinmath and zr_tu_skin.hip (zr_scene_animate with a skin set) all compile these functions; under the arithmetic contract of zr_detmath.h (+ - * / sqrt fma, round to nearest
+ * (the setter's check), tests/skinmath and zr_tu_pose.hip (zr_scene_animate with a skin set) all compile these functions; under the arithmetic contract of zr_detmath.h (+ - * / sqrt fma, round to nearest
  * even, -ffp-contract=off) they give the same bytes.  Every fma below is written; nothing else is fused.
  *
  * Matrices are 3 x 4 row-major in the column-vector convention (zr_scene_desc.instance_to_world, the node matrices of zr_anim.h): M[4 r + c].
@@ -102,9 +102,6 @@ ZR_HD void SkinVertex(const zr_vertex& rest, const zr_skin_influence& f, const f
         jointMatrices + 12 * (size_t)f.joint[3], f.weight, M);
     PoseVertex(rest, M, out);
 }
-
-/* a range as zr_scene_set_skinning lays it out for the kernels of zr_tu_skin.hip: restFirst = where its rest records start in the set's own buffer */
-struct DeviceRange { uint32_t firstVertex, numVertices, firstInfluence, restFirst; };
 
 /* ---- host side: the whole set.  nodeWorld: the node matrices of zran::EvalNodeWorlds; J: num_joints x 12 floats */
 static inline void EvalJointMatrices(const zr_skin_desc& d, const float* nodeWorld, float* J)

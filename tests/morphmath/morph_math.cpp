@@ -1,5 +1,5 @@
 // TEST-ONLY: include/zr_morph.h compiled for the host on its own, so that tests/test_morph_cpu.py can hold the header's functions -- the ones the device
-// kernels of zr_tu_morph.hip compile -- against a float64 restatement, and tests/test_morph_gpu.py can pose vertices for the host form.
+// kernels of zr_tu_pose.hip compile -- against a float64 restatement, and tests/test_morph_gpu.py can pose vertices for the host form.
 #include "../../include/zr_morph.h"
 
 extern "C" {

@@ -1,5 +1,5 @@
 // TEST-ONLY: include/zr_skin.h compiled for the host on its own, so that tests/test_skin_cpu.py can hold the header's functions -- the ones the device
-// kernels of zr_tu_skin.hip compile -- against a float64 restatement stage by stage, and tests/test_skin_gpu.py can pose vertices for the host form.
+// kernels of zr_tu_pose.hip compile -- against a float64 restatement stage by stage, and tests/test_skin_gpu.py can pose vertices for the host form.
 #include "../../include/zr_skin.h"
 
 extern "C" {

@@ -246,7 +246,7 @@ def test_wire_records_and_the_surface():
     api = open(os.path.join(ROOT, "include", "zetaray_amd.h")).read()
     assert "int zr_scene_set_morph(zr_scene* scene, const zr_morph_desc* desc);" in api and "int zr_scene_has_morph(const zr_scene* scene);" in api
     mk = open(os.path.join(ROOT, "zetaray_amd", "csrc", "Makefile")).read()
-    assert "zr_tu_morph.o" in mk.split("OBJS :=")[1].split("\n")[0]
+    assert "zr_tu_pose.o" in mk.split("OBJS :=")[1].split("\n")[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------- the loader

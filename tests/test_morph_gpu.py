@@ -1,4 +1,4 @@
-"""zr_scene_set_morph: morph targets weighted and applied on the device by every zr_scene_animate (zr_tu_morph.hip), against the host form --
+"""zr_scene_set_morph: morph targets weighted and applied on the device by every zr_scene_animate (zr_tu_pose.hip), against the host form --
 zrh_scene_data_animate, zr_scene_update_vertices with the vertices include/zr_morph.h (then include/zr_skin.h, where the range is skinned) computes on the
 host, then the host-form emissive and instance updates -- bit for bit: the vertex buffer, both instance buffers, toWorld, the emissive records, rendered
 frames (through which the hit tables and the refit tree are held), a fresh scene made from the posed vertices, two streams, the picked-instance mask,
@@ -427,6 +427,142 @@ def test_clearing_restores_the_rest_bytes(api, world):
     S.animate(0.8)
     S.set_animation(None)
     assert not S.has_morph() and S.download_vertices().tobytes() == rest
+    S.close()
+
+
+def _skin_only(anim, skin, vertices, t):
+    """the whole vertex array of the host form at time t with the skin set alone"""
+    out = vertices.copy()
+    sk = scases.host_posed(anim, skin, scases.rest_of_ranges(skin, vertices), t)
+    k = 0
+    for r in skin.ranges:
+        f, n = int(r["first_vertex"]), int(r["num_vertices"])
+        out[f:f + n] = sk[k:k + n]
+        k += n
+    return out
+
+
+def test_the_skin_only_ranges_follow_the_morph_set(api, world):
+    """a skin set with two ranges R0, R1; morph set A lists R0, then B lists R1 and not R0 (R0 is skin-only again, R1 fused), then no morph set (both skin-only):
+    every animate equals the host form.  A replaced or cleared morph set puts ITS ranges back to rest at the call; a skin-only range keeps its last pose until
+    the next animate.  set_skinning(None) leaves the rest bytes"""
+    sc, firsts = world
+    aj = scases.joint_chain(4)
+    anim = aj[0]
+    R0, R1 = (firsts[0] + 1, 201), (firsts[0] + 300, 130)
+    skin = _skin(sc, aj, [R0, R1])
+    rng = np.random.default_rng(51)
+    A = cases.morph_set([R0 + (0,)], [cases.keyed_track(rng, 2)], seed=52)
+    B = cases.morph_set([R1 + (0,)], [cases.keyed_track(rng, 2, loop=1)], seed=53)
+    rest = sc.vertices
+    S = api.Scene(sc)
+    S.set_animation(anim)
+    S.set_skinning(skin)
+    S.set_morph(A)
+    S.animate(0.5)
+    at_a = cases.posed_scene_vertices(anim, skin, A, rest, 0.5)
+    assert S.download_vertices().tobytes() == at_a.tobytes() != rest.tobytes()
+    S.set_morph(B)
+    want = at_a.copy()
+    want[R0[0]:R0[0] + R0[1]] = rest[R0[0]:R0[0] + R0[1]]      # A's range is at rest; R1, skin-only under A, still holds the pose of t = 0.5
+    assert S.download_vertices().tobytes() == want.tobytes()
+    S.animate(0.8)
+    at_b = cases.posed_scene_vertices(anim, skin, B, rest, 0.8)
+    assert S.download_vertices().tobytes() == at_b.tobytes() != at_a.tobytes()
+    S.set_morph(None)
+    want = at_b.copy()
+    want[R1[0]:R1[0] + R1[1]] = rest[R1[0]:R1[0] + R1[1]]
+    assert S.has_skinning() and not S.has_morph() and S.download_vertices().tobytes() == want.tobytes()
+    S.animate(1.1)
+    assert S.download_vertices().tobytes() == _skin_only(anim, skin, rest, 1.1).tobytes() != rest.tobytes()
+    S.set_skinning(None)
+    assert not S.has_skinning() and S.download_vertices().tobytes() == rest.tobytes()
+    S.close()
+
+
+def test_a_new_skin_set_over_a_morphed_only_range(api, world):
+    """no skin set, [f, f + 300) morphed and animated; set_skinning with [f + 100, f + 400), which partly covers it: the morph set goes, the vertices are the
+    rest bytes right after the call, and animate poses the skin range from the REST records -- not from the morphed bytes the buffer held at the call"""
+    sc, firsts = world
+    aj = scases.joint_chain(4)
+    anim = aj[0]
+    f = firsts[1] + 3
+    morph = cases.morph_set([(f, 300, 0)], [cases.keyed_track(np.random.default_rng(54), 2)], seed=55)
+    skin = _skin(sc, aj, [(f + 100, 300)])
+    rest = sc.vertices
+    S = api.Scene(sc)
+    S.set_animation(anim)
+    S.set_morph(morph)
+    S.animate(0.8)
+    assert S.download_vertices().tobytes() == cases.posed_scene_vertices(anim, None, morph, rest, 0.8).tobytes() != rest.tobytes()
+    S.set_skinning(skin)
+    assert not S.has_morph() and S.has_skinning() and S.download_vertices().tobytes() == rest.tobytes()
+    S.animate(0.5)
+    assert S.download_vertices().tobytes() == _skin_only(anim, skin, rest, 0.5).tobytes() != rest.tobytes()
+    S.set_skinning(None)
+    assert S.download_vertices().tobytes() == rest.tobytes()
+    S.close()
+
+
+def test_empty_ranges(api, world):
+    """a skin set and morph sets that each list a range of no vertices between two non-empty ones, one empty morph range starting where a skin range starts:
+    set, two times, a replacing morph set, clearing -- the host form / the rest bytes at every step"""
+    sc, firsts = world
+    aj = scases.joint_chain(4)
+    anim = aj[0]
+    a, c = firsts[0] + 5, firsts[0] + 400
+    skin = _skin(sc, aj, [(a, 100), (a + 150, 0), (c, 120)])
+    rng = np.random.default_rng(56)
+    first = cases.morph_set([(firsts[1] + 3, 150, 0), (a, 0, 0), (firsts[1] + 500, 0, 0), (c, 120, 0)], [cases.keyed_track(rng, 2)], seed=57)
+    second = cases.morph_set([(a, 100, 0), (c, 0, 0), (firsts[1] + 100, 200, 0)], [cases.keyed_track(rng, 2, loop=1)], seed=58)
+    rest = sc.vertices
+    S = api.Scene(sc)
+    S.set_animation(anim)
+    S.set_skinning(skin)
+    S.set_morph(first)
+    for t in (0.5, 1.1):
+        S.animate(t)
+        assert S.download_vertices().tobytes() == cases.posed_scene_vertices(anim, skin, first, rest, t).tobytes() != rest.tobytes()
+    S.set_morph(second)
+    for t in (0.2, 0.8):
+        S.animate(t)
+        assert S.download_vertices().tobytes() == cases.posed_scene_vertices(anim, skin, second, rest, t).tobytes()
+    S.set_morph(None)
+    S.animate(0.8)
+    assert S.download_vertices().tobytes() == _skin_only(anim, skin, rest, 0.8).tobytes() != rest.tobytes()
+    S.set_morph(first)
+    S.animate(0.5)
+    S.set_skinning(None)
+    assert not S.has_morph() and not S.has_skinning() and S.download_vertices().tobytes() == rest.tobytes()
+    S.close()
+
+
+def test_update_vertices_inside_a_posed_range(api, world):
+    """16 arbitrary records written by hand into a morphed and skinned range: the next animate overwrites them from the rest records captured when the sets
+    were laid out, and clearing puts THOSE back, not the records written by hand"""
+    sc, firsts = world
+    aj = scases.joint_chain(4)
+    anim = aj[0]
+    first, n = firsts[0] + 7, 257
+    skin = _skin(sc, aj, [(first, n)])
+    morph = cases.morph_set([(first, n, 0)], [cases.keyed_track(np.random.default_rng(59), 2)], seed=60)
+    rest = sc.vertices
+    S = api.Scene(sc)
+    S.set_animation(anim)
+    S.set_skinning(skin)
+    S.set_morph(morph)
+    S.animate(0.5)
+    junk = rest[first + 40:first + 56].copy()
+    junk["pos"] += np.float32(0.37)
+    junk["normal"], junk["tangent"] = junk["tangent"].copy(), junk["normal"].copy()
+    S.update_vertices(first + 100, junk)
+    got = S.download_vertices()
+    assert got[first + 100:first + 116].tobytes() == junk.tobytes()
+    S.animate(0.8)
+    assert S.download_vertices().tobytes() == cases.posed_scene_vertices(anim, skin, morph, rest, 0.8).tobytes()
+    S.update_vertices(first + 100, junk)
+    S.set_skinning(None)
+    assert not S.has_morph() and not S.has_skinning() and S.download_vertices().tobytes() == rest.tobytes()
     S.close()
 
 

@@ -182,7 +182,7 @@ def test_wire_records_and_the_surface():
         assert hasattr(api.Scene, m)
     assert hasattr(api.Renderer, "set_skinning")
     mk = open(os.path.join(ROOT, "zetaray_amd", "csrc", "Makefile")).read()
-    assert "zr_tu_skin.o" in mk.split("OBJS :=")[1].split("\n")[0]
+    assert "zr_tu_pose.o" in mk.split("OBJS :=")[1].split("\n")[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------- the loader (zrh_gltf_load: "skins", JOINTS_0, WEIGHTS_0)

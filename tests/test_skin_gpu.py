@@ -1,4 +1,4 @@
-"""zr_scene_update_vertices / zr_scene_set_skinning: skinned vertices posed on the device by every zr_scene_animate (zr_tu_skin.hip), against the host form --
+"""zr_scene_update_vertices / zr_scene_set_skinning: skinned vertices posed on the device by every zr_scene_animate (zr_tu_pose.hip), against the host form --
 zrh_scene_data_animate, zr_scene_update_vertices with the vertices include/zr_skin.h computes on the host, then the host-form emissive and instance
 updates -- bit for bit: the vertex buffer, both instance buffers, toWorld, the emissive records, rendered frames (through which the hit tables and the
 refit tree are held), a fresh scene made from the posed vertices, update_vertices on its own across streams and under the background rebuild, the

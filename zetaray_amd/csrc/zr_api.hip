@@ -86,15 +86,7 @@ namespace zr { hipError_t LaunchMoveInstances(hipStream_t st, zr_mesh_instance* 
     const uint32_t* moved, uint32_t nMoved, zr_emissive_triangle* emissives, const zr_emissive_triangle* object, const uint32_t* owner, uint32_t emFirst, uint32_t emEnd); }   // zr_tu_scene_update.hip
 namespace zr { hipError_t LaunchAnimate(hipStream_t st, float t, const zr_anim_node* nodes, const zr_keyframe* keys, const uint32_t* animated, uint32_t nAnimated,
     const uint32_t* levelNodes, const uint32_t* levelOffsets, uint32_t numLevels, float* nodeLocal, float* nodeWorld, const uint32_t* instNode, uint32_t nInst, uint32_t* moved); }   // zr_tu_anim.hip
-#include "../../include/zr_skin.h"
-namespace zr { using SkinRange = zrsk::DeviceRange;      // zr_tu_skin.hip
-    hipError_t LaunchSkin(hipStream_t st, float* J, const float* nodeWorld, const uint32_t* jointNode, const float* inverseBind, uint32_t numJoints, const SkinRange* ranges,
-        uint32_t numRanges, const zr_vertex* rest, const zr_skin_influence* influences, zr_vertex* vertices, VtxDir* vtxNormals, VtxDir* vtxTangents); }
-#include "../../include/zr_morph.h"
-namespace zr { using MorphRange = zrmo::DeviceRange;      // zr_tu_morph.hip
-    hipError_t LaunchMorph(hipStream_t st, float t, float* weights, uint32_t numWeights, const zr_morph_track* tracks, const uint32_t* trackOfWeight, const uint32_t* weightFirst,
-        const float* times, const float* values, const float* restWeights, const zr_morph_target* targets, const float* deltas, const MorphRange* ranges, uint32_t numRanges,
-        const zr_vertex* restOwn, const zr_vertex* restSkin, const zr_skin_influence* influences, const float* J, zr_vertex* vertices, VtxDir* vtxNormals, VtxDir* vtxTangents); }
+#include "zr_pose.h"      // zr_tu_pose.hip
 namespace zr { hipError_t LaunchFillInstRecs(hipStream_t st, InstRec* recs, const zr_mesh_instance* instances, uint32_t n);      // zr_tu_scene_update.hip
                hipError_t LaunchFillVtxNormals(hipStream_t st, VtxDir* out, const zr_vertex* vertices, uint32_t n, bool tangent); }
 namespace zr { size_t AliasScratchWords(uint32_t n);      // zr_tu_alias.hip
@@ -669,28 +661,30 @@ struct zr_scene
         float lastT = 0; bool hasT = false, hostStale = false;
     };
     std::unique_ptr<Anim> anim; std::mutex animMtx;
-    // ---- skinned meshes (zr_scene_set_skinning; kernels in zr_tu_skin.hip, arithmetic in include/zr_skin.h): with a set, every zr_scene_animate also poses
+    // ---- skinned meshes (zr_scene_set_skinning; kernels in zr_tu_pose.hip, arithmetic in include/zr_skin.h): with a set, every zr_scene_animate also poses
     // the listed vertex ranges from their rest records.  What set_skinning lays out once: the joints' nodes and inverse bind matrices as two arrays (48-byte
-    // matrices: 16-byte rows), the influences, the rest records of the ranges, range after range, in a buffer of the set's own, and the joint matrices
-    // the frame's first kernel writes.  ranges / hRest: the host's copies (hRest in the device layout); a clear puts hRest back.  hVertices keeps the rest pose (only the background builder reads it: topology)
+    // matrices: 16-byte rows), the influences, and the joint matrices the frame's first kernel writes.  ranges: the caller's, which a later set_morph is
+    // checked and laid out against
     struct Skin
     {
-        std::vector<zr::SkinRange> ranges; std::vector<zr_vertex> hRest; uint32_t numJoints = 0;
-        DevBuf<uint32_t> dJointNode; DevBuf<float> dInverseBind, dJ; DevBuf<zr_skin_influence> dInfluences; DevBuf<zr_vertex> dRest;
+        std::vector<zr_skin_range> ranges; uint32_t numJoints = 0;
+        DevBuf<uint32_t> dJointNode; DevBuf<float> dInverseBind, dJ; DevBuf<zr_skin_influence> dInfluences;
     };
     std::unique_ptr<Skin> skin;
-    // ---- morph targets (zr_scene_set_morph; kernels in zr_tu_morph.hip, arithmetic in include/zr_morph.h): with a set, every zr_scene_animate also samples
+    // ---- morph targets (zr_scene_set_morph; kernels in zr_tu_pose.hip, arithmetic in include/zr_morph.h): with a set, every zr_scene_animate also samples
     // the tracks' weights into dWeights (track after track) and poses the listed ranges.  What set_morph lays out once: the tables, each weight's track
-    // and each track's first weight, the rest records of the morph-only ranges (range after range, hRest the host's copy; a clear puts it back) -- a
-    // range that is also a range of the skin set takes the skin set's rest records and is posed by the fused kernel alone: skinLeft are the skin
-    // ranges LaunchSkin still gets
+    // and each track's first weight
     struct Morph
     {
-        std::vector<zr::MorphRange> ranges; std::vector<zr::SkinRange> skinLeft; std::vector<zr_vertex> hRest; uint32_t numWeights = 0;
+        uint32_t numWeights = 0;
         DevBuf<zr_morph_track> dTracks; DevBuf<zr_morph_target> dTargets; DevBuf<uint32_t> dTrackOfWeight, dWeightFirst;
-        DevBuf<float> dTimes, dValues, dRestWeights, dDeltas, dWeights; DevBuf<zr_vertex> dRest;
+        DevBuf<float> dTimes, dValues, dRestWeights, dDeltas, dWeights;
     };
     std::unique_ptr<Morph> morph;
+    // ---- what the two sets pose each frame (ScenePoseRebuild is the one writer): the ranges of both as one list (zr_pose.h) -- the skin-only ranges in the
+    // skin set's order, then the morph set's in its order, a range both list once -- and the ranges' rest records, range after range, on the device and
+    // (hRest, same layout) on the host: what a range goes back to when its set goes.  hVertices keeps the rest pose (only the background builder reads it: topology)
+    struct Pose { std::vector<zr::PoseRange> ranges; std::vector<zr_vertex> hRest; DevBuf<zr_vertex> dRest; } pose;
     // zr_scene_update_vertices while a background build reads hVertices: the ranges wait here and reach hVertices once the builder's thread is done
     // (SceneFlushVertexCopies) -- the builder delivers topology, so the pose it saw does not matter, and the call does not wait for it
     std::vector<std::pair<uint32_t, std::vector<zr_vertex>>> hVertexPending;
@@ -1959,24 +1953,22 @@ static int RefitWriteRecords(zr_scene* s, hipStream_t st, const FrameUpdate& u, 
             HIP_TRY(zr::LaunchAnimate(st, u.t, A.dNodes.p, A.dKeys.p, A.dAnimated.p, A.nAnimated, A.dLevelNodes.p, A.levelOffsets.data(),
                 (uint32_t)A.levelOffsets.size() - 1, A.dLocal.p, A.dWorld.p, A.dInstNode.p, u.nMoved, A.dMoved.p));
             movedList = A.dMoved.p;
-            VtxDir* tangents = nullptr;
+            if (s->skin || s->morph)
+            {   // the node matrices are on the device: joint matrices and weights of time t, then the listed vertices and their hit-table entries, ahead of the refit that reads them
+                zr::PoseTables T{};
+                if (const zr_scene::Skin* K = s->skin.get())
+                { T.J = K->dJ.p; T.nodeWorld = A.dWorld.p; T.jointNode = K->dJointNode.p; T.inverseBind = K->dInverseBind.p; T.numJoints = K->numJoints; T.influences = K->dInfluences.p; }
+                if (const zr_scene::Morph* M = s->morph.get())
+                {
+                    T.weights = M->dWeights.p; T.numWeights = M->numWeights; T.tracks = M->dTracks.p; T.trackOfWeight = M->dTrackOfWeight.p; T.weightFirst = M->dWeightFirst.p;
+                    T.times = M->dTimes.p; T.values = M->dValues.p; T.restWeights = M->dRestWeights.p; T.targets = M->dTargets.p; T.deltas = M->dDeltas.p;
+                }
+                T.rest = s->pose.dRest.p;
+                VtxDir* tangents = nullptr;
 #if ZR_HIT_TANGENTS
-            tangents = s->vtxTangents.p;
+                tangents = s->vtxTangents.p;
 #endif
-            if (s->skin)
-            {   // the node matrices are on the device: joint matrices, then the listed vertices and their hit-table entries, ahead of the refit that reads them
-                // (with a morph set: only the ranges that are not morphed -- a morphed and skinned range is posed once, by the fused kernel below)
-                zr_scene::Skin& K = *s->skin;
-                const std::vector<zr::SkinRange>& ranges = s->morph ? s->morph->skinLeft : K.ranges;
-                HIP_TRY(zr::LaunchSkin(st, K.dJ.p, A.dWorld.p, K.dJointNode.p, K.dInverseBind.p, K.numJoints, ranges.data(), (uint32_t)ranges.size(), K.dRest.p,
-                    K.dInfluences.p, s->vertices.p, s->vtxNormals.p, tangents));
-            }
-            if (s->morph)
-            {   // the weights of time t, then the morph ranges from their rest records (the skin set's, its influences and the joint matrices just written, for a range that is also skinned)
-                zr_scene::Morph& M = *s->morph;
-                HIP_TRY(zr::LaunchMorph(st, u.t, M.dWeights.p, M.numWeights, M.dTracks.p, M.dTrackOfWeight.p, M.dWeightFirst.p, M.dTimes.p, M.dValues.p, M.dRestWeights.p,
-                    M.dTargets.p, M.dDeltas.p, M.ranges.data(), (uint32_t)M.ranges.size(), M.dRest.p, s->skin ? s->skin->dRest.p : nullptr,
-                    s->skin ? s->skin->dInfluences.p : nullptr, s->skin ? s->skin->dJ.p : nullptr, s->vertices.p, s->vtxNormals.p, tangents));
+                HIP_TRY(zr::LaunchPose(st, u.t, T, s->pose.ranges.data(), (uint32_t)s->pose.ranges.size(), s->vertices.p, s->vtxNormals.p, tangents));
             }
         }
         else if (u.nMoved) HIP_TRY(hipMemcpyAsync(s->movedDev.p, h + F.seedBytes, F.listBytes, hipMemcpyHostToDevice, st));
@@ -2256,17 +2248,113 @@ int zr_scene_move_instances_async(zr_scene* s, void* stream, const uint32_t* ins
     SceneAnimSyncHost(s);      // (a frame moved by hand between animated ones: the host's matrices are compared and replaced per moved instance)
     return SceneRefitUpdate(s, (hipStream_t)stream, u);
 }
+// the hit-table entries of vertices [first, first + count) from the vertex buffer as it is on `st`
+static int SceneFillVtxTables(zr_scene* s, hipStream_t st, uint32_t first, uint32_t count)
+{
+    hipError_t e = zr::LaunchFillVtxNormals(st, s->vtxNormals.p + first, s->vertices.p + first, count, false);
+#if ZR_HIT_TANGENTS
+    if (e == hipSuccess) e = zr::LaunchFillVtxNormals(st, s->vtxTangents.p + first, s->vertices.p + first, count, true);
+#endif
+    if (e != hipSuccess) return Fail(ZR_ERR_HIP, "k_fill_vtx_normals failed: %s", hipGetErrorString(e));
+    return ZR_OK;
+}
+// ---- the vertices zr_scene_animate poses (zr_scene::Pose).  Every change of the skin set, the morph set, the range list and the rest records is this call.
+// The skin set stays (keepSkin), or newSkin takes its place (null: none); newMorph takes the morph set's place (null: none) -- a morph set is laid out
+// against the skin set and never outlives a change of it.  The descs have passed ValidateSkin / ValidateMorph, newMorph against the skin ranges that will
+// hold.  Host-synchronous.  What can fail for want of memory happens before the scene is touched.
+static int ScenePoseRebuild(zr_scene* s, bool keepSkin, const zr_skin_desc* newSkin, const zr_morph_desc* newMorph)
+{
+    if (!newSkin && !newMorph && !s->morph && (keepSkin || !s->skin)) return ZR_OK;      // nothing to lay out, nothing to drop
+    const zr_scene::Pose& O = s->pose;
+    // the range list: the skin ranges no morph range equals, then the morph ranges; a range with no vertices is not listed
+    std::vector<zr_skin_range> skinRanges;
+    if (newSkin) skinRanges.assign(newSkin->ranges, newSkin->ranges + newSkin->num_ranges);
+    else if (keepSkin && s->skin) skinRanges = s->skin->ranges;
+    zr_skin_desc skinDesc{};
+    skinDesc.ranges = skinRanges.data(); skinDesc.num_ranges = (uint32_t)skinRanges.size();
+    const uint32_t numMorphRanges = newMorph ? newMorph->num_ranges : 0;
+    std::vector<uint32_t> weightFirst(newMorph ? newMorph->num_tracks : 0);
+    const uint32_t numWeights = newMorph ? zrmo::WeightOffsets(*newMorph, weightFirst.data()) : 0;
+    std::vector<int64_t> skinOf(numMorphRanges);
+    std::vector<uint8_t> morphed(skinRanges.size(), 0);
+    for (uint32_t i = 0; i < numMorphRanges; i++) if ((skinOf[i] = zrmo::SkinRangeOf(newMorph->ranges[i], &skinDesc)) >= 0) morphed[skinOf[i]] = 1;
+    zr_scene::Pose P;
+    auto list = [&P](zr::PoseRange g)
+    {
+        if (!g.numVertices) return;
+        g.restFirst = (uint32_t)P.hRest.size();
+        P.hRest.resize(P.hRest.size() + g.numVertices);
+        P.ranges.push_back(g);
+    };
+    for (size_t q = 0; q < skinRanges.size(); q++)
+        if (!morphed[q]) list(zr::PoseRange{skinRanges[q].first_vertex, skinRanges[q].num_vertices, 0, skinRanges[q].first_influence, 0, 0, 0, zr::kPoseSkin});
+    for (uint32_t i = 0; i < numMorphRanges; i++)
+    {
+        const zr_morph_range& g = newMorph->ranges[i];
+        const bool skinned = skinOf[i] >= 0;
+        list(zr::PoseRange{g.first_vertex, g.num_vertices, 0, skinned ? skinRanges[skinOf[i]].first_influence : 0u, g.first_target, g.num_targets, weightFirst[g.track],
+            skinned ? zr::kPoseSkin | zr::kPoseMorph : zr::kPoseMorph});
+    }
+    // the rest records: what the new ranges hold with the ranges listed until now back at rest (those may lie outside the new ones) -- the new ranges alone
+    // are read back, and the old rest records laid over them where the two meet
+    HIP_TRY(hipDeviceSynchronize());      // an animate in flight still reads the tables and writes the vertices; renders in flight read them
+    for (const zr::PoseRange& g : P.ranges)
+    {
+        HIP_TRY(hipMemcpy(P.hRest.data() + g.restFirst, s->vertices.p + g.firstVertex, (size_t)g.numVertices * sizeof(zr_vertex), hipMemcpyDeviceToHost));
+        for (const zr::PoseRange& o : O.ranges)
+        {
+            const uint64_t lo = std::max(g.firstVertex, o.firstVertex), hi = std::min((uint64_t)g.firstVertex + g.numVertices, (uint64_t)o.firstVertex + o.numVertices);
+            if (hi > lo) std::copy(O.hRest.begin() + o.restFirst + (lo - o.firstVertex), O.hRest.begin() + o.restFirst + (hi - o.firstVertex), P.hRest.begin() + g.restFirst + (lo - g.firstVertex));
+        }
+    }
+    int r;
+    if ((r = P.dRest.Upload(P.hRest.data(), P.hRest.size()))) return r;
+    std::unique_ptr<zr_scene::Skin> K;
+    if (newSkin)
+    {
+        K.reset(new zr_scene::Skin());
+        K->ranges = skinRanges; K->numJoints = newSkin->num_joints;
+        std::vector<uint32_t> jointNode(K->numJoints); std::vector<float> inverseBind(12 * (size_t)K->numJoints);
+        for (uint32_t j = 0; j < K->numJoints; j++) { jointNode[j] = newSkin->joints[j].node; std::memcpy(inverseBind.data() + 12 * (size_t)j, newSkin->joints[j].inverse_bind, 12 * sizeof(float)); }
+        if ((r = K->dJointNode.Upload(jointNode.data(), jointNode.size())) || (r = K->dInverseBind.Upload(inverseBind.data(), inverseBind.size())) ||
+            (r = K->dJ.Alloc(inverseBind.size())) || (r = K->dInfluences.Upload(newSkin->influences, newSkin->num_influences))) return r;
+    }
+    std::unique_ptr<zr_scene::Morph> M;
+    if (newMorph)
+    {
+        const zr_morph_desc* d = newMorph;
+        M.reset(new zr_scene::Morph());
+        M->numWeights = numWeights;
+        std::vector<uint32_t> trackOfWeight;
+        for (uint32_t i = 0; i < d->num_tracks; i++) trackOfWeight.insert(trackOfWeight.end(), d->tracks[i].num_targets, i);
+        if ((r = M->dTracks.Upload(d->tracks, d->num_tracks)) || (r = M->dTargets.Upload(d->targets, d->num_targets)) ||
+            (r = M->dTrackOfWeight.Upload(trackOfWeight.data(), trackOfWeight.size())) || (r = M->dWeightFirst.Upload(weightFirst.data(), weightFirst.size())) ||
+            (r = M->dTimes.Upload(d->times, d->num_times)) || (r = M->dValues.Upload(d->values, d->num_values)) || (r = M->dRestWeights.Upload(d->rest_weights, d->num_rest_weights)) ||
+            (r = M->dDeltas.Upload(d->deltas, 3 * (size_t)d->num_deltas)) || (r = M->dWeights.Alloc(M->numWeights))) return r;
+    }
+    // nothing of the scene has changed up to here.  The rest pose back into the ranges of a set that goes or is replaced, and their hit-table entries (a
+    // skin-only range of a skin set that stays keeps its last pose: the next animate writes it)
+    const uint32_t going = keepSkin ? zr::kPoseMorph : zr::kPoseSkin | zr::kPoseMorph;
+    for (const zr::PoseRange& o : O.ranges)
+    {
+        if (!(o.kind & going)) continue;
+        HIP_TRY(hipMemcpy(s->vertices.p + o.firstVertex, O.hRest.data() + o.restFirst, (size_t)o.numVertices * sizeof(zr_vertex), hipMemcpyHostToDevice));
+        if ((r = SceneFillVtxTables(s, nullptr, o.firstVertex, o.numVertices))) return r;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    if (!keepSkin) s->skin = std::move(K);
+    s->morph = std::move(M);
+    s->pose.ranges.swap(P.ranges); s->pose.hRest.swap(P.hRest); s->pose.dRest.Swap(P.dRest);
+    return ZR_OK;
+}
 // ---- keyframe animation: the tables once (zr_scene_set_animation), then one float per frame (zr_scene_animate_async)
-static int SceneClearSkin(zr_scene* s);
-static int SceneClearMorph(zr_scene* s);
 int zr_scene_set_animation(zr_scene* s, const zr_anim_desc* d)
 {
     if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_animation: null scene");
     HIP_TRY(hipSetDevice(s->device));
     if (!d || (!d->num_nodes && !d->num_instances))
     {
-        if (int r = SceneClearMorph(s)) return r;     // (a morph set goes with the animation it was set on, ahead of the skin whose rest records it uses)
-        if (int r = SceneClearSkin(s)) return r;      // (its joints are nodes of the table that goes)
+        if (int r = ScenePoseRebuild(s, false, nullptr, nullptr)) return r;      // (a skin set and a morph set go with the animation they were set on: the joints are nodes of the table that goes)
         SceneAnimSyncHost(s);
         HIP_TRY(hipDeviceSynchronize());      // an animate in flight still reads the tables
         std::lock_guard<std::mutex> lock(s->animMtx);
@@ -2308,8 +2396,7 @@ int zr_scene_set_animation(zr_scene* s, const zr_anim_desc* d)
     // nothing of the scene has changed up to here.  The animation it replaces: its last frame reaches the host's matrices, its kernels finish
     SceneAnimSyncHost(s);
     HIP_TRY(hipDeviceSynchronize());
-    if ((r = SceneClearMorph(s))) return r;
-    if ((r = SceneClearSkin(s))) return r;      // a skin belongs to the animation it was set on: its joints index the table this call replaces
+    if ((r = ScenePoseRebuild(s, false, nullptr, nullptr))) return r;      // a skin set and a morph set belong to the animation they were set on: the joints index the table this call replaces
     for (uint32_t i : A->instIdx) s->movedEver[i] = 1;      // the background builder gives each animated instance a subtree of its own
     std::lock_guard<std::mutex> lock(s->animMtx);
     s->anim = std::move(A);
@@ -2356,15 +2443,6 @@ int zr_scene_get_emissives(const zr_scene* s, void* stream, zr_emissive_triangle
 
 int zr_scene_has_skinning(const zr_scene* s) { return s && s->skin ? 1 : 0; }
 // ---- deformed geometry: a vertex range replaced by the caller (the host form), or posed on the device by every zr_scene_animate (zr_scene_set_skinning)
-static int SceneFillVtxTables(zr_scene* s, hipStream_t st, uint32_t first, uint32_t count)
-{
-    hipError_t e = zr::LaunchFillVtxNormals(st, s->vtxNormals.p + first, s->vertices.p + first, count, false);
-#if ZR_HIT_TANGENTS
-    if (e == hipSuccess) e = zr::LaunchFillVtxNormals(st, s->vtxTangents.p + first, s->vertices.p + first, count, true);
-#endif
-    if (e != hipSuccess) return Fail(ZR_ERR_HIP, "k_fill_vtx_normals failed: %s", hipGetErrorString(e));
-    return ZR_OK;
-}
 int zr_scene_update_vertices_async(zr_scene* s, void* stream, uint32_t first, uint32_t count, const zr_vertex* vertices)
 {
     if (!s || (!vertices && count)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_update_vertices: null argument");
@@ -2397,27 +2475,11 @@ int zr_scene_get_vertices(const zr_scene* s, void* stream, zr_vertex* out, uint3
     HIP_TRY(hipMemcpy(out, s->vertices.p + first, (size_t)count * sizeof(zr_vertex), hipMemcpyDeviceToHost));
     return ZR_OK;
 }
-// the rest pose back into the listed ranges and their hit-table entries, host-synchronous; the set is dropped
-static int SceneClearSkin(zr_scene* s)
-{
-    if (!s->skin) return ZR_OK;
-    HIP_TRY(hipDeviceSynchronize());      // an animate in flight still reads the tables; renders in flight read the vertices
-    zr_scene::Skin& K = *s->skin;
-    for (const zr::SkinRange& g : K.ranges)
-    {
-        if (!g.numVertices) continue;
-        HIP_TRY(hipMemcpy(s->vertices.p + g.firstVertex, K.hRest.data() + g.restFirst, (size_t)g.numVertices * sizeof(zr_vertex), hipMemcpyHostToDevice));
-        if (int r = SceneFillVtxTables(s, nullptr, g.firstVertex, g.numVertices)) return r;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    s->skin.reset();
-    return ZR_OK;
-}
 int zr_scene_set_skinning(zr_scene* s, const zr_skin_desc* d)
 {
     if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_skinning: null scene");
     HIP_TRY(hipSetDevice(s->device));
-    if (!d || (!d->num_joints && !d->num_ranges && !d->num_influences)) { if (int r = SceneClearMorph(s)) return r; return SceneClearSkin(s); }
+    if (!d || (!d->num_joints && !d->num_ranges && !d->num_influences)) return ScenePoseRebuild(s, false, nullptr, nullptr);      // (a morph set is laid out against the skin set: it goes too)
     uint32_t animNodes = 0;
     {
         std::lock_guard<std::mutex> lock(s->animMtx);
@@ -2426,120 +2488,25 @@ int zr_scene_set_skinning(zr_scene* s, const zr_skin_desc* d)
     }
     char msg[256];
     if (zrsk::ValidateSkin(*d, animNodes, (uint32_t)s->vertices.n, msg, sizeof(msg))) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_skinning: %s", msg);
-    if (int r = SceneClearMorph(s)) return r;      // a morph set is laid out against the skin set it was set after: it goes, and its ranges are at rest before the read-back below
-    std::unique_ptr<zr_scene::Skin> K(new zr_scene::Skin());
-    K->numJoints = d->num_joints;
-    std::vector<uint32_t> jointNode(d->num_joints); std::vector<float> inverseBind(12 * (size_t)d->num_joints);
-    for (uint32_t j = 0; j < d->num_joints; j++) { jointNode[j] = d->joints[j].node; std::memcpy(inverseBind.data() + 12 * (size_t)j, d->joints[j].inverse_bind, 12 * sizeof(float)); }
-    size_t restRecords = 0;
-    for (uint32_t i = 0; i < d->num_ranges; i++)
-    {
-        K->ranges.push_back(zr::SkinRange{d->ranges[i].first_vertex, d->ranges[i].num_vertices, d->ranges[i].first_influence, (uint32_t)restRecords});
-        restRecords += d->ranges[i].num_vertices;
-    }
-    // the rest records: what the ranges hold once the set this one replaces has put its own rest pose back (ranges of the old set may lie outside the new one's)
-    // -- the new ranges alone are read back, and the old set's rest records laid over them where the two meet
-    HIP_TRY(hipDeviceSynchronize());
-    K->hRest.assign(restRecords, zr_vertex{});
-    for (const zr::SkinRange& g : K->ranges)
-    {
-        if (!g.numVertices) continue;
-        HIP_TRY(hipMemcpy(K->hRest.data() + g.restFirst, s->vertices.p + g.firstVertex, (size_t)g.numVertices * sizeof(zr_vertex), hipMemcpyDeviceToHost));
-        if (s->skin) for (const zr::SkinRange& o : s->skin->ranges)
-        {
-            const uint64_t lo = std::max(g.firstVertex, o.firstVertex), hi = std::min((uint64_t)g.firstVertex + g.numVertices, (uint64_t)o.firstVertex + o.numVertices);
-            if (hi > lo) std::copy(s->skin->hRest.begin() + o.restFirst + (lo - o.firstVertex), s->skin->hRest.begin() + o.restFirst + (hi - o.firstVertex), K->hRest.begin() + g.restFirst + (lo - g.firstVertex));
-        }
-    }
-    int r;
-    if ((r = K->dJointNode.Upload(jointNode.data(), jointNode.size())) || (r = K->dInverseBind.Upload(inverseBind.data(), inverseBind.size())) ||
-        (r = K->dJ.Alloc(inverseBind.size())) || (r = K->dInfluences.Upload(d->influences, d->num_influences)) || (r = K->dRest.Upload(K->hRest.data(), K->hRest.size()))) return r;
-    // nothing of the scene has changed up to here
-    if ((r = SceneClearSkin(s))) return r;
-    s->skin = std::move(K);
-    return ZR_OK;
+    return ScenePoseRebuild(s, false, d, nullptr);
 }
 
 // ---- morph targets: the tables once (zr_scene_set_morph), then every zr_scene_animate samples the weights and poses the ranges
 int zr_scene_has_morph(const zr_scene* s) { return s && s->morph ? 1 : 0; }
-// the rest pose back into the listed ranges and their hit-table entries, host-synchronous; the set is dropped
-static int SceneClearMorph(zr_scene* s)
-{
-    if (!s->morph) return ZR_OK;
-    HIP_TRY(hipDeviceSynchronize());      // an animate in flight still reads the tables; renders in flight read the vertices
-    zr_scene::Morph& M = *s->morph;
-    for (const zr::MorphRange& g : M.ranges)
-    {
-        if (!g.numVertices) continue;
-        const zr_vertex* rest = g.skinned ? s->skin->hRest.data() + g.restFirst : M.hRest.data() + g.restFirst;
-        HIP_TRY(hipMemcpy(s->vertices.p + g.firstVertex, rest, (size_t)g.numVertices * sizeof(zr_vertex), hipMemcpyHostToDevice));
-        if (int r = SceneFillVtxTables(s, nullptr, g.firstVertex, g.numVertices)) return r;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    s->morph.reset();
-    return ZR_OK;
-}
 int zr_scene_set_morph(zr_scene* s, const zr_morph_desc* d)
 {
     if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_morph: null scene");
     HIP_TRY(hipSetDevice(s->device));
-    if (!d || (!d->num_tracks && !d->num_targets && !d->num_ranges)) return SceneClearMorph(s);
+    if (!d || (!d->num_tracks && !d->num_targets && !d->num_ranges)) return ScenePoseRebuild(s, true, nullptr, nullptr);
     {
         std::lock_guard<std::mutex> lock(s->animMtx);
         if (!s->anim) return Fail(ZR_ERR_NOT_INITIALIZED, "zr_scene_set_morph: no animation set (zr_scene_set_animation): zr_scene_animate owns the frame's time");
     }
-    // the skin set as a desc over its laid-out ranges: what the check and the fused kernel need of it
-    std::vector<zr_skin_range> skinRanges;
-    if (s->skin) for (const zr::SkinRange& g : s->skin->ranges) skinRanges.push_back(zr_skin_range{g.firstVertex, g.numVertices, g.firstInfluence});
-    zr_skin_desc skinDesc{};
-    skinDesc.ranges = skinRanges.data(); skinDesc.num_ranges = (uint32_t)skinRanges.size();
+    zr_skin_desc skinDesc{};      // the skin set's ranges: all the check needs of it
+    if (s->skin) { skinDesc.ranges = s->skin->ranges.data(); skinDesc.num_ranges = (uint32_t)s->skin->ranges.size(); }
     char msg[256];
     if (zrmo::ValidateMorph(*d, s->skin ? &skinDesc : nullptr, (uint32_t)s->vertices.n, msg, sizeof(msg))) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_morph: %s", msg);
-    std::unique_ptr<zr_scene::Morph> M(new zr_scene::Morph());
-    std::vector<uint32_t> weightFirst(d->num_tracks), trackOfWeight;
-    M->numWeights = zrmo::WeightOffsets(*d, weightFirst.data());
-    for (uint32_t i = 0; i < d->num_tracks; i++) trackOfWeight.insert(trackOfWeight.end(), d->tracks[i].num_targets, i);
-    std::vector<uint8_t> skinTaken(skinRanges.size(), 0);
-    size_t restRecords = 0;
-    for (uint32_t i = 0; i < d->num_ranges; i++)
-    {
-        const zr_morph_range& g = d->ranges[i];
-        const int64_t sr = zrmo::SkinRangeOf(g, s->skin ? &skinDesc : nullptr);
-        if (sr >= 0)
-        {
-            skinTaken[sr] = 1;
-            M->ranges.push_back(zr::MorphRange{g.first_vertex, g.num_vertices, g.first_target, g.num_targets, weightFirst[g.track], s->skin->ranges[sr].restFirst, s->skin->ranges[sr].firstInfluence, 1u});
-        }
-        else
-        {
-            M->ranges.push_back(zr::MorphRange{g.first_vertex, g.num_vertices, g.first_target, g.num_targets, weightFirst[g.track], (uint32_t)restRecords, 0u, 0u});
-            restRecords += g.num_vertices;
-        }
-    }
-    if (s->skin) for (size_t q = 0; q < skinRanges.size(); q++) if (!skinTaken[q]) M->skinLeft.push_back(s->skin->ranges[q]);
-    // the rest records of the morph-only ranges: what they hold once the set this one replaces has put its own rest pose back (as zr_scene_set_skinning)
-    HIP_TRY(hipDeviceSynchronize());
-    M->hRest.assign(restRecords, zr_vertex{});
-    for (const zr::MorphRange& g : M->ranges)
-    {
-        if (!g.numVertices || g.skinned) continue;
-        HIP_TRY(hipMemcpy(M->hRest.data() + g.restFirst, s->vertices.p + g.firstVertex, (size_t)g.numVertices * sizeof(zr_vertex), hipMemcpyDeviceToHost));
-        if (s->morph) for (const zr::MorphRange& o : s->morph->ranges)
-        {
-            if (o.skinned) continue;      // (a morph-only range of the new set cannot meet a skin range)
-            const uint64_t lo = std::max(g.firstVertex, o.firstVertex), hi = std::min((uint64_t)g.firstVertex + g.numVertices, (uint64_t)o.firstVertex + o.numVertices);
-            if (hi > lo) std::copy(s->morph->hRest.begin() + o.restFirst + (lo - o.firstVertex), s->morph->hRest.begin() + o.restFirst + (hi - o.firstVertex), M->hRest.begin() + g.restFirst + (lo - g.firstVertex));
-        }
-    }
-    int r;
-    if ((r = M->dTracks.Upload(d->tracks, d->num_tracks)) || (r = M->dTargets.Upload(d->targets, d->num_targets)) ||
-        (r = M->dTrackOfWeight.Upload(trackOfWeight.data(), trackOfWeight.size())) || (r = M->dWeightFirst.Upload(weightFirst.data(), weightFirst.size())) ||
-        (r = M->dTimes.Upload(d->times, d->num_times)) || (r = M->dValues.Upload(d->values, d->num_values)) || (r = M->dRestWeights.Upload(d->rest_weights, d->num_rest_weights)) ||
-        (r = M->dDeltas.Upload(d->deltas, 3 * (size_t)d->num_deltas)) || (r = M->dWeights.Alloc(M->numWeights)) || (r = M->dRest.Upload(M->hRest.data(), M->hRest.size()))) return r;
-    // nothing of the scene has changed up to here
-    if ((r = SceneClearMorph(s))) return r;
-    s->morph = std::move(M);
-    return ZR_OK;
+    return ScenePoseRebuild(s, true, nullptr, d);
 }
 
 int zr_wire_layout(char* buf, size_t cap)

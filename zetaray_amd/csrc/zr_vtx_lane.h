@@ -1,5 +1,5 @@
-// zr_vtx_lane.h -- how one lane moves a vertex record, an influence record and a joint matrix: shared by the kernels that pose vertices (zr_tu_skin.hip,
-// zr_tu_morph.hip).  A zr_vertex is 28 bytes, so consecutive lanes' records are not 16-byte aligned: each lane loads and stores its record as 7 dwords (a
+// zr_vtx_lane.h -- how one lane moves a vertex record, an influence record and a joint matrix: what the kernels that pose vertices
+// (zr_tu_pose.hip) move through.  A zr_vertex is 28 bytes, so consecutive lanes' records are not 16-byte aligned: each lane loads and stores its record as 7 dwords (a
 // wave's 64 records are 1 792 contiguous bytes, every cache line of which is used whole).  The influence record travels as one 8-byte and one 16-byte
 // word, the joint matrices as 16-byte rows.
 #ifndef ZR_VTX_LANE_H
