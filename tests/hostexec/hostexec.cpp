@@ -118,6 +118,8 @@ struct HxOrderBackend
     static int Record(Event e, Stream s) { OrderLog(HX_LOG_RECORD, e, s, 0); return 0; }
     static int Wait(Stream s, Event e) { OrderLog(HX_LOG_WAIT, s, e, 0); return 0; }
 };
+// ---- the plan of a call's texture sources as zr_api.hip builds it (zhx_tex_plan)
+#include "../../zetaray_amd/csrc/zr_tex_plan.h"
 
 extern "C" {
 
@@ -981,6 +983,40 @@ int zhx_stream_order_run(const int32_t* ops, uint32_t n, int32_t* log, uint32_t 
     g_orderLog = nullptr;
     if (log && cap) std::memcpy(log, out.data(), std::min<size_t>(out.size(), cap) * sizeof(int32_t));
     return (int)out.size();
+}
+
+// The texture planner the library runs (zr_tex_plan.h) on caller arrays.  zhx_tex_plan builds the plan and keeps it: returns the ZR_* code, the message in
+// msg, and in counts[12] the entries of the seven tables below followed by numBlocks, jpegBlocks, jpegItems, planeBytes and 0.  zhx_tex_plan_table copies
+// table `which` of the kept plan to out as flat arrays:
+//   0 zrbc::Job   1 Copy (3 x u64)   2 zrjp::BlockJob   3 zrjp::TexJob   4 zrmg::Job   5 Level (3 x u32)   6 chains (2 x u64)
+static zr::TexturePlan g_texPlan;
+int zhx_tex_plan(const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n, uint64_t payloadBytes, uint64_t texelBytes, const uint8_t* payload,
+    uint32_t accept, uint32_t stages, char* msg, uint32_t msgCap, uint64_t* counts)
+{
+    g_texPlan = zr::TexturePlan();
+    std::string err;
+    const int r = zr::BuildTexturePlan(descs, sources, n, payloadBytes, texelBytes, payload, accept, stages, g_texPlan, err);
+    if (msg && msgCap) snprintf(msg, msgCap, "%s", err.c_str());
+    const zr::TexturePlan& p = g_texPlan;
+    const uint64_t c[12] = {p.blockJobs.size(), p.copies.size(), p.jpegBlockJobs.size(), p.jpegTexJobs.size(), p.mipJobs.size(), p.levels.size(), p.chains.size(),
+                            p.numBlocks, p.jpegBlocks, p.jpegItems, p.planeBytes, 0};
+    std::memcpy(counts, c, sizeof(c));
+    return r;
+}
+void zhx_tex_plan_table(int which, void* out)
+{
+    const zr::TexturePlan& p = g_texPlan;
+    auto put = [&](const auto& v) { if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(v[0])); };
+    switch (which)
+    {
+    case 0: put(p.blockJobs); break;
+    case 1: put(p.copies); break;
+    case 2: put(p.jpegBlockJobs); break;
+    case 3: put(p.jpegTexJobs); break;
+    case 4: put(p.mipJobs); break;
+    case 5: put(p.levels); break;
+    default: { uint64_t* o = (uint64_t*)out; for (const auto& c : p.chains) { *o++ = c.first; *o++ = c.second; } break; }
+    }
 }
 
 } // extern "C"

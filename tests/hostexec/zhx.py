@@ -441,6 +441,41 @@ def stream_order_run(ops):
     return [(ORDER_LOG[k], int(a), int(b), int(c)) for k, a, b, c in out[:need].reshape(-1, 4)]
 
 
+TEX_SRC_STORED, TEX_SRC_MIP0, TEX_SRC_JPEG, TEX_SRC_ALL = 1, 2, 4, 7      # zr_tex_plan.h: the source encodings a caller accepts ...
+TEX_PLAN_BLOCKS, TEX_PLAN_JPEG, TEX_PLAN_LEVELS, TEX_PLAN_ALL = 1, 2, 4, 7      # ... and the stages it wants planned
+BCN_JOB = np.dtype([("src", "<u8"), ("dst", "<u8"), ("w", "<u4"), ("h", "<u4"), ("first_block", "<u4"), ("encoding", "<u4")])
+TEX_COPY = np.dtype([("src", "<u8"), ("dst", "<u8"), ("bytes", "<u8")])
+JPEG_BLOCK_JOB = np.dtype([("coef_begin", "<u8"), ("coef", "<u8"), ("plane", "<u8"), ("bw", "<u4"), ("comp_first", "<u4"), ("first_block", "<u4"), ("pad", "<u4"), ("q2", "<u4", 32)])
+JPEG_TEX_JOB = np.dtype([("dst", "<u8"), ("plane", "<u8", 3), ("stride", "<u4", 3), ("w", "<u4"), ("h", "<u4"), ("ncomp", "<u4"), ("hs", "<u4"), ("vs", "<u4"), ("map", "<u4"),
+                         ("first_item", "<u4")])
+MIP_JOB = np.dtype([("src", "<u8"), ("dst", "<u8"), ("sw", "<u4"), ("sh", "<u4"), ("dw", "<u4"), ("dh", "<u4"), ("format", "<u4"), ("first_item", "<u4")])
+MIP_LEVEL = np.dtype([("first_job", "<u4"), ("num_jobs", "<u4"), ("num_items", "<u4")])
+TEX_CHAIN = np.dtype([("first", "<u8"), ("end", "<u8")])
+assert (BCN_JOB.itemsize, JPEG_BLOCK_JOB.itemsize, JPEG_TEX_JOB.itemsize, MIP_JOB.itemsize) == (32, 168, 72, 40)
+
+
+def tex_plan(descs, sources, payload_bytes, texel_bytes, payload=None, accept=TEX_SRC_ALL, stages=TEX_PLAN_ALL):
+    """zr::BuildTexturePlan (zr_tex_plan.h) on caller arrays: descs wire.TEXTURE_DESC, sources wire.TEXTURE_SOURCE or None (accept == 0), payload the
+    bytes JPEG records are read from or None.  payload_bytes is what the planner is told and need not be the size of `payload`.  Returns
+    (ZR_* code, message, dict of the plan's tables and counts)."""
+    from zetaray_amd import wire
+    L = lib()
+    L.zhx_tex_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p]
+    L.zhx_tex_plan_table.argtypes = [C.c_int, C.c_void_p]
+    descs = np.ascontiguousarray(descs, wire.TEXTURE_DESC)
+    sources = None if sources is None else np.ascontiguousarray(sources, wire.TEXTURE_SOURCE)
+    payload = None if payload is None else np.ascontiguousarray(payload, np.uint8)
+    msg, counts = C.create_string_buffer(512), np.zeros(12, np.uint64)
+    code = L.zhx_tex_plan(descs.ctypes.data, None if sources is None else sources.ctypes.data, len(descs), int(payload_bytes), int(texel_bytes),
+                          None if payload is None else payload.ctypes.data, accept, stages, msg, len(msg), counts.ctypes.data)
+    plan = {"num_blocks": int(counts[7]), "jpeg_blocks": int(counts[8]), "jpeg_items": int(counts[9]), "plane_bytes": int(counts[10])}
+    for which, (name, dt) in enumerate((("block_jobs", BCN_JOB), ("copies", TEX_COPY), ("jpeg_block_jobs", JPEG_BLOCK_JOB), ("jpeg_tex_jobs", JPEG_TEX_JOB),
+                                        ("mip_jobs", MIP_JOB), ("levels", MIP_LEVEL), ("chains", TEX_CHAIN))):
+        plan[name] = np.zeros(int(counts[which]), dt)
+        L.zhx_tex_plan_table(which, plan[name].ctypes.data)
+    return code, msg.value.decode(), plan
+
+
 def svgf(signal_rgba, depth, normal, motion, prev_depth, prev_normal, hist_color, hist_moments, temporal_valid=True, alpha=0.2, alpha_moments=0.2,
          sigma_l=4.0, sigma_z=1.0, normal_power_log2=7, iterations=5):
     """the denoise pass's HIP stage functions (zr_svgf.h) run serially on the host; same interface as oracle.zro.svgf"""

@@ -368,3 +368,34 @@ def tiny_gray_jpeg(scan, w=8, h=8, dc=((1,), (0,)), ac=((1,), (0xF1,)), extra=b"
         return segment(0xC4, bytes([cls << 4]) + bytes(counts) + bytes(t[1]))
     sof = segment(0xC0, bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([1, 1, 0x11, 0]))
     return b"\xff\xd8" + extra + segment(0xDB, bytes([0]) + bytes([1] * 64)) + sof + dht(0, dc) + dht(1, ac) + segment(0xDA, bytes([1, 1, 0x00, 0, 63, 0])) + bytes(scan) + b"\xff\xd9"
+
+
+def five_encoding_box(rng):
+    """The untextured Cornell box with a map of every source encoding, at sizes on the seams: a 5 x 3 RG8 RAW_MIP0 map, a 37 x 21 sRGB RAW map with its
+    stored chain, a 4 x 4 BC7 map of 3 mips, a 33 x 17 4:2:0 JPEG as an sRGB map and a grey 17 x 23 JPEG as an RG8 map of 2 mips (level 0 from the record,
+    the rest generated), and a 5 x 3 BC5 map.  The chains are then moved: they lie in the heap in another order than the textures, 8 bytes of padding in
+    front, 4 .. 44 bytes between them and 24 behind the last.  Returns (scene, the order of the chains in the heap)."""
+    from tests.bcnmath import zbc
+    from tests.mipmath import zmg
+    from zetaray_amd import scene_io
+    fx = {name: data for name, data, _ in load_fixture()}
+    sc = scene_io.load_npz(os.path.join(ROOT, "tests", "golden", "cornell.npz"))
+
+    def blocks(w, h, mips):
+        return rng.integers(0, 256, 16 * sum(zbc.mip_blocks(max(1, w >> m), max(1, h >> m)) for m in range(mips)), dtype=np.uint8)
+
+    sc.add_texture_blocks(rng.integers(0, 256, 5 * 3 * 2, dtype=np.uint8), 5, 3, zmg.full_mips(5, 3), wire.TEX_RG8, wire.TEX_SRC_RAW_MIP0)
+    mips = zmg.full_mips(37, 21)
+    sc.add_texture_blocks(rng.integers(0, 256, zmg.chain_bytes(37, 21, mips, wire.TEX_RGBA8_SRGB), dtype=np.uint8), 37, 21, mips, wire.TEX_RGBA8_SRGB, wire.TEX_SRC_RAW)
+    sc.add_texture_blocks(blocks(4, 4, 3), 4, 4, 3, wire.TEX_RGBA8, wire.TEX_SRC_BC7)
+    sc.add_texture_blocks(scene_io.pack_jpeg(fx["33x17_420_q90_noise"], "a.jpg"), 33, 17, zmg.full_mips(33, 17), wire.TEX_RGBA8_SRGB, wire.TEX_SRC_JPEG_COEF)
+    sc.add_texture_blocks(scene_io.pack_jpeg(fx["17x23_gray_restart_rows"], "b.jpg", wire.JPEG_MAP_RG), 17, 23, 2, wire.TEX_RG8, wire.TEX_SRC_JPEG_COEF)
+    sc.add_texture_blocks(blocks(5, 3, 3), 5, 3, 3, wire.TEX_RG8, wire.TEX_SRC_BC5)
+    order, at = [3, 0, 5, 2, 4, 1], 8
+    for k, i in enumerate(order):
+        t = sc.textures[i]
+        sc.textures["offset"][i] = at
+        at += zmg.chain_bytes(int(t["width"]), int(t["height"]), int(t["num_mips"]), int(t["format"]))
+        at = (at + 3) // 4 * 4 + (4 + 8 * k if k + 1 < len(order) else 24)
+    sc.texel_heap_bytes = at
+    return sc, order

@@ -145,7 +145,7 @@ def test_scene_path_on_the_jpeg_cornell(api, tmp_path):
         assert ca == cb_ and ca[0] > 0, (ca, cb_)
 
 
-# ---- 3. refusals: PlanJpegDecode validates the whole record before anything is enqueued
+# ---- 3. refusals: zr::BuildTexturePlan (zr_tex_plan.h) validates the whole record before anything is enqueued
 def _u32(payload, at, value):
     payload[at:at + 4] = np.frombuffer(np.uint32(value).tobytes(), np.uint8)
 

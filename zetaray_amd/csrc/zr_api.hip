@@ -91,10 +91,8 @@ namespace zr { hipError_t LaunchFillInstRecs(hipStream_t st, InstRec* recs, cons
                hipError_t LaunchFillVtxNormals(hipStream_t st, VtxDir* out, const zr_vertex* vertices, uint32_t n, bool tangent); }
 namespace zr { size_t AliasScratchWords(uint32_t n);      // zr_tu_alias.hip
                hipError_t LaunchAliasBuild(hipStream_t st, const float* power, uint32_t n, zr_alias_entry* out, uint64_t* scratch); }
-#include "../../include/zr_bcn.h"
+#include "zr_tex_plan.h"
 namespace zr { hipError_t LaunchBcnDecode(hipStream_t st, const zrbc::Job* jobs, uint32_t numJobs, uint32_t numBlocks, const uint8_t* payload, uint8_t* texels); }   // zr_tu_texdecode.hip
-#include "../../include/zr_mipgen.h"
-#include "../../include/zr_jpeg.h"
 namespace zr { hipError_t LaunchJpegDecode(hipStream_t st, const zrjp::BlockJob* blockJobs, uint32_t numBlockJobs, uint32_t numBlocks, const zrjp::TexJob* texJobs, uint32_t numTexJobs,
                    uint32_t numItems, const uint8_t* payload, uint8_t* planes, uint8_t* texels); }   // zr_tu_jpeg.hip
 namespace zr { hipError_t LaunchMipLevel(hipStream_t st, const zrmg::Job* jobs, uint32_t numJobs, uint32_t numItems, uint8_t* texels); }   // zr_tu_mipgen.hip
@@ -1393,145 +1391,44 @@ static zr_scene_desc SceneBuilderDesc(const zr_scene* s, const zr_mesh_instance*
     d.instances = instances; d.num_instances = n; d.instance_to_world = toWorld; d.instance_mask = s->hMask.data(); d.instance_num_tris = s->hNumTris.data();
     return d;
 }
-// is texture i one zr_scene_create accepts?  (its chain inside the texel blob, its offset a multiple of 4)
-static bool TextureDescOk(const zr_texture_desc& t, uint64_t texelBytes)
+// zr::BuildTexturePlan (zr_tex_plan.h: everything a caller refuses about descs, sources and records, before anything is allocated), its refusal as this library's
+static int PlanTextures(const char* fn, const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n, uint64_t payloadBytes, uint64_t texelBytes, const uint8_t* hostPayload,
+    uint32_t accept, uint32_t stages, zr::TexturePlan& plan)
 {
-    const zr_tex_mip last = zr_tex_mip_of(&t, t.num_mips ? t.num_mips - 1u : 0u);
-    const uint64_t end = last.offset + (uint64_t)last.w * last.h * (t.format == ZR_TEX_RG8 ? 2u : 4u);
-    return t.num_mips && t.width && t.height && t.format <= ZR_TEX_RG8 && !(t.offset & 3u) && end <= texelBytes;
+    std::string err;
+    const int r = zr::BuildTexturePlan(descs, sources, n, payloadBytes, texelBytes, hostPayload, accept, stages, plan, err);
+    return r ? Fail(r, "%s: %s", fn, err.c_str()) : ZR_OK;
 }
-// What the device decode of n textures takes (zr_scene_create_compressed, zr_bcn_decode_device): one zrbc::Job per mip of every BC7 / BC5 chain, in
-// texture order, and one copy per RAW chain.  Everything either entry point refuses about descs and sources is refused here, before anything is allocated
-// chains: the bytes [first, second) of the heap each texture's chain fills, in texture order (everything else is what a caller sees as padding)
-struct BcnPlan { std::vector<zrbc::Job> jobs; struct Copy { uint64_t src, dst, bytes; }; std::vector<Copy> copies; uint32_t numBlocks = 0;
-                 std::vector<uint32_t> mip0;      // the textures whose source is level 0 alone (ZR_TEX_SRC_RAW_MIP0): their other levels are generated (MipPlan)
-                 std::vector<std::pair<uint64_t, uint64_t>> chains; };
-// What the ZR_TEX_SRC_JPEG_COEF sources of a call take (PlanJpegDecode, below): one zrjp::BlockJob per component and one zrjp::TexJob per texture, in texture
-// order, for the two launches of zr_tu_jpeg.hip, and the bytes of the sample planes between them
-struct JpegPlan { std::vector<zrjp::BlockJob> blockJobs; std::vector<zrjp::TexJob> texJobs; uint64_t numBlocks = 0, numItems = 0, planeBytes = 0; };
-// One JPEG_COEF source: the whole record is validated here, on the host, before anything is enqueued -- the kernels trust what this accepted.
-// payload: the payload ON THE HOST
-static int PlanJpegDecode(const char* fn, uint32_t i, const zr_texture_desc& t, const zr_texture_source& src, const uint8_t* payload, uint64_t payloadBytes, JpegPlan& jp)
+// Enqueues on `st` whatever the plan holds, in this order: the block decode, the raw copies, the JPEG blocks and then their texels, the
+// mip levels top down.  The job tables and the JPEG sample planes share one stream-ordered allocation, freed behind whatever was enqueued, on the error
+// path too: nothing here waits for the stream's earlier work.  The tables are copied from the plan's pageable vectors, which the caller destroys on
+// return: hipMemcpyAsync from pageable memory is synchronous towards the host buffer (the runtime has staged or sent it when it returns), so the
+// vectors may go; it is no wait for earlier work of the stream
+static int RunTexturePlan(const char* fn, hipStream_t st, const zr::TexturePlan& plan, const uint8_t* dPayload, uint8_t* dTexels)
 {
-    if (src.offset & 15u) return Fail(ZR_ERR_INVALID_ARG, "%s: the source offset of texture %u is not a multiple of 16", fn, i);
-    if (src.offset > payloadBytes) return Fail(ZR_ERR_INVALID_ARG, "%s: the record of texture %u starts beyond the payload", fn, i);
-    zrjp::Header h;
-    if (const char* why = zrjp::CheckRecord(payload + src.offset, payloadBytes - src.offset, &h)) return Fail(ZR_ERR_INVALID_ARG, "%s: the JPEG record of texture %u: %s", fn, i, why);
-    if (h.w != t.width || h.h != t.height) return Fail(ZR_ERR_INVALID_ARG, "%s: the JPEG record of texture %u is %u x %u, its desc %u x %u", fn, i, h.w, h.h, (unsigned)t.width, (unsigned)t.height);
-    if ((h.map == (uint32_t)zrjp::kMapRgba) != (t.format != ZR_TEX_RG8)) return Fail(ZR_ERR_INVALID_ARG, "%s: the channel map of the JPEG record of texture %u does not fit its format", fn, i);
-    if (jp.numBlocks + h.num_blocks > 0xffffffffull || jp.numItems + (uint64_t)h.w * h.h > 0xffffffffull) return Fail(ZR_ERR_INVALID_ARG, "%s: more than 2^32 - 1 JPEG blocks or texels", fn);
-    zrjp::BlockJob bj[3]; zrjp::TexJob tj;
-    zrjp::MakeJobs(h, src.offset, jp.planeBytes, t.offset, (uint32_t)jp.numBlocks, (uint32_t)jp.numItems, bj, &tj);
-    jp.blockJobs.insert(jp.blockJobs.end(), bj, bj + h.ncomp); jp.texJobs.push_back(tj);
-    jp.numBlocks += h.num_blocks; jp.numItems += (uint64_t)h.w * h.h; jp.planeBytes += zrjp::PlaneBytes(h);
-    return ZR_OK;
-}
-// jpeg / hostPayload: where JPEG_COEF sources are planned and the payload on the host they are validated in (null: such a source is an unknown encoding)
-static int PlanBcnDecode(const char* fn, const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n, uint64_t payloadBytes, uint64_t texelBytes, BcnPlan& plan,
-    bool allowMip0, JpegPlan* jpeg = nullptr, const uint8_t* hostPayload = nullptr)
-{
-    uint64_t blocks = 0;
-    for (uint32_t i = 0; i < n; i++)
-    {
-        const zr_texture_desc& t = descs[i]; const zr_texture_source& src = sources[i];
-        if (!TextureDescOk(t, texelBytes)) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is malformed or lies outside the texel blob", fn, i);
-        if (jpeg && src.encoding == ZR_TEX_SRC_JPEG_COEF)
-        {   // level 0 from the record; the other levels generated like a RAW_MIP0 chain's
-            if (int r = PlanJpegDecode(fn, i, t, src, hostPayload, payloadBytes, *jpeg)) return r;
-            if (t.num_mips > 1u) plan.mip0.push_back(i);
-            const zr_tex_mip last = zr_tex_mip_of(&t, t.num_mips - 1u);
-            plan.chains.push_back({t.offset, last.offset + (uint64_t)last.w * last.h * (t.format == ZR_TEX_RG8 ? 2u : 4u)});
-            continue;
-        }
-        const bool mip0 = allowMip0 && src.encoding == ZR_TEX_SRC_RAW_MIP0, raw = src.encoding == ZR_TEX_SRC_RAW || mip0;
-        if (src.encoding > ZR_TEX_SRC_BC5 && !mip0) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u has the unknown source encoding %u", fn, i, (unsigned)src.encoding);
-        if (src.encoding == ZR_TEX_SRC_BC7 && t.format != ZR_TEX_RGBA8 && t.format != ZR_TEX_RGBA8_SRGB) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is BC7 but its format is not RGBA8 / RGBA8_SRGB", fn, i);
-        if (src.encoding == ZR_TEX_SRC_BC5 && t.format != ZR_TEX_RG8) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is BC5 but its format is not RG8", fn, i);
-        if (src.offset & (raw ? 3u : 15u)) return Fail(ZR_ERR_INVALID_ARG, "%s: the source offset of texture %u is not a multiple of %u", fn, i, raw ? 4u : 16u);
-        const uint32_t bpp = t.format == ZR_TEX_RG8 ? 2u : 4u;
-        uint64_t at = src.offset;      // (a chain is < 2^37 bytes, so `at` cannot wrap before it is compared)
-        if (at > payloadBytes) return Fail(ZR_ERR_INVALID_ARG, "%s: the chain of texture %u starts beyond the payload", fn, i);
-        for (uint32_t m = 0; m < t.num_mips; m++)
-        {
-            const zr_tex_mip mip = zr_tex_mip_of(&t, m);
-            if (mip0 && m) break;      // (the source ends with level 0)
-            if (raw) { at += (uint64_t)mip.w * mip.h * bpp; continue; }
-            zrbc::Job j; j.src = at; j.dst = mip.offset; j.w = mip.w; j.h = mip.h; j.first_block = (uint32_t)blocks; j.encoding = src.encoding;
-            const uint64_t nb = (uint64_t)((mip.w + 3u) >> 2) * ((mip.h + 3u) >> 2);
-            blocks += nb; at += 16u * nb;
-            if (blocks > 0xffffffffull) return Fail(ZR_ERR_INVALID_ARG, "%s: more than 2^32 - 1 blocks", fn);
-            plan.jobs.push_back(j);
-        }
-        if (at > payloadBytes) return Fail(ZR_ERR_INVALID_ARG, "%s: the chain of texture %u ends beyond the payload (%llu > %llu bytes)", fn, i, (unsigned long long)at, (unsigned long long)payloadBytes);
-        if (raw) plan.copies.push_back({src.offset, t.offset, at - src.offset});
-        if (mip0 && t.num_mips > 1u) plan.mip0.push_back(i);
-        const zr_tex_mip last = zr_tex_mip_of(&t, t.num_mips - 1u);
-        plan.chains.push_back({t.offset, last.offset + (uint64_t)last.w * last.h * bpp});
-    }
-    plan.numBlocks = (uint32_t)blocks;
-    return ZR_OK;
-}
-// enqueues the plan on `st`: dJobs = the plan's jobs on the device (unused without jobs)
-static int RunBcnPlan(hipStream_t st, const BcnPlan& plan, const zrbc::Job* dJobs, const uint8_t* dPayload, uint8_t* dTexels)
-{
-    if (!plan.jobs.empty()) HIP_TRY(zr::LaunchBcnDecode(st, dJobs, (uint32_t)plan.jobs.size(), plan.numBlocks, dPayload, dTexels));
-    for (const BcnPlan::Copy& c : plan.copies) if (c.bytes) HIP_TRY(hipMemcpyAsync(dTexels + c.dst, dPayload + c.src, c.bytes, hipMemcpyDeviceToDevice, st));
-    return ZR_OK;
-}
-// enqueues the plan on `st`: the job tables and the sample planes in stream-ordered allocations, the two launches, the frees behind them.  The tables are
-// copied from the plan's pageable vectors (synchronous towards the host buffer: see zr_bcn_decode_device)
-static int RunJpegPlan(const char* fn, hipStream_t st, const JpegPlan& jp, const uint8_t* dPayload, uint8_t* dTexels)
-{
-    if (jp.texJobs.empty()) return ZR_OK;
-    const size_t bBytes = jp.blockJobs.size() * sizeof(zrjp::BlockJob), tBytes = jp.texJobs.size() * sizeof(zrjp::TexJob);
-    void* mem[3] = {nullptr, nullptr, nullptr};
-    const size_t sizes[3] = {bBytes, tBytes, (size_t)jp.planeBytes};
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipMallocAsync(&mem[k], sizes[k], st);
-    if (e == hipSuccess) e = hipMemcpyAsync(mem[0], jp.blockJobs.data(), bBytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(mem[1], jp.texJobs.data(), tBytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = zr::LaunchJpegDecode(st, (const zrjp::BlockJob*)mem[0], (uint32_t)jp.blockJobs.size(), (uint32_t)jp.numBlocks, (const zrjp::TexJob*)mem[1],
-                                                  (uint32_t)jp.texJobs.size(), (uint32_t)jp.numItems, dPayload, (uint8_t*)mem[2], dTexels);
-    for (int k = 0; k < 3; k++) if (mem[k]) { const hipError_t f = hipFreeAsync(mem[k], st); if (e == hipSuccess) e = f; }      // freed behind whatever was enqueued
-    if (e != hipSuccess) return Fail(ZR_ERR_HIP, "%s: the JPEG decode could not be enqueued: %s", fn, hipGetErrorString(e));
-    return ZR_OK;
-}
-// What the mip generation of n textures takes (zr_scene_create_compressed for its RAW_MIP0 sources, zr_mipgen_device): one zrmg::Job per generated level of
-// every texture, grouped by level -- levels[k - 1] names the jobs of the launch that writes level k -- each group in texture order.
-// which: the indices into descs of the n textures (null: 0 .. n - 1); the descs passed TextureDescOk
-struct MipPlan { std::vector<zrmg::Job> jobs; struct Level { uint32_t firstJob, numJobs, numItems; }; std::vector<Level> levels; };
-static int PlanMipGen(const char* fn, const zr_texture_desc* descs, const uint32_t* which, uint32_t n, MipPlan& plan)
-{
-    uint32_t maxMips = 0;
-    for (uint32_t i = 0; i < n; i++) maxMips = std::max<uint32_t>(maxMips, descs[which ? which[i] : i].num_mips);
-    for (uint32_t k = 1; k < maxMips; k++)
-    {
-        MipPlan::Level lv = {(uint32_t)plan.jobs.size(), 0u, 0u};
-        uint64_t items = 0;
-        for (uint32_t i = 0; i < n; i++)
-        {
-            const zr_texture_desc& t = descs[which ? which[i] : i];
-            if (t.num_mips <= k) continue;
-            const zr_tex_mip s = zr_tex_mip_of(&t, k - 1u), d = zr_tex_mip_of(&t, k);
-            zrmg::Job j; j.src = s.offset; j.dst = d.offset; j.sw = s.w; j.sh = s.h; j.dw = d.w; j.dh = d.h; j.format = t.format; j.first_item = (uint32_t)items;
-            items += (uint64_t)d.w * d.h;
-            if (items > 0xffffffffull) return Fail(ZR_ERR_INVALID_ARG, "%s: more than 2^32 - 1 texels in mip level %u", fn, k);
-            plan.jobs.push_back(j);
-        }
-        lv.numJobs = (uint32_t)plan.jobs.size() - lv.firstJob; lv.numItems = (uint32_t)items;
-        plan.levels.push_back(lv);
-    }
-    return ZR_OK;
-}
-// enqueues the plan's launches on `st`, top down: dJobs = the plan's jobs on the device
-static int RunMipPlan(hipStream_t st, const MipPlan& plan, const zrmg::Job* dJobs, uint8_t* dTexels)
-{
-    for (const MipPlan::Level& lv : plan.levels) if (lv.numItems) HIP_TRY(zr::LaunchMipLevel(st, dJobs + lv.firstJob, lv.numJobs, lv.numItems, dTexels));
+    enum { kBlock, kJpegBlock, kJpegTex, kMip, kPlanes, kParts };
+    const void* src[kParts] = {plan.blockJobs.data(), plan.jpegBlockJobs.data(), plan.jpegTexJobs.data(), plan.mipJobs.data(), nullptr};
+    const size_t bytes[kParts] = {plan.blockJobs.size() * sizeof(zrbc::Job), plan.jpegBlockJobs.size() * sizeof(zrjp::BlockJob), plan.jpegTexJobs.size() * sizeof(zrjp::TexJob),
+                                  plan.mipJobs.size() * sizeof(zrmg::Job), (size_t)plan.planeBytes};
+    size_t at[kParts], total = 0;
+    for (int k = 0; k < kParts; k++) { at[k] = total; total += (bytes[k] + 255u) & ~(size_t)255u; }      // (each part as aligned as an allocation of its own)
+    uint8_t* mem = nullptr;
+    hipError_t e = total ? hipMallocAsync((void**)&mem, total, st) : hipSuccess;
+    for (int k = 0; k < kPlanes && e == hipSuccess; k++) if (bytes[k]) e = hipMemcpyAsync(mem + at[k], src[k], bytes[k], hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !plan.blockJobs.empty()) e = zr::LaunchBcnDecode(st, (const zrbc::Job*)(mem + at[kBlock]), (uint32_t)plan.blockJobs.size(), plan.numBlocks, dPayload, dTexels);
+    for (const zr::TexturePlan::Copy& c : plan.copies) if (e == hipSuccess && c.bytes) e = hipMemcpyAsync(dTexels + c.dst, dPayload + c.src, c.bytes, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && !plan.jpegTexJobs.empty())
+        e = zr::LaunchJpegDecode(st, (const zrjp::BlockJob*)(mem + at[kJpegBlock]), (uint32_t)plan.jpegBlockJobs.size(), (uint32_t)plan.jpegBlocks, (const zrjp::TexJob*)(mem + at[kJpegTex]),
+                                 (uint32_t)plan.jpegTexJobs.size(), (uint32_t)plan.jpegItems, dPayload, mem + at[kPlanes], dTexels);
+    for (const zr::TexturePlan::Level& lv : plan.levels)
+        if (e == hipSuccess && lv.numItems) e = zr::LaunchMipLevel(st, (const zrmg::Job*)(mem + at[kMip]) + lv.firstJob, lv.numJobs, lv.numItems, dTexels);
+    if (mem) { const hipError_t f = hipFreeAsync(mem, st); if (e == hipSuccess) e = f; }
+    if (e != hipSuccess) return Fail(ZR_ERR_HIP, "%s: the texture decode could not be enqueued: %s", fn, hipGetErrorString(e));
     return ZR_OK;
 }
 // zero-fills what no chain of the plan covers in a heap of `bytes` bytes (the decode and the copies write every byte of a chain): the padding between
 // chains, a few bytes each for a loader's heap, instead of the whole heap twice.  On the null stream
-static int ClearHeapGaps(const BcnPlan& plan, uint8_t* dTexels, uint64_t bytes)
+static int ClearHeapGaps(const zr::TexturePlan& plan, uint8_t* dTexels, uint64_t bytes)
 {
     std::vector<std::pair<uint64_t, uint64_t>> c = plan.chains;
     std::sort(c.begin(), c.end());
@@ -1550,16 +1447,15 @@ static int SceneCreate(const char* fn, int device, const zr_scene_desc* d, const
     if (!d || !out) return Fail(ZR_ERR_INVALID_ARG, "%s: null argument", fn);
     if (!d->vertices || !d->indices || !d->instances || !d->materials || !d->rho_lut || !d->instance_to_world || !d->instance_mask || !d->instance_num_tris)
         return Fail(ZR_ERR_INVALID_ARG, "%s: incomplete scene description", fn);
-    BcnPlan plan; MipPlan mipPlan; JpegPlan jpegPlan;
+    zr::TexturePlan plan;
     if (blocks)
     {   // refused before the acceleration structure is built
         if (!blocks->sources || !blocks->payload) return Fail(ZR_ERR_INVALID_ARG, "%s: null sources / payload", fn);
         if (d->texels) return Fail(ZR_ERR_INVALID_ARG, "%s: desc->texels must be null: the heap is decoded from the blocks", fn);
         if (d->num_textures && !d->textures) return Fail(ZR_ERR_INVALID_ARG, "%s: num_textures > 0 without textures", fn);
-        if (int pr = PlanBcnDecode(fn, d->textures, blocks->sources, d->num_textures, blocks->payload_bytes, d->texel_bytes, plan, true, &jpegPlan, blocks->payload)) return pr;
-        if (int pr = PlanMipGen(fn, d->textures, plan.mip0.data(), (uint32_t)plan.mip0.size(), mipPlan)) return pr;
+        if (int pr = PlanTextures(fn, d->textures, blocks->sources, d->num_textures, blocks->payload_bytes, d->texel_bytes, blocks->payload, zr::kTexSrcAll, zr::kTexPlanAll, plan)) return pr;
     }
-    DevBuf<uint8_t> payload; DevBuf<zrbc::Job> jobs; DevBuf<zrmg::Job> mipJobs;      // (live until the synchronize at the end)
+    DevBuf<uint8_t> payload;      // (live until the synchronize at the end)
     int r = RequireDevice(device);
     if (r) return r;
     std::unique_ptr<zr_scene> s(new (std::nothrow) zr_scene());      // (every early return below frees it)
@@ -1589,18 +1485,13 @@ static int SceneCreate(const char* fn, int device, const zr_scene_desc* d, const
     if (d->num_textures && blocks)
     {   // the blocks cross the bus once; the heap's padding is zero-filled, its chains decoded into, on the null stream like the uploads around it
         if ((r = s->texDescs.Upload(d->textures, d->num_textures)) || (r = payload.Upload(blocks->payload, blocks->payload_bytes)) ||
-            (r = s->texels.Alloc(d->texel_bytes)) || (r = ClearHeapGaps(plan, s->texels.p, d->texel_bytes)) || (r = jobs.Upload(plan.jobs.data(), plan.jobs.size())) ||
-            (r = RunBcnPlan(nullptr, plan, jobs.p, payload.p, s->texels.p))) return r;
-        // ... level 0 of the JPEG_COEF sources: the inverse DCT into sample planes, then the texels
-        if ((r = RunJpegPlan(fn, nullptr, jpegPlan, payload.p, s->texels.p))) return r;
-        // ... and behind the decode and the copies of level 0, the other levels of the RAW_MIP0 and JPEG_COEF chains: one launch per level
-        if (!mipPlan.jobs.empty() && ((r = mipJobs.Upload(mipPlan.jobs.data(), mipPlan.jobs.size())) || (r = RunMipPlan(nullptr, mipPlan, mipJobs.p, s->texels.p)))) return r;
+            (r = s->texels.Alloc(d->texel_bytes)) || (r = ClearHeapGaps(plan, s->texels.p, d->texel_bytes)) || (r = RunTexturePlan(fn, nullptr, plan, payload.p, s->texels.p))) return r;
     }
     else if (d->num_textures)
     {
         if (!d->textures || !d->texels) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: num_textures > 0 without textures / texels");
         for (uint32_t i = 0; i < d->num_textures; i++)
-            if (!TextureDescOk(d->textures[i], d->texel_bytes)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: texture %u is malformed or lies outside the texel blob", i);
+            if (!zr::TextureDescOk(d->textures[i], d->texel_bytes)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create: texture %u is malformed or lies outside the texel blob", i);
         if ((r = s->texDescs.Upload(d->textures, d->num_textures)) || (r = s->texels.Upload(d->texels, d->texel_bytes))) return r;
     }
     if ((r = s->srgb.Upload(zr_srgb_to_linear_table, 256))) return r;
@@ -1658,35 +1549,17 @@ int zr_scene_create_compressed(int device, const zr_scene_desc* d, const zr_text
     if (!blocks) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_create_compressed: null blocks");
     return SceneCreate("zr_scene_create_compressed", device, d, blocks, out);
 }
-// the decode of zr_scene_create_compressed on caller buffers.  Nothing here waits for the stream's earlier work: the job table lives in a stream-ordered
-// allocation freed behind the kernel; its copy from the host is synchronous towards the host buffer only (below)
+// the decode of zr_scene_create_compressed on caller buffers; enqueues only (RunTexturePlan)
 int zr_bcn_decode_device(int device, void* stream, const zr_texture_desc* descs, const zr_texture_source* sources, uint32_t n, const void* d_payload, uint64_t payload_bytes,
     void* d_texels, uint64_t texel_bytes)
 {
     const char* fn = "zr_bcn_decode_device";
     if (!descs || !sources || !d_payload || !d_texels || n == 0) return Fail(ZR_ERR_INVALID_ARG, "%s: null/empty input", fn);
     if (((uintptr_t)d_payload & 15u) || ((uintptr_t)d_texels & 3u)) return Fail(ZR_ERR_INVALID_ARG, "%s: d_payload must be 16-byte and d_texels 4-byte aligned", fn);
-    BcnPlan plan;
-    if (int r = PlanBcnDecode(fn, descs, sources, n, payload_bytes, texel_bytes, plan, false)) return r;
+    zr::TexturePlan plan;
+    if (int r = PlanTextures(fn, descs, sources, n, payload_bytes, texel_bytes, nullptr, zr::kTexSrcStored, zr::kTexPlanBlocks, plan)) return r;
     if (hipSetDevice(device) != hipSuccess) return Fail(ZR_ERR_NO_DEVICE, "%s: no usable HIP device %d", fn, device);
-    hipStream_t st = (hipStream_t)stream;
-    zrbc::Job* dJobs = nullptr;
-    if (!plan.jobs.empty())
-    {
-        // the table is copied from the plan's pageable vector, which this call destroys on return: hipMemcpyAsync from pageable memory is synchronous
-        // towards the host buffer (the runtime has staged or sent it when it returns), so the vector may go; it is no wait for earlier work of the stream
-        const size_t bytes = plan.jobs.size() * sizeof(zrbc::Job);
-        HIP_TRY(hipMallocAsync((void**)&dJobs, bytes, st));
-        const hipError_t e = hipMemcpyAsync(dJobs, plan.jobs.data(), bytes, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) { (void)hipFreeAsync(dJobs, st); return Fail(ZR_ERR_HIP, "%s: the copy of the job table failed: %s", fn, hipGetErrorString(e)); }
-    }
-    const int r = RunBcnPlan(st, plan, dJobs, (const uint8_t*)d_payload, (uint8_t*)d_texels);
-    if (dJobs)
-    {   // freed behind whatever was enqueued, on the error path too
-        const hipError_t e = hipFreeAsync(dJobs, st);
-        if (e != hipSuccess && !r) return Fail(ZR_ERR_HIP, "%s: hipFreeAsync failed: %s", fn, hipGetErrorString(e));
-    }
-    return r;
+    return RunTexturePlan(fn, (hipStream_t)stream, plan, (const uint8_t*)d_payload, (uint8_t*)d_texels);
 }
 // level 0 of the JPEG_COEF sources of zr_scene_create_compressed on caller buffers.  The records are validated on the host like the scene path's, so the
 // payload is read back first (a wait on the stream); the decode itself is enqueued only
@@ -1707,9 +1580,9 @@ int zr_jpeg_decode_device(int device, void* stream, const zr_texture_desc* descs
         HIP_TRY(hipMemcpyAsync(host.data(), d_payload, payload_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    BcnPlan plan; JpegPlan jp;
-    if (int r = PlanBcnDecode(fn, descs, sources, n, payload_bytes, texel_bytes, plan, true, &jp, host.data())) return r;
-    return RunJpegPlan(fn, st, jp, (const uint8_t*)d_payload, (uint8_t*)d_texels);
+    zr::TexturePlan plan;
+    if (int r = PlanTextures(fn, descs, sources, n, payload_bytes, texel_bytes, host.data(), zr::kTexSrcAll, zr::kTexPlanJpeg, plan)) return r;
+    return RunTexturePlan(fn, st, plan, (const uint8_t*)d_payload, (uint8_t*)d_texels);
 }
 // the level launches of zr_scene_create_compressed on caller buffers; enqueues only, like zr_bcn_decode_device
 int zr_mipgen_device(int device, void* stream, const zr_texture_desc* descs, uint32_t n, void* d_texels, uint64_t texel_bytes)
@@ -1718,22 +1591,11 @@ int zr_mipgen_device(int device, void* stream, const zr_texture_desc* descs, uin
     if (n == 0) return ZR_OK;
     if (!descs || !d_texels) return Fail(ZR_ERR_INVALID_ARG, "%s: null argument", fn);
     if ((uintptr_t)d_texels & 3u) return Fail(ZR_ERR_INVALID_ARG, "%s: d_texels must be 4-byte aligned", fn);
-    for (uint32_t i = 0; i < n; i++) if (!TextureDescOk(descs[i], texel_bytes)) return Fail(ZR_ERR_INVALID_ARG, "%s: texture %u is malformed or lies outside the texel blob", fn, i);
-    MipPlan plan;
-    if (int r = PlanMipGen(fn, descs, nullptr, n, plan)) return r;
-    if (plan.jobs.empty()) return ZR_OK;
+    zr::TexturePlan plan;
+    if (int r = PlanTextures(fn, descs, nullptr, n, 0, texel_bytes, nullptr, 0u, zr::kTexPlanLevels, plan)) return r;
+    if (plan.mipJobs.empty()) return ZR_OK;      // (chains of one level: nothing to enqueue, and the device is not looked at)
     if (hipSetDevice(device) != hipSuccess) return Fail(ZR_ERR_NO_DEVICE, "%s: no usable HIP device %d", fn, device);
-    hipStream_t st = (hipStream_t)stream;
-    // (the table's copy from the plan's pageable vector: see zr_bcn_decode_device)
-    zrmg::Job* dJobs = nullptr;
-    const size_t bytes = plan.jobs.size() * sizeof(zrmg::Job);
-    HIP_TRY(hipMallocAsync((void**)&dJobs, bytes, st));
-    hipError_t e = hipMemcpyAsync(dJobs, plan.jobs.data(), bytes, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) { (void)hipFreeAsync(dJobs, st); return Fail(ZR_ERR_HIP, "%s: the copy of the job table failed: %s", fn, hipGetErrorString(e)); }
-    const int r = RunMipPlan(st, plan, dJobs, (uint8_t*)d_texels);
-    e = hipFreeAsync(dJobs, st);      // freed behind whatever was enqueued, on the error path too
-    if (e != hipSuccess && !r) return Fail(ZR_ERR_HIP, "%s: hipFreeAsync failed: %s", fn, hipGetErrorString(e));
-    return r;
+    return RunTexturePlan(fn, (hipStream_t)stream, plan, nullptr, (uint8_t*)d_texels);
 }
 int zr_scene_get_texels(const zr_scene* s, void* stream, uint8_t* out, uint64_t first, uint64_t count)
 {
