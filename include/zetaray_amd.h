@@ -441,8 +441,9 @@ int zr_scene_animate(zr_scene* scene, float t);
  * [first, first + count) through the staging ring, refreshes their entries of the hit tables (zr_hit_tables.h) with the kernel that filled them, and
  * is ordered as a write of the scene like the other updates.  The ACCELERATION STRUCTURE FOLLOWS WITH THE FRAME'S INSTANCE UPDATE, of any form
  * (zr_scene_update_instances, zr_scene_move_instances with n_moved == 0 included, zr_scene_animate): every such update refits from the vertex buffer.
- * A render between the two traces the old triangles and shades them with the new attributes.  Emissive records are not touched: a deformed light keeps
- * shining from its rest pose.  The host's copy of the vertices follows (once a background build in flight, which reads it, is done: no call waits).
+ * A render between the two traces the old triangles and shades them with the new attributes.  Emissive records are not touched: a caller whose
+ * range holds light triangles follows with zr_scene_refresh_emissives (below).  The host's copy of the vertices follows (once a background build in
+ * flight, which reads it, is done: no call waits).
  * A range that a skin set or a morph set covers is rewritten by the next zr_scene_animate from the set's rest records: what this call put there does not last.
  * Refused, with nothing changed: a range past the scene's vertices, a null pointer with count > 0 (ZR_ERR_INVALID_ARG); ZR_SCENE_UPDATE=rebuild /
  * rebuild_host (ZR_ERR_UNSUPPORTED).  zr_scene_update_vertices = _async on the null stream, then wait.  zr_scene_get_vertices reads the device's
@@ -494,6 +495,38 @@ int zr_scene_has_skinning(const zr_scene* scene);      /* 1 while a skin set is 
  * times not finite or not strictly increasing; a weight, rest weight, t0 or delta that is not finite. */
 int zr_scene_set_morph(zr_scene* scene, const zr_morph_desc* desc);
 int zr_scene_has_morph(const zr_scene* scene);         /* 1 while a morph set is in place, else 0 */
+/* Deformed lights: the EmissiveTriangle records of light triangles whose vertices changed, re-derived on the device from the vertex buffer.  The rule is
+ * zrsm::EmissiveFromVertices (include/zr_scene_math.h; the host compiles it as zrh_emissive_from_vertices): the object-space record takes the triangle's
+ * three positions as the vertex buffer holds them (StoreEmissiveVertices, the loader's geometry step), the world record is EmissiveToWorld of that with
+ * the owner's object-to-world matrix, and every non-geometric field (ID, factor, strength, texture index, UVs) is kept.  There is no identity-matrix
+ * shortcut (the loader's first-frame rule; the moved-light rule has none either).  BOTH records are written -- the scene's emissive buffer and the
+ * object-space records of zr_scene_set_object_emissives -- so a later rigid move of the owner starts from the posed shape.
+ * zr_scene_refresh_emissives_async(scene, stream, first_tri, count) is the RANGE form, for a caller that deforms geometry through
+ * zr_scene_update_vertices: light triangles [first_tri, first_tri + count), each from its owner's first light triangle, index and vertex offsets and the
+ * index buffer; a triangle no instance carries is skipped.  It reads the owner's matrix as it stands on the stream, and may be called before or after the
+ * frame's instance update: both orders end in the same bytes, because the update derives a moved owner's world records from the object records this call
+ * wrote.  It is ordered as a write of the scene like every other update.  In every device byte it equals zrh_scene_data_refresh_emissives
+ * (zetaray_amd/host/zr_scene_io.h) followed by zr_scene_update_emissives_async on the dirty range.
+ * Pose sets need no call: zr_scene_set_skinning / zr_scene_set_morph also list every light triangle with a vertex in one of the set's ranges (16-byte
+ * entries {triangle, three absolute vertex indices}) and save those triangles' object and world records next to the rest vertices; every
+ * zr_scene_animate_async then runs the LISTED form of the same kernel behind the instance kernels, so it equals the host sequences stated above with
+ * zrh_scene_data_refresh_emissives between the vertex hand-over and the host-form updates.  Clearing a set, or replacing the animation, puts the saved
+ * records back together with the rest vertices (the world record is the saved bytes while the owner's matrix is the one it had when they were saved;
+ * where an animation has moved the owner since, it is the moved-light rule on the saved object record under the owner's current matrix); a set that replaces
+ * another keeps the records the first one saved.  A set whose ranges touch lights before zr_scene_set_object_emissives is refused
+ * (ZR_ERR_NOT_INITIALIZED).  A scene whose pose ranges touch no light launches nothing new.  While a set lists lights, zr_scene_set_object_emissives
+ * is refused (ZR_ERR_UNSUPPORTED, nothing changed): the set has saved those lights' records and rewrites them every frame; clear the set first.
+ * Powers: as for moved lights, nothing here re-estimates triangle powers or rebuilds the alias table, although a deformation changes areas.  A caller
+ * who wants the table to follow calls zr_scene_invalidate_alias_table at whatever cadence it likes; under ZR_ALIAS_BUILD_DEVICE that is stream work only.
+ * Presampled sets and the light voxel grid read the records and follow with the next PRELIGHTING render.
+ * Caller guarantee, as for moved lights: no deformed light triangle has a zero-length edge (else that record's bytes are unspecified; nothing is written
+ * out of bounds).  The byte equivalence holds for the contract build, not for -DZR_ARITH_FAST.
+ * Refused, with nothing changed: a range past the scene's emissive count (ZR_ERR_INVALID_ARG); no zr_scene_set_object_emissives yet
+ * (ZR_ERR_NOT_INITIALIZED); ZR_SCENE_UPDATE=rebuild / rebuild_host (ZR_ERR_UNSUPPORTED).  zr_scene_refresh_emissives = _async on the null stream, then
+ * wait.  zr_scene_get_object_emissives reads the object-space records back after waiting for `hip_stream`, for tests and tools. */
+int zr_scene_refresh_emissives_async(zr_scene* scene, void* hip_stream, uint32_t first_tri, uint32_t count);
+int zr_scene_refresh_emissives(zr_scene* scene, uint32_t first_tri, uint32_t count);
+int zr_scene_get_object_emissives(const zr_scene* scene, void* hip_stream, zr_emissive_triangle* out, uint32_t first, uint32_t count);
 /* Read-backs for tests and tools, after waiting for `hip_stream` (pass the stream of the last update).  which: 0 = the current instance buffer,
  * 1 = the previous one (the current one while the scene has never been updated); to_world_or_null: n x 12 floats. */
 int zr_scene_get_instances(const zr_scene* scene, void* hip_stream, int which, zr_mesh_instance* out, float* to_world_or_null, uint32_t n);

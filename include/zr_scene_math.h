@@ -176,6 +176,18 @@ ZR_HD void EmissiveToWorld(const zr_emissive_triangle& in, const float* M, zr_em
     out = in;
     StoreEmissiveVertices(out, w0, w1, w2);
 }
+/* a light triangle whose vertices were deformed (skinning, morph targets, zr_scene_update_vertices): p0..p2 are its object-space positions as the
+   vertex buffer holds them.  The loader's geometry step (PackEmissiveTriangle: StoreVertices of the object-space triangle) followed by the moved-light
+   rule above with the owner's matrix M -- the same functions in the same order; every non-geometric field of `rec` is kept in both records.  No
+   identity-matrix shortcut: that belongs to the reference's first frame (SceneCore.cpp:196-236), UpdateEmissivePositions has none.  A zero-length
+   edge: unspecified bytes, as in StoreEmissiveVertices */
+ZR_HD void EmissiveFromVertices(const zr_emissive_triangle& rec, const float* p0, const float* p1, const float* p2, const float* M,
+    zr_emissive_triangle& objectOut, zr_emissive_triangle& worldOut)
+{
+    objectOut = rec;
+    StoreEmissiveVertices(objectOut, p0, p1, p2);
+    EmissiveToWorld(objectOut, M, worldOut);
+}
 
 } /* namespace zrsm */
 

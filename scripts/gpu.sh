@@ -16,6 +16,7 @@
 #   jpeg [ARGS]        tools/jpeg_decode_bench.py: JPEG files decoded on the host and uploaded as RAW_MIP0 against their coefficient records decoded on the device (JPEG_COEF) -> ${TAG}_jpeg_decode.json
 #   skin [ARGS]        tools/refit_bench.py --skin: a skinned tube posed by the host form against zr_scene_animate with the skin set -> ${TAG}_scene_skin.json
 #   morph [ARGS]       tools/refit_bench.py --morph: a tube under 8 morph targets posed by the host form against zr_scene_animate with the morph set -> ${TAG}_scene_morph.json
+#   lights [ARGS]      tools/refit_bench.py --lights: the skinned tube with an emissive material, host form against zr_scene_animate with deformed lights and against the same tube not emissive -> ${TAG}_scene_lights.json
 #   prof LIB           section profiler (-DZR_PROF build LIB) on Cornell + atrium -> ${TAG}_section_profile_*.json
 R=${GRAFT_REPO_ROOT:-$PWD}; TAG=${TAG:-r06}; OUT=$R/gpurun_out; mkdir -p $OUT
 task=$1; shift
@@ -127,6 +128,10 @@ skin)
 morph)
   cd $R; set -o pipefail
   timeout 1100 python tools/refit_bench.py --morph "$@" 2> $OUT/${TAG}_morph_err.log | tail -1 | tee $OUT/${TAG}_scene_morph.json || { echo "refit_bench --morph: requirement missed or failed"; tail -5 $OUT/${TAG}_morph_err.log; exit 1; }
+  ;;
+lights)
+  cd $R; set -o pipefail
+  timeout 1100 python tools/refit_bench.py --lights "$@" 2> $OUT/${TAG}_lights_err.log | tail -1 | tee $OUT/${TAG}_scene_lights.json || { echo "refit_bench --lights: failed"; tail -5 $OUT/${TAG}_lights_err.log; exit 1; }
   ;;
 *) echo "unknown task $task"; exit 2;;
 esac

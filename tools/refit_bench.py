@@ -26,7 +26,15 @@ one looping track of 3 keys.  (A) the host form: zrh_morph_pose on the host, zr_
 (B) zr_scene_animate_async with the morph set, in two variants: all 8 weights non-zero at every time, and 1 of 8 non-zero (the other 7 targets are
 skipped: no loads); (C) the same animation without the set, whose stream time taken from (B)'s leaves the morph kernels' own, reported next to the
 bytes they must move (28 in, 28 + 16 out and 24 per applied target per vertex).  Same statistics, same JSON line; exit status 1 when (B)'s host time
-at 16 N exceeds that at N by more than the smaller run's p10 - p90 spread, or when the twin scenes' vertex buffers differ."""
+at 16 N exceeds that at N by more than the smaller run's p10 - p90 spread, or when the twin scenes' vertex buffers differ.
+
+--lights: the --skin tube (--vertices N and 16 N, the clutter as above) with an EMISSIVE material: every tube triangle is a light triangle the pose
+deforms, about 2 N of them.  (A) the host form: zrh_skin_pose, zr_scene_update_vertices_async, zrh_scene_data_refresh_emissives over all lights, the
+host-form emissive and instance updates; (B) zr_scene_animate_async with the skin set, which lists the lights and runs k_refresh_emissives; (C) the same
+tube, animation and skin set with the material not emissive.  B - C is the light kernel's stream time, reported next to the bytes it moves (per light:
+the 16-byte entry, the owner word, three 12-byte positions, 48 bytes of object record in, two 48-byte records out: 200) and, unless the difference lies
+within the two runs' p10 - p90 drift, the bandwidth that implies; the device state carries the copy probe.  Whether (B)'s host time grows with the light
+count and whether its stream time is below (A)'s are reported, not gated: exit status 1 only when the twin scenes' vertices or light records differ."""
 import json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -479,6 +487,120 @@ def morph(n_small, frames, warmup):
     return 0 if ok else 1
 
 
+def _lit_tube(api_mod, sc, nv):
+    """the tube of _tube_scene with an emissive material: one light triangle per tube triangle.  The records are made by the library itself -- records whose
+    non-geometric fields are set and whose geometry is not go to a throw-away scene, whose range form derives both records of every triangle at rest"""
+    lit = scene_io.Scene()
+    for name in ("vertices", "indices", "instance_to_world", "instance_num_tris", "rho", "rho_dim"):
+        setattr(lit, name, getattr(sc, name))
+    lit.materials = np.concatenate([sc.materials, np.array([scene_io.pack_material(base_color=(0.8, 0.8, 0.8, 1), roughness=1.0, double_sided=True,
+                                                                                     emissive_factor=(1.0, 0.85, 0.7), emissive_strength=5.0)], wire.MATERIAL)])
+    lit.instances, lit.instance_mask = sc.instances.copy(), sc.instance_mask.copy()
+    n = int(sc.instance_num_tris[0])
+    lit.instances["mat_idx"][0], lit.instances["base_emissive_tri_offset"][0], lit.instance_mask[0] = 1, 0, wire.SUBGROUP_EMISSIVE
+    one = scene_io.pack_emissive_triangle([0, 0, 0], [1, 0, 0], [0, 1, 0], [(0, 0), (1, 0), (0, 1)], 0xB3D9FF, 0xFFFF, int(scene_io.f32_to_f16_bits([5.0])[0]), 0, True)
+    rec = np.repeat(np.array([one], wire.EMISSIVE_TRI), n)
+    rec["id"] = (np.arange(1, n + 1, dtype=np.uint64) * 0x9E3779B1 & 0xFFFFFFFF).astype(np.uint32)
+    lit.emissives = lit.emissives_initial = rec
+    S = api_mod.Scene(lit)
+    S.set_object_emissives(rec)
+    S.refresh_emissives(0, n)
+    lit.emissives, lit.emissives_initial = S.download_emissives(), S.download_object_emissives()
+    lit._desc = None
+    S.close()
+    return lit
+
+
+def lights(n_small, frames, warmup):
+    """--lights: the --skin tube with an emissive material, so every tube triangle is a light the pose deforms (about 2 N lights)"""
+    import ctypes as C
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import bench
+    out = {"mode": "lights", "frames": frames, "warmup": warmup, "library": os.path.basename(api.LIB_PATH), "device_state": bench.device_state(api, 0), "joints": 64, "sizes": []}
+    L = scene_io._sceneio_lib()
+    vp = C.c_void_p
+    L.zrh_scene_data_from_desc.argtypes = [vp] * 3
+    L.zrh_scene_data_begin_frame.argtypes = [vp]
+    L.zrh_scene_data_refresh_emissives.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
+    L.zrh_scene_data_dirty_emissives.argtypes = [vp] * 3
+    n_large, raw = 16 * n_small, {}
+    for nv in (n_small, n_large):
+        plain = _tube_scene(nv, 2 * (n_large - nv))
+        anim, sk = _tube_skin(plain, nv)
+        lit = _lit_tube(api, plain, nv)
+        nl = len(lit.emissives)
+        rest = lit.vertices[:nv].copy()
+        A, B, Cn = api.Scene(lit), api.Scene(lit), api.Scene(plain)
+        B.set_object_emissives(lit.emissives_initial)
+        B.set_animation(anim); B.set_skinning(sk)
+        Cn.set_animation(anim); Cn.set_skinning(sk)
+        desc, init = lit.desc(), np.ascontiguousarray(lit.emissives_initial.copy())
+        h = vp()
+        assert L.zrh_scene_data_from_desc(C.addressof(desc), init.ctypes.data, C.byref(h)) == 0, L.zrh_scene_io_last_error()
+        d = L.zrh_scene_data_desc(h).contents
+        ems = np.ctypeslib.as_array(C.cast(d.emissives, C.POINTER(C.c_uint8)), (nl * 48,)).view(wire.EMISSIVE_TRI)
+        posed_all = lit.vertices.copy()
+        st = torch.cuda.Stream()
+
+        def host_form(t):
+            posed_all[:nv] = scene_io.skin_pose(anim, sk, rest, t)
+            A.update_vertices(0, posed_all[:nv], stream=st.cuda_stream)
+            L.zrh_scene_data_begin_frame(h)
+            assert L.zrh_scene_data_refresh_emissives(h, posed_all.ctypes.data, 0, nl) == 0
+            f, c = C.c_uint32(), C.c_uint32()
+            L.zrh_scene_data_dirty_emissives(h, C.byref(f), C.byref(c))
+            A.update_emissives(ems[f.value:f.value + c.value], f.value, stream=st.cuda_stream)
+            A.update_instances(lit.instances, lit.instance_to_world, stream=st.cuda_stream)
+
+        def device_form(t):
+            B.animate(t, stream=st.cuda_stream)
+
+        def not_emissive(t):
+            Cn.animate(t, stream=st.cuda_stream)
+
+        res = {"skinned_vertices": nv, "light_triangles": nl, "num_tris": int(lit.num_tris)}
+        for name, fn in (("A_host_form", host_form), ("B_scene_animate", device_form), ("C_animate_not_emissive", not_emissive)):
+            wall, stream_ms = [], []
+            for k in range(1, warmup + frames + 1):
+                t = 0.013 * k
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record(st)
+                a = time.perf_counter()
+                fn(t)
+                b = time.perf_counter()
+                e1.record(st)
+                torch.cuda.synchronize()
+                if k > warmup:
+                    wall.append((b - a) * 1e3); stream_ms.append(e0.elapsed_time(e1))
+            res[name] = {"host_wall_ms": _stats(wall), "stream_ms": _stats(stream_ms)}
+            raw[(nv, name)] = (np.asarray(wall, np.float64), np.asarray(stream_ms, np.float64))
+        res["same_device_bytes"] = bool(A.download_vertices().tobytes() == B.download_vertices().tobytes() and A.download_emissives().tobytes() == B.download_emissives().tobytes())
+        bs, cs = raw[(nv, "B_scene_animate")][1], raw[(nv, "C_animate_not_emissive")][1]
+        kern_ms = float(np.median(bs) - np.median(cs))
+        drift = float(max(np.percentile(bs, 90) - np.percentile(bs, 10), np.percentile(cs, 90) - np.percentile(cs, 10)))
+        # per light: the 16-byte entry, the owner word, three 12-byte positions, the 48-byte object record read, two 48-byte records written (the owner's
+        # 48-byte matrix row is one line for every lane here and is not counted)
+        moved = nl * (16 + 4 + 36 + 48 + 96)
+        res["refresh_kernel_stream_ms"], res["stream_p10_p90_drift_ms"] = round(kern_ms, 4), round(drift, 4)
+        res["refresh_kernel_within_drift"] = bool(kern_ms <= drift)
+        res["refresh_kernel_bytes"], res["bytes_per_light"] = int(moved), 200
+        res["refresh_kernel_gb_per_s"] = None if kern_ms <= drift else round(moved / (kern_ms * 1e-3) / 1e9, 1)
+        res["host_wall_ratio_A_over_B"] = round(res["A_host_form"]["host_wall_ms"]["median"] / res["B_scene_animate"]["host_wall_ms"]["median"], 2)
+        out["sizes"].append(res)
+        A.close(); B.close(); Cn.close()
+        L.zrh_scene_data_destroy(h)
+    small, large = raw[(n_small, "B_scene_animate")][0], raw[(n_large, "B_scene_animate")][0]
+    growth, spread = float(np.median(large) - np.median(small)), float(np.percentile(small, 90) - np.percentile(small, 10))
+    out["B_host_wall_growth_ms"], out["small_p10_p90_spread_ms"], out["B_host_wall_flat"] = growth, spread, bool(growth <= spread)
+    out["B_stream_below_A"] = [bool(np.median(raw[(nv, "B_scene_animate")][1]) < np.median(raw[(nv, "A_host_form")][1])) for nv in (n_small, n_large)]
+    out["not_measured"] = "hardware counters; several ranges (one launch per range of the pose kernel; the light kernel is one launch however many ranges)"
+    ok = all(r["same_device_bytes"] for r in out["sizes"])
+    print(json.dumps(out))
+    return 0 if ok else 1
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
@@ -486,13 +608,16 @@ if __name__ == "__main__":
     ap.add_argument("--animate", action="store_true")
     ap.add_argument("--skin", action="store_true")
     ap.add_argument("--morph", action="store_true")
+    ap.add_argument("--lights", action="store_true")
     ap.add_argument("--vertices", type=int, default=65536)
     ap.add_argument("--instances", type=int, default=4096)
     ap.add_argument("--emissive", type=int, default=100000)
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=16)
     a = ap.parse_args()
-    if a.morph:
+    if a.lights:
+        sys.exit(lights(a.vertices, max(a.frames, 64), max(a.warmup, 16)))
+    elif a.morph:
         sys.exit(morph(a.vertices, max(a.frames, 64), max(a.warmup, 16)))
     elif a.skin:
         sys.exit(skin(a.vertices, max(a.frames, 64), max(a.warmup, 16)))

@@ -65,6 +65,7 @@ EXPORTS = [
     "zr_scene_set_object_emissives", "zr_scene_has_object_emissives", "zr_scene_move_instances", "zr_scene_move_instances_async", "zr_scene_get_instances", "zr_scene_get_emissives",
     "zr_scene_set_animation", "zr_scene_animate", "zr_scene_animate_async",
     "zr_scene_update_vertices", "zr_scene_update_vertices_async", "zr_scene_get_vertices", "zr_scene_set_skinning", "zr_scene_has_skinning", "zr_scene_set_morph", "zr_scene_has_morph",
+    "zr_scene_refresh_emissives", "zr_scene_refresh_emissives_async", "zr_scene_get_object_emissives",
     "zr_scene_set_alias_build", "zr_alias_table_build_device", "zr_pass_get_emissive_powers",
     "zr_scene_create_compressed", "zr_bcn_decode_device", "zr_scene_get_texels", "zr_mipgen_device", "zr_jpeg_decode_device",
 ]
@@ -426,6 +427,30 @@ class Scene:
         out = np.zeros(count, wire.EMISSIVE_TRI)
         L.zr_scene_get_emissives.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         _check(L.zr_scene_get_emissives(self.h, stream, out.ctypes.data, first, count))
+        return out
+
+    def refresh_emissives(self, first, count, stream=False):
+        """deformed lights (zr_scene_refresh_emissives): the records of light triangles [first, first + count) re-derived on the device from the vertex buffer
+        -- the call that follows update_vertices over vertices of light triangles.  Object-space and world records are both written; powers and the alias
+        table follow only with invalidate_alias_table().  set_object_emissives first.  stream as update_instances"""
+        L = lib()
+        if stream is False:
+            L.zr_scene_refresh_emissives.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+            _check(L.zr_scene_refresh_emissives(self.h, int(first), int(count)))
+        else:
+            L.zr_scene_refresh_emissives_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+            _check(L.zr_scene_refresh_emissives_async(self.h, stream, int(first), int(count)))
+        self.version += 1
+
+    def download_object_emissives(self, first=0, count=None, stream=None):
+        """the OBJECT-space EmissiveTriangle records [first, first + count) as the device holds them (set_object_emissives, then what the pose sets and
+        refresh_emissives wrote)"""
+        L = lib()
+        if count is None:
+            count = len(self.host.emissives) - first
+        out = np.zeros(count, wire.EMISSIVE_TRI)
+        L.zr_scene_get_object_emissives.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        _check(L.zr_scene_get_object_emissives(self.h, stream, out.ctypes.data, first, count))
         return out
 
     def set_background_rebuild(self, on=True):
@@ -914,6 +939,10 @@ class Renderer:
     def animate(self, t, stream=False):
         """the frame's scene update from the time alone (Scene.animate)"""
         self.scene.animate(t, stream=stream)
+
+    def refresh_emissives(self, first, count, stream=False):
+        """deformed lights: light triangles [first, first + count) re-derived from the vertex buffer (Scene.refresh_emissives)"""
+        self.scene.refresh_emissives(first, count, stream=stream)
 
     def set_rgi_spatial(self, num_samples, radius_px=0.0):
         """ReSTIR GI: the spatial reuse stage of the indirect pass (Pass.set_rgi_spatial); stored without effect by the other integrators"""

@@ -682,7 +682,15 @@ struct zr_scene
     // ---- what the two sets pose each frame (ScenePoseRebuild is the one writer): the ranges of both as one list (zr_pose.h) -- the skin-only ranges in the
     // skin set's order, then the morph set's in its order, a range both list once -- and the ranges' rest records, range after range, on the device and
     // (hRest, same layout) on the host: what a range goes back to when its set goes.  hVertices keeps the rest pose (only the background builder reads it: topology)
-    struct Pose { std::vector<zr::PoseRange> ranges; std::vector<zr_vertex> hRest; DevBuf<zr_vertex> dRest; } pose;
+    // lights: the light triangles with a vertex in one of the ranges, by triangle index (zr::LightEntry; from hIndices and hInstances), which every
+    // zr_scene_animate re-derives behind the instance kernels (k_refresh_emissives, listed form); hLightObject / hLightWorld: their object-space and world
+    // records as the first set that listed them found them, entry after entry -- what they go back to with the rest vertices
+    struct Pose
+    {
+        std::vector<zr::PoseRange> ranges; std::vector<zr_vertex> hRest; DevBuf<zr_vertex> dRest;
+        std::vector<zr::LightEntry> lights; std::vector<zr_emissive_triangle> hLightObject, hLightWorld; DevBuf<zr::LightEntry> dLights;
+        std::vector<uint32_t> lightOwner; std::vector<float> hLightXf;      // each entry's instance, and its matrix (12 floats) when the records were saved
+    } pose;
     // zr_scene_update_vertices while a background build reads hVertices: the ranges wait here and reach hVertices once the builder's thread is done
     // (SceneFlushVertexCopies) -- the builder delivers topology, so the pose it saw does not matter, and the call does not wait for it
     std::vector<std::pair<uint32_t, std::vector<zr_vertex>>> hVertexPending;
@@ -1795,6 +1803,12 @@ static int SceneDuplicate(zr_scene* s, hipStream_t st)
     s->refitReady = true;
     return ZR_OK;
 }
+// what k_refresh_emissives reads and writes (zr_pose.h), from the set that is current
+static zr::RefreshBuffers SceneRefreshBuffers(const zr_scene* s)
+{
+    return zr::RefreshBuffers{s->emissives.p, s->objectEmissives.p, s->emissiveOwner.p, s->toWorld.p, s->vertices.p, (uint32_t)s->vertices.n,
+        s->cur.instances.p, s->indices.p, (uint32_t)s->indices.n};
+}
 // the frame's records and matrices into the set that has just become current: uploaded, or computed on the device from the previous set's records
 // and the moved list (zr_tu_scene_update.hip; the animation writes its list first, zr_tu_anim.hip); then their decoded table
 static int RefitWriteRecords(zr_scene* s, hipStream_t st, const FrameUpdate& u, const RefitFrame& F, const zr_scene::StageSlot* t)
@@ -1836,6 +1850,9 @@ static int RefitWriteRecords(zr_scene* s, hipStream_t st, const FrameUpdate& u, 
         else if (u.nMoved) HIP_TRY(hipMemcpyAsync(s->movedDev.p, h + F.seedBytes, F.listBytes, hipMemcpyHostToDevice, st));
         HIP_TRY(zr::LaunchMoveInstances(st, s->cur.instances.p, s->prev.instances.p, s->toWorld.p, F.n, s->movedSlot.p, movedList, u.nMoved,
             s->emissives.p, s->objectEmissives.p, s->emissiveOwner.p, u.emFirst, u.emEnd));
+        // deformed lights: the listed triangles from the vertices LaunchPose wrote and the matrices k_move_instances has just left in toWorld
+        if (u.form == UpdateForm::Animated && (s->skin || s->morph) && !s->pose.lights.empty())
+            HIP_TRY(zr::LaunchRefreshEmissives(st, SceneRefreshBuffers(s), s->pose.dLights.p, 0, (uint32_t)s->pose.lights.size()));
     }
     s->toWorldDev = true;
     return SceneFillInstRecs(s, st);
@@ -2070,6 +2087,8 @@ int zr_scene_set_object_emissives(zr_scene* s, const zr_emissive_triangle* objec
 {
     if (!s || (!object_space && n)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_object_emissives: null argument");
     if (n != s->emissives.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_set_object_emissives: %u records, the scene has %zu emissive triangles", n, s->emissives.n);
+    // a pose set that lists lights has saved their records and writes them every frame: new ones under it would be lost to the next animate or the next clear
+    if (!s->pose.lights.empty()) return Fail(ZR_ERR_UNSUPPORTED, "zr_scene_set_object_emissives: a skin or morph set poses %zu light triangles of this scene: clear it first", s->pose.lights.size());
     // the instance that carries each light triangle, from the instances' first light triangle and triangle counts
     std::vector<uint32_t> owner(n, 0xffffffffu);
     for (size_t i = 0; i < s->hInstances.size(); i++)
@@ -2157,9 +2176,57 @@ static int ScenePoseRebuild(zr_scene* s, bool keepSkin, const zr_skin_desc* newS
         list(zr::PoseRange{g.first_vertex, g.num_vertices, 0, skinned ? skinRanges[skinOf[i]].first_influence : 0u, g.first_target, g.num_targets, weightFirst[g.track],
             skinned ? zr::kPoseSkin | zr::kPoseMorph : zr::kPoseMorph});
     }
+    // the light list: every light triangle with a vertex in one of the new ranges, by triangle index (the host's index copy and instance records say which)
+    auto inRanges = [](const std::vector<zr::PoseRange>& ranges, uint32_t kinds, uint32_t v)
+    { for (const zr::PoseRange& g : ranges) if ((g.kind & kinds) && v >= g.firstVertex && v - g.firstVertex < g.numVertices) return true; return false; };
+    const uint32_t anyKind = zr::kPoseSkin | zr::kPoseMorph;
+    if (s->emissives.n && !P.ranges.empty())
+        for (size_t i = 0; i < s->hInstances.size(); i++)
+        {
+            const zr_mesh_instance& I = s->hInstances[i];
+            if (I.base_emissive_tri_offset == 0xffffffffu) continue;
+            for (uint32_t t = 0; t < s->hNumTris[i]; t++)
+            {
+                const uint64_t at = (uint64_t)I.base_idx_offset + 3ull * t, k = (uint64_t)I.base_emissive_tri_offset + t;
+                if (at + 3 > s->hIndices.size() || k >= s->emissives.n) break;
+                const uint64_t v[3] = {(uint64_t)I.base_vtx_offset + s->hIndices[at], (uint64_t)I.base_vtx_offset + s->hIndices[at + 1], (uint64_t)I.base_vtx_offset + s->hIndices[at + 2]};
+                if (v[0] >= s->vertices.n || v[1] >= s->vertices.n || v[2] >= s->vertices.n) continue;
+                if (inRanges(P.ranges, anyKind, (uint32_t)v[0]) || inRanges(P.ranges, anyKind, (uint32_t)v[1]) || inRanges(P.ranges, anyKind, (uint32_t)v[2]))
+                { P.lights.push_back(zr::LightEntry{(uint32_t)k, (uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2]}); P.lightOwner.push_back((uint32_t)i); }
+            }
+        }
+    if (!P.lights.empty() && !s->objectEmissives.p)
+        return Fail(ZR_ERR_NOT_INITIALIZED, "%s: the ranges hold vertices of light triangle %u: call zr_scene_set_object_emissives first", newMorph ? "zr_scene_set_morph" : "zr_scene_set_skinning", P.lights[0].tri);
+    {   // by triangle index, the owners with them
+        std::vector<uint32_t> order(P.lights.size());
+        for (uint32_t j = 0; j < order.size(); j++) order[j] = j;
+        std::sort(order.begin(), order.end(), [&P](uint32_t a, uint32_t b) { return P.lights[a].tri < P.lights[b].tri; });
+        std::vector<zr::LightEntry> lights(order.size()); std::vector<uint32_t> owner(order.size());
+        for (size_t j = 0; j < order.size(); j++) { lights[j] = P.lights[order[j]]; owner[j] = P.lightOwner[order[j]]; }
+        P.lights.swap(lights); P.lightOwner.swap(owner);
+    }
+    SceneAnimSyncHost(s);      // (the owners' matrices as they stand: saved with the records below, compared when the records go back)
     // the rest records: what the new ranges hold with the ranges listed until now back at rest (those may lie outside the new ones) -- the new ranges alone
     // are read back, and the old rest records laid over them where the two meet
     HIP_TRY(hipDeviceSynchronize());      // an animate in flight still reads the tables and writes the vertices; renders in flight read them
+    if (!P.lights.empty())
+    {   // ... and the listed lights' records likewise: read back over the span of the list, the records an earlier set saved laid over them
+        const uint32_t lo = P.lights.front().tri, hi = P.lights.back().tri + 1;
+        std::vector<zr_emissive_triangle> object(hi - lo), world(hi - lo);
+        HIP_TRY(hipMemcpy(object.data(), s->objectEmissives.p + lo, (size_t)(hi - lo) * sizeof(zr_emissive_triangle), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(world.data(), s->emissives.p + lo, (size_t)(hi - lo) * sizeof(zr_emissive_triangle), hipMemcpyDeviceToHost));
+        P.hLightObject.resize(P.lights.size()); P.hLightWorld.resize(P.lights.size()); P.hLightXf.resize(12 * P.lights.size());
+        size_t q = 0;
+        for (size_t j = 0; j < P.lights.size(); j++)
+        {
+            const uint32_t k = P.lights[j].tri;
+            while (q < O.lights.size() && O.lights[q].tri < k) q++;
+            const bool saved = q < O.lights.size() && O.lights[q].tri == k;
+            P.hLightObject[j] = saved ? O.hLightObject[q] : object[k - lo];
+            P.hLightWorld[j] = saved ? O.hLightWorld[q] : world[k - lo];
+            std::memcpy(P.hLightXf.data() + 12 * j, saved ? O.hLightXf.data() + 12 * q : s->hToWorld.data() + 12 * (size_t)P.lightOwner[j], 12 * sizeof(float));
+        }
+    }
     for (const zr::PoseRange& g : P.ranges)
     {
         HIP_TRY(hipMemcpy(P.hRest.data() + g.restFirst, s->vertices.p + g.firstVertex, (size_t)g.numVertices * sizeof(zr_vertex), hipMemcpyDeviceToHost));
@@ -2170,7 +2237,7 @@ static int ScenePoseRebuild(zr_scene* s, bool keepSkin, const zr_skin_desc* newS
         }
     }
     int r;
-    if ((r = P.dRest.Upload(P.hRest.data(), P.hRest.size()))) return r;
+    if ((r = P.dRest.Upload(P.hRest.data(), P.hRest.size())) || (!P.lights.empty() && (r = P.dLights.Upload(P.lights.data(), P.lights.size())))) return r;
     std::unique_ptr<zr_scene::Skin> K;
     if (newSkin)
     {
@@ -2203,10 +2270,31 @@ static int ScenePoseRebuild(zr_scene* s, bool keepSkin, const zr_skin_desc* newS
         HIP_TRY(hipMemcpy(s->vertices.p + o.firstVertex, O.hRest.data() + o.restFirst, (size_t)o.numVertices * sizeof(zr_vertex), hipMemcpyHostToDevice));
         if ((r = SceneFillVtxTables(s, nullptr, o.firstVertex, o.numVertices))) return r;
     }
+    // ... and the saved records of the lights with a vertex in such a range, both buffers, run of consecutive triangles after run
+    for (size_t j = 0; j < O.lights.size();)
+    {
+        auto goes = [&](const zr::LightEntry& e) { return inRanges(O.ranges, going, e.v0) || inRanges(O.ranges, going, e.v1) || inRanges(O.ranges, going, e.v2); };
+        if (!goes(O.lights[j])) { j++; continue; }
+        size_t e = j + 1;
+        while (e < O.lights.size() && O.lights[e].tri == O.lights[e - 1].tri + 1 && goes(O.lights[e])) e++;
+        HIP_TRY(hipMemcpy(s->objectEmissives.p + O.lights[j].tri, O.hLightObject.data() + j, (e - j) * sizeof(zr_emissive_triangle), hipMemcpyHostToDevice));
+        // the world record: the saved one while the owner stands where it stood when the record was saved (the very bytes, the loader's identity-matrix
+        // shortcut among them); the moved-light rule on the saved object record where an animation has moved the owner since
+        std::vector<zr_emissive_triangle> world(O.hLightWorld.begin() + j, O.hLightWorld.begin() + e);
+        for (size_t q = j; q < e; q++)
+        {
+            const float* M = s->hToWorld.data() + 12 * (size_t)O.lightOwner[q];
+            if (std::memcmp(M, O.hLightXf.data() + 12 * q, 12 * sizeof(float))) zrsm::EmissiveToWorld(O.hLightObject[q], M, world[q - j]);
+        }
+        HIP_TRY(hipMemcpy(s->emissives.p + O.lights[j].tri, world.data(), (e - j) * sizeof(zr_emissive_triangle), hipMemcpyHostToDevice));
+        j = e;
+    }
     HIP_TRY(hipDeviceSynchronize());
     if (!keepSkin) s->skin = std::move(K);
     s->morph = std::move(M);
     s->pose.ranges.swap(P.ranges); s->pose.hRest.swap(P.hRest); s->pose.dRest.Swap(P.dRest);
+    s->pose.lights.swap(P.lights); s->pose.hLightObject.swap(P.hLightObject); s->pose.hLightWorld.swap(P.hLightWorld); s->pose.dLights.Swap(P.dLights);
+    s->pose.lightOwner.swap(P.lightOwner); s->pose.hLightXf.swap(P.hLightXf);
     return ZR_OK;
 }
 // ---- keyframe animation: the tables once (zr_scene_set_animation), then one float per frame (zr_scene_animate_async)
@@ -2335,6 +2423,51 @@ int zr_scene_get_vertices(const zr_scene* s, void* stream, zr_vertex* out, uint3
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     HIP_TRY(hipMemcpy(out, s->vertices.p + first, (size_t)count * sizeof(zr_vertex), hipMemcpyDeviceToHost));
+    return ZR_OK;
+}
+// ---- deformed lights, the range form: the caller has replaced vertices (zr_scene_update_vertices) and names the light triangles that use them
+int zr_scene_refresh_emissives_async(zr_scene* s, void* stream, uint32_t first, uint32_t count)
+{
+    if (!s) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_refresh_emissives: null scene");
+    if ((uint64_t)first + count > s->emissives.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_refresh_emissives: [%u, %llu) exceeds the scene's %zu emissive triangles", first, (unsigned long long)first + count, s->emissives.n);
+    if (s->emissives.n && !s->objectEmissives.p) return Fail(ZR_ERR_NOT_INITIALIZED, "zr_scene_refresh_emissives: call zr_scene_set_object_emissives first");
+    if (int r = RefuseRebuildMode("zr_scene_refresh_emissives")) return r;
+    if (!count) return ZR_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    int r;
+    const size_t n = s->cur.instances.n, xfBytes = 12 * n * sizeof(float);
+    const bool seed = !s->toWorldDev || s->toWorld.n != 12 * n;      // a scene no refit update has touched: the matrices are the host's alone
+    zr_scene::StageSlot* t = nullptr;
+    if (seed)
+    {
+        SceneAnimSyncHost(s);
+        if ((r = StageAcquire(s, xfBytes, &t))) return r;
+        memcpy(t->host, s->hToWorld.data(), xfBytes);
+    }
+    if ((r = SceneWaitUsers(s, st))) return r;          // renders of earlier frames on other streams may still sample the old records
+    if (seed)
+    {
+        std::lock_guard<std::mutex> lock(s->mtx);
+        if (s->toWorld.n != 12 * n && (r = s->toWorld.Alloc(12 * n))) return r;
+        HIP_TRY(hipMemcpyAsync(s->toWorld.p, t->host, xfBytes, hipMemcpyHostToDevice, st));
+        if ((r = StageCommit(t, st))) return r;
+        s->toWorldDev = true;
+    }
+    hipError_t e = zr::LaunchRefreshEmissives(st, SceneRefreshBuffers(s), nullptr, first, count);
+    if (e != hipSuccess) return Fail(ZR_ERR_HIP, "k_refresh_emissives failed: %s", hipGetErrorString(e));
+    return SceneMarkUpdated(s, st);
+}
+int zr_scene_refresh_emissives(zr_scene* s, uint32_t first, uint32_t count) { const int r = zr_scene_refresh_emissives_async(s, nullptr, first, count); return count ? ThenWait(r) : r; }
+int zr_scene_get_object_emissives(const zr_scene* s, void* stream, zr_emissive_triangle* out, uint32_t first, uint32_t count)
+{
+    if (!s || (!out && count)) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_object_emissives: null argument");
+    if ((uint64_t)first + count > s->emissives.n) return Fail(ZR_ERR_INVALID_ARG, "zr_scene_get_object_emissives: [%u, %llu) exceeds the scene's %zu emissive triangles", first, (unsigned long long)first + count, s->emissives.n);
+    if (s->emissives.n && !s->objectEmissives.p) return Fail(ZR_ERR_NOT_INITIALIZED, "zr_scene_get_object_emissives: no object-space records (zr_scene_set_object_emissives)");
+    if (!count) return ZR_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(hipMemcpy(out, s->objectEmissives.p + first, (size_t)count * sizeof(zr_emissive_triangle), hipMemcpyDeviceToHost));
     return ZR_OK;
 }
 int zr_scene_set_skinning(zr_scene* s, const zr_skin_desc* d)

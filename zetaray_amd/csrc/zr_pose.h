@@ -32,6 +32,22 @@ struct PoseTables
 // k_pose_vertices launch per range in list order.  tangents: null without ZR_HIT_TANGENTS
 hipError_t LaunchPose(hipStream_t st, float t, const PoseTables& T, const PoseRange* ranges, uint32_t numRanges, zr_vertex* vertices, VtxDir* normals, VtxDir* tangents);
 
+// ---- deformed lights: a light triangle with a vertex in one of the ranges, as the host lists it when the range list is made (ScenePoseRebuild): the
+// triangle's index among the scene's light triangles and its three ABSOLUTE vertex indices -- instance -> index -> vertex resolved once, so the frame's
+// kernel does one 16-byte load and three gathers
+struct LightEntry { uint32_t tri, v0, v1, v2; };
+static_assert(sizeof(LightEntry) == 16, "LightEntry travels as one 16-byte word");
+// zr_tu_scene_update.hip: k_refresh_emissives, zrsm::EmissiveFromVertices per light triangle -- object[k] and emissives[k] from the vertex buffer and the
+// owner's row of toWorld as they stand on `st`.  list != null: the LISTED form over list[0 .. count).  list == null: the RANGE form over light triangles
+// [first, first + count), indices from the owner's record and the index buffer; a triangle without an owner is skipped.  A triangle whose indices reach
+// past numIndices / numVertices is skipped too (nothing is read or written out of bounds)
+struct RefreshBuffers
+{
+    zr_emissive_triangle* emissives; zr_emissive_triangle* object; const uint32_t* owner; const float* toWorld; const zr_vertex* vertices; uint32_t numVertices;
+    const zr_mesh_instance* instances; const uint32_t* indices; uint32_t numIndices;
+};
+hipError_t LaunchRefreshEmissives(hipStream_t st, const RefreshBuffers& B, const LightEntry* list, uint32_t first, uint32_t count);
+
 } // namespace zr
 
 #endif // ZR_POSE_H

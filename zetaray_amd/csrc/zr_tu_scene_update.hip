@@ -1,10 +1,12 @@
 // zr_tu_scene_update.hip -- the device form of a frame's scene update (zr_scene_move_instances, include/zetaray_amd.h): the MeshInstance records
 // and the EmissiveTriangle records of the instances that moved, computed on the device from their new world matrices by the same functions the
 // host form compiles (include/zr_scene_math.h), byte for byte.  Two per-element streams bound by HBM and launch latency: no LDS (`make resources` reports 0 bytes for each kernel), no wave operations.
+// k_refresh_emissives: the records of light triangles whose VERTICES changed (pose sets, zr_scene_refresh_emissives), by the same header.
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include "../../include/zr_scene_math.h"
 #include "zr_hit_tables.h"
+#include "zr_pose.h"
 
 namespace zr {
 
@@ -88,6 +90,56 @@ __global__ void __launch_bounds__(kBlock) k_move_emissives(zr_emissive_triangle*
     zr_emissive_triangle out;
     zrsm::EmissiveToWorld(in, M, out);
     StoreRecord(emissives + k, out);
+}
+
+// one lane per light triangle whose vertices were deformed: object[k] and emissives[k] = EmissiveFromVertices(object[k], the triangle's three positions in
+// the vertex buffer, the owner's row of toWorld) -- behind k_move_instances of the same frame, so the row is this frame's whether the owner moved or not.
+// kListed: entry j of `list` names the triangle and its absolute vertex indices.  Else: triangle first + j, indices from the owner's record (first light
+// triangle, index and vertex offsets: words 0, 1 and 6 of the 64-byte record) and the index buffer.  The loads that do not depend on each other (entry ->
+// owner -> matrix; entry -> three positions; entry -> record) are issued together; no LDS, no wave operations
+template<bool kListed>
+__global__ void __launch_bounds__(kBlock) k_refresh_emissives(RefreshBuffers B, const LightEntry* list, uint32_t first, uint32_t count)
+{
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= count) return;
+    uint32_t k, v[3];
+    uint32_t o;
+    if constexpr (kListed)
+    {
+        const uint4 e = *reinterpret_cast<const uint4*>(list + j);
+        k = e.x; v[0] = e.y; v[1] = e.z; v[2] = e.w;
+        o = B.owner[k];
+        if (o == kNone) return;
+    }
+    else
+    {
+        k = first + j;
+        o = B.owner[k];
+        if (o == kNone) return;
+        const uint4 a = reinterpret_cast<const uint4*>(B.instances + o)[0], b = reinterpret_cast<const uint4*>(B.instances + o)[1];
+        const uint64_t i = (uint64_t)a.y + 3ull * (k - b.z);      // a.x base_vtx_offset, a.y base_idx_offset, b.z base_emissive_tri_offset
+        if (i + 3 > B.numIndices) return;
+        ZR_UNROLL
+        for (int c = 0; c < 3; c++) v[c] = a.x + B.indices[i + c];
+    }
+    if (v[0] >= B.numVertices || v[1] >= B.numVertices || v[2] >= B.numVertices) return;
+    float p[3][3];
+    ZR_UNROLL
+    for (int c = 0; c < 3; c++) { ZR_UNROLL for (int r = 0; r < 3; r++) p[c][r] = B.vertices[v[c]].pos[r]; }
+    float M[12]; LoadMatrix(B.toWorld + 12 * (size_t)o, M);
+    const zr_emissive_triangle rec = LoadRecord(B.object + k);
+    zr_emissive_triangle obj, world;
+    zrsm::EmissiveFromVertices(rec, p[0], p[1], p[2], M, obj, world);
+    StoreRecord(B.object + k, obj);
+    StoreRecord(B.emissives + k, world);
+}
+hipError_t LaunchRefreshEmissives(hipStream_t st, const RefreshBuffers& B, const LightEntry* list, uint32_t first, uint32_t count)
+{
+    if (!count) return hipSuccess;
+    const dim3 grid((count + kBlock - 1) / kBlock), block(kBlock);
+    if (list) hipLaunchKernelGGL(k_refresh_emissives<true>, grid, block, 0, st, B, list, 0u, count);
+    else hipLaunchKernelGGL(k_refresh_emissives<false>, grid, block, 0, st, B, nullptr, first, count);
+    return hipGetLastError();
 }
 
 // one lane per instance: the record of the buffer that becomes previous -> the begin-frame rule -> (moved: the set_instance_world rule from the new

@@ -822,7 +822,8 @@ extern "C" int zrh_scene_apply_updates(zr_scene* scene, const zrh_scene_data* da
 // A skinned scene (zrh_scene_data_skinning: a glTF with skins, or zrh_scene_data_set_skinning).  Host form: zrh_scene_data_skin_pose for time t, handed over
 // range by range with zr_scene_update_vertices_async AHEAD of the frame's instance update, which refits from the new vertices.  After
 // zrh_scene_data_set_device_skinning(data, 1), on the device path: zr_scene_set_skinning once per device scene, behind its animation tables.
-static int HandSkinnedVertices(zrh_scene_data* data, zr_scene* scene, void* stream, float t)
+// all: null, or the scene's whole vertex array, into which the posed ranges are laid as well (RefreshPosedLights reads it)
+static int HandSkinnedVertices(zrh_scene_data* data, zr_scene* scene, void* stream, float t, std::vector<zr_vertex>* all)
 {
     const zr_skin_desc* k = zrh_scene_data_skinning(data);
     const zr_vertex* posed = zrh_scene_data_skin_pose(data, t);
@@ -830,6 +831,7 @@ static int HandSkinnedVertices(zrh_scene_data* data, zr_scene* scene, void* stre
     for (uint32_t i = 0; i < k->num_ranges; i++)
     {
         if (const int r = zr_scene_update_vertices_async(scene, stream, k->ranges[i].first_vertex, k->ranges[i].num_vertices, posed)) return r;
+        if (all) std::copy(posed, posed + k->ranges[i].num_vertices, all->begin() + k->ranges[i].first_vertex);
         posed += k->ranges[i].num_vertices;
     }
     return 0;
@@ -839,7 +841,7 @@ static int HandSkinnedVertices(zrh_scene_data* data, zr_scene* scene, void* stre
 // with both is written twice on the stream; the second record stands).  After zrh_scene_data_set_device_morph(data, 1), on the device path:
 // zr_scene_set_morph once per device scene, behind its animation and skin tables.  A file with skinned AND morphed ranges takes the device form of both
 // or of neither: one kernel poses such a range.
-static int HandMorphedVertices(zrh_scene_data* data, zr_scene* scene, void* stream, float t)
+static int HandMorphedVertices(zrh_scene_data* data, zr_scene* scene, void* stream, float t, std::vector<zr_vertex>* all)
 {
     const zr_morph_desc* m = zrh_scene_data_morph(data);
     const zr_vertex* posed = zrh_scene_data_morph_pose(data, t);
@@ -847,21 +849,41 @@ static int HandMorphedVertices(zrh_scene_data* data, zr_scene* scene, void* stre
     for (uint32_t i = 0; i < m->num_ranges; i++)
     {
         if (const int r = zr_scene_update_vertices_async(scene, stream, m->ranges[i].first_vertex, m->ranges[i].num_vertices, posed)) return r;
+        if (all) std::copy(posed, posed + m->ranges[i].num_vertices, all->begin() + m->ranges[i].first_vertex);
         posed += m->ranges[i].num_vertices;
     }
     return 0;
+}
+// Deformed lights (a file loaded with ZRH_LOAD_DEFORMED_LIGHTS, or tables set by hand over light-carrying vertices): the light triangles with a vertex in
+// a posed range (zrh_scene_data_pose_lights), run of consecutive triangles after run.  Host path: zrh_scene_data_refresh_emissives from the posed vertices,
+// behind zrh_scene_data_animate and ahead of the hand-over, which uploads them with the dirty range.  Device path with both sets on the device: nothing,
+// zr_scene_animate_async re-derives them.  Device path with a set posed on the host: zr_scene_refresh_emissives_async behind the frame's update.
+static std::vector<std::pair<uint32_t, uint32_t>> LightRuns(const uint32_t* tris, uint32_t n)
+{
+    std::vector<std::pair<uint32_t, uint32_t>> runs;      // (first triangle, count)
+    for (uint32_t j = 0; j < n; j++)
+    {
+        if (j && tris[j] == tris[j - 1] + 1) runs.back().second++;
+        else runs.emplace_back(tris[j], 1u);
+    }
+    return runs;
 }
 extern "C" int zrh_scene_animate(zrh_scene_data* data, zr_scene* scene, void* stream, float t)
 {
     if (!scene || !data || !zrh_scene_data_animation(data)) return -1;
     const zr_skin_desc* skin = zrh_scene_data_skinning(data);
     const zr_morph_desc* morph = zrh_scene_data_morph(data);
+    const uint32_t* lights = nullptr;
+    const uint32_t numLights = skin || morph ? zrh_scene_data_pose_lights(data, &lights) : 0u;
     if (!zrh_scene_data_device_animation(data))
     {
+        std::vector<zr_vertex> all;
+        if (numLights) { const zr_scene_desc* d = zrh_scene_data_desc(data); all.assign(d->vertices, d->vertices + d->num_vertices); }
         zrh_scene_data_begin_frame(data);
         if (zrh_scene_data_animate(data, t)) return -1;
-        if (skin) { if (const int r = HandSkinnedVertices(data, scene, stream, t)) return r; }
-        if (morph) { if (const int r = HandMorphedVertices(data, scene, stream, t)) return r; }
+        if (skin) { if (const int r = HandSkinnedVertices(data, scene, stream, t, numLights ? &all : nullptr)) return r; }
+        if (morph) { if (const int r = HandMorphedVertices(data, scene, stream, t, numLights ? &all : nullptr)) return r; }
+        for (const auto& run : LightRuns(lights, numLights)) if (zrh_scene_data_refresh_emissives(data, all.data(), run.first, run.second)) return -1;
         return zrh_scene_apply_updates_on(scene, data, stream);
     }
     const bool devMorph = morph && zrh_scene_data_device_morph(data) && (!skin || zrh_scene_data_device_skinning(data));
@@ -880,7 +902,7 @@ extern "C" int zrh_scene_animate(zrh_scene_data* data, zr_scene* scene, void* st
             if (r) return r;
         }
     }
-    else if (skin) { if ((r = HandSkinnedVertices(data, scene, stream, t))) return r; }      // (the vertices first: zr_scene_animate refits from them)
+    else if (skin) { if ((r = HandSkinnedVertices(data, scene, stream, t, nullptr))) return r; }      // (the vertices first: zr_scene_animate refits from them)
     if (devMorph)
     {
         if (!zr_scene_has_morph(scene))
@@ -890,11 +912,17 @@ extern "C" int zrh_scene_animate(zrh_scene_data* data, zr_scene* scene, void* st
             if (r) return r;
         }
     }
-    else if (morph) { if ((r = HandMorphedVertices(data, scene, stream, t))) return r; }
+    else if (morph) { if ((r = HandMorphedVertices(data, scene, stream, t, nullptr))) return r; }
     r = zr_scene_animate_async(scene, stream, t);
-    if (r != ZR_ERR_NOT_INITIALIZED) return r;
-    if ((r = handTables())) return r;
-    return zr_scene_animate_async(scene, stream, t);
+    if (r == ZR_ERR_NOT_INITIALIZED) { if ((r = handTables())) return r; r = zr_scene_animate_async(scene, stream, t); }
+    if (r) return r;
+    if (numLights && ((skin && !devSkin) || (morph && !devMorph)))
+    {   // a set posed on the host: its lights from the vertices handed over above and the matrices the update has just written
+        if (!zr_scene_has_object_emissives(scene) && zrh_scene_data_initial_emissives(data))
+            if ((r = zr_scene_set_object_emissives(scene, zrh_scene_data_initial_emissives(data), zrh_scene_data_desc(data)->num_emissives))) return r;
+        for (const auto& run : LightRuns(lights, numLights)) if ((r = zr_scene_refresh_emissives_async(scene, stream, run.first, run.second))) return r;
+    }
+    return 0;
 }
 
 int zrh_render_sequence_sky_display(const zr_scene_desc* desc, const zr_frame_constants* cbs, uint32_t n, uint32_t w, uint32_t h, int integrator, float* finalOut, float* skyDiOut,

@@ -74,6 +74,10 @@ int zrh_scene_apply_updates_on(zr_scene* scene, const struct zrh_scene_data* dat
 // A morphed scene (zrh_scene_data_morph) likewise: zrh_scene_data_morph_pose handed over with zr_scene_update_vertices_async by default; after
 // zrh_scene_data_set_device_morph(data, 1) the tables go to the device scene once (zr_scene_set_morph).  A file with ranges that are skinned AND morphed
 // takes the device form of both (set both switches) or of neither.
+// Deformed lights (ZRH_LOAD_DEFORMED_LIGHTS): the light triangles with a vertex in a posed range (zrh_scene_data_pose_lights) follow the pose.  Host path:
+// zrh_scene_data_refresh_emissives from the posed vertices, between the vertex hand-over and the host-form emissive and instance updates.  Device path with
+// the sets on the device: nothing to add, zr_scene_animate_async re-derives the records (the same device bytes).  Device path with a set posed on the
+// host: zr_scene_refresh_emissives_async behind the frame's update.
 int zrh_scene_animate(struct zrh_scene_data* data, zr_scene* scene, void* hip_stream, float t);
 }
 

@@ -742,6 +742,7 @@ struct zrh_scene_data
     std::vector<zr_texture_desc> textures; std::vector<uint8_t> texels; uint32_t texOffsets[4] = {0, 0, 0, 0};
     // ZRH_LOAD_KEEP_COMPRESSED: `texels` stays empty; texSources[i] names the chain of textures[i] in texPayload, heapBytes is the size of the heap they decode to
     bool loadJpeg = false;      // ZRH_LOAD_JPEG
+    bool deformedLights = false;      // ZRH_LOAD_DEFORMED_LIGHTS: a skinned or morphed primitive may carry an emissive material
     bool keepCompressed = false; std::vector<zr_texture_source> texSources; std::vector<uint8_t> texPayload; uint64_t heapBytes = 0; zr_texture_blocks blocks{};
     std::vector<float> prevWorld; uint32_t dirtyFirst = 0xffffffffu, dirtyEnd = 0;      // per-frame maintenance (zrh_scene_data_begin_frame / _set_instance_world)
     // the instances set_instance_world named this frame, each once, with their matrices; movedSlot[i] = where instance i stands in that list
@@ -759,6 +760,7 @@ struct zrh_scene_data
     std::vector<float> morphTimes, morphValues, morphRestWeights, morphDeltas;
     zr_morph_desc morph{}; bool hasMorph = false, deviceMorph = false;      // deviceMorph: zrh_scene_data_set_device_morph (zr_host.h: zrh_scene_animate)
     std::vector<zr_vertex> morphRest, morphPosed;      // zrh_scene_data_morph_pose
+    std::vector<uint32_t> poseLights;      // zrh_scene_data_pose_lights
     void PointMorph()
     {
         std::memset(&morph, 0, sizeof(morph));
@@ -1219,7 +1221,7 @@ void Load(const std::string& path, zrh_scene_data& sc)
         void MorphPrimitive(int nidx, int mesh, int pi, const Json& prim, const MeshPrim& mp, uint32_t first, int track, const std::vector<float>& weights)
         {
             const std::string where = "glTF: node " + std::to_string(nidx) + " (mesh " + std::to_string(mesh) + ", primitive " + std::to_string(pi) + "): ";
-            if (isEm(mp.mat)) Throw(where + "a morphed primitive with an emissive material is not supported (a deformed light would keep shining from its rest pose)");
+            if (isEm(mp.mat) && !sc.deformedLights) Throw(where + "a morphed primitive with an emissive material is not supported (a deformed light would keep shining from its rest pose)");
             const uint32_t T = meshTargets[(size_t)mesh];
             if (track >= 0)
             {
@@ -1275,7 +1277,7 @@ void Load(const std::string& path, zrh_scene_data& sc)
             if (hj && !hw) Throw(where + "JOINTS_0 without WEIGHTS_0");
             if (hw && !hj) Throw(where + "WEIGHTS_0 without JOINTS_0");
             if (!hj) Throw(where + "a primitive of a skinned node has neither JOINTS_0 nor WEIGHTS_0");
-            if (isEm(mp.mat)) Throw(where + "a skinned primitive with an emissive material is not supported (a deformed light would keep shining from its rest pose)");
+            if (isEm(mp.mat) && !sc.deformedLights) Throw(where + "a skinned primitive with an emissive material is not supported (a deformed light would keep shining from its rest pose)");
             const Accessor ja = g.Acc((int)at.At("JOINTS_0").num), wa = g.Acc((int)at.At("WEIGHTS_0").num);
             if (ja.ncomp != 4 || (ja.comp != 5121 && ja.comp != 5123) || ja.normalized) Throw(where + "JOINTS_0 must be VEC4 of unsigned bytes or unsigned shorts");
             if (wa.ncomp != 4 || !(wa.comp == 5126 || ((wa.comp == 5121 || wa.comp == 5123) && wa.normalized))) Throw(where + "WEIGHTS_0 must be VEC4 of floats, or of normalised unsigned bytes / shorts");
@@ -1501,7 +1503,8 @@ void Load(const std::string& path, zrh_scene_data& sc)
             float po[3][3], uv[6];
             for (int k = 0; k < 3; k++)
             {
-                const zr_vertex& v = sc.vertices[em.mp.vtx + sc.indices[em.mp.idx + 3 * p + k]];
+                // (the instance's own vertices: the mesh's, or the copy a skinned / morphed node poses -- equal at rest, default morph weights applied)
+                const zr_vertex& v = sc.vertices[sc.instances[em.inst].base_vtx_offset + sc.indices[em.mp.idx + 3 * p + k]];
                 for (int r = 0; r < 3; r++) po[k][r] = v.pos[r];
                 uv[2 * k] = v.uv[0]; uv[2 * k + 1] = v.uv[1];
             }
@@ -1532,9 +1535,10 @@ const zr_texture_blocks* zrh_scene_data_texture_blocks(const zrh_scene_data* s) 
 int zrh_gltf_load_ex(const char* path, const uint16_t* rho, const uint32_t* rhoDim, uint32_t flags, zrh_scene_data** out)
 {
     if (!path || !out) { g_err = "null argument"; return -1; }
-    if (flags & ~(uint32_t)(ZRH_LOAD_KEEP_COMPRESSED | ZRH_LOAD_JPEG)) { g_err = "zrh_gltf_load_ex: unknown flag"; return -1; }
+    if (flags & ~(uint32_t)(ZRH_LOAD_KEEP_COMPRESSED | ZRH_LOAD_JPEG | ZRH_LOAD_DEFORMED_LIGHTS)) { g_err = "zrh_gltf_load_ex: unknown flag"; return -1; }
     std::unique_ptr<zrh_scene_data> sc(new zrh_scene_data());
     sc->keepCompressed = (flags & ZRH_LOAD_KEEP_COMPRESSED) != 0; sc->loadJpeg = (flags & ZRH_LOAD_JPEG) != 0;
+    sc->deformedLights = (flags & ZRH_LOAD_DEFORMED_LIGHTS) != 0;
     try { Load(path, *sc); }
     catch (const Error& e) { g_err = e.what; return -1; }
     catch (const std::exception& e) { g_err = std::string("glTF: malformed file (") + e.what() + ")"; return -1; }
@@ -1745,6 +1749,71 @@ int zrh_scene_data_from_desc(const zr_scene_desc* d, const zr_emissive_triangle*
     return 0;
 }
 void zrh_emissive_to_world(const zr_emissive_triangle* in, const float* to_world_3x4, zr_emissive_triangle* out) { zr_emissive_triangle t; EmissiveToWorld(*in, to_world_3x4, t); *out = t; }
+void zrh_emissive_from_vertices(const zr_emissive_triangle* rec, const float* p0, const float* p1, const float* p2, const float* to_world_3x4,
+    zr_emissive_triangle* object_out, zr_emissive_triangle* world_out)
+{ zr_emissive_triangle o, w; EmissiveFromVertices(*rec, p0, p1, p2, to_world_3x4, o, w); *object_out = o; *world_out = w; }
+// the light triangles of instance i are [base_emissive_tri_offset, + numTris): triangle k's owner, or instances.size() for none
+static size_t LightOwner(const zrh_scene_data* s, uint32_t k)
+{
+    for (size_t i = 0; i < s->instances.size(); i++)
+    {
+        const uint32_t b = s->instances[i].base_emissive_tri_offset;
+        if (b != 0xffffffffu && k >= b && k - b < s->numTris[i]) return i;
+    }
+    return s->instances.size();
+}
+int zrh_scene_data_refresh_emissives(zrh_scene_data* s, const zr_vertex* vertices, uint32_t first_tri, uint32_t count)
+{
+    if (!s) { g_err = "zrh_scene_data_refresh_emissives: null scene"; return -1; }
+    if ((uint64_t)first_tri + count > s->emissives.size()) { g_err = "zrh_scene_data_refresh_emissives: the range exceeds the scene's emissive triangles"; return -1; }
+    if (!s->emissives.empty() && s->emissivesInitial.empty()) { g_err = "zrh_scene_data_refresh_emissives: the scene has no object-space light records"; return -1; }
+    const zr_vertex* V = vertices ? vertices : s->vertices.data();
+    size_t owner = s->instances.size();
+    for (uint32_t k = first_tri; k < first_tri + count; k++)
+    {
+        // (triangles of one instance follow each other: the owner is looked up when the range leaves it)
+        if (owner == s->instances.size() || k < s->instances[owner].base_emissive_tri_offset || k - s->instances[owner].base_emissive_tri_offset >= s->numTris[owner]) owner = LightOwner(s, k);
+        if (owner == s->instances.size()) continue;
+        const zr_mesh_instance& I = s->instances[owner];
+        const uint64_t at = (uint64_t)I.base_idx_offset + 3ull * (k - I.base_emissive_tri_offset);
+        if (at + 3 > s->indices.size()) continue;
+        const uint64_t v[3] = {(uint64_t)I.base_vtx_offset + s->indices[at], (uint64_t)I.base_vtx_offset + s->indices[at + 1], (uint64_t)I.base_vtx_offset + s->indices[at + 2]};
+        if (v[0] >= s->vertices.size() || v[1] >= s->vertices.size() || v[2] >= s->vertices.size()) continue;
+        zr_emissive_triangle o, w;
+        EmissiveFromVertices(s->emissivesInitial[k], V[v[0]].pos, V[v[1]].pos, V[v[2]].pos, s->toWorld.data() + 12 * owner, o, w);
+        s->emissivesInitial[k] = o; s->emissives[k] = w;
+        s->dirtyFirst = std::min(s->dirtyFirst, k); s->dirtyEnd = std::max(s->dirtyEnd, k + 1);
+    }
+    return 0;
+}
+uint32_t zrh_scene_data_pose_lights(zrh_scene_data* s, const uint32_t** tris)
+{
+    if (tris) *tris = nullptr;
+    if (!s) return 0;
+    s->poseLights.clear();
+    auto posed = [s](uint64_t v)
+    {
+        if (s->hasSkin) for (const zr_skin_range& r : s->skinRanges) if (v >= r.first_vertex && v - r.first_vertex < r.num_vertices) return true;
+        if (s->hasMorph) for (const zr_morph_range& r : s->morphRanges) if (v >= r.first_vertex && v - r.first_vertex < r.num_vertices) return true;
+        return false;
+    };
+    if ((s->hasSkin || s->hasMorph) && !s->emissives.empty())
+        for (size_t i = 0; i < s->instances.size(); i++)
+        {
+            const zr_mesh_instance& I = s->instances[i];
+            if (I.base_emissive_tri_offset == 0xffffffffu) continue;
+            for (uint32_t t = 0; t < s->numTris[i]; t++)
+            {
+                const uint64_t at = (uint64_t)I.base_idx_offset + 3ull * t, k = (uint64_t)I.base_emissive_tri_offset + t;
+                if (at + 3 > s->indices.size() || k >= s->emissives.size()) break;
+                if (posed((uint64_t)I.base_vtx_offset + s->indices[at]) || posed((uint64_t)I.base_vtx_offset + s->indices[at + 1]) || posed((uint64_t)I.base_vtx_offset + s->indices[at + 2]))
+                    s->poseLights.push_back((uint32_t)k);
+            }
+        }
+    std::sort(s->poseLights.begin(), s->poseLights.end());
+    if (tris) *tris = s->poseLights.data();
+    return (uint32_t)s->poseLights.size();
+}
 const zr_emissive_triangle* zrh_scene_data_initial_emissives(const zrh_scene_data* s) { return s && !s->emissivesInitial.empty() ? s->emissivesInitial.data() : nullptr; }
 void zrh_pack_emissive_triangle(const float* v0, const float* v1, const float* v2, const float* uv6, uint32_t factor, uint32_t tex, uint16_t strength, uint32_t id,
     int doubleSided, zr_emissive_triangle* out) { PackEmissiveTriangle(v0, v1, v2, uv6, factor, tex, strength, id, doubleSided != 0, *out); }

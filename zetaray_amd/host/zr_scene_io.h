@@ -37,7 +37,10 @@ int zrh_gltf_load(const char* path, const uint16_t* rho_lut, const uint32_t* rho
 // Huffman files of 8 bits, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0 (zrh_jpeg_decode below), same slots, same chain.  The default mode decodes it here through
 // include/zr_jpeg.h; with ZRH_LOAD_KEEP_COMPRESSED only the entropy decode runs here and the record of quantised coefficients travels as a
 // ZR_TEX_SRC_JPEG_COEF source, which the same header turns into level 0 on the device.  A file may mix .dds, .png and .jpg.
-enum { ZRH_LOAD_KEEP_COMPRESSED = 1u, ZRH_LOAD_JPEG = 2u };
+// ZRH_LOAD_DEFORMED_LIGHTS: a skinned or morphed primitive may carry an emissive material (without the flag it is refused by name, as before).  Its light
+// records come from the rest pose, as for any mesh; zrh_scene_animate (zr_host.h) re-derives them each frame on either of its paths (zrh_scene_data_refresh_emissives
+// below; zr_scene_refresh_emissives, include/zetaray_amd.h).  A file without such a primitive loads to the same bytes with and without the flag.
+enum { ZRH_LOAD_KEEP_COMPRESSED = 1u, ZRH_LOAD_JPEG = 2u, ZRH_LOAD_DEFORMED_LIGHTS = 4u };
 int zrh_gltf_load_ex(const char* path, const uint16_t* rho_lut, const uint32_t* rho_dim3, uint32_t flags, zrh_scene_data** out);
 const zr_texture_blocks* zrh_scene_data_texture_blocks(const zrh_scene_data* s);
 const char* zrh_scene_io_last_error(void);
@@ -78,7 +81,7 @@ int zrh_scene_data_animate(zrh_scene_data* s, float t);
 // handedness rule.  zrh_scene_data_skinning returns the tables (zr_scene_set_skinning takes them after zr_scene_set_animation), null for a file
 // without a skinned node.  Refused by name and reason: a skin whose joints are not nodes of the file (or not in the scene's hierarchy), JOINTS_0
 // without WEIGHTS_0 or the other way round, JOINTS_1 / WEIGHTS_1, a joint index >= the skin's joint count, weights without a positive finite sum, a
-// skinned primitive with an emissive material, a skin in a file with no animation
+// skinned primitive with an emissive material (without ZRH_LOAD_DEFORMED_LIGHTS), a skin in a file with no animation
 const zr_skin_desc* zrh_scene_data_skinning(const zrh_scene_data* s);
 // ... and for a scene that did not come from a file: a deep copy of `desc` (null or empty clears), after zrh_scene_data_set_animation, refused (-1) for what
 // zr_scene_set_skinning refuses as invalid; zrh_scene_data_set_animation clears a skin, as zr_scene_set_animation does.
@@ -99,7 +102,7 @@ int zrh_scene_data_device_skinning(const zrh_scene_data* s);
 // default weights are applied once at load by zrmo::MorphVertex (to a copy of the node's own) and no morph set is made for them.
 // Refused by name and reason: primitives of one mesh with different target counts, a weights array whose length is not the target count, a target
 // accessor shorter than POSITION, a CUBICSPLINE or STEP weights sampler, a weights channel on a node whose mesh has no targets, a sparse index out of
-// range, a morphed primitive with an emissive material (a deformed light would keep shining from its rest pose).
+// range, a morphed primitive with an emissive material without ZRH_LOAD_DEFORMED_LIGHTS (a deformed light would keep shining from its rest pose).
 // zrh_scene_data_set_morph replaces the tables (a deep copy; null or empty: clears) after the checks of zr_scene_set_morph; zrh_scene_data_set_animation and
 // _set_skinning clear them, as the device scene's calls do.  zrh_scene_data_morph_pose(s, t) is the HOST FORM of a frame's morphing: zrh_morph_pose (below)
 // on this scene's tables and vertices, which keep the rest pose; returns the posed records of the ranges, range after range (valid until the next call).
@@ -140,6 +143,21 @@ void zrh_pack_emissive_triangle(const float* v0, const float* v1, const float* v
 // directions, half lengths), transform them by the 3 x 4 object-to-world matrix, encode again; every other field is kept.  Per frame, for a moving
 // emissive instance: out[t] = zrh_emissive_to_world(initial[t], new matrix) for its triangles, then zr_scene_update_emissives (zetaray_amd.h)
 void zrh_emissive_to_world(const zr_emissive_triangle* in, const float* to_world_3x4, zr_emissive_triangle* out);
+// A light triangle whose vertices were deformed (zrsm::EmissiveFromVertices, include/zr_scene_math.h -- the rule k_refresh_emissives compiles): the
+// object-space record takes the three object-space positions p0..p2 (the loader's geometry step), the world record is zrh_emissive_to_world of that;
+// every non-geometric field of `rec` is kept in both.  No identity-matrix shortcut.  Caller guarantee: no zero-length edge
+void zrh_emissive_from_vertices(const zr_emissive_triangle* rec, const float* p0, const float* p1, const float* p2, const float* to_world_3x4,
+                                zr_emissive_triangle* object_out, zr_emissive_triangle* world_out);
+// ... over a scene's light triangles [first_tri, first_tri + count): each from its owner's index and vertex offsets, the scene's indices and `vertices`
+// (the scene's WHOLE vertex array with the pose in it; null: the scene's own), with the owner's current matrix.  Writes the world records
+// (zr_scene_desc.emissives) AND the object-space records (zrh_scene_data_initial_emissives: a later zrh_scene_data_set_instance_world starts from the
+// posed shape), skips a triangle no instance carries, and adds the triangles to the dirty range zrh_scene_data_dirty_emissives reports, so the host-form
+// update uploads them.  The HOST FORM zr_scene_refresh_emissives and the pose sets of zr_scene_animate are held to, byte for byte.  -1
+// (zrh_scene_io_last_error()) for a range past the scene's emissive triangles or a scene without object-space records
+int zrh_scene_data_refresh_emissives(zrh_scene_data* s, const zr_vertex* vertices, uint32_t first_tri, uint32_t count);
+// the light triangles with a vertex in a range of the scene's skin or morph tables, ascending (valid until the next call): what zr_scene_set_skinning /
+// zr_scene_set_morph list on the device, and what the host path of zrh_scene_animate refreshes
+uint32_t zrh_scene_data_pose_lights(zrh_scene_data* s, const uint32_t** tris);
 // the object-space records of the scene's emissive triangles as loaded (same order as zr_scene_desc.emissives; ID already hashed)
 const zr_emissive_triangle* zrh_scene_data_initial_emissives(const zrh_scene_data* s);
 // BC7 / BC5 block decompression: w x h texels (multiples of 4 not required) -> RGBA8 / RG8 rows top-down

@@ -539,6 +539,56 @@ def _sceneio_lib():
 
 LOAD_KEEP_COMPRESSED = 1      # ZRH_LOAD_KEEP_COMPRESSED
 LOAD_JPEG = 2      # ZRH_LOAD_JPEG
+LOAD_DEFORMED_LIGHTS = 4      # ZRH_LOAD_DEFORMED_LIGHTS
+
+
+def emissive_from_vertices(rec, p0, p1, p2, to_world_3x4):
+    """zrh_emissive_from_vertices: a light triangle whose vertices were deformed -- (object-space record, world record) from the record `rec` (a
+    wire.EMISSIVE_TRI scalar or 1-element array; its non-geometric fields are kept), the three object-space positions and the owner's matrix"""
+    import ctypes as C
+    L = _sceneio_lib()
+    L.zrh_emissive_from_vertices.argtypes = [C.c_void_p] * 7
+    rec = np.ascontiguousarray(rec, wire.EMISSIVE_TRI).reshape(1)
+    p = [np.ascontiguousarray(q, np.float32).reshape(3) for q in (p0, p1, p2)]
+    M = np.ascontiguousarray(to_world_3x4, np.float32).reshape(12)
+    obj, world = np.zeros(1, wire.EMISSIVE_TRI), np.zeros(1, wire.EMISSIVE_TRI)
+    L.zrh_emissive_from_vertices(rec.ctypes.data, p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, M.ctypes.data, obj.ctypes.data, world.ctypes.data)
+    return obj[0], world[0]
+
+
+def refresh_emissives(sc, vertices, first, count):
+    """zrh_scene_data_refresh_emissives on a Scene: light triangles [first, first + count) re-derived from `vertices` (the scene's whole vertex array with
+    the pose in it; None: sc.vertices) and their owners' matrices.  Writes sc.emissives and sc.emissives_initial (the object-space records) in place and
+    returns the dirty range (first, count) the host-form update uploads -- the host form of api.Scene.refresh_emissives"""
+    import ctypes as C
+    L = _sceneio_lib()
+    vp = C.c_void_p
+    L.zrh_scene_data_from_desc.argtypes = [vp] * 3
+    L.zrh_scene_data_refresh_emissives.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
+    L.zrh_scene_data_dirty_emissives.argtypes = [vp] * 3
+    L.zrh_scene_data_initial_emissives.restype = vp
+    L.zrh_scene_data_initial_emissives.argtypes = [vp]
+    desc = sc.desc()
+    init = np.ascontiguousarray(sc.emissives_initial, wire.EMISSIVE_TRI)
+    h = vp()
+    if L.zrh_scene_data_from_desc(C.addressof(desc), init.ctypes.data if len(init) else None, C.byref(h)) != 0:
+        raise ValueError(L.zrh_scene_io_last_error().decode())
+    try:
+        v = None if vertices is None else np.ascontiguousarray(vertices, wire.VERTEX).reshape(-1)
+        if v is not None and len(v) != len(sc.vertices):
+            raise ValueError(f"refresh_emissives: {len(v)} vertices, the scene has {len(sc.vertices)}")
+        if L.zrh_scene_data_refresh_emissives(h, v.ctypes.data if v is not None else None, int(first), int(count)) != 0:
+            raise ValueError(L.zrh_scene_io_last_error().decode())
+        n = len(sc.emissives)
+        d = L.zrh_scene_data_desc(h).contents
+        if n:
+            sc.emissives[:] = np.frombuffer(C.string_at(d.emissives, n * 48), wire.EMISSIVE_TRI)
+            sc.emissives_initial[:] = np.frombuffer(C.string_at(L.zrh_scene_data_initial_emissives(h), n * 48), wire.EMISSIVE_TRI)
+        f, c = C.c_uint32(), C.c_uint32()
+        L.zrh_scene_data_dirty_emissives(h, C.byref(f), C.byref(c))
+        return f.value, c.value
+    finally:
+        L.zrh_scene_data_destroy(h)
 
 
 def skin_pose(anim, skin, rest, t):
@@ -652,7 +702,7 @@ def jpeg_expand(record):
     return out
 
 
-def load_gltf_native(path, rho=None, textures="decoded", jpeg=False):
+def load_gltf_native(path, rho=None, textures="decoded", jpeg=False, deformed_lights=False):
     """glTF -> wire formats through the C++ loader (MeshInstance quantisation by decomposeSRT of the world matrix, node hierarchies, matrix
     nodes, DDS material textures decoded to the texel heap, PNG ones with their mip chain generated by include/zr_mipgen.h).  Returns (Scene, texture-table offsets dict for set_texture_heap_offsets).
     A file with "animations" (LINEAR translation / rotation / scale channels) also gives sc.animation, a wire.AnimDesc over the dynamic closure of
@@ -665,7 +715,9 @@ def load_gltf_native(path, rho=None, textures="decoded", jpeg=False):
     carry the blocks and api.Scene decodes them on the device (zr_scene_create_compressed); sc.decode_textures() makes the texels on the host.
     A .png image travels as its level 0 (wire.TEX_SRC_RAW_MIP0) and its other levels are generated on the device.
     jpeg=True (ZRH_LOAD_JPEG): .jpg / .jpeg images are read wherever a .png is (refused by name without it): decoded on the host through include/zr_jpeg.h, or
-    with textures="compressed" entropy-decoded only and handed over as wire.TEX_SRC_JPEG_COEF records, which the same header turns into level 0 on the device."""
+    with textures="compressed" entropy-decoded only and handed over as wire.TEX_SRC_JPEG_COEF records, which the same header turns into level 0 on the device.
+    deformed_lights=True (ZRH_LOAD_DEFORMED_LIGHTS): a skinned or morphed primitive may carry an emissive material (refused by name without it); its light
+    records come from the rest pose and follow the pose with every Scene.animate once the skin / morph set is on the device."""
     import ctypes as C
     if textures not in ("decoded", "compressed"):
         raise ValueError("textures must be 'decoded' or 'compressed', not %r" % (textures,))
@@ -674,7 +726,7 @@ def load_gltf_native(path, rho=None, textures="decoded", jpeg=False):
     rho_data = np.ascontiguousarray(rho_data, np.uint16)
     dims = (C.c_uint32 * 3)(*rho_dim)
     h = C.c_void_p()
-    if L.zrh_gltf_load_ex(os.fsencode(path), rho_data.ctypes.data, dims, (LOAD_KEEP_COMPRESSED if textures == "compressed" else 0) | (LOAD_JPEG if jpeg else 0), C.byref(h)) != 0:
+    if L.zrh_gltf_load_ex(os.fsencode(path), rho_data.ctypes.data, dims, (LOAD_KEEP_COMPRESSED if textures == "compressed" else 0) | (LOAD_JPEG if jpeg else 0) | (LOAD_DEFORMED_LIGHTS if deformed_lights else 0), C.byref(h)) != 0:
         raise RuntimeError(L.zrh_scene_io_last_error().decode())
     try:
         d = L.zrh_scene_data_desc(h).contents
