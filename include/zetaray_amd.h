@@ -210,7 +210,15 @@ typedef enum zr_output {
     /* K12 thread maps (ReSTIR_PT_Sort.hlsl; Util.hlsli:20-42), R16_UINT 2 B: x offset + 31 | (y offset + 31) << 7 | error << 15 of the pixel
        the thread at this position shifts; CtN = Sort_CtT then Sort_CtS, NtC = Sort_TtC then Sort_StC (DESC_TABLE_RPT::THREAD_MAP_*).
        Built under ZR_IND_SORT_TEMPORAL / ZR_IND_SORT_SPATIAL; wave order inside a bucket = wave index (the shader leaves it to the
-       arrival order of an LDS atomic). */
+       arrival order of an LDS atomic).
+       A frame launches only the sorts whose maps its own kernels read (Sort_CtT, Sort_StC).  The other two (Sort_TtC, Sort_CtS) are outputs and
+       nothing else: zr_pass_get_output / zr_pass_download_output launch the one whose map is asked for, on the stream of the stage it belongs to,
+       when it is asked for -- so the planes hold what the lines above say at every point a caller can ask (after the temporal stage: CtT / TtC;
+       after a spatial round: CtS / StC; any flags, 0 - 2 rounds, frame overlap on or off, the next frame's CANDIDATES stage enqueued or not), and
+       a renderer that never asks pays for neither.  A sort that has not been asked for is launched by the pass itself before a stage overwrites
+       the reservoir plane it reads; it reads the G-buffer planes of its frame, which must not have been rendered over twice (three times with
+       frame overlap) without this pass rendering in between -- otherwise the map keeps its previous contents.  Consumers run on the stream of the
+       frame's last stage, as for every output.  The tile-split path (zr_pass_halo_*) does not move the maps. */
     ZR_OUT_RPT_THREAD_MAP_CTN = 18, ZR_OUT_RPT_THREAD_MAP_NTC = 19,
     /* ReSTIR DI (ZR_PASS_DI_EMISSIVE) persistent state written by the last frame (Reservoir.hlsli:150-213) */
     ZR_OUT_RDI_RESERVOIR_A = 20,   /* RGBA32_UINT 16 B: bary unorm2, le.xy half2, le.z half | M << 16, lightIdx */

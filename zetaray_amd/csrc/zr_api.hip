@@ -13,6 +13,7 @@
 #include <cstring>
 #include <new>
 #include <mutex>
+#include <unordered_map>
 #include "zr_stages.h"
 #include "zr_rpt.h"
 #include "zr_rdi.h"
@@ -809,6 +810,9 @@ struct zr_gbuffer
     // frame N + 1 still read the sets of frames N + 1 and N)
     DevBuf<uint8_t> planeSets[3][ZR_GB_COUNT];
     int cur = 0, numSets = 2; uint64_t numRendered = 0;
+    // which object this is and which render filled each plane set (numRendered at the time; 0 = never): what a ReSTIR PT pass checks before a K12 sort it
+    // put off reads these planes after the frame that rendered them (RptPendingSort).  uid: zr_gbuffer_create; g_liveGBuffers knows the ones that still exist
+    uint64_t uid = 0, renderAt[3] = {0, 0, 0};
     int Next() const { return (cur + 1) % numSets; }
     int Prev() const { return (cur + numSets - 1) % numSets; }
     // the scene's material class (zr_scene::plainMaterials) at the time each plane set was rendered: the PLAIN kernel permutations take a pixel's flags as known,
@@ -841,6 +845,11 @@ struct zr_gbuffer
         return g;
     }
 };
+
+// the G-buffers that exist, by address, with their uids (an address can be handed out again)
+static std::mutex g_liveGBuffersMtx;
+static std::unordered_map<const zr_gbuffer*, uint64_t> g_liveGBuffers;
+static uint64_t g_gbufferUid = 0;
 
 struct QueueStorage
 {
@@ -943,6 +952,17 @@ struct zr_pass
     const Plane<F4>& TargetPlane(int i) const { return i ? rptTargetAlt : rptTarget; }
     const Plane<float, 4>& FinalPlane(int i) const { return i == 0 ? finalRGBA : (i == 1 ? finalAlt : finalAlt2); }
     Plane<uint16_t> rptMap[2];      // K12 thread maps: [0] CtN, [1] NtC
+    // A K12 sort that no kernel reads -- Sort_TtC of the temporal stage, Sort_CtS of a spatial round: their maps are outputs only -- is not launched by its
+    // stage but kept here, with everything its launch needs, for whoever asks for the map (RptRunPendingSort below says when it runs and why its inputs still
+    // stand then).  [0]: Sort_CtS into the CtN map, [1]: Sort_TtC into the NtC map.  live: the map plane does not hold the sort's result yet.
+    struct RptPendingSort
+    {
+        bool live = false; int variant = 0;
+        rpt::RptFrame F; zr_frame_constants cb; uint32_t sortTilesX = 0, numTiles = 0;      // the launch arguments of the stage that put it off
+        hipStream_t stream = nullptr;                 // that stage's stream: where a consumer of the stage's outputs runs
+        int set = 0;                                  // the reservoir set whose plane A it reads (index into res[])
+        zr_gbuffer* gb = nullptr; uint64_t gbUid = 0, gbRenderAt = 0; int gbSet = 0;      // the G-buffer plane set whose flags and motion vectors it reads
+    } rptPending[2];
     DevBuf<uint32_t> trip; DevBuf<unsigned long long> tripStats;      // ZR_K11=trip diagnostic
     DevBuf<uint32_t> carry[2], carryCount;                             // K11 with per-bounce compaction: path-state planes (ping-pong), alive counts
     DevBuf<uint32_t> costMap; bool costOn = false, costRays = false;      // rays per 32 x 32-px cell (zr_pass_enable_cost_map)
@@ -2660,10 +2680,16 @@ int zr_gbuffer_create(int device, uint32_t w, uint32_t h, zr_gbuffer** out)
     for (int i = 0; i < ZR_GB_COUNT; i++)
         if ((r = g->planeSets[k][i].AllocZero((size_t)w * h * ZR_GB_PLANE_BYTES[i]))) { delete g; return r; }
     { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) { delete g; return Fail(ZR_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(e)); } }   // see zr_pass_init
+    { std::lock_guard<std::mutex> lk(g_liveGBuffersMtx); g->uid = ++g_gbufferUid; g_liveGBuffers[g] = g->uid; }
     *out = g;
     return ZR_OK;
 }
-int zr_gbuffer_destroy(zr_gbuffer* g) { delete g; return ZR_OK; }
+int zr_gbuffer_destroy(zr_gbuffer* g)
+{
+    { std::lock_guard<std::mutex> lk(g_liveGBuffersMtx); g_liveGBuffers.erase(g); }
+    delete g;
+    return ZR_OK;
+}
 int zr_gbuffer_set_tile_origin(zr_gbuffer* g, uint32_t x0, uint32_t y0)
 {
     if (!g) return Fail(ZR_ERR_INVALID_ARG, "null gbuffer");
@@ -2792,6 +2818,7 @@ static int AllocPass(zr_pass* p)
             if ((r = p->rptTarget.AllocZero(cap))) return r;
             if ((r = p->rptNeighbor.AllocZero(cap))) return r;
             for (auto& m : p->rptMap) if ((r = m.AllocZero(cap))) return r;
+            for (auto& q : p->rptPending) q.live = false;      // (the planes it would read and write are gone)
             if ((r = p->costMap.AllocZero((size_t)((p->w + 31u) / 32u + 1u) * ((p->h + 31u) / 32u + 1u)))) return r;
             if ((r = p->rptSampleSet.Upload(kRptSampleSet, 1024))) return r;
             if ((r = p->rptLists.Alloc(4 * cap))) return r;
@@ -2872,7 +2899,7 @@ static int RenderGBuffer(zr_pass* p, hipStream_t s, const zr_frame_constants* cb
     const uint32_t tilesX = (gb->w + 15) / 16, tilesY = (gb->h + 15) / 16;
     if (int wr = gb->AcquireWrite(gb->Next(), s)) return wr;     // (tracked G-buffers: the set about to be overwritten may still be read on another stream)
     gb->cur = gb->Next(); gb->numRendered++;
-    gb->plainAt[gb->cur] = sc->plainMaterials.load(std::memory_order_relaxed); gb->sceneAt[gb->cur] = sc->uid;
+    gb->plainAt[gb->cur] = sc->plainMaterials.load(std::memory_order_relaxed); gb->sceneAt[gb->cur] = sc->uid; gb->renderAt[gb->cur] = gb->numRendered;
     TimerBegin(p, s, "gbuffer");
     uint32_t pickXY = 0xffffffffu;
     if (p->pickXY != 0xffffffffu)
@@ -3235,6 +3262,66 @@ static bool FewerRoundsAtFourWaves(uint32_t waves)
     return !off && waves > 3072u && waves <= 4096u;
 }
 
+// ---- the K12 sorts a stage puts off (zr_pass::RptPendingSort).  A sorted map is a function of the G-buffer flags (and, Sort_TtC, the motion vectors) of
+// the stage's frame, of plane A of ONE reservoir set -- Sort_TtC: the "previous" set of the temporal stage, Sort_CtS: the set the spatial round reads --
+// and of doSpatial / the frame constants, which the record holds by value.  The stage only reads that set (zr_rpt_overlap.h: BeginTemporalReuse declares
+// Oth() read, BeginSpatialRound declares Cur() read), so the sort gives the same map for as long as nobody writes the set or that G-buffer plane set.
+// The record ends in one of three ways, whichever comes first:
+//   * somebody asks for the map (zr_pass_get_output): launched there, on the stream of the stage that put it off, where that stage's consumers run;
+//   * a stage is about to write the reservoir set it reads (RptSettleMaps, called by every stage ahead of its Begin...): launched there, on that stage's
+//     stream.  Who writes which set: K11 the set that takes the "current" role (without overlap the very set the last spatial round read, or the previous
+//     set of a frame without a spatial round; with overlap the free set, which a record outlives only when a frame ran no sort at all); a spatial round
+//     the set the temporal stage read as "previous", and the second round the set the first one read;
+//   * a later sort launch gives the map new contents (the spatial stage's Sort_StC replaces the temporal stage's TtC map, the next frame's Sort_CtT the
+//     CtS map): dropped, nobody can see the map it would have written.  This is the frame's ordinary course: it launches neither.
+// With frame overlap on, the launch is a reader of its set and of its G-buffer plane set under the stream-order trackers like any stage: behind their
+// last writes, and marked, so that the next writer on another stream waits for it.  The G-buffer belongs to the caller: a record whose G-buffer has been
+// destroyed, or whose plane set has been rendered again (possible only for a caller that renders G-buffers without rendering this pass), is dropped.
+// The tile-split path moves reservoir sets only, never the maps (HaloPlanes), and never into a set a record reads: between the stages it addresses
+// Cur() -- the records read Oth() there: the temporal stage's "previous" set, and after a round's flip the set that round read -- and after the frame
+// Oth(), the set the last stage wrote, where the records read the other one.
+// (the stages' own kernel instantiations, with the map that a stage left out in the place of the one it sorted: a launch of one map is numTiles blocks)
+static void LaunchPendingSort(const zr_pass::RptPendingSort& q, uint16_t* map, hipStream_t s)
+{
+    uint16_t* const none = nullptr; uint32_t* const noList = nullptr;
+    if (q.variant == rpt::RPT_SORT_TTC)
+        hipLaunchKernelGGL((k_rpt_sort<rpt::RPT_SORT_CTT, rpt::RPT_SORT_TTC, true>), dim3(q.numTiles), dim3(256), 0, s, q.F, q.cb, q.sortTilesX, q.F.ox0 / 32u, q.F.oy0 / 32u, q.numTiles, none, map, 0u, noList, noList, noList);
+    else
+        hipLaunchKernelGGL((k_rpt_sort<rpt::RPT_SORT_STC, rpt::RPT_SORT_CTS, false>), dim3(q.numTiles), dim3(256), 0, s, q.F, q.cb, q.sortTilesX, q.F.ox0 / 32u, q.F.oy0 / 32u, q.numTiles, none, map, 0u, noList, noList, noList);
+}
+static int RptRunPendingSort(zr_pass* p, int idx, hipStream_t s)
+{
+    zr_pass::RptPendingSort& q = p->rptPending[idx];
+    if (!q.live) return ZR_OK;
+    q.live = false;
+    {
+        std::lock_guard<std::mutex> lk(g_liveGBuffersMtx);
+        auto it = g_liveGBuffers.find(q.gb);
+        if (it == g_liveGBuffers.end() || it->second != q.gbUid) return ZR_OK;
+    }
+    zr_gbuffer* gb = q.gb;
+    if (gb->renderAt[q.gbSet] != q.gbRenderAt) return ZR_OK;
+    const bool tracked = p->ov.overlap;
+    if (tracked) { if (int r = p->ov.sets[q.set].AcquireRead(p->ov.points, s)) return r; }
+    if (gb->tracked) { if (int r = gb->order[q.gbSet].AcquireRead(gb->points, s)) return r; }
+    LaunchPendingSort(q, p->rptMap[idx].p, s);
+    HIP_TRY(hipGetLastError());
+    if (tracked) { if (int r = p->ov.sets[q.set].MarkRead(p->ov.points, s)) return r; }
+    return gb->MarkRead(q.gbSet, s);
+}
+// a stage on stream s is about to write reservoir set `set`: the sorts that still have to read it run first
+static int RptSettleMaps(zr_pass* p, hipStream_t s, int set)
+{
+    for (int i = 0; i < 2; i++) if (p->rptPending[i].live && p->rptPending[i].set == set) if (int r = RptRunPendingSort(p, i, s)) return r;
+    return ZR_OK;
+}
+static void RptPutOffSort(zr_pass* p, int idx, int variant, const rpt::RptFrame& F, const zr_frame_constants& cb, uint32_t sortTilesX, uint32_t numTiles, hipStream_t s, int set, zr_gbuffer* gb)
+{
+    zr_pass::RptPendingSort& q = p->rptPending[idx];
+    q.live = true; q.variant = variant; q.F = F; q.cb = cb; q.sortTilesX = sortTilesX; q.numTiles = numTiles; q.stream = s; q.set = set;
+    q.gb = gb; q.gbUid = gb->uid; q.gbSet = gb->cur; q.gbRenderAt = gb->renderAt[gb->cur];
+}
+
 static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* cb, const zr_scene* sc, zr_gbuffer* gb, int stages)
 {
     using namespace rpt;
@@ -3250,6 +3337,8 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
             if (!gb->tracked || gb->numSets < 3) return Fail(ZR_ERR_INVALID_ARG, "ReSTIR PT with frame overlap: this G-buffer is not the one given to zr_pass_set_frame_overlap (call it again with the new G-buffer)");
             if (roles.frameOpen) return Fail(ZR_ERR_INVALID_ARG, "ReSTIR PT with frame overlap: the previous frame's last stage has not been enqueued (stage order: CANDIDATES, TEMPORAL_REUSE, SPATIAL[, SPATIAL2])");
         }
+        // K11 writes the set that takes the "current" role -- with overlap the free set, else Cur(): a K12 sort put off that reads it runs first (RptRunPendingSort)
+        if (int sr = RptSettleMaps(p, s, p->ov.overlap ? roles.set[2] : roles.Cur())) return sr;
         // K11's accesses (with overlap: after the roles have moved on to this frame's).  Only host work lies between here and its launches.
         if (int br = p->ov.BeginCandidates(s, cb->accumulate && cb->camera_static)) return br;
     }
@@ -3405,9 +3494,17 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
         if (prm.doTemporal)
         {
             // K12 Sort_TtC / Sort_CtT (IndirectLighting.cpp:383-441: dispatched whether or not SORT_TEMPORAL is set).  The temporal reconnect
-            // passes have no wave operations, so these two maps cannot change a result; they are outputs (ZR_OUT_RPT_THREAD_MAP_*)
-            RPT_TIMED("rpt_sort_temporal", hipLaunchKernelGGL((k_rpt_sort<rpt::RPT_SORT_TTC, rpt::RPT_SORT_CTT>), dim3(gridSort.x * 2), dim3(256), 0, s, F, *cb, sortTilesX, F.ox0 / 32u, F.oy0 / 32u, F.mapNtC, F.mapCtN));
-            RPT_TIMED("rpt_classify_temporal", hipLaunchKernelGGL(k_rpt_light<0>, gridLight, block, 0, s, F, *cb, tilesX, lists[0], lists[1], listCnt + 0));
+            // passes have no wave operations, so these two maps cannot change a result; they are outputs (ZR_OUT_RPT_THREAD_MAP_*), and the CtT map
+            // schedules K14 (temporalMap).  Sort_CtT is launched here -- K14 rewrites the plane it buckets by, it cannot wait.  Sort_TtC is launched here only
+            // when K14 is scheduled by its map (ZR_TEMPORAL_MAP=2); otherwise it is put off until somebody asks for the NtC map (RptRunPendingSort), which
+            // the spatial stage's Sort_StC overwrites in the same frame.  The blocks behind the sort tiles classify the pixels into the two replay work
+            // lists (k_rpt_light<0>'s work; once a launch of its own, timer "rpt_classify_temporal"): the launch reports as "rpt_sort_temporal".
+            const bool sortTtCNow = prm.temporalMap == 2u;
+            p->rptPending[0].live = false;      // (the CtN map gets new contents: a Sort_CtS still put off has nobody left to show it to)
+            if (sortTtCNow) p->rptPending[1].live = false;
+            else RptPutOffSort(p, 1, rpt::RPT_SORT_TTC, F, *cb, sortTilesX, gridSort.x, s, roles.Oth(), gb);
+            RPT_TIMED("rpt_sort_temporal", hipLaunchKernelGGL((k_rpt_sort<rpt::RPT_SORT_CTT, rpt::RPT_SORT_TTC, true>), dim3(gridSort.x * (sortTtCNow ? 2u : 1u) + gridLight.x), dim3(256), 0, s, F, *cb,
+                sortTilesX, F.ox0 / 32u, F.oy0 / 32u, gridSort.x, F.mapCtN, sortTtCNow ? F.mapNtC : (uint16_t*)nullptr, tilesX, lists[0], lists[1], listCnt + 0));
             RPT_TIMED("rpt_replay_temporal", RPT_LAUNCH_PE(k_rpt_replay, RPT_REPLAY_CTT, gridReplay, block, 0, s, F, *cb, lists[0], lists[1], listCnt + 0, ctr + 2 * 2));
             if (view != ZR_RPT_VIEW_NONE) RPT_TIMED("rpt_reconnect_temporal", RPT_LAUNCH_VIEW(k_rpt_temporal_view, gridRecon, blockRecon, 0, s, F, *cb, tilesX, ctr + 2 * 4));
             else RPT_TIMED("rpt_reconnect_temporal", RPT_LAUNCH_E(k_rpt_temporal, gridRecon, blockRecon, 0, s, F, *cb, tilesX, ctr + 2 * 4));
@@ -3420,6 +3517,10 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
     {
         if (!(stages & (spass == 0 ? ZR_STAGE_SPATIAL : ZR_STAGE_SPATIAL2))) continue;
         // a round reads the current set and writes the other one, which then becomes "current" (IndirectLighting.cpp:609-612, 682-688: one flip per round)
+        // K12 sorts put off: this round's Sort_StC gives the NtC map new contents and its Sort_CtS stands for the CtN map's -- what was put off before is dropped;
+        // without SORT_SPATIAL the maps stay what they are, and a sort that reads the set this round writes runs first (RptRunPendingSort)
+        if (prm.sortSpatial) { p->rptPending[0].live = false; p->rptPending[1].live = false; }
+        else if (int sr = RptSettleMaps(p, s, roles.Oth())) return sr;
         if (int br = p->ov.BeginSpatialRound(s)) return br;
         F.cur = p->res[roles.Cur()].View(); F.prev = p->res[roles.Oth()].View();
         // replay work lists + their device-side counts of this round: {2, 3} for the first, {6, 7} for the second (zeroed at the start of the frame)
@@ -3435,7 +3536,10 @@ static int RenderReSTIR_PT(zr_pass* p, hipStream_t s, const zr_frame_constants* 
         // population of its boiling-suppression averages
         if (prm.sortSpatial)
         {
-            RPT_TIMED("rpt_sort_spatial", hipLaunchKernelGGL((k_rpt_sort<rpt::RPT_SORT_CTS, rpt::RPT_SORT_STC>), dim3(gridSort.x * 2), dim3(256), 0, s, F, *cb, sortTilesX, F.ox0 / 32u, F.oy0 / 32u, F.mapCtN, F.mapNtC));
+            // (Sort_StC alone: K16 reads its map.  The CtS map is an output only -- put off until somebody asks for it)
+            RPT_TIMED("rpt_sort_spatial", hipLaunchKernelGGL((k_rpt_sort<rpt::RPT_SORT_STC, rpt::RPT_SORT_CTS, false>), gridSort, dim3(256), 0, s, F, *cb, sortTilesX, F.ox0 / 32u, F.oy0 / 32u, gridSort.x,
+                F.mapNtC, (uint16_t*)nullptr, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr));
+            RptPutOffSort(p, 0, rpt::RPT_SORT_CTS, F, *cb, sortTilesX, gridSort.x, s, roles.Cur(), gb);
         }
         RPT_TIMED("rpt_replay_spatial", RPT_LAUNCH_PE(k_rpt_replay, RPT_REPLAY_CTS, dim3(gridList.x * 2), block, 0, s, F, *cb, lists[2], lists[3], sCnt, ctr + 2 * 5));
         if (view != ZR_RPT_VIEW_NONE) RPT_TIMED("rpt_reconnect_spatial", RPT_LAUNCH_VIEW(k_rpt_stc_view, gridStc, blockStc, 0, s, F, *cb, tilesX, ctr + 2 * 7));
@@ -3876,6 +3980,8 @@ int zr_pass_set_frame_overlap(zr_pass* p, zr_gbuffer* gb, int enable)
     if (p->ov.roles.frameOpen) return Fail(ZR_ERR_INVALID_ARG, "zr_pass_set_frame_overlap: call between frames (a frame's last stage has not been enqueued)");
     if (gb->device != p->device) return Fail(ZR_ERR_INVALID_ARG, "gbuffer / pass live on different devices");
     HIP_TRY(hipSetDevice(p->device));
+    // (the K12 sorts put off run now, each on its stage's stream: the trackers they would order themselves by are about to forget everything)
+    for (int i = 0; i < 2; i++) if (int r = RptRunPendingSort(p, i, p->rptPending[i].stream)) return r;
     HIP_TRY(hipDeviceSynchronize());      // (a host call between frames; the planes allocated below are cleared on the null stream)
     if (enable && !p->res[2].A.p) { if (int r = AllocOverlapPlanes(p)) return r; HIP_TRY(hipDeviceSynchronize()); }
     if (enable && !p->overlapStream) HIP_TRY(hipStreamCreateWithFlags(&p->overlapStream, hipStreamNonBlocking));
@@ -3892,7 +3998,7 @@ int zr_pass_set_frame_overlap(zr_pass* p, zr_gbuffer* gb, int enable)
         if (gb->cur == 0)
         {
             for (int i = 0; i < ZR_GB_COUNT; i++) gb->planeSets[1][i].Swap(gb->planeSets[2][i]);
-            std::swap(gb->plainAt[1], gb->plainAt[2]); std::swap(gb->sceneAt[1], gb->sceneAt[2]);
+            std::swap(gb->plainAt[1], gb->plainAt[2]); std::swap(gb->sceneAt[1], gb->sceneAt[2]); std::swap(gb->renderAt[1], gb->renderAt[2]);
         }
         gb->numSets = 3;
     }
@@ -4075,6 +4181,11 @@ static int RenderStageInner(zr_pass* p, void* stream, const zr_frame_constants* 
     }
 }
 
+// The two K12 thread maps of a ReSTIR PT pass are complete when they are asked for, not before.  A stage launches the sort whose map one of its kernels
+// reads (Sort_CtT, Sort_StC) and puts the other one off (Sort_TtC, Sort_CtS: zr_pass::RptPendingSort); asking for a map here launches the sort put off for it,
+// on the stream of the stage it belongs to -- the stream a consumer of that stage's outputs runs on (zetaray_amd.h) -- so the plane holds what it has always
+// held at this point: CtT / TtC after the temporal stage, CtS / StC after a spatial round, whatever the flags, the number of rounds and the overlap mode.
+// RptRunPendingSort states why the sort's inputs still stand.  A renderer that never asks pays for neither map.
 int zr_pass_get_output(const zr_pass* p, int which, void** dev, uint32_t* w, uint32_t* h, uint32_t* bpp)
 {
     if (!p || !dev) return Fail(ZR_ERR_INVALID_ARG, "null argument");
@@ -4154,7 +4265,15 @@ int zr_pass_get_output(const zr_pass* p, int which, void** dev, uint32_t* w, uin
     else if (which >= ZR_OUT_RPT_RBUF_CTN_A && which <= ZR_OUT_RPT_RBUF_NTC_D && p->integrator == ZR_INTEGRATOR_RESTIR_PT)
         PlanesOutput(p->rb[(which - ZR_OUT_RPT_RBUF_CTN_A) / 4], (which - ZR_OUT_RPT_RBUF_CTN_A) % 4, dev, bpp);
     else if ((which == ZR_OUT_RPT_THREAD_MAP_CTN || which == ZR_OUT_RPT_THREAD_MAP_NTC) && p->integrator == ZR_INTEGRATOR_RESTIR_PT)
-        p->rptMap[which - ZR_OUT_RPT_THREAD_MAP_CTN].Output(dev, bpp);
+    {
+        const int idx = which - ZR_OUT_RPT_THREAD_MAP_CTN;
+        if (p->rptPending[idx].live)
+        {   // (the pass is const for what a caller can see of it: the plane gets the contents it is documented to have)
+            HIP_TRY(hipSetDevice(p->device));
+            if (int r = RptRunPendingSort(const_cast<zr_pass*>(p), idx, p->rptPending[idx].stream)) return r;
+        }
+        p->rptMap[idx].Output(dev, bpp);
+    }
     else if (which >= ZR_OUT_RPT_RESERVOIR_A && which <= ZR_OUT_RPT_NEIGHBOR && p->integrator == ZR_INTEGRATOR_RESTIR_PT)
     {
         if (which <= ZR_OUT_RPT_RESERVOIR_G) PlanesOutput(p->res[p->ov.roles.Oth()], which - ZR_OUT_RPT_RESERVOIR_A, dev, bpp);      // the set the next frame reads as "previous"
@@ -4169,11 +4288,16 @@ int zr_pass_get_output(const zr_pass* p, int which, void** dev, uint32_t* w, uin
 int zr_pass_download_output(const zr_pass* p, int which, void* stream, void* dst, size_t bytes)
 {
     void* dev = nullptr; uint32_t w, h, bpp;
+    // (a thread map may be completed by the call below, on the stream of the stage it belongs to: the copy waits for that stream too)
+    const bool isMap = p && p->initialized && p->kind == ZR_PASS_INDIRECT && p->integrator == ZR_INTEGRATOR_RESTIR_PT && (which == ZR_OUT_RPT_THREAD_MAP_CTN || which == ZR_OUT_RPT_THREAD_MAP_NTC);
+    const bool sortRuns = isMap && p->rptPending[which - ZR_OUT_RPT_THREAD_MAP_CTN].live;
+    const hipStream_t sortStream = sortRuns ? p->rptPending[which - ZR_OUT_RPT_THREAD_MAP_CTN].stream : nullptr;
     int r = zr_pass_get_output(p, which, &dev, &w, &h, &bpp);
     if (r) return r;
     if (!dst || bytes != (size_t)w * h * bpp) return Fail(ZR_ERR_INVALID_ARG, "destination must hold %zu bytes", (size_t)w * h * bpp);
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (sortRuns && sortStream != (hipStream_t)stream) HIP_TRY(hipStreamSynchronize(sortStream));
     HIP_TRY(hipMemcpy(dst, dev, bytes, hipMemcpyDeviceToHost));
     return ZR_OK;
 }

@@ -347,8 +347,9 @@ enum RptPixelPass { RPT_REPLAY_CTT = 0, RPT_REPLAY_TTC, RPT_RECONNECT_TEMPORAL, 
 // ~88 dequeues per microsecond one word sustains, MI355X_MICROARCH.md).  Four tiles per block: a quarter of the atomics.
 // (the search kernel does real work per pixel -- three dependent candidate gathers -- and is latency-bound rather than atomic-bound: two tiles)
 static constexpr uint32_t kLightTilesPerBlock = 4, kSearchTilesPerBlock = 2;
+// (a device function over a block index of its own: k_rpt_light runs it with blockIdx.x, k_rpt_sort<.., .., true> runs PASS 0 in the blocks behind its sort tiles)
 template<int PASS>
-__global__ void __launch_bounds__(kBlock) k_rpt_light(rpt::RptFrame F, zr_frame_constants g, uint32_t tilesX, uint32_t* listA, uint32_t* listB, uint32_t* counts)
+__device__ __forceinline__ void RptLightBlock(const rpt::RptFrame& F, const zr_frame_constants& g, uint32_t block, uint32_t tilesX, uint32_t* listA, uint32_t* listB, uint32_t* counts)
 {
     constexpr uint32_t TPB = PASS == 0 ? kLightTilesPerBlock : (PASS == 1 ? kSearchTilesPerBlock : 1u);      // (the LDS-tile experiment stages one tile's neighbourhood)
     constexpr uint32_t VW = TPB * (uint32_t)(kBlock / 64);             // "virtual waves" of the block: (tile, wave) pairs, in that order
@@ -358,7 +359,7 @@ __global__ void __launch_bounds__(kBlock) k_rpt_light(rpt::RptFrame F, zr_frame_
     __shared__ uint32_t sCnt[2][3][VW], sBase[2];
     for (uint32_t t = 0; t < TPB; t++)
     {
-        const uint32_t tile = blockIdx.x * TPB + t;
+        const uint32_t tile = block * TPB + t;
         const uint32_t tx = tile % tilesX, ty = tile / tilesX;
         const uint32_t x = F.ox0 + tx * 16u + (wave & 1u) * 8u + (lane & 7u), y = F.oy0 + ty * 16u + (wave >> 1) * 8u + (lane >> 3);
         const bool in = tile < numTiles && F.Owns(x, y);
@@ -425,6 +426,9 @@ __global__ void __launch_bounds__(kBlock) k_rpt_light(rpt::RptFrame F, zr_frame_
             oa += ta; ob += tb;
         }
 }
+template<int PASS>
+__global__ void __launch_bounds__(kBlock) k_rpt_light(rpt::RptFrame F, zr_frame_constants g, uint32_t tilesX, uint32_t* listA, uint32_t* listB, uint32_t* counts)
+{ RptLightBlock<PASS>(F, g, blockIdx.x, tilesX, listA, listB, counts); }
 
 // K13 replays over work lists (device-side counts, fixed grid, grid-stride): only pixels with k > 2 pay for the heavy kernel.  One launch runs the
 // two replays of a stage (CtT + TtC, CtS + StC: independent -- each writes its own r-buffer): the first half of the grid walks list A with
@@ -565,13 +569,19 @@ __device__ __forceinline__ void RptSortTile(const rpt::RptFrame& F, const zr_fra
     }
 }
 
-// one launch sorts a stage's two maps (Sort_TtC + Sort_CtT, Sort_CtS + Sort_StC): first half of the grid = variant VA into mapA, second half = VB into mapB
-template<int VA, int VB>
-__global__ void __launch_bounds__(256) k_rpt_sort(rpt::RptFrame F, zr_frame_constants g, uint32_t tilesX, uint32_t tile0x, uint32_t tile0y, uint16_t* mapA, uint16_t* mapB)
+// K12 of one stage in one launch.  A launch sorts the maps it is given, numTiles blocks each: variant VA into mapA, then VB into mapB; a null map has no
+// blocks.  A stage passes the map one of its kernels reads and leaves the other to zr_api.hip's RptPendingSort, which launches this kernel again for it when
+// somebody asks for that map.  CLASSIFY: the blocks behind the sort tiles do the work of k_rpt_light<0> -- the temporal stage's replay work lists, which
+// depend on the same planes as its sorts and on nothing the sorts write -- so the stage's prepass is one launch.
+template<int VA, int VB, bool CLASSIFY>
+__global__ void __launch_bounds__(256) k_rpt_sort(rpt::RptFrame F, zr_frame_constants g, uint32_t tilesX, uint32_t tile0x, uint32_t tile0y, uint32_t numTiles, uint16_t* mapA, uint16_t* mapB,
+    uint32_t lightTilesX, uint32_t* listA, uint32_t* listB, uint32_t* counts)
 {
-    const uint32_t half = gridDim.x / 2u;
-    if (blockIdx.x < half) RptSortTile<VA>(F, g, blockIdx.x, tilesX, tile0x, tile0y, mapA);
-    else RptSortTile<VB>(F, g, blockIdx.x - half, tilesX, tile0x, tile0y, mapB);
+    static_assert(kBlock == 256, "the classify blocks of k_rpt_sort are k_rpt_light's");
+    uint32_t b = blockIdx.x;      // (every branch below is uniform over the block)
+    if (mapA) { if (b < numTiles) { RptSortTile<VA>(F, g, b, tilesX, tile0x, tile0y, mapA); return; } b -= numTiles; }
+    if (mapB) { if (b < numTiles) { RptSortTile<VB>(F, g, b, tilesX, tile0x, tile0y, mapB); return; } b -= numTiles; }
+    if (CLASSIFY) RptLightBlock<0>(F, g, b, lightTilesX, listA, listB, counts);
 }
 
 // Block size of the two reconnect kernels (K14, K16): nothing in them is shared between the waves of a block, so a 16 x 16 tile can be one
